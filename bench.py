@@ -3,17 +3,23 @@
 21-layer table of configuration/model/wav2letter.yaml (mid_layers=20, 153 M params), bf16
 operands / fp32 accumulate, synthetic 64-mel x 1000-frame spectrograms, batch 32 per GPU.
 
-  python bench.py [--gpus N --steps K --warmup W]
+  python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]
 
 N > 1: under `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N` each process is one rank; a plain
 `python bench.py --gpus N` (no rendezvous variables in the environment) starts the N ranks itself
 (wav2letter_pytorch_amd/launch.py: N subprocesses of this command line, before this process touches the GPU) and
 forwards rank 0's line.  One rank per GPU, gradients averaged with RCCL (torch.distributed backend "nccl").
 
-Prints ONE JSON line on rank 0 (see the contract in the task statement).  `roofline` is the
-dominant kernel (conv_igemm_kernel: forward + data-gradient convolutions) timed with HIP events
-on its launch stream in a separate instrumented pass of the same step; `cpu_baseline` is the
-CPU oracle (torch-CPU restatement of the reference path) timed on this host's cores."""
+Prints ONE JSON line on rank 0: `metric`, `value` (frames/s of the timed region), `unit`, `higher_is_better`, `dtype` and
+`ms_per_step` (wall milliseconds of one of the --steps timed steps).  A plain run does only what that figure needs: set-up,
+warm-up (with the in-run choice of --defer-wgrad auto), the timed steps, the line.  `--dump-outputs DIR` writes what the
+last timed step computed as DIR/*.npy (see dump_outputs).
+
+`--full` adds everything else, after the timed region: the trainer-loop legs (`trainer_ms_per_step`, `trainer_loop`), the
+exposed-communication and bf16-transport legs of data-parallel runs, `roofline` -- the dominant kernel (conv_igemm_kernel:
+forward + data-gradient convolutions) timed with HIP events on its launch stream in a separate instrumented pass of the same
+step, with its HBM traffic from two rocprofv3 child passes -- and `cpu_baseline`, the CPU oracle (torch-CPU restatement of the
+reference path) timed on this host's cores.  Without --full those fields are null."""
 import argparse
 import json
 import os
@@ -173,8 +179,8 @@ def live_traffic(E, kernel, timeout_s=170):
         for counter in ('FETCH_SIZE', 'WRITE_SIZE'):
             out = os.path.join(tmp, counter)
             cmd = [exe, '--kernel-trace', '--pmc', counter, '--output-format', 'csv', '-d', out, '--', sys.executable,
-                   os.path.abspath(__file__), '--steps', '2', '--warmup', '1', '--no-cpu-baseline', '--no-live-traffic',
-                   '--no-trainer-leg', '--defer-wgrad', '4']
+                   os.path.abspath(__file__), '--steps', '2', '--warmup', '1', '--full', '--no-cpu-baseline',
+                   '--no-live-traffic', '--no-trainer-leg', '--defer-wgrad', '4']
             r = subprocess.run(cmd, cwd='/tmp', env=env, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=timeout_s)
             if r.returncode != 0:
                 return None, f'rocprofv3 --pmc {counter} exited with {r.returncode}'
@@ -216,6 +222,47 @@ def grad_byte_split(model, defer_k):
                 'fraction_beside_next_forward': round(fwd / total, 4)}
     except Exception as e:        # noqa: BLE001 -- a report field, never a reason to lose the record
         return {'error': repr(e)}
+
+
+DUMP_ELEMENTS_PER_FILE = 4_000_000     # dump_outputs: at most this many elements per .npy file (16 MB of float32)
+
+
+def dump_outputs(out_dir, model, loss, log_probs):
+    """What the timed step hands its caller, after its last step, as float32 / float64 .npy files in ``out_dir`` (at most
+    64 MB in all):
+      loss.npy       [1] float64, the loss of the last step
+      log_probs.npy  [N, T', labels] float32, the forward output of the last step (hand-rolled step only); a seeded sample
+                     of DUMP_ELEMENTS_PER_FILE of its elements, flattened, when it is larger
+      params.npy / buffers.npy  float32: every parameter after the update (every floating-point buffer, i.e. BatchNorm
+                     running statistics), in model order, each reduced to at most DUMP_ELEMENTS_PER_FILE // (number of
+                     tensors) elements at sorted positions drawn by a generator seeded with the tensor's index -- the same
+                     positions in every run of the same configuration -- concatenated.
+    (No gradients: those of the units whose weight gradients are held back, --defer-wgrad, are not left in p.grad.)"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+
+    def sample(t, cap, seed):
+        flat = t.detach().reshape(-1)
+        if flat.numel() > cap:
+            pos = np.sort(np.random.default_rng(seed).choice(flat.numel(), cap, replace=False))
+            flat = flat[torch.from_numpy(pos).to(flat.device)]
+        return flat.float().cpu().numpy()
+
+    def save(name, arr):
+        np.save(os.path.join(out_dir, name + '.npy'), arr)
+
+    save('loss', np.array([float(loss.detach())], dtype=np.float64))
+    if log_probs is not None:
+        lp = log_probs.detach()
+        save('log_probs', lp.float().cpu().numpy() if lp.numel() <= DUMP_ELEMENTS_PER_FILE
+             else sample(lp, DUMP_ELEMENTS_PER_FILE, 0))
+
+    def save_sampled(name, tensors):
+        cap = DUMP_ELEMENTS_PER_FILE // max(1, len(tensors))
+        save(name, np.concatenate([sample(t, cap, i) for i, t in enumerate(tensors)]) if tensors else np.zeros(0, np.float32))
+
+    save_sampled('params', list(model.parameters()))
+    save_sampled('buffers', [b for b in model.buffers() if b.is_floating_point()])
 
 
 def main():
@@ -268,9 +315,18 @@ def main():
                          'forward + CTC + per-step greedy decode + CER/WER + log_dict, then backward, optimizer step and the '
                          'on_train_batch_end hook (base_asr_models.py:78-85 driven as train.py:34-37 drives it)')
     ap.add_argument('--no-trainer-leg', action='store_true',
-                    help='skip the extra timed regions that put trainer_ms_per_step (and its synchronous-metrics "before" figure) '
-                         'into the record')
+                    help='with --full: skip the extra timed regions that put trainer_ms_per_step (and its synchronous-metrics '
+                         '"before" figure) into the record')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed region also run the trainer-loop legs, the exposed-communication legs (data-parallel '
+                         'runs), the instrumented roofline pass (+ its rocprofv3 traffic passes) and the CPU baseline; a plain '
+                         'run leaves those fields null')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='write what the last timed step computed (loss, log-probabilities, seeded samples of the updated '
+                         'parameters and the float buffers) as DIR/<name>.npy, rank 0 only')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
 
     L = _launcher()
     if args.gpus > 1 and not L.under_launcher():
@@ -349,9 +405,13 @@ def main():
         defer_k = args.defer_wgrad
         opt.defer_wgrad(model, defer_spec(defer_k))
 
+    last_out = {} if args.dump_outputs else None       # --dump-outputs: the log-probabilities of the latest step
+
     def raw_step():
         opt.zero_grad(set_to_none=True)
         out, _ = model(x, lens_arg)
+        if last_out is not None:
+            last_out['log_probs'] = out
         loss = model.criterion(out.transpose(0, 1), tg_d, ol, tl_d)
         loss.backward()
         if not args.no_optimizer:
@@ -554,6 +614,10 @@ def main():
         model.grad_reducer.wire_bytes = 0
     ms, rank_ms, loss = timed_region()
     value = world * N * T / (ms * 1e-3)
+    if args.dump_outputs and rank == 0:           # (after timed_region's fence: no update of the last step is in flight)
+        dump_outputs(args.dump_outputs, model, loss, (last_out or {}).get('log_probs'))
+    if last_out is not None:
+        last_out.clear()
     comm_bytes = None
     if getattr(model, 'grad_reducer', None) is not None and model.grad_reducer.active:
         # payload handed to the gradient collectives per step in the timed region (fp32 unless W2L_DP_BF16=1: then the large
@@ -566,7 +630,7 @@ def main():
     # the reference's order restored (async_metrics = False: decode, CER / WER and float(loss) inside training_step, i.e.
     # before backward() is enqueued).  Host enqueue time per step of each leg rides along.
     trainer = None
-    if not args.no_trainer_leg and not args.graph and not args.no_optimizer:
+    if args.full and not args.no_trainer_leg and not args.graph and not args.no_optimizer:
         trainer = {}
         legs = (('raw_loop', raw_step, True),) if args.through_trainer else ()
         legs += (('async_metrics', trainer_step, True), ('sync_metrics_before', trainer_step, False))
@@ -590,7 +654,7 @@ def main():
     # ---- exposed communication: the same step with the gradient reducer detached (no collectives), same run, per rank ----
     exposed_comm_ms = exposed_by_rank = solo_ms = bf16_leg = None
     reducer = getattr(model, 'grad_reducer', None)
-    if reducer is not None and not args.graph:
+    if args.full and reducer is not None and not args.graph:
         model.grad_reducer = None
         _replay_was, _replay.ENABLED = _replay.ENABLED, False      # the data-parallel step runs eagerly (its collectives are not
         k2 = max(2, min(args.steps, 10))                            # entry points): so does the step it is compared with
@@ -632,16 +696,17 @@ def main():
     roof = None
     # every rank runs these steps (a data-parallel step contains collectives: a rank stepping alone would wait forever);
     # only rank 0 records and reports the events
-    if rank == 0:
-        E.KERNEL_TIMER = []
-    model._overlap_wgrad = False      # serialise the side stream so per-launch durations are not shared-GPU times
-    for _ in range(3):
-        eager_step()                  # (the captured graph carries no timing events)
-    if hasattr(opt, 'join'):
-        opt.join()                    # the last step's deferred weight gradients are launched (and timed) here
-    torch.cuda.synchronize()
-    model._overlap_wgrad = not args.serial_wgrad
-    if rank == 0:
+    if args.full:
+        if rank == 0:
+            E.KERNEL_TIMER = []
+        model._overlap_wgrad = False      # serialise the side stream so per-launch durations are not shared-GPU times
+        for _ in range(3):
+            eager_step()                  # (the captured graph carries no timing events)
+        if hasattr(opt, 'join'):
+            opt.join()                    # the last step's deferred weight gradients are launched (and timed) here
+        torch.cuda.synchronize()
+        model._overlap_wgrad = not args.serial_wgrad
+    if rank == 0 and args.full:
         agg = {}
         fused = [0.0, 0.0, 0]
         by_shape = {}
@@ -758,7 +823,7 @@ def main():
 
     if rank == 0:
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             if args.model != 'wav2letter':
                 cpu = cpu_baseline_jasper()
             elif args.mid_layers >= 20:
@@ -776,7 +841,7 @@ def main():
                                     (trainer or {}).get('async_metrics', {}).get('ms_per_step')),
             'trainer_loop': trainer,
             'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
-            'dtype': args.dtype, 'data': 'synthetic',
+            'dtype': args.dtype, 'data': 'synthetic', 'full': args.full,
             'config': {'workload': ('Jasper 10x5 (13 dense blocks, repeat 5, 322 M params), ' if args.model == 'jasper10x5' else '')
                                    + f'Wav2Letter mid_layers={args.mid_layers} (configuration/model/wav2letter.yaml table), ' * (args.model == 'wav2letter')
                                    +

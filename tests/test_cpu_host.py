@@ -523,7 +523,7 @@ def test_tune_cache_roundtrip(tmp_path):
     assert L.lib.w2l_tune_load(str(old).encode()) == -1
 
 
-def test_data_loader_host_side(tmp_path):
+def test_data_loader_host_side(tmp_path, monkeypatch):
     """load_audio (stdlib WAV path), manifest parsing, target mapping and the host collate (data_loader.py:20-31,90-158)"""
     import wave
     from wav2letter_pytorch_amd.data import data_loader as DL
@@ -543,6 +543,7 @@ def test_data_loader_host_side(tmp_path):
     np.testing.assert_array_equal(il.numpy(), z['col_il'])
     np.testing.assert_array_equal(tg.numpy(), z['col_tg'])
     np.testing.assert_array_equal(tl.numpy(), z['col_tl'])
+    monkeypatch.setattr(torch.cuda, 'is_available', lambda: False)      # (a GPU host too: what happens without a device)
     with pytest.raises(RuntimeError):                   # no CPU feature path
         DL.SpectrogramExtractor(dict(window='hamming', window_stride=0.01, window_size=0.02, sample_rate=16000), 64)
 

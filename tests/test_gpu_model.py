@@ -1061,7 +1061,7 @@ def test_bench_two_rank_command_line(tmp_path):
     env = dict(os.environ, W2L_DIST_BACKEND='gloo')
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1',
            '--master-port', str(port), os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1',
-           '--mid-layers', '2', '--batch', '2', '--frames', '200', '--no-cpu-baseline']
+           '--mid-layers', '2', '--batch', '2', '--frames', '200', '--full', '--no-cpu-baseline']
     out = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=280)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith('{"metric"')]
@@ -1081,7 +1081,7 @@ def test_bench_self_launch_two_ranks(tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT')}
     env['W2L_DIST_BACKEND'] = 'gloo'
     cmd = [sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1', '--mid-layers', '2',
-           '--batch', '2', '--frames', '200', '--no-cpu-baseline', '--defer-wgrad', '1', '--collective-ab']
+           '--batch', '2', '--frames', '200', '--full', '--no-cpu-baseline', '--defer-wgrad', '1', '--collective-ab']
     out = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=280)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith('{"metric"')]
@@ -1115,6 +1115,32 @@ def test_bench_self_launch_two_ranks(tmp_path):
     bad = subprocess.run(cmd, env=dict(env, RANK='0', WORLD_SIZE='3', MASTER_ADDR='127.0.0.1', MASTER_PORT='1'), cwd=root,
                          capture_output=True, text=True, timeout=120)
     assert bad.returncode != 0 and 'must agree' in bad.stderr
+
+
+def test_bench_plain_run_dumps_outputs(tmp_path):
+    """plain `bench.py` (no --full): one JSON line with the headline fields, exactly --steps timed steps, the --full legs
+    left null, and --dump-outputs writing the last timed step's results as float32 / float64 .npy files"""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT')}
+    cmd = [sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1', '--mid-layers', '2',
+           '--batch', '2', '--frames', '200', '--dump-outputs', str(tmp_path / 'out')]
+    out = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=280)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith('{"metric"')]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d['steps'] == 3 and d['ms_per_step'] > 0 and d['value'] > 0 and d['unit'] == 'frames/s'
+    assert d['higher_is_better'] is True and d['dtype'] == 'bf16' and d['full'] is False
+    assert d['roofline'] is None and d['cpu_baseline'] is None and d['trainer_loop'] is None
+    files = {f.name: np.load(f) for f in (tmp_path / 'out').iterdir()}
+    assert set(files) == {'loss.npy', 'log_probs.npy', 'params.npy', 'buffers.npy'}
+    assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in files.values())
+    assert sum(a.nbytes for a in files.values()) <= 64 << 20
+    assert abs(float(files['loss.npy'][0]) - d['config']['loss']) < 1e-3
+    assert files['log_probs.npy'].shape[0] == 2 and files['params.npy'].size > 0 and files['buffers.npy'].size > 0
 
 
 @pytest.mark.parametrize('amsgrad', [False, True])

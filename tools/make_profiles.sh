@@ -13,9 +13,9 @@ export W2L_TUNE_CACHE=$PWD/$OUT/tune_cache_$STAGE.txt   # the first run measures
 last() { tail -1; }
 if [ "$STAGE" = headline ] || [ "$STAGE" = all ]; then
 # ---- headline (BASELINE config 2): bench line, rocprofv3 kernel statistics (overlapped = default, and serialised), PMC traffic
-python3 bench.py --steps 20 --warmup 5 2>/dev/null | last > $OUT/bench.json
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_default -- python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline > $OUT/prof_default.log 2>&1
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_serial -- python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline --serial-wgrad > $OUT/prof_serial.log 2>&1
+python3 bench.py --full --steps 20 --warmup 5 2>/dev/null | last > $OUT/bench.json
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_default -- python3 bench.py --full --steps 10 --warmup 3 --no-cpu-baseline > $OUT/prof_default.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_serial -- python3 bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --serial-wgrad > $OUT/prof_serial.log 2>&1
 for d in default serial; do
   f=$(ls $OUT/prof_$d/*/*kernel_stats.csv | head -1)
   cp $f $OUT/${d}_kernel_stats.csv
@@ -38,7 +38,7 @@ python3 tools/step_ab.py --rounds 4 --variants "base;nowgrad=PROBE:nowgrad,DEFER
 python3 tools/step_ab.py --rounds 4 --batch 16 --variants "base;nogroups=GROUPS:0;groups8=WGROUP_MAX:8;slowbn=FAST_BN_BWD:0" 2>/dev/null >> $OUT/step_ab.txt
 python3 tools/step_ab.py --rounds 4 --model jasper10x5 --batch 16 --defer 4 --variants "base;nogroups=GROUPS:0;groups8=WGROUP_MAX:8;slowbn=FAST_BN_BWD:0;round4=GROUPS:0,FAST_BN_BWD:0,DEFER_SPREAD:start" 2>/dev/null >> $OUT/step_ab.txt
 for c in FETCH_SIZE WRITE_SIZE; do
-  rocprofv3 --kernel-trace --pmc $c --output-format csv -d $OUT/pmc_bench_$c -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline > /dev/null 2>&1
+  rocprofv3 --kernel-trace --pmc $c --output-format csv -d $OUT/pmc_bench_$c -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline > /dev/null 2>&1
 done
 python3 tools/prof_summary.py pmc $OUT/pmc_bench.json $OUT/pmc_bench_FETCH_SIZE $OUT/pmc_bench_WRITE_SIZE
 rm -rf $OUT/pmc_bench_FETCH_SIZE $OUT/pmc_bench_WRITE_SIZE $OUT/prof_default $OUT/prof_serial $OUT/prof_default.log $OUT/prof_serial.log
@@ -60,26 +60,26 @@ python3 tools/bench_elem.py > $OUT/bn_kernels.txt 2>&1
 fi
 if [ "$STAGE" = workloads ] || [ "$STAGE" = all ]; then
 # ---- the other workloads
-python3 bench.py --model jasper10x5 --batch 16 --steps 10 --warmup 4 2>/dev/null | last > $OUT/bench_jasper10x5.json
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_jasper -- python3 bench.py --model jasper10x5 --batch 16 --steps 8 --warmup 3 --no-cpu-baseline > /dev/null 2>&1
+python3 bench.py --full --model jasper10x5 --batch 16 --steps 10 --warmup 4 2>/dev/null | last > $OUT/bench_jasper10x5.json
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_jasper -- python3 bench.py --full --model jasper10x5 --batch 16 --steps 8 --warmup 3 --no-cpu-baseline > /dev/null 2>&1
 python3 tools/prof_summary.py stats $(ls $OUT/prof_jasper/*/*kernel_stats.csv | head -1) > $OUT/jasper10x5_kernel_families.txt
 rm -rf $OUT/prof_jasper
-python3 bench.py --dtype fp8 --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | last > $OUT/bench_fp8.json
-python3 bench.py --model jasper10x5 --batch 16 --dtype fp8 --steps 10 --warmup 4 2>/dev/null | last > $OUT/bench_jasper10x5_fp8.json
-python3 bench.py --model jasper10x5 --batch 16 --frames 16000 --dtype fp8 --steps 3 --warmup 2 2>/dev/null | last > $OUT/bench_jasper10x5_fp8_T16000.json
-python3 bench.py --model jasper10x5 --batch 16 --frames 16000 --steps 3 --warmup 2 2>/dev/null | last > $OUT/bench_jasper10x5_T16000.json
-python3 bench.py --mid-layers 1 --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | last > $OUT/bench_w2l_mid1.json
-for n in 8 16; do python3 bench.py --batch $n --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | last > $OUT/bench_w2l_n$n.json; done
+python3 bench.py --full --dtype fp8 --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | last > $OUT/bench_fp8.json
+python3 bench.py --full --model jasper10x5 --batch 16 --dtype fp8 --steps 10 --warmup 4 2>/dev/null | last > $OUT/bench_jasper10x5_fp8.json
+python3 bench.py --full --model jasper10x5 --batch 16 --frames 16000 --dtype fp8 --steps 3 --warmup 2 2>/dev/null | last > $OUT/bench_jasper10x5_fp8_T16000.json
+python3 bench.py --full --model jasper10x5 --batch 16 --frames 16000 --steps 3 --warmup 2 2>/dev/null | last > $OUT/bench_jasper10x5_T16000.json
+python3 bench.py --full --mid-layers 1 --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | last > $OUT/bench_w2l_mid1.json
+for n in 8 16; do python3 bench.py --full --batch $n --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | last > $OUT/bench_w2l_n$n.json; done
 # one rank, RCCL path forced: what the gradient collectives cost when nothing has to cross a link (plumbing, exposed_comm_ms)
-python3 bench.py --force-dp --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | last > $OUT/bench_force_dp_1rank.json
+python3 bench.py --full --force-dp --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | last > $OUT/bench_force_dp_1rank.json
 # the multi-rank creation order rehearsed on one GPU (communicator before the first step), with and without the measured
 # choice of side streams, and the same through the C ABI's RCCL helpers; the probe matrix of a fresh process
-python3 bench.py --force-dp --early-collective --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | last > $OUT/bench_force_dp_comm_first.json
-W2L_STREAM_PROBE=0 python3 bench.py --force-dp --early-collective --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | last > $OUT/bench_force_dp_comm_first_noprobe.json
-W2L_DP_NATIVE=1 python3 bench.py --force-dp --early-collective --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | last > $OUT/bench_force_dp_native_rccl.json
+python3 bench.py --full --force-dp --early-collective --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | last > $OUT/bench_force_dp_comm_first.json
+W2L_STREAM_PROBE=0 python3 bench.py --full --force-dp --early-collective --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | last > $OUT/bench_force_dp_comm_first_noprobe.json
+W2L_DP_NATIVE=1 python3 bench.py --full --force-dp --early-collective --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | last > $OUT/bench_force_dp_native_rccl.json
 python3 tools/stream_map.py 12 2>/dev/null > $OUT/stream_map.txt
 python3 tools/bench_features.py 2>/dev/null | last > $OUT/bench_features.txt
-python3 bench.py --ragged --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | last > $OUT/bench_ragged.json
+python3 bench.py --full --ragged --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | last > $OUT/bench_ragged.json
 fi
 if [ "$STAGE" = replay ] || [ "$STAGE" = all ]; then
 # ---- round 6: the reference's loop body and the recorded launch lists
@@ -93,11 +93,11 @@ for cfg in "" "--batch 8" "--batch 16" "--mid-layers 1" "--model jasper10x5 --ba
   echo "== tools/replay_ab.py $cfg"; python3 tools/replay_ab.py $cfg 2>/dev/null | head -3
 done > $OUT/replay_ab.txt
 # the timed region through training_step (host batch, per-step greedy decode + CER / WER): value / ms_per_step ARE the trainer's
-python3 bench.py --through-trainer --steps 20 --warmup 5 --no-cpu-baseline --no-live-traffic 2>/dev/null | last > $OUT/bench_through_trainer.json
-python3 bench.py --through-trainer --model jasper10x5 --batch 16 --steps 10 --warmup 4 --no-cpu-baseline 2>/dev/null | last > $OUT/bench_through_trainer_jasper10x5.json
-python3 bench.py --through-trainer --model jasper10x5 --batch 16 --dtype fp8 --steps 10 --warmup 4 --no-cpu-baseline 2>/dev/null | last > $OUT/bench_through_trainer_jasper10x5_fp8.json
+python3 bench.py --full --through-trainer --steps 20 --warmup 5 --no-cpu-baseline --no-live-traffic 2>/dev/null | last > $OUT/bench_through_trainer.json
+python3 bench.py --full --through-trainer --model jasper10x5 --batch 16 --steps 10 --warmup 4 --no-cpu-baseline 2>/dev/null | last > $OUT/bench_through_trainer_jasper10x5.json
+python3 bench.py --full --through-trainer --model jasper10x5 --batch 16 --dtype fp8 --steps 10 --warmup 4 --no-cpu-baseline 2>/dev/null | last > $OUT/bench_through_trainer_jasper10x5_fp8.json
 # SURVEY 8d's other CPU-baseline legs: the shipped default mid_layers: 1 at N = 32, Jasper at N = 2 (cpu_baseline of each line)
-python3 bench.py --mid-layers 1 --steps 20 --warmup 5 2>/dev/null | last > $OUT/bench_w2l_mid1_cpu_baseline.json
-python3 bench.py --model jasper10x5 --batch 16 --steps 6 --warmup 4 --no-trainer-leg 2>/dev/null | last > $OUT/bench_jasper10x5_cpu_baseline.json
+python3 bench.py --full --mid-layers 1 --steps 20 --warmup 5 2>/dev/null | last > $OUT/bench_w2l_mid1_cpu_baseline.json
+python3 bench.py --full --model jasper10x5 --batch 16 --steps 6 --warmup 4 --no-trainer-leg 2>/dev/null | last > $OUT/bench_jasper10x5_cpu_baseline.json
 fi
 ls $OUT | head -80

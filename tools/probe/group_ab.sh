@@ -1,5 +1,5 @@
 mkdir -p gpurun_out/r5e
-B="python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-live-traffic"
+B="python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-live-traffic"
 run() { # name, env...
   name=$1; shift
   env "$@" $B 2> gpurun_out/r5e/$name.err | tail -1 > gpurun_out/r5e/$name.json

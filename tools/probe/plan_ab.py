@@ -16,8 +16,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 
 def bench(cache, steps, extra=()):
     env = dict(os.environ, W2L_TUNE_CACHE=cache)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', str(steps), '--warmup', '5', '--defer-wgrad', '4',
-                          '--no-cpu-baseline', '--no-live-traffic', *extra], env=env, capture_output=True, text=True, timeout=900)
+    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--full', '--steps', str(steps), '--warmup', '5',
+                          '--defer-wgrad', '4', '--no-cpu-baseline', '--no-live-traffic', *extra],
+                         env=env, capture_output=True, text=True, timeout=900)
     for line in reversed(out.stdout.splitlines()):
         if line.startswith('{'):
             return json.loads(line)
