@@ -556,6 +556,37 @@ typedef struct { float* p; const float* g; float* m; int32_t n; int32_t pad_; } 
 int w2l_sgd_small_multi(const w2l_sgd_small_t* items_dev, int nitems, int max_n /* the largest items[i].n */, float lr,
                         float momentum, float weight_decay, int nesterov, void* stream);
 
+/* ---- gradient clipping (torch.nn.utils.clip_grad_norm_ / clip_grad_value_; Lightning's Trainer(gradient_clip_val=,
+ * gradient_clip_algorithm=) around the reference's fit, train.py:34-37), applied on read by the SGD updates ---------------
+ * Called by optim.FusedSGD.clip_grad_norm_ / clip_grad_value_ between backward() and step().
+ *
+ * clip: a float[4] device buffer owned by the caller: [W2L_CLIP_NORM] total norm, [W2L_CLIP_COEF] coefficient,
+ * [W2L_CLIP_BOUND] clamp bound.  w2l_grad_sqnorm_multi: the total norm of all gradients in the table (norm type 2, or inf
+ * if inf_norm != 0) in one launch of at most W2L_GNORM_BLOCKS blocks over the W2L_GNORM_CHUNK-element chunks of every row
+ * (float4 loads where a row is 16-byte aligned), per-block fp64 partials in `partials` (>= W2L_GNORM_BLOCKS doubles), and
+ * a one-block finalize that sums them in a fixed order (deterministic: no atomics) and writes
+ * norm, coef = min(1, max_norm / (norm + 1e-6)) in fp32 (torch's formula: an inf norm gives 0, a NaN norm NaN), bound = +inf;
+ * norm_out (optional): the norm once more (the 0-dim tensor clip_grad_norm_ returns).  Rows: g, n = element count,
+ * chunk0 = sum over the rows before of ceil(n / W2L_GNORM_CHUNK) (rows with n == 0 are left out); nchunks = the total.
+ * w2l_grad_clip_value: coef = 1, bound = clip_value (value mode, no reduction).
+ * w2l_sgd_pack_clip / w2l_sgd_small_multi_clip: w2l_sgd_pack / w2l_sgd_small_multi reading each gradient as
+ * clamp(g * coef, -bound, bound) (product rounded on its own, NaN kept) before the weight decay; with coef == 1 and
+ * bound == +inf bit-identical to the unclipped entry points.  The gradient buffers are not written. */
+#define W2L_CLIP_NORM 0
+#define W2L_CLIP_COEF 1
+#define W2L_CLIP_BOUND 2
+#define W2L_GNORM_CHUNK 8192
+#define W2L_GNORM_BLOCKS 2048
+typedef struct { const float* g; int64_t n; int64_t chunk0; } w2l_gnorm_item_t;
+int w2l_grad_sqnorm_multi(const w2l_gnorm_item_t* items_dev, int nitems, int64_t nchunks, int inf_norm, double* partials,
+                          float max_norm, float* clip, float* norm_out, void* stream);
+int w2l_grad_clip_value(float* clip, float clip_value, void* stream);
+int w2l_sgd_pack_clip(float* p, float* g, float* m, int first_step, float lr, float momentum, float weight_decay,
+                      int nesterov, int zero_grad, int Cout, int Cin, int Kw, void* w_fwd_hi, void* w_fwd_lo, void* w_dgr_hi,
+                      void* w_dgr_lo, void* w_fwd_q, void* w_dgr_q, float q_scale, const float* clip, void* stream);
+int w2l_sgd_small_multi_clip(const w2l_sgd_small_t* items_dev, int nitems, int max_n, float lr, float momentum,
+                             float weight_decay, int nesterov, const float* clip, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

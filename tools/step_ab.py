@@ -8,7 +8,11 @@ turns in blocks of steps (A B C A B C ...), so box-to-box and run-to-run drift (
 A variant is name=FLAG:value[,FLAG:value...] over the module-level switches of wav2letter_pytorch_amd.engine that are read at
 run time (FOLD_BN_FWD, STAT_SLOTS, DEFER_SPREAD, FOLD_BN_FINALIZE, FUSED_BN_REDUCE, DETERMINISTIC_WGRAD, DEALT_WGRAD) plus
 GROUPS:<W2L_WGRAD_GROUPS value> and DEFER:<k> (optim.FusedSGD.defer_wgrad).  'base' = the defaults.  Every variant gets
---settle steps after a switch (plans are measured then) before its block is timed."""
+--settle steps after a switch (plans are measured then) before its block is timed.
+
+Gradient clipping between backward() and step() (deferral 0 unless the variant names DEFER too): CLIP:<max_norm> =
+optim.FusedSGD.clip_grad_norm_ (fused, applied on read), TORCHCLIP:<max_norm> = torch.nn.utils.clip_grad_norm_ over p.grad
+(what a user had to do before), VCLIP:<value> = optim.FusedSGD.clip_grad_value_."""
 import argparse
 import os
 import statistics
@@ -51,12 +55,20 @@ def main():
     lens_arg = il if args.model == 'jasper10x5' else None
     opt = model.configure_optimizers()[0][0]
     opt.overlap = True
+    clip = {'mode': None, 'val': 0.0}
+    params = list(model.parameters())
 
     def step():
         opt.zero_grad(set_to_none=True)
         out, _ = model(x, lens_arg)
         loss = model.criterion(out.transpose(0, 1), tg_d, ol, tl_d)
         loss.backward()
+        if clip['mode'] == 'CLIP':
+            opt.clip_grad_norm_(clip['val'])
+        elif clip['mode'] == 'TORCHCLIP':
+            torch.nn.utils.clip_grad_norm_([p for p in params if p.grad is not None], clip['val'])
+        elif clip['mode'] == 'VCLIP':
+            opt.clip_grad_value_(clip['val'])
         opt.step()
         return loss
 
@@ -88,6 +100,10 @@ def main():
         fence()
         cfg = dict(defaults)
         cfg.update(over)
+        clip['mode'] = next((k for k in ('CLIP', 'TORCHCLIP', 'VCLIP') if k in over), None)
+        clip['val'] = float(over[clip['mode']]) if clip['mode'] else 0.0
+        if clip['mode'] and 'DEFER' not in over:
+            cfg['DEFER'] = 0
         for k, v in cfg.items():
             if k == 'GROUPS':                # explicit groups as 8.9.10|11.12.13 (',' and ';' separate flags and variants here)
                 os.environ['W2L_WGRAD_GROUPS'] = str(v).replace('.', ',').replace('|', ';')
@@ -98,6 +114,8 @@ def main():
                 # the eager step (same device time: tools/replay_ab.py), everything else the replayed one
                 from wav2letter_pytorch_amd import replay
                 replay.ENABLED = not str(v)
+            elif k in ('CLIP', 'TORCHCLIP', 'VCLIP'):
+                pass
             elif k == 'DEFER':
                 opt.defer_wgrad(model, [int(t) for t in str(v).split('|')] if '|' in str(v) else int(v))
             else:

@@ -164,9 +164,17 @@ _SIGNATURES = {
     'w2l_counter_add': (c_i, [c_p, c_i64, c_p]),
     'w2l_add_i64_multi': (c_i, [c_p, c_i, c_i64, c_p]),
     'w2l_sgd_small_multi': (c_i, [c_p, c_i, c_i, c_f, c_f, c_f, c_i, c_p]),
+    'w2l_sgd_small_multi_clip': (c_i, [c_p, c_i, c_i, c_f, c_f, c_f, c_i, c_p, c_p]),
+    'w2l_sgd_pack_clip': (c_i, [c_p, c_p, c_p, c_i, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_p,
+                                c_p]),
+    'w2l_grad_sqnorm_multi': (c_i, [c_p, c_i, c_i64, c_i, c_p, c_f, c_p, c_p, c_p]),
+    'w2l_grad_clip_value': (c_i, [c_p, c_f, c_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
+GNORM_CHUNK = 8192            # W2L_GNORM_CHUNK: elements per chunk of w2l_grad_sqnorm_multi (its table's chunk0 column)
+GNORM_BLOCKS = 2048           # W2L_GNORM_BLOCKS: the most blocks (= fp64 partials) it launches
+CLIP_NORM, CLIP_COEF, CLIP_BOUND = 0, 1, 2     # slots of the float[4] clip buffer
 
 
 class W2LError(RuntimeError):
@@ -229,6 +237,7 @@ TRACE_NAMES = {
     'w2l_bn_act_bwd_reduce_slots': 'bn_act_bwd_reduce_kernel', 'w2l_bn_act_bwd_apply_slots': 'bn_act_bwd_apply_kernel', 'w2l_bn_bwd_finalize': 'bn_bwd_finalize_kernel',
     'w2l_bn_act_bwd_apply': 'bn_act_bwd_apply_kernel', 'w2l_bn_act_bwd_apply_amax': 'bn_act_bwd_apply_kernel',
     'w2l_bn_act_bwd_apply_fin': 'bn_act_bwd_apply_kernel', 'w2l_sgd_pack': 'sgd_pack_kernel', 'w2l_pack_weights': 'pack_weights_kernel',
+    'w2l_sgd_pack_clip': 'sgd_pack_kernel', 'w2l_grad_sqnorm_multi': 'grad_norm_kernels',
     'w2l_ctc_loss': 'ctc_kernels', 'w2l_log_softmax_fwd': 'log_softmax_fwd', 'w2l_log_softmax_bwd': 'log_softmax_bwd',
     'w2l_nct_to_ntc': 'nct_to_ntc_kernel', 'w2l_pad_cast': 'pad_cast_kernel', 'w2l_quantize_e4m3': 'quantize_e4m3',
     'w2l_quantize_e4m3_dyn': 'quantize_e4m3_dyn', 'w2l_dwconv_fwd': 'dw_fwd_kernel', 'w2l_dwconv_dgrad': 'dw_dgrad_kernel',

@@ -263,6 +263,25 @@ class ConvCTCASR(_Base):
         scheduler = instantiate(self._cfg.scheduler, optimizer=optimizer)
         return [optimizer], [scheduler]
 
+    def configure_gradient_clipping(self, optimizer, *args, **kwargs):
+        """Lightning's hook behind Trainer(gradient_clip_val=, gradient_clip_algorithm=), called between backward() and step().
+        Both signatures: (optimizer, optimizer_idx, gradient_clip_val, gradient_clip_algorithm) of Lightning 1.x and
+        (optimizer, gradient_clip_val, gradient_clip_algorithm) of 2.x, positional or by keyword.  optim.FusedSGD clips on
+        the device, applied by its next step() as the update reads each gradient (p.grad keeps the unclipped values); any
+        other optimizer gets torch.nn.utils.clip_grad_norm_ / clip_grad_value_.  A value of None or 0 clips nothing."""
+        kwargs.pop('optimizer_idx', None)
+        named = [k for k in ('gradient_clip_val', 'gradient_clip_algorithm') if k in kwargs]
+        if len(args) + len(named) > 2:                  # Lightning 1.x: the optimizer index comes first
+            args = args[1:]
+        vals = dict(zip([k for k in ('gradient_clip_val', 'gradient_clip_algorithm') if k not in kwargs], args))
+        vals.update(kwargs)
+        clip_val = vals.get('gradient_clip_val')
+        if not clip_val:
+            return None
+        algorithm = getattr(vals.get('gradient_clip_algorithm'), 'value', vals.get('gradient_clip_algorithm')) or 'norm'
+        from .optim import clip_gradients
+        return clip_gradients(optimizer, float(clip_val), algorithm, model=self)
+
     def _device_batch(self, inputs):
         """the spectrograms on the model's device without stalling the host: a host tensor that is not page-locked is staged
         through one of two pinned buffers owned by the module (an H2D copy from pageable memory makes the HIP runtime wait

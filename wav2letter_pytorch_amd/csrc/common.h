@@ -33,6 +33,22 @@ __device__ __forceinline__ void f32_split_bf16(float f, bf16_raw& hi, bf16_raw& 
     lo = f32_to_bf16_bits(f - bf16_bits_to_f32(hi));
 }
 
+// ---- gradient clipping applied on read (w2l_grad_sqnorm_multi / w2l_grad_clip_value write the buffer; the _clip update
+// kernels read it).  Slots of the float[4] clip buffer, as in include/w2l_hip.h. ----
+#ifndef W2L_CLIP_NORM
+#define W2L_CLIP_NORM 0
+#define W2L_CLIP_COEF 1
+#define W2L_CLIP_BOUND 2
+#endif
+// clamp(g * coef, -bound, bound) in torch's order (clip_grad_norm_ multiplies, clip_grad_value_ clamps).  The product is rounded
+// on its own, so that a caller's following `g + wd * p` contracts exactly as it does without clipping; comparisons instead of
+// fminf / fmaxf keep a NaN a NaN (torch.clamp propagates it).
+__device__ __forceinline__ float clip_grad_read(float g, float coef, float bound) {
+    g = __fmul_rn(g, coef);
+    g = g < -bound ? -bound : g;
+    return g > bound ? bound : g;
+}
+
 // ---- error reporting across the C ABI (no exceptions, no exit) ----
 void w2l_set_error(const char* fmt, ...);
 #define W2L_CHECK_ARG(cond, ...)                 \

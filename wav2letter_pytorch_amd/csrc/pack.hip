@@ -57,19 +57,32 @@ __device__ __forceinline__ uint8_t quant1_e4m3(float v) {
     return (uint8_t)(__builtin_amdgcn_cvt_pk_fp8_f32(v, 0.f, 0, false) & 0xFF);
 }
 
+// CLIP (w2l_sgd_pack_clip): the gradient is read as clamp(g * coef, -bound, bound) -- torch.nn.utils.clip_grad_norm_ /
+// clip_grad_value_ applied on read, before the weight decay, in torch's order.  The product is rounded on its own
+// (__fmul_rn: no contraction into the decay's FMA), so coef == 1 and bound == +inf leave the update bit-identical to CLIP off;
+// the clamp is written with comparisons so that a NaN gradient (or a NaN coefficient) stays NaN, as torch.clamp keeps it.
+template <bool CLIP>
 __global__ void sgd_pack_kernel(float* p, float* g, float* m, int first, float lr, float mu, float wd,
                                 int nesterov, int zero_grad, int Cout, int Cin, int Kw, bf16_raw* fwd_hi, bf16_raw* fwd_lo,
-                                bf16_raw* dgr_hi, bf16_raw* dgr_lo, uint8_t* fwd_q, uint8_t* dgr_q, float q_scale) {
+                                bf16_raw* dgr_hi, bf16_raw* dgr_lo, uint8_t* fwd_q, uint8_t* dgr_q, float q_scale,
+                                const float* clip) {
     __shared__ float tile[32][33];
     const int tx = threadIdx.x, ty = threadIdx.y;
     const int ci0 = blockIdx.x * 32, co0 = blockIdx.y * 32, kw = blockIdx.z;
+    float coef = 1.f, bound = 0.f;
+    if constexpr (CLIP) {
+        coef = clip[W2L_CLIP_COEF];
+        bound = clip[W2L_CLIP_BOUND];
+    }
     for (int j = ty; j < 32; j += 8) {
         const int co = co0 + j, ci = ci0 + tx;
         float v = 0.f;
         if (co < Cout && ci < Cin) {
             const int64_t off = ((int64_t)kw * Cout + co) * Cin + ci;
             float pv = p[off];
-            float gv = g[off] + wd * pv;
+            float gv = g[off];
+            if constexpr (CLIP) gv = clip_grad_read(gv, coef, bound);
+            gv = gv + wd * pv;
             if (zero_grad) g[off] = 0.f;       // the buffer comes back as the next step's (split-K, atomically accumulated) dW
             float mv = first ? gv : mu * m[off] + gv;
             m[off] = mv;
@@ -262,9 +275,25 @@ extern "C" int w2l_sgd_pack(float* p, float* g, float* m, int first_step, float 
     W2L_CHECK_ARG(Cout > 0 && Cin > 0 && Kw > 0, "sgd_pack: bad sizes");
     W2L_CHECK_ARG(!(w_fwd_lo && !w_fwd_hi) && !(w_dgr_lo && !w_dgr_hi), "sgd_pack: lo without hi");
     dim3 grid((Cin + 31) / 32, (Cout + 31) / 32, Kw), block(32, 8);
-    hipLaunchKernelGGL(sgd_pack_kernel, grid, block, 0, (hipStream_t)stream, p, g, m, first_step, lr, momentum,
+    hipLaunchKernelGGL(sgd_pack_kernel<false>, grid, block, 0, (hipStream_t)stream, p, g, m, first_step, lr, momentum,
                        weight_decay, nesterov, zero_grad, Cout, Cin, Kw, (bf16_raw*)w_fwd_hi, (bf16_raw*)w_fwd_lo,
-                       (bf16_raw*)w_dgr_hi, (bf16_raw*)w_dgr_lo, (uint8_t*)w_fwd_q, (uint8_t*)w_dgr_q, q_scale);
+                       (bf16_raw*)w_dgr_hi, (bf16_raw*)w_dgr_lo, (uint8_t*)w_fwd_q, (uint8_t*)w_dgr_q, q_scale, nullptr);
+    W2L_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int w2l_sgd_pack_clip(float* p, float* g, float* m, int first_step, float lr, float momentum,
+                                 float weight_decay, int nesterov, int zero_grad, int Cout, int Cin, int Kw, void* w_fwd_hi,
+                                 void* w_fwd_lo, void* w_dgr_hi, void* w_dgr_lo, void* w_fwd_q, void* w_dgr_q, float q_scale,
+                                 const float* clip, void* stream) {
+    W2L_CHECK_ARG((!w_fwd_q && !w_dgr_q) || (q_scale > 0.f && w_fwd_hi && w_dgr_hi), "sgd_pack_clip: e4m3 operands need a scale");
+    W2L_CHECK_ARG(p && g && m && clip, "sgd_pack_clip: null pointer");
+    W2L_CHECK_ARG(Cout > 0 && Cin > 0 && Kw > 0, "sgd_pack_clip: bad sizes");
+    W2L_CHECK_ARG(!(w_fwd_lo && !w_fwd_hi) && !(w_dgr_lo && !w_dgr_hi), "sgd_pack_clip: lo without hi");
+    dim3 grid((Cin + 31) / 32, (Cout + 31) / 32, Kw), block(32, 8);
+    hipLaunchKernelGGL(sgd_pack_kernel<true>, grid, block, 0, (hipStream_t)stream, p, g, m, first_step, lr, momentum,
+                       weight_decay, nesterov, zero_grad, Cout, Cin, Kw, (bf16_raw*)w_fwd_hi, (bf16_raw*)w_fwd_lo,
+                       (bf16_raw*)w_dgr_hi, (bf16_raw*)w_dgr_lo, (uint8_t*)w_fwd_q, (uint8_t*)w_dgr_q, q_scale, clip);
     W2L_CHECK_LAUNCH();
     return 0;
 }

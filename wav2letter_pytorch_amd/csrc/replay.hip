@@ -94,12 +94,21 @@ __global__ void add_i64_multi_kernel(long long* const* table, int n, long long d
 // grid = (items, chunks of SGD_SMALL_CHUNK elements): most items are one chunk (a few hundred channels); the classifier weight
 // (29 x 1024) is fifteen -- one block walking it alone took 96 us on the caller's stream at every step boundary
 constexpr int SGD_SMALL_CHUNK = 2048;
-__global__ __launch_bounds__(256) void sgd_small_multi_kernel(const w2l_sgd_small_t* items, float lr, float mu, float wd, int nesterov) {
+// CLIP (w2l_sgd_small_multi_clip): the gradient is read through clip_grad_read (common.h), as in w2l_sgd_pack_clip
+template <bool CLIP>
+__global__ __launch_bounds__(256) void sgd_small_multi_kernel(const w2l_sgd_small_t* items, float lr, float mu, float wd, int nesterov,
+                                                              const float* clip) {
     const w2l_sgd_small_t it = items[blockIdx.x];
     const int lo = blockIdx.y * SGD_SMALL_CHUNK, hi = min(it.n, lo + SGD_SMALL_CHUNK);
+    float coef = 1.f, bound = 0.f;
+    if constexpr (CLIP) {
+        coef = clip[W2L_CLIP_COEF];
+        bound = clip[W2L_CLIP_BOUND];
+    }
     for (int i = lo + threadIdx.x; i < hi; i += 256) {
         float pv = it.p[i];
         float gv = it.g[i];
+        if constexpr (CLIP) gv = clip_grad_read(gv, coef, bound);
         if (wd != 0.f) gv += wd * pv;
         float step = gv;
         if (it.m != nullptr) {
@@ -139,8 +148,20 @@ extern "C" int w2l_sgd_small_multi(const w2l_sgd_small_t* items_dev, int nitems,
     W2L_CHECK_ARG(max_n >= 0 && max_n <= (1 << 26), "sgd_small_multi: max_n (the largest item's element count) out of range");
     if (nitems <= 0 || max_n == 0) return 0;
     const int chunks = (max_n + SGD_SMALL_CHUNK - 1) / SGD_SMALL_CHUNK;
-    hipLaunchKernelGGL(sgd_small_multi_kernel, dim3(nitems, chunks), dim3(256), 0, (hipStream_t)stream, items_dev, lr, momentum,
-                       weight_decay, nesterov);
+    hipLaunchKernelGGL(sgd_small_multi_kernel<false>, dim3(nitems, chunks), dim3(256), 0, (hipStream_t)stream, items_dev, lr,
+                       momentum, weight_decay, nesterov, nullptr);
+    W2L_CHECK_LAUNCH();
+    return 0;
+}
+extern "C" int w2l_sgd_small_multi_clip(const w2l_sgd_small_t* items_dev, int nitems, int max_n, float lr, float momentum,
+                                        float weight_decay, int nesterov, const float* clip, void* stream) {
+    W2L_CHECK_ARG(items_dev != nullptr || nitems == 0, "sgd_small_multi_clip: null table");
+    W2L_CHECK_ARG(clip != nullptr, "sgd_small_multi_clip: null clip buffer");
+    W2L_CHECK_ARG(max_n >= 0 && max_n <= (1 << 26), "sgd_small_multi_clip: max_n (the largest item's element count) out of range");
+    if (nitems <= 0 || max_n == 0) return 0;
+    const int chunks = (max_n + SGD_SMALL_CHUNK - 1) / SGD_SMALL_CHUNK;
+    hipLaunchKernelGGL(sgd_small_multi_kernel<true>, dim3(nitems, chunks), dim3(256), 0, (hipStream_t)stream, items_dev, lr,
+                       momentum, weight_decay, nesterov, clip);
     W2L_CHECK_LAUNCH();
     return 0;
 }
@@ -184,6 +205,7 @@ struct Entry {
 const Entry kEntries[] = {
     W2L_E(w2l_event_record), W2L_E(w2l_stream_wait_event), W2L_E(w2l_stream_wait_stream), W2L_E(w2l_fill_zero),
     W2L_E(w2l_pad_vec_f32), W2L_E(w2l_counter_add), W2L_E(w2l_add_i64_multi), W2L_E(w2l_sgd_small_multi),
+    W2L_E(w2l_sgd_small_multi_clip), W2L_E(w2l_sgd_pack_clip), W2L_E(w2l_grad_sqnorm_multi), W2L_E(w2l_grad_clip_value),
     W2L_E(w2l_conv_stats_mode), W2L_E(w2l_wgrad_deterministic),
     W2L_E(w2l_pack_weights), W2L_E(w2l_sgd_pack), W2L_E(w2l_novograd_pack), W2L_E(w2l_nct_to_ntc), W2L_E(w2l_pad_cast),
     W2L_E(w2l_conv1d_igemm), W2L_E(w2l_conv1d_igemm_ws), W2L_E(w2l_conv1d_igemm_fp8), W2L_E(w2l_conv1d_dgrad_bnreduce_ws),

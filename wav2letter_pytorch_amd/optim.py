@@ -17,7 +17,14 @@ optimizer's fused update of that weight (engine.StackEngine.flush_deferred).  Th
 pass and the last of the forward pass, so their gradients are the ones with slack; launched beside the forward they give
 the matrix cores work while the forward's own BatchNorm / CTC kernels run.  One optimizer step per batch, as before: a
 layer's forward convolution waits for the event behind its update.  ``p.grad`` of those weights stays ``None`` (the update
-consumes the gradient directly); ``join()`` flushes whatever is pending."""
+consumes the gradient directly); ``join()`` flushes whatever is pending.
+
+``clip_grad_norm_(max_norm)`` / ``clip_grad_value_(v)`` between backward() and step(): torch.nn.utils.clip_grad_norm_ /
+clip_grad_value_ with the coefficient computed on the device (w2l_grad_sqnorm_multi: every gradient read once, in one launch)
+and applied by the NEXT step()'s update kernels as they read each gradient (w2l_sgd_pack_clip, w2l_sgd_small_multi_clip): no
+host read, no pass that rewrites the gradients -- ``p.grad`` keeps the unclipped values.  Held-back weight gradients are
+computed at the clip call (they belong in the norm).  Anything the fused path does not cover takes torch's own functions
+(``clip_gradients``)."""
 from __future__ import annotations
 
 import os
@@ -28,6 +35,53 @@ import torch
 from . import _lib
 from . import engine as E
 from ._lib import check, lib, ptr, stream_ptr
+
+
+def _dense(t: torch.Tensor) -> bool:
+    """do the elements of ``t`` fill a dense block of memory (in any dimension order)?"""
+    if t.is_contiguous():
+        return True
+    expect = 1
+    for st, n in sorted((st, n) for st, n in zip(t.stride(), t.shape) if n > 1):
+        if st != expect:
+            return False
+        expect *= n
+    return True
+
+
+def materialize_held_back(engines, opt=None):
+    """compute now, on the current stream, the weight gradients that a backward pass held back (FusedSGD.defer_wgrad) and
+    that no step() has consumed yet, into ``p.grad`` -- and drop their records, so that nothing applies them a second time"""
+    for eng in engines:
+        dopt = eng.deferred if opt is None else opt
+        recs = [r for r in eng._deferred if not (dopt is not None and dopt.stepped(r['token']))]
+        if recs:
+            eng._deferred = [r for r in eng._deferred if not any(r is q for q in recs)]
+            eng._materialize(recs)
+
+
+def clip_gradients(optimizer, clip_val, algorithm='norm', model=None, norm_type=2.0):
+    """Lightning's gradient clipping (Trainer(gradient_clip_val=, gradient_clip_algorithm=)) for any optimizer: FusedSGD takes
+    its fused path (clip_grad_norm_ / clip_grad_value_), every other optimizer torch.nn.utils.clip_grad_norm_ /
+    clip_grad_value_ over its parameters' gradients, after the held-back weight gradients of ``model``'s step engine (if any)
+    have been computed.  Returns the total norm (norm mode) or None."""
+    opt = getattr(optimizer, '_optimizer', optimizer)           # (a Lightning optimizer wrapper)
+    algorithm = getattr(algorithm, 'value', algorithm)           # (Lightning's GradClipAlgorithmType)
+    if algorithm not in ('norm', 'value'):
+        raise ValueError(f'gradient_clip_algorithm {algorithm!r} is not supported: use "norm" or "value"')
+    if isinstance(opt, FusedSGD):
+        return opt.clip_grad_norm_(clip_val, norm_type) if algorithm == 'norm' else opt.clip_grad_value_(clip_val)
+    hit = model.__dict__.get('_engine_cache') if model is not None else None
+    if hit is not None:
+        materialize_held_back([hit[1]])
+    return _torch_clip([p for g in opt.param_groups for p in g['params'] if p.grad is not None], clip_val, algorithm, norm_type)
+
+
+def _torch_clip(params, clip_val, algorithm, norm_type=2.0):
+    if algorithm == 'norm':
+        return torch.nn.utils.clip_grad_norm_(params, clip_val, norm_type=norm_type)
+    torch.nn.utils.clip_grad_value_(params, clip_val)
+    return None
 
 
 def _is_tap_major(t: torch.Tensor) -> bool:
@@ -88,9 +142,11 @@ class FusedSGD(torch.optim.SGD):
 
     def zero_grad(self, set_to_none: bool = True):
         """torch's zero_grad, plus: weight gradients held back by a backward pass that no step() followed are dropped with
-        the rest (a skipped step -- non-finite loss guard, manual skip -- must not leak into the next one)"""
+        the rest (a skipped step -- non-finite loss guard, manual skip -- must not leak into the next one), and so is an armed
+        gradient clip"""
         for eng in self._engines():
             eng.drop_unstepped()
+        self.__dict__.pop('_w2l_clip_arm', None)          # (so is a clip call whose step was skipped)
         return super().zero_grad(set_to_none=set_to_none)
 
     def accepts(self, p) -> bool:
@@ -153,6 +209,85 @@ class FusedSGD(torch.optim.SGD):
         self.join()
         return super().state_dict()
 
+    # ------------------------------------------------------------------ gradient clipping
+    @torch.no_grad()
+    def clip_grad_norm_(self, max_norm, norm_type=2.0):
+        """torch.nn.utils.clip_grad_norm_ over this optimizer's gradients, between backward() and step(): returns the total
+        norm (a 0-dim device tensor, no host sync) and arms the NEXT step() to apply min(1, max_norm / (norm + 1e-6)) as its
+        update kernels read the gradients (``p.grad`` itself is left unclipped).  Held-back weight gradients are computed now.
+        Norm types other than 2 and inf, and gradients the fused path does not take, go through torch's function."""
+        norm_type = float(norm_type)
+        grads = self._clip_prepare()
+        if grads is None or norm_type not in (2.0, float('inf')):
+            return _torch_clip(self._grad_params(), max_norm, 'norm', norm_type)
+        st = self._clip_state(grads[0].device)
+        table, nitems, nchunks = self._norm_table(st, grads)
+        out = torch.empty((), dtype=torch.float32, device=grads[0].device)
+        check(lib.w2l_grad_sqnorm_multi(ptr(table), nitems, nchunks, int(norm_type != 2.0), ptr(st['partials']), float(max_norm),
+                                        ptr(st['buf']), ptr(out), stream_ptr()), 'w2l_grad_sqnorm_multi')
+        self.__dict__['_w2l_clip_arm'] = 'norm'
+        return out
+
+    @torch.no_grad()
+    def clip_grad_value_(self, clip_value):
+        """torch.nn.utils.clip_grad_value_ on read: arms the NEXT step() to clamp every gradient to [-clip_value, clip_value]
+        as its update kernels read it (``p.grad`` is left as it is)"""
+        grads = self._clip_prepare()
+        if grads is None:
+            return _torch_clip(self._grad_params(), clip_value, 'value')
+        st = self._clip_state(grads[0].device)
+        check(lib.w2l_grad_clip_value(ptr(st['buf']), float(clip_value), stream_ptr()), 'w2l_grad_clip_value')
+        self.__dict__['_w2l_clip_arm'] = 'value'
+        return None
+
+    def _grad_params(self):
+        return [p for g in self.param_groups for p in g['params'] if p.grad is not None]
+
+    def _clip_prepare(self):
+        """the gradients of the next step, complete: held-back weight gradients computed, the updates of the last step that
+        still read the clip buffer done.  -> their list, or None if the fused path cannot take them"""
+        self.__dict__.pop('_w2l_clip_arm', None)
+        materialize_held_back(self._engines(), self)
+        side = self._side_state()
+        if side['pending'] and side['stream'] is not None:
+            _lib.stream_wait_stream(_lib.raw_stream(), side['stream'])
+        grads = [p.grad for p in self._grad_params()]
+        if (not grads or torch.cuda.is_current_stream_capturing()
+                or not all(g.is_cuda and g.dtype == torch.float32 and g.device == grads[0].device and not g.is_sparse and _dense(g)
+                           for g in grads)):
+            return None
+        return grads
+
+    def _clip_state(self, dev):
+        st = self.__dict__.get('_w2l_clip')
+        if st is None or st['buf'].device != dev:
+            st = self.__dict__['_w2l_clip'] = {
+                'buf': torch.tensor([0.0, 1.0, float('inf'), 0.0], dtype=torch.float32, device=dev),
+                'partials': torch.empty(_lib.GNORM_BLOCKS, dtype=torch.float64, device=dev), 'tables': {}}
+        return st
+
+    def _norm_table(self, st, grads):
+        """the device table of w2l_grad_sqnorm_multi (g, n, first chunk), built once per set of gradient addresses (a
+        replayed step's static gradient buffers: one table per record set)"""
+        rows = tuple((g.data_ptr(), g.numel()) for g in grads if g.numel() > 0)
+        hit = st['tables'].get(rows)
+        if hit is None:
+            if len(st['tables']) > 8:
+                st['tables'].clear()
+            flat, c0 = [], 0
+            for gp, n in rows:
+                flat += [gp, n, c0]
+                c0 += -(-n // _lib.GNORM_CHUNK)
+            table = torch.tensor(flat, dtype=torch.int64).to(grads[0].device) if rows else None
+            hit = st['tables'][rows] = (table, len(rows), c0)
+        return hit
+
+    def _clip_signature(self):
+        """what a recorded optimizer phase depends on besides the hyper-parameters: armed or not, in which mode, and which
+        buffer it reads (max_norm / clip_value only reach the buffer: changing them needs no new record)"""
+        mode = self.__dict__.get('_w2l_clip_arm')
+        return None if mode is None else (mode, self.__dict__['_w2l_clip']['buf'].data_ptr())
+
     @torch.no_grad()
     def step(self, closure=None):
         loss = None
@@ -161,12 +296,16 @@ class FusedSGD(torch.optim.SGD):
                 loss = closure()
         # the gradients of a recorded / replayed backward pass: the step is replayed as ONE w2l_replay call, or recorded now
         from . import replay
-        if replay._last_backward[0] is not None and replay.optimizer_step(self, self._step_eager):
-            return loss
-        self._step_eager()
+        try:
+            if replay._last_backward[0] is not None and replay.optimizer_step(self, self._step_eager):
+                return loss
+            self._step_eager()
+        finally:
+            self.__dict__.pop('_w2l_clip_arm', None)          # clipping is armed for one step
         return loss
 
     def _step_eager(self):
+        clip = self.__dict__['_w2l_clip']['buf'] if self.__dict__.get('_w2l_clip_arm') else None
         rp_hit = None
         for eng in self._engines():
             rp_hit = eng.__dict__.get('_replayer') or rp_hit
@@ -197,12 +336,12 @@ class FusedSGD(torch.optim.SGD):
                 else:
                     rest.append(p)
             if rest:
-                self._plain(rest, lr, mu, wd, nesterov, dampening, maximize)
+                self._plain(rest, lr, mu, wd, nesterov, dampening, maximize, clip)
             if not fused:
                 continue
             if not self.overlap:
                 for p, g in fused:
-                    self._fused_conv(p, g, lr, mu, wd, nesterov)
+                    self._fused_conv(p, g, lr, mu, wd, nesterov, clip)
                 continue
             dev = fused[0][0].device
             if st['stream'] is None or st['stream'].device != dev:
@@ -213,7 +352,7 @@ class FusedSGD(torch.optim.SGD):
             _lib.stream_wait_stream(side, _lib.raw_stream())     # gradients (wgrad join, all-reduce) are complete there
             with torch.cuda.stream(side):
                 for p, g in fused:               # parameter order = forward order: layer 0's event fires first
-                    pk = self._fused_conv(p, g, lr, mu, wd, nesterov)
+                    pk = self._fused_conv(p, g, lr, mu, wd, nesterov, clip)
                     pk.ready = E.weight_event(p)
                     pk.ready.record(side)
                     st['held'].append(g)         # zero_grad() must not hand this memory back while the kernel reads it
@@ -222,7 +361,7 @@ class FusedSGD(torch.optim.SGD):
             if self._release_held not in E.AFTER_FORWARD:
                 E.AFTER_FORWARD.append(self._release_held)
 
-    def _fused_conv(self, p, g, lr, mu, wd, nesterov):
+    def _fused_conv(self, p, g, lr, mu, wd, nesterov, clip=None):
         state = self.state[p]
         first = 'momentum_buffer' not in state or state['momentum_buffer'] is None
         if first:
@@ -258,10 +397,13 @@ class FusedSGD(torch.optim.SGD):
         f8 = p.__dict__.get('_w2l_fp8')
         if f8 is not None and (precise or f8['q'].shape != fwd_hi.shape or f8['q'].device != dev):
             f8 = None
-        check(lib.w2l_sgd_pack(ptr(p), ptr(g), ptr(buf), int(first), float(lr), float(mu), float(wd), int(nesterov),
-                               int(recycle), cout, cin, kw, ptr(fwd_hi), ptr(fwd_lo), ptr(dgr_hi), ptr(dgr_lo),
-                               ptr(f8['q']) if f8 else None, ptr(f8['qd']) if f8 else None, f8['scale'] if f8 else 1.0,
-                               stream_ptr()), 'w2l_sgd_pack')
+        args = (ptr(p), ptr(g), ptr(buf), int(first), float(lr), float(mu), float(wd), int(nesterov), int(recycle), cout, cin, kw,
+                ptr(fwd_hi), ptr(fwd_lo), ptr(dgr_hi), ptr(dgr_lo), ptr(f8['q']) if f8 else None, ptr(f8['qd']) if f8 else None,
+                f8['scale'] if f8 else 1.0)
+        if clip is None:
+            check(lib.w2l_sgd_pack(*args, stream_ptr()), 'w2l_sgd_pack')
+        else:                                                        # (gradient clipping armed: clip_grad_norm_ / _value_)
+            check(lib.w2l_sgd_pack_clip(*args, ptr(clip), stream_ptr()), 'w2l_sgd_pack_clip')
         if recycle:
             p._w2l_dw_zeroed = g.permute(2, 0, 1)                    # the dense [Kw, Cout, Cin] storage of g
         torch.autograd.graph.increment_version(p)                    # p changed through its raw pointer
@@ -273,7 +415,7 @@ class FusedSGD(torch.optim.SGD):
             f8['age'] += 1
         return pk
 
-    def _small_multi(self, params, lr, mu, wd, nesterov) -> bool:
+    def _small_multi(self, params, lr, mu, wd, nesterov, clip=None) -> bool:
         """torch.optim.SGD's update of all the small parameters (conv biases, BatchNorm gamma / beta) in ONE launch
         (w2l_sgd_small_multi) instead of five torch._foreach_* calls over ~60 tensors: a device table of (p, g, m, n) built once
         per set of addresses (``params``: those _multi_ok admits); an entry point, so a recorded launch list replays it."""
@@ -294,8 +436,12 @@ class FusedSGD(torch.optim.SGD):
             for pp, gp, mp, n in rows:
                 flat += [pp, gp, mp, n]                    # w2l_sgd_small_t: three pointers, then {int32 n, int32 pad} = one int64 < 2^31
             table = cache[key] = torch.tensor(flat, dtype=torch.int64).to(params[0].device)
-        check(lib.w2l_sgd_small_multi(ptr(table), len(rows), max(r[3] for r in rows), float(lr), float(mu), float(wd), int(nesterov),
-                                      stream_ptr()), 'w2l_sgd_small_multi')
+        if clip is None:
+            check(lib.w2l_sgd_small_multi(ptr(table), len(rows), max(r[3] for r in rows), float(lr), float(mu), float(wd),
+                                          int(nesterov), stream_ptr()), 'w2l_sgd_small_multi')
+        else:
+            check(lib.w2l_sgd_small_multi_clip(ptr(table), len(rows), max(r[3] for r in rows), float(lr), float(mu), float(wd),
+                                               int(nesterov), ptr(clip), stream_ptr()), 'w2l_sgd_small_multi_clip')
         for p in params:
             torch.autograd.graph.increment_version(p)
         return True
@@ -317,18 +463,21 @@ class FusedSGD(torch.optim.SGD):
                 return False
         return True
 
-    def _plain(self, params, lr, mu, wd, nesterov, dampening, maximize):
+    def _plain(self, params, lr, mu, wd, nesterov, dampening, maximize, clip=None):
         # (not under hipGraph capture: the gradient addresses -- and with them the table -- are the capture's own, and building
         # the table is a host-to-device copy from pageable memory, which a capturing stream refuses)
         if not maximize and dampening == 0 and params and not torch.cuda.is_current_stream_capturing():
             multi = [p for p in params if self._multi_ok(p, mu)]
-            if multi and self._small_multi(multi, lr, mu, wd, nesterov):
+            if multi and self._small_multi(multi, lr, mu, wd, nesterov, clip):
                 if len(multi) == len(params):
                     return
                 taken = set(id(p) for p in multi)
                 params = [p for p in params if id(p) not in taken]
         _lib.poison('torch foreach update of the small parameters')
         grads = [p.grad for p in params]
+        if clip is not None:            # the armed coefficient and bound, read on the device (no host sync)
+            coef, bound = clip[_lib.CLIP_COEF], clip[_lib.CLIP_BOUND]
+            grads = [torch.clamp(g, min=-bound, max=bound) for g in torch._foreach_mul(grads, coef)]
         if maximize:
             grads = torch._foreach_neg(grads)
         if wd != 0:

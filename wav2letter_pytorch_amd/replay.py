@@ -137,6 +137,7 @@ class RecordSet:
         self.grads = None                # [(parameter, static gradient tensor)] in engine.parameters() order (None: no gradient)
         self.deferred = []               # the held-back weight-gradient records of this set's backward pass
         self.O_ptrs = None
+        self.O_spare = None              # the phase O of the other signature's clipping mode (armed / not): (O, O_sig, O_ptrs, lease_O, pool_O)
 
     def ensure_pool(self):
         if self.pool is None:
@@ -159,8 +160,9 @@ class Group:
 
 
 def opt_signature(opt):
+    clip = opt._clip_signature() if hasattr(opt, '_clip_signature') else None        # armed gradient clipping: its own phase O
     return tuple((g['lr'], g['momentum'], g['weight_decay'], g['nesterov'], g['dampening'], g.get('maximize', False))
-                 for g in opt.param_groups)
+                 for g in opt.param_groups) + (clip,)
 
 
 class StepReplayer:
@@ -597,6 +599,11 @@ def optimizer_step(opt, eager_body) -> bool:
     if any(id(p) not in mine for p, _ in rset.grads):
         return False
     sig = (opt_signature(opt), bool(opt.overlap), _lib.raw_stream())
+    if rset.O_sig != sig and rset.O_spare is not None and rset.O_spare[1] == sig:
+        # an armed (gradient clipping) and an unarmed optimizer step each keep a phase O of their own
+        cur = (rset.O, rset.O_sig, rset.O_ptrs, rset.lease_O, rset.pool_O)
+        rset.O, rset.O_sig, rset.O_ptrs, rset.lease_O, rset.pool_O = rset.O_spare
+        rset.O_spare = cur if cur[0] is not None else None
     if rset.O is not None and rset.O_sig == sig:
         for (p, gbuf), want in zip(rset.grads, rset.O_ptrs):
             have = p.grad.data_ptr() if p.grad is not None else 0
@@ -611,6 +618,9 @@ def optimizer_step(opt, eager_body) -> bool:
         STATS['replayed_O'] += 1
         return True
     # record: the eager body under the recorder, allocating from a pool of the phase's own
+    if rset.O is not None and rset.O_sig is not None and rset.O_sig[0][-1:] != sig[0][-1:]:
+        rset.O_spare = (rset.O, rset.O_sig, rset.O_ptrs, rset.lease_O, rset.pool_O)     # (the other clipping mode's phase)
+        rset.O = rset.O_sig = None
     rset.lease_O = _Lease()
     rset.pool_O = new_pool(rset.lease_O)
     with torch.cuda.use_mem_pool(rset.pool_O), _lib.Recorder() as rec:

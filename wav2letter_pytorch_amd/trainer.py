@@ -39,13 +39,21 @@ class _EpochMean:
 class Trainer:
     def __init__(self, default_root_dir: str = '.', max_epochs: int = 5, max_steps: Optional[int] = None, gpus=0,
                  log_every_n_steps: int = 50, enable_checkpointing: bool = True, resume_from_checkpoint: Optional[str] = None,
-                 **unused):
+                 gradient_clip_val=None, gradient_clip_algorithm: Optional[str] = 'norm', **unused):
         self.default_root_dir = default_root_dir
         self.max_epochs = max_epochs
         self.max_steps = max_steps
         self.log_every_n_steps = log_every_n_steps
         self.enable_checkpointing = enable_checkpointing
         self.resume_from_checkpoint = resume_from_checkpoint
+        # Lightning's gradient clipping: model.configure_gradient_clipping between loss.backward() and opt.step()
+        if gradient_clip_val is not None and (isinstance(gradient_clip_val, bool) or float(gradient_clip_val) < 0):
+            raise ValueError(f'gradient_clip_val must be a non-negative number or None, got {gradient_clip_val!r}')
+        algorithm = getattr(gradient_clip_algorithm, 'value', gradient_clip_algorithm) or 'norm'
+        if algorithm not in ('norm', 'value'):
+            raise ValueError(f'gradient_clip_algorithm {gradient_clip_algorithm!r} is not supported: use "norm" or "value"')
+        self.gradient_clip_val = float(gradient_clip_val) if gradient_clip_val else None
+        self.gradient_clip_algorithm = algorithm
         self.global_step = 0
         self.current_epoch = 0
         self.logged = []
@@ -82,6 +90,14 @@ class Trainer:
         self.global_step = int(ck.get('global_step', 0))
         return int(ck.get('epoch', -1)) + 1          # the checkpoint is written at the END of its epoch
 
+    def _clip(self, model, opt):
+        hook = getattr(model, 'configure_gradient_clipping', None)
+        if hook is not None:
+            hook(opt, gradient_clip_val=self.gradient_clip_val, gradient_clip_algorithm=self.gradient_clip_algorithm)
+        else:
+            from .optim import clip_gradients
+            clip_gradients(opt, self.gradient_clip_val, self.gradient_clip_algorithm, model=model)
+
     # ------------------------------------------------------------------ loop
     def fit(self, model, train_dataloader, val_dataloader=None, ckpt_path: Optional[str] = None):
         if not torch.cuda.is_available():
@@ -102,17 +118,22 @@ class Trainer:
             # While a gradient is held back ``p.grad`` of that weight is None at step() ("Deferred weight
             # gradients"): set W2L_DEFER_WGRAD=0 for anything that reads gradients between backward() and step().
             # (after the restore: load_state_dict drops the step engine, which is what counts the units)
+            # With gradient clipping on, the default is 0: the clip call computes every held-back gradient at once anyway.
             n_units = len(model.engine().units) if hasattr(model, 'engine') else 0
-            k = int(os.environ.get('W2L_DEFER_WGRAD', min(4, n_units // 4)))
+            k = int(os.environ.get('W2L_DEFER_WGRAD', 0 if self.gradient_clip_val else min(4, n_units // 4)))
             if k and hasattr(opt, 'defer_wgrad'):
                 opt.defer_wgrad(model, k)
+                if self.gradient_clip_val:
+                    self._say(f'W2L_DEFER_WGRAD={k} with gradient clipping: every held-back weight gradient is computed at the '
+                              'clip call (correct, but deferral buys nothing; W2L_DEFER_WGRAD=0 is the default while clipping)')
         from . import engine as _E, replay as _replay
         self._say('wav2letter_pytorch_amd: '
                   + ('bit-reproducible step (W2L_DETERMINISTIC=1)' if _E.DETERMINISTIC_WGRAD else
                      'default step: fp32 atomics in split reductions, not bit-reproducible from run to run (W2L_DETERMINISTIC=1: +0.6 %)')
                   + ('; warm step shapes are replayed from recorded launch lists (W2L_REPLAY=0: eager)' if _replay.ENABLED else
                      '; eager step (W2L_REPLAY=0)')
-                  + ('; string metrics scored behind backward()' if getattr(model, 'async_metrics', False) else ''))
+                  + ('; string metrics scored behind backward()' if getattr(model, 'async_metrics', False) else '')
+                  + (f'; gradient clipping: {self.gradient_clip_algorithm} {self.gradient_clip_val:g}' if self.gradient_clip_val else ''))
         done = self.max_steps is not None and self.global_step >= self.max_steps
         for epoch in range(first_epoch, self.max_epochs):
             if done:
@@ -127,6 +148,8 @@ class Trainer:
                 opt.zero_grad(set_to_none=True)
                 loss = model.training_step(batch, i)
                 loss.backward()
+                if self.gradient_clip_val:           # Lightning's order: backward, clip, step
+                    self._clip(model, opt)
                 opt.step()
                 # Lightning's hook order: the batch's string metrics (greedy decode, CER / WER) are scored HERE, with the
                 # backward pass and the update already enqueued -- training_step itself never waits for the GPU
