@@ -301,6 +301,47 @@ def test_recorder_records_and_replays_host_state_calls():
     assert _lib.recording() is None and lib.w2l_conv_stats_mode is orig
 
 
+def test_replay_pointer_audit_classification():
+    """replay.audit's rule on a synthetic allocator snapshot (the format of torch.cuda.memory._snapshot()): a pointer a recorded
+    phase names is sound in an allocated block of any pool, or in a freed block of a segment of the record set's own live pool
+    (the record reuses its own freed blocks on purpose); it is a finding in a freed block of the default pool or of another
+    pool, in a freed block of its own pool once that pool is no longer live, and when its segment has gone back to the driver"""
+    import ctypes as C
+    from wav2letter_pytorch_amd import _lib
+    own, other, default = (7, 1), (9, 2), (0, 0)
+
+    def seg(addr, pool, blocks):
+        return {'address': addr, 'total_size': sum(b[0] for b in blocks), 'segment_pool_id': pool, 'stream': 0,
+                'blocks': [{'size': sz, 'state': st} for sz, st in blocks]}     # (no block addresses: derived from the sizes)
+    snap = {'segments': [
+        seg(0x300000, other, [(0x1000, 'inactive'), (0x1000, 'active_allocated')]),
+        seg(0x100000, default, [(0x1000, 'active_allocated'), (0x2000, 'inactive'), (0x1000, 'active_pending_free')]),
+        seg(0x200000, own, [(0x1000, 'inactive'), (0x1000, 'active_allocated')]),
+    ]}
+    ptrs = [(0x100010, default, '0:w2l_conv1d_igemm_ws'),      # allocated, default pool: a weight, a workspace
+            (0x301000, other, '1:w2l_sgd_pack'),               # allocated in another pool
+            (0x200800, own, '2:w2l_bn_act_fwd'),               # own live pool, freed block: a transient buffer of the step
+            (0x101800, default, '3:w2l_conv1d_igemm_ws'),      # freed block of the default pool: an outgrown workspace
+            (0x103000, default, '4:w2l_sgd_pack'),             # freed, not yet reusable: still a finding
+            (0x300400, other, '5:w2l_sgd_small_multi'),        # freed block of a foreign pool (a purged record's table)
+            (0x200400, other, '6:w2l_fill_zero'),              # recorded in another pool, now in a freed block of ours
+            (0x500000, default, '7:w2l_pack_weights')]         # its segment is gone
+    bad = _lib.classify_pointers(ptrs, snap, [own])
+    assert [b.split(':')[0] for b in bad] == ['3', '4', '5', '6', '7'], bad
+    assert 'no allocator segment' in bad[-1] and 'freed block (inactive)' in bad[0] and 'active_pending_free' in bad[1]
+    assert _lib.classify_pointers(ptrs[:3], snap, [own]) == []
+    # the same transient buffer once its pool is no longer the record set's (re-recorded, pool purged): a finding
+    assert [b.split(':')[0] for b in _lib.classify_pointers(ptrs[:3], snap, [(8, 1)])] == ['2']
+    assert _lib.classify_pointers([], snap, []) == []
+    # the device pointers a by-reference struct carries are audited too (the struct copy itself is host memory)
+    d = _lib.BnActDesc()
+    d.y, d.scale, d.mask = 0x100010, 0x200800, None
+    items = (_lib.WgradItem * 2)()
+    items[0].dy, items[1].dw = 0x301000, 0x101800
+    assert _lib._struct_ptrs(d) == [0x100010, 0x200800] and _lib._struct_ptrs(items) == [0x301000, 0x101800]
+    assert _lib._struct_ptrs(C.c_int(3)) == []
+
+
 def test_config_loader_hydra_tree(tmp_path):
     """defaults list, `# @package model` groups, ${a.b} interpolation, key=value and group overrides
     (the structure of configuration/config.yaml:1-28, rebuilt here from Python dicts)"""

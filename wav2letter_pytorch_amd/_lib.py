@@ -361,6 +361,9 @@ class Call(C.Structure):
 
 
 _recorder = [None]            # the Recorder of the phase being recorded (module-wide: a phase runs on ONE thread at a time)
+# AUDIT = True (tests): Recorder.finish() resolves every pointer argument against the caching allocator's snapshot and keeps
+# those that are device memory on the Phase (replay.audit checks them later).  Off by default: a snapshot per recorded phase.
+AUDIT = False
 _REPLAY_OPS = {}              # entry point name -> (op index, per-argument kind: 'p' / 'i' / 'd')
 
 
@@ -386,10 +389,11 @@ def _replay_ops():
 class Phase:
     """One recorded phase of a step: C segments (arrays of w2l_call_t, replayed by ONE w2l_replay call each) and -- only
     where the engine had to call back into Python between launches -- Python items run with their recorded current stream."""
-    __slots__ = ('items', 'keep', 'n_calls')
+    __slots__ = ('items', 'keep', 'n_calls', 'dev_ptrs')
 
-    def __init__(self, items, keep, n_calls):
+    def __init__(self, items, keep, n_calls, dev_ptrs=None):
         self.items, self.keep, self.n_calls = items, keep, n_calls
+        self.dev_ptrs = dev_ptrs         # AUDIT only: [(address, segment pool id, 'call index:entry point')] of the device buffers named
 
     def replay(self):
         failed = C.c_int(-1)
@@ -414,11 +418,12 @@ class Recorder:
     phase as not replayable (a code path that still uses torch ops between launches).  ``finish()`` -> Phase or None."""
 
     def __init__(self):
-        self.calls = []          # pending C calls of the current segment: (op, kinds, args)
+        self.calls = []          # pending C calls of the current segment: (op, kinds, args, entry point)
         self.items = []
         self.keep = []
         self.poisoned = None
         self.n_calls = 0
+        self.ptrs = []           # AUDIT only: (pointer value, 'call index:entry point') of every pointer argument and struct field
         self._saved = {}
         self._thread = None
 
@@ -434,7 +439,7 @@ class Recorder:
             def wrapper(*args, _fn=fn, _op=op, _kinds=kinds, _name=name):
                 rc = _fn(*args)
                 if threading.get_ident() == self._thread and (rc == 0 or rc is None):
-                    self.calls.append((_op, _kinds, args))
+                    self.calls.append((_op, _kinds, args, _name))
                 return rc
 
             setattr(lib, name, wrapper)
@@ -461,8 +466,9 @@ class Recorder:
         if not self.calls:
             return
         arr = (Call * len(self.calls))()
-        for c, (op, kinds, args) in zip(arr, self.calls):
+        for j, (c, (op, kinds, args, name)) in enumerate(zip(arr, self.calls)):
             c.op, c.nargs = op, len(kinds)
+            where = '%d:%s' % (self.n_calls + j, name)
             for slot, kind, v in zip(c.a, kinds, args):
                 if kind == 'i':
                     slot.i = int(v)
@@ -480,6 +486,11 @@ class Recorder:
                     copy = type(obj).from_buffer_copy(obj)
                     self.keep.append(copy)
                     slot.p = C.addressof(copy)
+                    if AUDIT:                # (the host copy itself is no device buffer; the pointers it holds may be)
+                        self.ptrs += [(q, where) for q in _struct_ptrs(copy)]
+                    continue
+                if AUDIT and slot.p:
+                    self.ptrs.append((slot.p, where))
         self.items.append(('c', arr, len(self.calls)))
         self.n_calls += len(self.calls)
         self.calls = []
@@ -488,7 +499,67 @@ class Recorder:
         self._flush()
         if self.poisoned is not None:
             return None
-        return Phase(self.items, self.keep, self.n_calls)
+        dev_ptrs = None
+        if AUDIT:
+            segs = _segments(torch.cuda.memory._snapshot())
+            dev_ptrs = []
+            for q, where in self.ptrs:
+                seg = _find_segment(segs, q)
+                if seg is not None:      # (stream / event handles, pinned host buffers: in no device segment)
+                    dev_ptrs.append((q, seg[2], where))
+        return Phase(self.items, self.keep, self.n_calls, dev_ptrs)
+
+
+def _struct_ptrs(obj):
+    """the pointer fields of a ctypes Structure, or of every Structure of an array of them (BnActDesc, WgradItem, ...)"""
+    if isinstance(obj, C.Array):
+        return [q for e in obj for q in (_struct_ptrs(e) if isinstance(e, C.Structure) else ())]
+    if not isinstance(obj, C.Structure):
+        return []
+    return [getattr(obj, f) for f, t in obj._fields_ if t is c_p and getattr(obj, f)]
+
+
+def _segments(snapshot):
+    """allocator segments of a torch.cuda.memory._snapshot() as sorted (start, end, pool id, [(block start, end, state)])"""
+    out = []
+    for sg in snapshot['segments']:
+        a = int(sg['address'])
+        blocks = []
+        for b in sg['blocks']:
+            ba = int(b['address']) if 'address' in b else a + sum(e - s for s, e, _ in blocks)
+            blocks.append((ba, ba + int(b['size']), b['state']))
+        out.append((a, a + int(sg['total_size']), tuple(sg.get('segment_pool_id') or (0, 0)), blocks))
+    out.sort()
+    return out
+
+
+def _find_segment(segs, q):
+    import bisect
+    i = bisect.bisect_right(segs, (q, float('inf'))) - 1
+    if i >= 0 and segs[i][0] <= q < segs[i][1]:
+        return segs[i]
+    return None
+
+
+def classify_pointers(dev_ptrs, snapshot, own_pools):
+    """the entries of ``dev_ptrs`` (Phase.dev_ptrs) that are no longer safe to replay in the allocator state ``snapshot``: an
+    address must lie in an allocated block, or in a free block of a segment of one of ``own_pools`` (the record set's live
+    pools, whose freed blocks the record reuses on purpose).  -> findings as strings"""
+    segs = _segments(snapshot)
+    own = set(tuple(p) for p in own_pools)
+    bad = []
+    for q, pool, where in dev_ptrs:
+        seg = _find_segment(segs, q)
+        if seg is None:
+            bad.append('%s: 0x%x lies in no allocator segment any more' % (where, q))
+            continue
+        state = next((st for s, e, st in seg[3] if s <= q < e), None)
+        if state == 'active_allocated':
+            continue
+        if seg[2] in own and seg[2] == tuple(pool):
+            continue
+        bad.append('%s: 0x%x lies in a freed block (%s) of pool %s, not of the record\'s own pools' % (where, q, state, seg[2]))
+    return bad
 
 
 def recording() -> 'Recorder | None':

@@ -355,14 +355,16 @@ def invalidate_packed(params) -> int:
     The cache is keyed on ``Parameter._version``, which in-place writes through ``.data`` / raw pointers do not bump
     (old-style optimizers doing ``p.data.add_``, EMA, weight clipping, ``dist.broadcast(p.data)``).  Whoever updates
     weights that way calls this afterwards; the next forward then repacks from the fp32 master weights.  Weights updated
-    through version-bumping in-place ops (torch.optim, optim.FusedSGD, novograd.Novograd) need nothing."""
+    through version-bumping in-place ops (torch.optim, optim.FusedSGD, novograd.Novograd) need nothing.
+    The packs are marked stale, not freed: recorded launch lists (replay.py) name their buffers, and the repack writes into them."""
     if isinstance(params, torch.nn.Module):
         params = params.parameters()
     n = 0
     for p in params:
         cache = getattr(p, '_w2l_pack', None)
         if cache:
-            cache.clear()
+            for pk in cache.values():
+                pk.version = -1
             n += 1
     return n
 
@@ -396,6 +398,8 @@ def _splitk_workspace(dev, n, cout, tout):
     need = min(int(lib.w2l_conv_splitk_workspace_bytes(n, cout, tout)), SPLITK_WS_CAP)
     ws = _splitk_ws.get(dev.index)
     if ws is None or ws.numel() < need:
+        if ws is not None:
+            _retired_ws.append(ws)         # recorded launch lists of smaller shapes name it: never hand the memory back
         _lib.poison('split-K workspace grown')
         ws = torch.zeros(need, dtype=torch.uint8, device=dev)
         _splitk_ws[dev.index] = ws

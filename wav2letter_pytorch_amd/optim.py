@@ -209,6 +209,24 @@ class FusedSGD(torch.optim.SGD):
         self.join()
         return super().state_dict()
 
+    def load_state_dict(self, state_dict):
+        """torch's load_state_dict, except that a loaded momentum buffer is copied INTO the buffer it replaces when their
+        layouts agree: recorded optimizer phases (replay.py, phases O and X) name the buffers by address"""
+        self.join()
+        old = {id(p): self.state[p].get('momentum_buffer') for g in self.param_groups for p in g['params'] if p in self.state}
+        super().load_state_dict(state_dict)
+        for g in self.param_groups:
+            for p in g['params']:
+                buf, new = old.get(id(p)), self.state[p].get('momentum_buffer') if p in self.state else None
+                if buf is None or new is buf:
+                    continue
+                if (new is not None and new.shape == buf.shape and new.stride() == buf.stride() and new.dtype == buf.dtype
+                        and new.device == buf.device):
+                    buf.copy_(new)
+                    self.state[p]['momentum_buffer'] = buf
+                else:                        # a buffer went or changed layout: recorded optimizer phases are stale
+                    self.__dict__['_w2l_state_epoch'] = self.__dict__.get('_w2l_state_epoch', 0) + 1
+
     # ------------------------------------------------------------------ gradient clipping
     @torch.no_grad()
     def clip_grad_norm_(self, max_norm, norm_type=2.0):
@@ -436,6 +454,9 @@ class FusedSGD(torch.optim.SGD):
             for pp, gp, mp, n in rows:
                 flat += [pp, gp, mp, n]                    # w2l_sgd_small_t: three pointers, then {int32 n, int32 pad} = one int64 < 2^31
             table = cache[key] = torch.tensor(flat, dtype=torch.int64).to(params[0].device)
+        rec = _lib.recording()
+        if rec is not None:
+            rec.keep.append(table)          # the recorded phase O owns its table: evicting it from the cache must not free it
         if clip is None:
             check(lib.w2l_sgd_small_multi(ptr(table), len(rows), max(r[3] for r in rows), float(lr), float(mu), float(wd),
                                           int(nesterov), stream_ptr()), 'w2l_sgd_small_multi')

@@ -162,7 +162,7 @@ class Group:
 def opt_signature(opt):
     clip = opt._clip_signature() if hasattr(opt, '_clip_signature') else None        # armed gradient clipping: its own phase O
     return tuple((g['lr'], g['momentum'], g['weight_decay'], g['nesterov'], g['dampening'], g.get('maximize', False))
-                 for g in opt.param_groups) + (clip,)
+                 for g in opt.param_groups) + (opt.__dict__.get('_w2l_state_epoch', 0), clip)      # (epoch: FusedSGD.load_state_dict)
 
 
 class StepReplayer:
@@ -178,6 +178,7 @@ class StepReplayer:
         self.after_replayed_O = False                 # an eager phase must first wait for the optimizer's stream
         self.opt_stream = None
         self.first_seen = {}                          # step shapes seen so far that have no group yet -> how often
+        self._fused_ws = None                         # (engine units, their conv weights): what _weights_moved looks at
 
     # ------------------------------------------------------------------ eligibility
     def _mode_flags(self):
@@ -246,11 +247,38 @@ class StepReplayer:
                 g.eager_left = FP8_EAGER_STEPS - 1
                 self._age_fp8_weights(FP8_EAGER_EVERY)
                 return None
+        if self._weights_moved(eng):
+            return None
         s = g.sets[g.next]
         if self.pending is s:                          # (never run a set whose own held-back gradients are still pending)
             return None
         g.next ^= 1
         return ('replay' if s.F is not None and s.B is not None else 'record'), s
+
+    def _weights_moved(self, eng) -> bool:
+        """Has a conv weight whose operand pack the fused optimizer maintains changed outside the step since its last update?
+        Recorded F reads those packs as they are and never repacks (load_state_dict, an in-place write under no_grad bump
+        ``_version``; engine.invalidate_packed marks the pack stale).  Such a step runs eagerly: its forward repacks into the
+        SAME buffers the records name.  A weight tensor that was replaced (new address) drops every record."""
+        moved = False
+        for w in self._conv_weights(eng):
+            if '_w2l_ready_ev' not in w.__dict__:          # (no fused update: a recorded forward repacks it every step)
+                continue
+            pk = (getattr(w, '_w2l_pack', None) or {}).get(False)
+            if pk is None or pk.src_ptr != w.data_ptr():
+                self.groups.clear()                    # records name the old weight / pack addresses
+                self.pending = None                    # (its held-back gradients go to the eager flush_deferred)
+                return True
+            if pk.version != w._version:
+                moved = True
+        return moved
+
+    def _conv_weights(self, eng):
+        ws = self._fused_ws
+        if ws is None or ws[0] is not eng.units:
+            ws = self._fused_ws = (eng.units, [c.weight for u in eng.units for c in (u.main, u.res) if c is not None] +
+                                   ([eng.head.weight] if eng.head is not None else []))
+        return ws[1]
 
     def _age_fp8_weights(self, n):
         eng = self.engine()
@@ -307,11 +335,17 @@ class StepReplayer:
         # what the held-back updates are applied with: the hyper-parameters of the LAST step() call (optim.FusedSGD.apply), by
         # value in the record -- not necessarily the optimizer's current ones (a scheduler may have stepped since)
         hp = opt._deferred_state()['hp']
-        sig = tuple(hp[id(r['conv'].weight)][2] for r in eng._deferred)
+        sig = tuple(hp[id(r['conv'].weight)][2] for r in eng._deferred) + (opt.__dict__.get('_w2l_state_epoch', 0),)
         if s.X is not None and s.X_sig != sig:
             s.X = None
         if s.X is not None:
             s.X.replay()
+            # (the eager forward after a replayed X: its packs carry the weight events X recorded, as opt.apply() sets them)
+            from . import engine as E
+            for r in eng._deferred:
+                w = r['conv'].weight
+                for pk in (getattr(w, '_w2l_pack', None) or {}).values():
+                    pk.ready, pk.version = E.weight_event(w), w._version
             eng._deferred = []
             eng._side_used = True
             STATS['replayed_X'] += 1
@@ -598,6 +632,13 @@ def optimizer_step(opt, eager_body) -> bool:
         mine = opt.__dict__['_w2l_param_ids'] = frozenset(id(p) for g in opt.param_groups for p in g['params'])
     if any(id(p) not in mine for p, _ in rset.grads):
         return False
+    # parameters of the optimizer outside the engine: their gradient addresses are baked into the recorded small-parameter
+    # table of phase O, so they are validated like the engine's own (O_ptrs)
+    extra = opt.__dict__.get('_w2l_extra_params')
+    if extra is None or extra[0]() is not engine:
+        ids = frozenset(id(p) for p in engine.parameters())
+        extra = opt.__dict__['_w2l_extra_params'] = (weakref.ref(engine), [p for g in opt.param_groups for p in g['params'] if id(p) not in ids])
+    watched = [(p, None) for p in extra[1]]
     sig = (opt_signature(opt), bool(opt.overlap), _lib.raw_stream())
     if rset.O_sig != sig and rset.O_spare is not None and rset.O_spare[1] == sig:
         # an armed (gradient clipping) and an unarmed optimizer step each keep a phase O of their own
@@ -605,11 +646,16 @@ def optimizer_step(opt, eager_body) -> bool:
         rset.O, rset.O_sig, rset.O_ptrs, rset.lease_O, rset.pool_O = rset.O_spare
         rset.O_spare = cur if cur[0] is not None else None
     if rset.O is not None and rset.O_sig == sig:
-        for (p, gbuf), want in zip(rset.grads, rset.O_ptrs):
+        for (p, gbuf), want in zip(rset.grads + watched, rset.O_ptrs):
             have = p.grad.data_ptr() if p.grad is not None else 0
             if have != want:
                 return False                           # someone replaced a gradient tensor: the eager step takes what is there
         rset.O.replay()
+        # (an eager forward after it: the conv weights O updated in the small-parameter launch -- the classifier -- get the
+        # version bump the eager step gives them, so that their operand packs are rebuilt; recorded F repacks them anyway)
+        for w in rp._conv_weights(engine):
+            if '_w2l_ready_ev' not in w.__dict__:
+                torch.autograd.graph.increment_version(w)
         st, dst = opt._side_state(), opt._deferred_state()
         dst['seq'] += 1
         st['pending'] = True
@@ -637,9 +683,40 @@ def optimizer_step(opt, eager_body) -> bool:
         _say('optimizer phase dropped: ' + str(rec.poisoned))
         return True
     rset.O, rset.O_sig = ph, sig
-    rset.O_ptrs = [p.grad.data_ptr() if p.grad is not None else 0 for p, _ in rset.grads]
+    rset.O_ptrs = [p.grad.data_ptr() if p.grad is not None else 0 for p, _ in rset.grads + watched]
     rp.opt_stream = opt._side_state()['stream']
     return True
+
+
+def audit(engine) -> list:
+    """Every device address a live recorded phase of ``engine`` names that is no longer safe to replay (an empty list: the
+    records are sound).  Needs the phases recorded with ``_lib.AUDIT = True``; a phase recorded without it fails the audit.
+    Live phases: F, B, O, X and the spare phase O of every record set of every step shape, and the set whose held-back
+    gradients are pending.  An address must lie in an allocated block, or in a free block of one of its record set's own
+    live pools (_lib.classify_pointers)."""
+    rp = engine.__dict__.get('_replayer')
+    if rp is None:
+        return []
+    sets = [s for g in rp.groups.values() for s in g.sets]
+    if rp.pending is not None and not any(rp.pending is s for s in sets):
+        sets.append(rp.pending)
+    todo = []
+    for s in sets:
+        phases = [('F', s.F), ('B', s.B), ('O', s.O), ('X', s.X)] + ([('O_spare', s.O_spare[0])] if s.O_spare is not None else [])
+        own = [p.id for p in (s.pool, s.pool_O, s.pool_X, s.O_spare[4] if s.O_spare is not None else None) if p is not None]
+        for name, ph in phases:
+            if ph is not None:
+                todo.append(('set %d %s' % (s.index, name), ph, own))
+    if not todo:
+        return []
+    snap = torch.cuda.memory._snapshot()
+    out = []
+    for label, ph, own in todo:
+        if ph.dev_ptrs is None:
+            out.append(label + ': recorded without _lib.AUDIT, its pointers are unknown')
+            continue
+        out += [label + ' ' + f for f in _lib.classify_pointers(ph.dev_ptrs, snap, own)]
+    return out
 
 
 def report(engine) -> dict:
