@@ -434,6 +434,23 @@ int w2l_ctc_loss(const float* log_probs, const int32_t* targets, const int32_t* 
 /* ---- greedy decode (decoder.py:136) + Levenshtein (decoder.py:49,60) ---- */
 /* argmax over the last dim, ties -> lowest index (torch.max): probs fp32 [rows][C] -> idx int32 [rows] */
 int w2l_argmax(const float* probs, int64_t rows, int C, int32_t* idx, void* stream);
+/* ---- CTC prefix beam search (decoder.py:147-267 without a language model; beam_search.prefix_beam_search) ---- */
+/* workspace bytes for w2l_ctc_beam_search (per utterance: a trie of k*T+1 nodes and its intern table); -1 if out of range */
+int64_t w2l_ctc_beam_search_workspace_bytes(int N, int T, int k);
+/* One workgroup per utterance, one launch for the batch, masses as fp64 logs.  probs fp32 [N][T][A] contiguous: probabilities,
+ * or log-probabilities if log_probs; sizes int32 [N] (NULL: T) = the frames decoded of each utterance.  label_info_host[A]:
+ * bits 0-7 the first index of the label's character (duplicate labels: the first index wins), bit 8 the label's character
+ * is the blank's, bit 9 it is a word character (\w), bit 10 a word separator ([\s|>]).  end_index: first index of end_char,
+ * -1 if absent (a prefix ending in it is carried unchanged).  A frame extends with the labels whose probability is > prune
+ * (lp > log(prune) for log input); ranking = mass * (words + 1)^beta, ties in the host's first-insertion order.
+ * out (one buffer, one copy to the host): double score[N][k] (log of the ranking weight, -inf for an empty slot) |
+ * int32 len[N][k] (-1: empty slot) | int32 status[N] (1: a probability was negative or NaN) | int32 labels[N][k][T]
+ * (first label indices, the first len of each row valid); slot 0 is the best prefix.  Limits: 1 <= k <= 64, 1 <= A <= 128,
+ * and the candidate tables (48 * k * (A + 1) + 8 * k * A bytes) fit in LDS beside 9 KB of fixed state: k=32 with A=64 is
+ * 114 KB; an error otherwise. */
+int w2l_ctc_beam_search(const float* probs, const int32_t* sizes, int N, int T, int A, const int32_t* label_info_host,
+                        int blank, int end_index, int k, double beta, double prune, int log_probs, void* workspace,
+                        int64_t workspace_bytes, void* out, void* stream);
 /* host-side edit distance over int32 symbol arrays */
 int w2l_levenshtein_host(const int32_t* a_host, int na, const int32_t* b_host, int nb);
 /* ConvCTCASR.add_string_metrics (base_asr_models.py:53-69) for one batch in ONE host call (no device work, no interpreter

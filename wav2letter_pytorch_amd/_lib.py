@@ -130,6 +130,9 @@ _SIGNATURES = {
     'w2l_ctc_workspace_bytes': (c_i64, [c_i, c_i, c_i]),
     'w2l_ctc_loss': (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p]),
     'w2l_argmax': (c_i, [c_p, c_i64, c_i, c_p, c_p]),
+    'w2l_ctc_beam_search_workspace_bytes': (c_i64, [c_i, c_i, c_i]),
+    'w2l_ctc_beam_search': (c_i, [c_p, c_p, c_i, c_i, c_i, c_p, c_i, c_i, c_i, C.c_double, C.c_double, c_i, c_p, c_i64, c_p,
+                                  c_p]),
     'w2l_logmel': (c_i, [c_p, c_p, c_p, c_f, c_f, c_i, c_i64, c_p, c_i, c_i, c_i, c_p, c_p, c_i, c_i, c_f, c_p, c_i, c_p]),
     'w2l_feature_normalize': (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_p, c_p, c_p, c_p]),
     'w2l_zero_rects': (c_i, [c_p, c_i, c_i, c_i, c_p, c_i, c_p]),
@@ -242,6 +245,7 @@ TRACE_NAMES = {
     'w2l_nct_to_ntc': 'nct_to_ntc_kernel', 'w2l_pad_cast': 'pad_cast_kernel', 'w2l_quantize_e4m3': 'quantize_e4m3',
     'w2l_quantize_e4m3_dyn': 'quantize_e4m3_dyn', 'w2l_dwconv_fwd': 'dw_fwd_kernel', 'w2l_dwconv_dgrad': 'dw_dgrad_kernel',
     'w2l_dwconv_wgrad': 'dw_wgrad_kernel', 'w2l_argmax': 'argmax_kernel', 'w2l_novograd_pack': 'novograd_pack_kernel',
+    'w2l_ctc_beam_search': 'ctc_beam_search_kernel',
 }
 _trace = {'rows': None, 'saved': {}, 'pool': []}
 

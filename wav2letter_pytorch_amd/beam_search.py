@@ -5,14 +5,21 @@ Each hypothesis (prefix string) carries two masses per time step: ending in blan
 non-blank (``pnb``).  The reference's observable behaviour that callers rely on is kept: probabilities (not
 logs) in, the first index of a label wins on duplicates, an ``end_char`` freezes a prefix, the LM is applied
 when a word is closed (space or end char) with weight ``alpha``, ranking multiplies by (#words+1)**beta, only
-strictly positive masses survive a step, ties keep first-seen order."""
+strictly positive masses survive a step, ties keep first-seen order.
+
+prefix_beam_search_gpu / GPUPrefixBeamSearchDecoder run the same recursion without a language model as one HIP launch per
+batch (w2l_ctc_beam_search, csrc/beam_search.hip), in fp64 logs."""
 from __future__ import annotations
 
+import ctypes as C
 import re
 from typing import Callable, Dict, List, Optional, Sequence
 
 import numpy as np
+import torch
 
+from . import _lib
+from ._lib import check, lib, ptr, stream_ptr
 from .decoder import Decoder
 
 _WORD_RE = re.compile(r'\w+[\s|>]')
@@ -132,6 +139,129 @@ class PrefixBeamSearchLMDecoder(Decoder):
             return [self.decode(p) for p in probs]
         raise RuntimeError('Decoding with wrong shape: %s, expected either [Batch X Frames X Labels] or '
                            '[Frames X Labels]' % str(probs.shape))
+
+
+# ---------------------------------------------------------------------------------------------------------------- device
+_SEP_RE = re.compile(r'[\s|>]')
+_WORDCH_RE = re.compile(r'\w')
+
+
+def _label_info(labels: Sequence[str], blank_index: int, end_char: str):
+    """per-label flags of w2l_ctc_beam_search (include/w2l_hip.h) and the first index of ``end_char`` (-1: absent)"""
+    labels = list(labels)
+    if not all(isinstance(ch, str) and len(ch) == 1 for ch in labels):
+        raise ValueError('prefix_beam_search_gpu: every label must be one character')
+    first_index = {}
+    for i, ch in enumerate(labels):
+        first_index.setdefault(ch, i)
+    blank = labels[blank_index]
+    info = np.array([first_index[ch] | (ch == blank) << 8 | bool(_WORDCH_RE.fullmatch(ch)) << 9
+                     | bool(_SEP_RE.fullmatch(ch)) << 10 for ch in labels], dtype=np.int32)
+    return info, first_index.get(end_char, -1)
+
+
+def _beam_search_device(probs, labels, blank_index, k, beta, prune, end_char, sizes, log_probs):
+    """one launch of w2l_ctc_beam_search for probs [N, T, A] on the current stream; returns the host arrays
+    (scores [N, k], lengths [N, k], labels [N, k, T])"""
+    if probs.dim() != 3:
+        raise ValueError('expected [N, T, labels] or [T, labels] posteriors, got shape %s' % (tuple(probs.shape),))
+    n, t, a = probs.shape
+    if a != len(labels):
+        raise ValueError('ctc size:%d, labels: %d' % (a, len(labels)))
+    if not 0 <= blank_index < a:
+        raise ValueError('blank_index %d outside %d labels' % (blank_index, a))
+    if t < 2:
+        raise ValueError('ctc length: %d was too short' % t)
+    info, end_index = _label_info(labels, blank_index, end_char)
+    if not probs.is_cuda:
+        if not torch.cuda.is_available():
+            raise _lib.W2LError('prefix_beam_search_gpu needs the MI355X device (there is no CPU fallback)')
+        probs = probs.cuda()
+    x = probs.detach().float().contiguous()
+    dev = x.device
+    sz = None
+    if sizes is not None:
+        host = torch.as_tensor(sizes).detach().cpu().to(torch.int64).reshape(-1)
+        if host.numel() != n:
+            raise ValueError('sizes holds %d lengths for %d utterances' % (host.numel(), n))
+        if bool((host < 2).any()) or bool((host > t).any()):
+            raise ValueError('sizes must lie in [2, %d], got %s' % (t, host.tolist()))
+        sz = host.to(torch.int32).to(dev, non_blocking=True)
+    ws_bytes = int(lib.w2l_ctc_beam_search_workspace_bytes(n, t, k))
+    if ws_bytes < 0:
+        raise ValueError('prefix_beam_search_gpu: k=%d with T=%d is out of range' % (k, t))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    out = torch.empty(12 * n * k + 4 * n + 4 * n * k * t, dtype=torch.uint8, device=dev)
+    check(lib.w2l_ctc_beam_search(ptr(x), ptr(sz), n, t, a, info.ctypes.data_as(C.c_void_p), int(blank_index), int(end_index),
+                                  int(k), float(beta), float(prune), int(bool(log_probs)), ptr(ws), ws_bytes, ptr(out),
+                                  stream_ptr()), 'w2l_ctc_beam_search')
+    host = out.cpu().numpy()                           # the one copy to the host (ordered after the launch on this stream)
+    scores = host[:8 * n * k].view(np.float64).reshape(n, k)
+    rest = host[8 * n * k:].view(np.int32)
+    lengths = rest[:n * k].reshape(n, k)
+    status = rest[n * k:n * k + n]
+    idx = rest[n * k + n:].reshape(n, k, t)
+    if status.any():
+        raise ValueError('ctc output contains negative numbers (utterances %s)' % np.nonzero(status)[0].tolist())
+    return scores, lengths, idx
+
+
+def prefix_beam_search_gpu(probs, labels: Sequence[str], blank_index: int = 0, k: int = 5, beta: float = 5,
+                           prune: float = 0.001, end_char: str = '>', sizes=None, log_probs: bool = False, nbest: int = 1,
+                           return_weights: bool = False):
+    """prefix_beam_search without a language model, on the MI355X: one launch for a whole batch, masses as fp64 logs (no
+    underflow on long utterances; the host function's float32 products do underflow), the host's candidate order and ties.
+
+    probs: [T, labels] or [N, T, labels] (numpy or torch, any device; probabilities, or log-probabilities if ``log_probs``);
+    ``sizes[n]``: decode only the first sizes[n] frames of utterance n (default: all T).  Per utterance the result is the best
+    prefix, ``(best, log weight)`` if ``return_weights``, or if ``nbest > 1`` a list of up to ``nbest`` ``(prefix, log weight)``
+    pairs, best first (log weight = log(mass * (words + 1) ** beta), the host's ranking weight).  A [T, labels] input gives one
+    result, a batch a list of N."""
+    labels = list(labels)
+    if not 1 <= nbest <= k:
+        raise ValueError('nbest=%d must lie in [1, k=%d]' % (nbest, k))
+    x = probs if torch.is_tensor(probs) else torch.from_numpy(np.ascontiguousarray(probs))
+    single = x.dim() == 2
+    if single:
+        x = x.unsqueeze(0)
+        if sizes is not None:
+            sizes = [int(np.asarray(sizes).reshape(-1)[0])]
+    scores, lengths, idx = _beam_search_device(x, labels, blank_index, k, beta, prune, end_char, sizes, log_probs)
+    results = []
+    for u in range(scores.shape[0]):
+        found = [(''.join(labels[j] for j in idx[u, r, :lengths[u, r]]), float(scores[u, r]))
+                 for r in range(k) if lengths[u, r] >= 0]
+        if not found:                                  # the beam emptied: '' as on the host (weight 0)
+            found = [('', float('-inf'))]
+        if nbest > 1:
+            results.append(found[:nbest])
+        elif return_weights:
+            results.append(found[0])
+        else:
+            results.append(found[0][0])
+    return results[0] if single else results
+
+
+class GPUPrefixBeamSearchDecoder(Decoder):
+    """PrefixBeamSearchLMDecoder on the MI355X (prefix_beam_search_gpu): the same constructor (plus ``log_probs``), no
+    language model -- a scoring callable cannot run on the device."""
+
+    def __init__(self, lm_path, labels, blank_index=0, k=5, alpha=0.3, beta=5, prune=1e-3, log_probs=False):
+        super(GPUPrefixBeamSearchDecoder, self).__init__(labels, blank_index)
+        if lm_path:
+            raise ValueError('GPUPrefixBeamSearchDecoder has no language model (lm_path=%r, alpha=%r): use '
+                             'PrefixBeamSearchLMDecoder, the host decoder, for LM scoring' % (lm_path, alpha))
+        self.k, self.alpha, self.beta, self.prune, self.log_probs = k, alpha, beta, prune, log_probs
+
+    def decode(self, probs, sizes=None, return_offsets=False):
+        """[N, T, labels] -> N strings (utterance n over its first sizes[n] frames); [T, labels] -> one string"""
+        if return_offsets:
+            raise NotImplementedError("Prefix beam search does not support offsets (yet).")
+        if len(probs.shape) not in (2, 3):
+            raise RuntimeError('Decoding with wrong shape: %s, expected either [Batch X Frames X Labels] or '
+                               '[Frames X Labels]' % str(tuple(probs.shape)))
+        return prefix_beam_search_gpu(probs, self.labels, self.blank_index, self.k, self.beta, self.prune, sizes=sizes,
+                                      log_probs=self.log_probs)
 
 
 def get_time_per_word(predictions, offsets, ratio=1.0):

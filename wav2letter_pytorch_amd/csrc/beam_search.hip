@@ -1,0 +1,409 @@
+// Batched CTC prefix beam search (decoder.py:147-267 without a language model; host restatement:
+// beam_search.prefix_beam_search, whose recursion this kernel reproduces candidate for candidate).
+//
+// One workgroup decodes one utterance and loops over its frames.  Masses are natural logs in fp64 (a frame's
+// contributions are log-added in the host's loop order), so a long utterance cannot underflow.
+//
+// Identity of a prefix.  Beam members are nodes of a per-utterance trie in the global workspace (parent, char),
+// interned by the exact key (parent node, char) in an open-addressing table, so one string has one node.  The
+// candidates of frame t are the beam members and their one-label extensions; candidate tables are indexed by beam
+// slot: E(i, c) is the beam member in slot i extended by canonical label c, S(i) is the member in slot i itself.  A
+// member whose parent is also in the beam is not S(i) but the E entry of its parent slot (mem[] says which), so every
+// string of the frame has exactly one entry.  The previous frame's masses (needed where an extension fell off the
+// beam) are found through the slot the same string's parent had one frame earlier (prevslot), or -- where that parent
+// was not in the previous beam -- through redir[], which names the previous frame's S entry of the string.
+//
+// Per frame, three phases, each ended by a workgroup barrier:
+//   P1  slot bookkeeping (parent slot, mem[], redir[]) and the frame's labels: log-probs, pruned alphabet in order
+//   P2  one thread per entry: its pb / pnb in the host's order of contributions, its rank key and tie key
+//   P3  one thread per live candidate: rank by counting the candidates ahead of it (score, then first insertion);
+//       the k first become the next beam, new members are interned
+// LDS holds two frames of entry masses plus the live-candidate list (see lds_bytes); limits in w2l_hip.h.
+#include "common.h"
+#include <math.h>
+
+namespace {
+
+constexpr int BS_THREADS = 256;
+constexpr int BS_KMAX = 64;          // beam slots live in one wave (P1)
+constexpr int BS_AMAX = 128;         // two labels per lane of the frame-loading wave
+constexpr uint64_t BS_EMPTY = ~0ull;
+constexpr int BS_NOT_PB = 1 << 30;   // tie key of a candidate that only ever entered pnb
+
+struct LabelInfo {
+    // bits 0-7: canonical (first) index of the label's character; 8: the blank character; 9: a word character (\w);
+    // 10: a word separator ([\s|>])
+    int32_t v[BS_AMAX];
+};
+
+__device__ __forceinline__ double lae(double a, double b) {          // log(exp(a) + exp(b))
+    if (a == -INFINITY) return b;
+    if (b == -INFINITY) return a;
+    const double m = a > b ? a : b, d = a > b ? b - a : a - b;
+    return m + log1p(exp(d));
+}
+
+// host loop position of an operation: beam slot i, label l (-1: the closed-hypothesis assignment), op within the label
+__device__ __forceinline__ int loop_pos(int i, int A, int l, int op) { return ((i * (A + 1) + l + 1) << 2) | op; }
+
+struct Acc {
+    double b = -INFINITY, nb = -INFINITY;
+    int bseq = 0x7fffffff, nbseq = 0x7fffffff;
+    __device__ void add_b(double v, int pos) { b = lae(b, v); bseq = min(bseq, pos); }
+    __device__ void add_nb(double v, int pos) { nb = lae(nb, v); nbseq = min(nbseq, pos); }
+};
+
+struct Beam {                         // one frame's beam, slot-indexed
+    int node[BS_KMAX], parent[BS_KMAX], chr[BS_KMAX], words[BS_KMAX], len[BS_KMAX], ps[BS_KMAX], prevslot[BS_KMAX];
+    double pb[BS_KMAX], pnb[BS_KMAX], score[BS_KMAX];
+};
+
+__device__ __forceinline__ uint32_t key_hash(uint64_t key) { return (uint32_t)((key * 0x9E3779B97F4A7C15ull) >> 32); }
+
+__global__ __launch_bounds__(BS_THREADS) void ctc_beam_search_kernel(
+    const float* __restrict__ probs, const int32_t* __restrict__ sizes, int T, int A, LabelInfo info, int blank, int endc,
+    int k, double beta, double prune, int log_probs, char* __restrict__ ws, int64_t ws_per_utt, int hash_cap,
+    double* __restrict__ out_score, int32_t* __restrict__ out_len, int32_t* __restrict__ out_status,
+    int32_t* __restrict__ out_labels) {
+    __shared__ Beam beams[2];
+    __shared__ double lpd[BS_AMAX];
+    __shared__ int alph[BS_AMAX], act[BS_AMAX], lab[BS_AMAX];
+    __shared__ int s_m[2], s_nalph, s_count, s_bad;
+    extern __shared__ __attribute__((aligned(16))) double dyn[];
+
+    const int n = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int nE = k * A + k;                              // E(i, c) = i*A + c, S(i) = k*A + i
+    double* mass = dyn;                                    // [2 frames][nE][pb, pnb]
+    double* lsc = mass + 4 * nE;                           // live candidates: rank score
+    int* lkey = (int*)(lsc + nE);                          //                  tie key (first insertion)
+    int* lent = lkey + nE;                                 //                  entry index
+    int* mem = lent + nE;                                  // [k][A] stamp | slot of the member that is E(i, c)
+    int* redir = mem + k * A;                              // [k][A] stamp | previous slot whose S entry is E(i, c)
+
+    char* wsn = ws + (int64_t)n * ws_per_utt;
+    int32_t* nd_parent = (int32_t*)wsn;
+    int32_t* nd_chr = nd_parent + ((int64_t)k * T + 1);
+    uint64_t* hkeys = (uint64_t*)(wsn + (((int64_t)k * T + 1) * 8 + 15) / 16 * 16);
+    int32_t* hvals = (int32_t*)(hkeys + hash_cap);
+
+    for (int i = tid; i < hash_cap; i += BS_THREADS) hkeys[i] = BS_EMPTY;
+    for (int i = tid; i < 2 * k * A; i += BS_THREADS) mem[i] = 0;         // mem and redir: stamp 0 never matches
+    for (int i = tid; i < A; i += BS_THREADS) { lab[i] = info.v[i]; act[i] = 0; }
+    if (tid == 0) {
+        nd_parent[0] = -1;
+        nd_chr[0] = -1;
+        Beam& b0 = beams[0];
+        b0.node[0] = 0; b0.parent[0] = -1; b0.chr[0] = -1; b0.words[0] = 0; b0.len[0] = 0; b0.prevslot[0] = -1;
+        b0.pb[0] = 0.0; b0.pnb[0] = -INFINITY; b0.score[0] = 0.0;
+        s_m[0] = 1;
+        s_m[1] = 0;
+        s_bad = 0;
+    }
+    int Tn = T;
+    if (sizes) Tn = min(max(sizes[n], 0), T);
+    const float* xn = probs + (int64_t)n * T * A;
+    const double log_prune = prune > 0 ? log(prune) : -INFINITY;
+    auto closed = [&](const Beam& b, int s) { return endc >= 0 && b.chr[s] == endc; };   // pre[-1] == end_char
+    float nxt[2] = {0.f, 0.f};                             // wave 2: the frame to come, two labels per lane
+    if (wave == 2 && Tn > 0)
+        for (int h = 0; h < 2; ++h) if (lane + 64 * h < A) nxt[h] = xn[lane + 64 * h];
+    __threadfence();
+    __syncthreads();
+
+    int cur = 0;                                           // parity of the current beam and of this frame's masses
+    for (int t = 0; t < Tn; ++t) {
+        const int m = s_m[cur], mprev = s_m[cur ^ 1];
+        if (m == 0) break;                                 // the beam emptied: the result is '' (uniform: read after a barrier)
+        const int stamp = (t + 1) << 7;
+        Beam& B = beams[cur];
+        const Beam& P = beams[cur ^ 1];
+        // ---------------------------------------------------------------- P1
+        if (wave == 0) {
+            if (lane < m) {
+                int ps = -1;
+                for (int j = 0; j < m; ++j) if (B.node[j] == B.parent[lane]) { ps = j; break; }
+                B.ps[lane] = ps;
+                if (ps >= 0) mem[ps * A + B.chr[lane]] = stamp | lane;
+            }
+            if (lane == 0) s_count = 0;
+        } else if (wave == 1) {
+            // a previous member that had its own S entry and whose parent is now in the beam: its extension entry finds
+            // last frame's mass there
+            if (t > 0 && lane < mprev && P.ps[lane] < 0 && P.parent[lane] >= 0) {
+                for (int j = 0; j < m; ++j)
+                    if (B.node[j] == P.parent[lane]) { redir[j * A + P.chr[lane]] = stamp | lane; break; }
+            }
+        } else if (wave == 2) {
+            int pass[2] = {0, 0};
+            uint64_t mask[2];
+            for (int h = 0; h < 2; ++h) {
+                const int l = lane + 64 * h;
+                if (l < A) {
+                    const float v = nxt[h];
+                    if (t + 1 < Tn) nxt[h] = xn[(int64_t)(t + 1) * A + l];      // the next frame's load hides behind this one
+                    double lp;
+                    if (log_probs) {
+                        lp = (double)v;
+                    } else {
+                        if (!(v >= 0.f)) s_bad = 1;
+                        lp = log((double)v);
+                    }
+                    lpd[l] = lp;
+                    // frame > prune as the host compares it (probabilities), or lp > log(prune)
+                    pass[h] = log_probs ? (prune < 0 || lp > log_prune) : (double)v > prune;
+                    if (pass[h] && !(lab[l] & 0x100)) act[lab[l] & 0xff] = t + 1;
+                }
+                mask[h] = __ballot(pass[h]);
+            }
+            const int n0 = __popcll(mask[0]);
+            if (pass[0]) alph[__popcll(mask[0] & ((1ull << lane) - 1))] = lane;
+            if (pass[1]) alph[n0 + __popcll(mask[1] & ((1ull << lane) - 1))] = lane + 64;
+            if (lane == 0) s_nalph = n0 + __popcll(mask[1]);
+        }
+        __syncthreads();
+        // ---------------------------------------------------------------- P2
+        const int L = s_nalph;
+        const double pblank = lpd[blank];
+        const double* mprev_tab = mass + (cur ^ 1) * 2 * nE;
+        double* mcur = mass + cur * 2 * nE;
+        for (int e = tid; e < m * A + m; e += BS_THREADS) {
+            const int ent = e < m * A ? e : k * A + (e - m * A);
+            Acc acc;
+            bool live = false;
+            int words = 0;
+            if (e < m * A) {
+                const int i = e / A, c = e - i * A;
+                const int mv = mem[ent];
+                const int s = (mv >> 7) == t + 1 ? (mv & 127) : -1;
+                const bool ext = act[c] == t + 1 && !closed(B, i);   // labels of c passed the prune; slot i is open
+                if (ext || s >= 0) {
+                    live = true;
+                    // contributions of slot i extended by c (beam_search.py: the non-blank branches of pre = slot i)
+                    auto parent_part = [&]() {
+                        if (!ext) return;
+                        const bool rep = B.parent[i] >= 0 && B.chr[i] == c;
+                        const double lin = rep ? B.pb[i] : lae(B.pb[i], B.pnb[i]);
+                        double fb = -INFINITY, fnb = -INFINITY;
+                        if (s < 0) {
+                            int pidx = -1;
+                            if (B.prevslot[i] >= 0) {
+                                pidx = B.prevslot[i] * A + c;
+                            } else {
+                                const int rv = redir[ent];
+                                if ((rv >> 7) == t + 1) pidx = k * A + (rv & 127);
+                            }
+                            if (pidx >= 0) {
+                                fb = lae(mprev_tab[2 * pidx], mprev_tab[2 * pidx + 1]);
+                                fnb = mprev_tab[2 * pidx + 1];
+                            }
+                        }
+                        const double p = lpd[c];
+                        for (int q = 0; q < L; ++q) {
+                            const int l = alph[q];
+                            if ((lab[l] & 0xff) != c || (lab[l] & 0x100)) continue;
+                            acc.add_nb(p + lin, loop_pos(i, A, l, 0));
+                            if (s < 0) {                   // the extension fell off the beam: last frame's mass joins
+                                acc.add_b(pblank + fb, loop_pos(i, A, l, 2));
+                                acc.add_nb(p + fnb, loop_pos(i, A, l, 3));
+                            }
+                        }
+                    };
+                    if (s < 0) {
+                        parent_part();
+                        words = B.words[i] + ((lab[c] & 0x400) && B.chr[i] >= 0 && (lab[B.chr[i]] & 0x200));
+                    } else {
+                        words = B.words[s];
+                        if (i < s) parent_part();
+                        // own contributions of member s (blank, repeated character, or the closed-hypothesis assignment)
+                        if (closed(B, s)) {
+                            acc.b = B.pb[s];
+                            acc.nb = B.pnb[s];
+                            acc.bseq = min(acc.bseq, loop_pos(s, A, -1, 0));
+                            acc.nbseq = min(acc.nbseq, loop_pos(s, A, -1, 1));
+                        } else {
+                            const double ms = lae(B.pb[s], B.pnb[s]);
+                            for (int q = 0; q < L; ++q) {
+                                const int l = alph[q];
+                                if (lab[l] & 0x100) acc.add_b(pblank + ms, loop_pos(s, A, l, 0));
+                                else if ((lab[l] & 0xff) == B.chr[s]) acc.add_nb(lpd[B.chr[s]] + B.pnb[s], loop_pos(s, A, l, 1));
+                            }
+                        }
+                        if (i > s) parent_part();
+                    }
+                }
+            } else {
+                const int s = e - m * A;
+                if (B.ps[s] < 0) {                         // a member whose parent is not in the beam (the root included)
+                    live = true;
+                    words = B.words[s];
+                    if (closed(B, s)) {
+                        acc.b = B.pb[s];
+                        acc.nb = B.pnb[s];
+                        acc.bseq = loop_pos(s, A, -1, 0);
+                        acc.nbseq = loop_pos(s, A, -1, 1);
+                    } else {
+                        const double ms = lae(B.pb[s], B.pnb[s]);
+                        const bool root = B.parent[s] < 0;
+                        for (int q = 0; q < L; ++q) {
+                            const int l = alph[q];
+                            if (lab[l] & 0x100) acc.add_b(pblank + ms, loop_pos(s, A, l, 0));
+                            else if (!root && (lab[l] & 0xff) == B.chr[s]) acc.add_nb(lpd[B.chr[s]] + B.pnb[s], loop_pos(s, A, l, 1));
+                        }
+                    }
+                }
+            }
+            mcur[2 * ent] = acc.b;
+            mcur[2 * ent + 1] = acc.nb;
+            const double total = lae(acc.b, acc.nb);
+            if (live && total > -INFINITY) {               // Counter addition keeps strictly positive masses only
+                const int slot = atomicAdd(&s_count, 1);
+                lsc[slot] = total + beta * log((double)(words + 1));
+                lkey[slot] = acc.bseq != 0x7fffffff ? acc.bseq : BS_NOT_PB + acc.nbseq;
+                lent[slot] = ent;
+            }
+        }
+        __syncthreads();
+        // ---------------------------------------------------------------- P3
+        const int M = s_count;
+        Beam& NB = beams[cur ^ 1];
+        for (int x = tid; x < M; x += BS_THREADS) {
+            const double sx = lsc[x];
+            const int kx = lkey[x];
+            int r = 0;
+            for (int y = 0; y < M && r < k; ++y) {
+                const double sy = lsc[y];
+                r += sy > sx || (sy == sx && lkey[y] < kx);
+            }
+            if (r >= k) continue;
+            const int ent = lent[x];
+            int s, i = -1, c = -1;
+            if (ent < k * A) {
+                i = ent / A;
+                c = ent - i * A;
+                const int mv = mem[ent];
+                s = (mv >> 7) == t + 1 ? (mv & 127) : -1;
+            } else {
+                s = ent - k * A;
+            }
+            if (s >= 0) {
+                NB.node[r] = B.node[s]; NB.parent[r] = B.parent[s]; NB.chr[r] = B.chr[s];
+                NB.words[r] = B.words[s]; NB.len[r] = B.len[s]; NB.prevslot[r] = s;
+            } else {
+                const int par = B.node[i];
+                const uint64_t key = ((uint64_t)par << 8) | (uint64_t)c;
+                uint32_t h = key_hash(key) & (hash_cap - 1);
+                int node = -1;
+                while (node < 0) {                         // probe by claiming: one round trip per slot
+                    const uint64_t cur_key =
+                        atomicCAS((unsigned long long*)&hkeys[h], (unsigned long long)BS_EMPTY, (unsigned long long)key);
+                    if (cur_key == BS_EMPTY) {             // a new string: its node id is reserved by (frame, rank)
+                        node = 1 + t * k + r;
+                        hvals[h] = node;
+                        nd_parent[node] = par;
+                        nd_chr[node] = c;
+                    } else if (cur_key == key) {           // interned in an earlier frame
+                        node = hvals[h];
+                    } else {
+                        h = (h + 1) & (hash_cap - 1);
+                    }
+                }
+                NB.node[r] = node; NB.parent[r] = par; NB.chr[r] = c;
+                NB.words[r] = B.words[i] + ((lab[c] & 0x400) && B.chr[i] >= 0 && (lab[B.chr[i]] & 0x200));
+                NB.len[r] = B.len[i] + 1;
+                NB.prevslot[r] = -1;
+            }
+            NB.pb[r] = mcur[2 * ent];
+            NB.pnb[r] = mcur[2 * ent + 1];
+            NB.score[r] = sx;
+        }
+        if (tid == 0) s_m[cur ^ 1] = min(M, k);
+        __threadfence();                                   // interned nodes are read by other waves in later frames
+        __syncthreads();
+        cur ^= 1;
+    }
+    // ---------------------------------------------------------------- output: backtrack the final beam
+    const int m = s_m[cur];
+    const Beam& B = beams[cur];
+    if (tid < k) {
+        const int64_t o = (int64_t)n * k + tid;
+        if (tid < m) {
+            const int len = B.len[tid];
+            out_score[o] = B.score[tid];
+            out_len[o] = len;
+            int32_t* lab_out = out_labels + o * T;
+            int node = B.node[tid];
+            for (int p = len - 1; p >= 0; --p) {
+                lab_out[p] = nd_chr[node];
+                node = nd_parent[node];
+            }
+        } else {
+            out_score[o] = -INFINITY;
+            out_len[o] = -1;
+        }
+    }
+    if (tid == 0) out_status[n] = s_bad;
+}
+
+int64_t lds_bytes(int k, int A) {
+    const int64_t nE = (int64_t)k * A + k;
+    return nE * (4 * 8 + 8 + 4 + 4) + 2 * (int64_t)k * A * 4;
+}
+
+int hash_capacity(int T, int k) {
+    int64_t need = 2 * ((int64_t)k * T + 1), cap = 1;
+    while (cap < need) cap <<= 1;
+    return (int)cap;
+}
+
+int64_t ws_stride(int T, int k) {
+    const int64_t nodes = (int64_t)k * T + 1;
+    const int64_t bytes = (nodes * 8 + 15) / 16 * 16 + (int64_t)hash_capacity(T, k) * 12;
+    return (bytes + 255) / 256 * 256;
+}
+
+}  // namespace
+
+extern "C" int64_t w2l_ctc_beam_search_workspace_bytes(int N, int T, int k) {
+    if (N <= 0 || T <= 0 || k <= 0 || (int64_t)k * T >= (1 << 29)) return -1;
+    return (int64_t)N * ws_stride(T, k);
+}
+
+extern "C" int w2l_ctc_beam_search(const float* probs, const int32_t* sizes, int N, int T, int A,
+                                   const int32_t* label_info_host, int blank, int end_index, int k, double beta, double prune,
+                                   int log_probs, void* workspace, int64_t workspace_bytes, void* out, void* stream) {
+    W2L_CHECK_ARG(probs && label_info_host && workspace && out && N > 0 && T > 0, "ctc_beam_search: bad arguments");
+    W2L_CHECK_ARG(A >= 1 && A <= BS_AMAX, "ctc_beam_search: %d labels, supported 1..%d", A, BS_AMAX);
+    W2L_CHECK_ARG(k >= 1 && k <= BS_KMAX, "ctc_beam_search: beam width k=%d, supported 1..%d", k, BS_KMAX);
+    W2L_CHECK_ARG(blank >= 0 && blank < A && end_index >= -1 && end_index < A, "ctc_beam_search: blank %d / end %d outside %d labels",
+                  blank, end_index, A);
+    W2L_CHECK_ARG((int64_t)k * T < (1 << 29) && T < (1 << 24), "ctc_beam_search: k*T = %lld too large", (long long)k * T);
+    const int64_t need = w2l_ctc_beam_search_workspace_bytes(N, T, k);
+    W2L_CHECK_ARG(workspace_bytes >= need, "ctc_beam_search: workspace of %lld bytes, %lld needed", (long long)workspace_bytes,
+                  (long long)need);
+    hipFuncAttributes fa;
+    W2L_CHECK_HIP(hipFuncGetAttributes(&fa, (const void*)ctc_beam_search_kernel));
+    const int64_t lds = lds_bytes(k, A);
+    W2L_CHECK_ARG(lds + (int64_t)fa.sharedSizeBytes <= 160 * 1024,
+                  "ctc_beam_search: k=%d with %d labels needs %lld bytes of LDS, the limit is %d (k*(A+1) <= ~3200)", k, A,
+                  (long long)(lds + fa.sharedSizeBytes), 160 * 1024);
+    LabelInfo info;
+    for (int i = 0; i < BS_AMAX; ++i) info.v[i] = 0;
+    for (int i = 0; i < A; ++i) {
+        const int canon = label_info_host[i] & 0xff;
+        W2L_CHECK_ARG(canon <= i && (label_info_host[canon] & 0xff) == canon, "ctc_beam_search: label %d: bad canonical index %d",
+                      i, canon);
+        info.v[i] = label_info_host[i];
+    }
+    if (lds > 64 * 1024)    // (the dynamic share is what the kernel's static state leaves of 160 KiB)
+        W2L_CHECK_HIP(hipFuncSetAttribute((const void*)ctc_beam_search_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                          160 * 1024 - (int)fa.sharedSizeBytes));
+    double* out_score = (double*)out;
+    int32_t* out_len = (int32_t*)(out_score + (int64_t)N * k);
+    int32_t* out_status = out_len + (int64_t)N * k;
+    int32_t* out_labels = out_status + N;
+    hipLaunchKernelGGL(ctc_beam_search_kernel, dim3(N), dim3(BS_THREADS), (size_t)lds, (hipStream_t)stream, probs, sizes, T, A,
+                       info, blank, end_index, k, beta, prune, log_probs, (char*)workspace, ws_stride(T, k),
+                       hash_capacity(T, k), out_score, out_len, out_status, out_labels);
+    W2L_CHECK_LAUNCH();
+    return 0;
+}
