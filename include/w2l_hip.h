@@ -451,6 +451,47 @@ int64_t w2l_ctc_beam_search_workspace_bytes(int N, int T, int k);
 int w2l_ctc_beam_search(const float* probs, const int32_t* sizes, int N, int T, int A, const int32_t* label_info_host,
                         int blank, int end_index, int k, double beta, double prune, int log_probs, void* workspace,
                         int64_t workspace_bytes, void* out, void* stream);
+/* ---- the same search with a word n-gram language model (ngram_lm.ArpaLM; decoder.py:210-212 with lm_weigh) ---- */
+/* Device tables of an ARPA model in reverse-suffix form (see ngram_lm.py).  Entry e of an n-gram: prob[e] (log10, NaN for a
+ * context-only entry that suffix closure inserted), bo[e] (log10 backoff, 0 if none); a unigram's entry is its word id
+ * (<unk> = 0, <s> = 1, </s> = 2).  The entry of h_2 h_1 w is ngram_vals[slot] where ngram_keys[slot] == (entry of h_1 w) << 32
+ * | h_2 (open addressing, linear probing, w2l_ngram_lm_build's hash).  The spelling trie: trie_keys[slot] == node << 8 |
+ * canonical label -> child node trie_vals[slot], root 0, trie_word[node] = the word id the node spells (-1: none).  Limits:
+ * n_entries < 2^30, capacities powers of two in [16, 2^31], at most half full. */
+typedef struct {
+    const float* prob;
+    const float* bo;
+    const uint64_t* ngram_keys;
+    const int32_t* ngram_vals;
+    int64_t ngram_cap;
+    const uint64_t* trie_keys;
+    const int32_t* trie_vals;
+    int64_t trie_cap;
+    const int32_t* trie_word;
+    int32_t n_entries;      /* prob / bo length */
+    int32_t n_words;        /* vocabulary size (the unigram entries) */
+    int32_t n_trie_nodes;   /* trie_word length */
+} w2l_ngram_lm_t;
+/* Insert n keys (each != ~0, distinct) with their values into an open-addressing table of cap slots (a power of two >= 2n),
+ * one CAS per probe; the table is cleared first.  *dups (device int32, not cleared) counts keys found already present. */
+int w2l_ngram_lm_build(const uint64_t* keys, const int32_t* vals, int64_t n, uint64_t* table_keys, int32_t* table_vals,
+                       int64_t cap, int32_t* dups, void* stream);
+/* workspace bytes for w2l_ctc_beam_search_lm (w2l_ctc_beam_search's plus a 64-byte LM state per trie node); -1 if out of
+ * range (order outside 1..6 included) */
+int64_t w2l_ctc_beam_search_lm_workspace_bytes(int N, int T, int k, int order);
+/* w2l_ctc_beam_search with the LM of lm (an order-`order` model, 1 <= order <= 6).  label_info_host as there, plus bit 11:
+ * the label's character is whitespace (only ' ' may be, an error otherwise); space_index: first index of ' ' (-1: none).
+ * Each trie node carries an LM state (the last order-1 word ids and their context backoffs, the float32 sum of the words
+ * closed so far, the spelling-trie node of the partial word: 0 empty, -1 left the trie (scored as <unk>)), computed once when
+ * the node is interned.  The weight of member i, alpha * ln 10 * (log10 of its words with </s>, float32 in ArpaLM.score's
+ * order), multiplies exactly one contribution: E(i, c)'s p * (pb + pnb) where c is the space or end_char, c is not member i's
+ * last character and member i has a character other than ' '.  out: w2l_ctc_beam_search's layout followed by float
+ * lm_log10[N][k], the LM total of each result (0 for an empty slot or a string of spaces).  LDS: 1.5 KB of static state more
+ * than w2l_ctc_beam_search; the same dynamic tables and limits. */
+int w2l_ctc_beam_search_lm(const float* probs, const int32_t* sizes, int N, int T, int A, const int32_t* label_info_host,
+                           int blank, int end_index, int space_index, int k, double alpha, double beta, double prune,
+                           int log_probs, const w2l_ngram_lm_t* lm, int order, void* workspace, int64_t workspace_bytes,
+                           void* out, void* stream);
 /* host-side edit distance over int32 symbol arrays */
 int w2l_levenshtein_host(const int32_t* a_host, int na, const int32_t* b_host, int nb);
 /* ConvCTCASR.add_string_metrics (base_asr_models.py:53-69) for one batch in ONE host call (no device work, no interpreter

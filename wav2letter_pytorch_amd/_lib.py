@@ -53,6 +53,13 @@ class BnFin(C.Structure):
                 ('shift', c_p)]
 
 
+class LmTables(C.Structure):
+    """w2l_ngram_lm_t (include/w2l_hip.h): the device tables of an n-gram language model (ngram_lm.DeviceLM)."""
+    _fields_ = [('prob', c_p), ('bo', c_p), ('ngram_keys', c_p), ('ngram_vals', c_p), ('ngram_cap', C.c_int64),
+                ('trie_keys', c_p), ('trie_vals', c_p), ('trie_cap', C.c_int64), ('trie_word', c_p), ('n_entries', C.c_int32),
+                ('n_words', C.c_int32), ('n_trie_nodes', C.c_int32)]
+
+
 class GradSrc(C.Structure):
     """w2l_gradsrc_t (include/w2l_hip.h)."""
     _fields_ = [('dxp', c_p), ('f32', C.c_int32), ('pad_l', C.c_int32), ('pad_r', C.c_int32),
@@ -133,6 +140,10 @@ _SIGNATURES = {
     'w2l_ctc_beam_search_workspace_bytes': (c_i64, [c_i, c_i, c_i]),
     'w2l_ctc_beam_search': (c_i, [c_p, c_p, c_i, c_i, c_i, c_p, c_i, c_i, c_i, C.c_double, C.c_double, c_i, c_p, c_i64, c_p,
                                   c_p]),
+    'w2l_ngram_lm_build': (c_i, [c_p, c_p, c_i64, c_p, c_p, c_i64, c_p, c_p]),
+    'w2l_ctc_beam_search_lm_workspace_bytes': (c_i64, [c_i, c_i, c_i, c_i]),
+    'w2l_ctc_beam_search_lm': (c_i, [c_p, c_p, c_i, c_i, c_i, c_p, c_i, c_i, c_i, c_i, C.c_double, C.c_double, C.c_double, c_i,
+                                     C.POINTER(LmTables), c_i, c_p, c_i64, c_p, c_p]),
     'w2l_logmel': (c_i, [c_p, c_p, c_p, c_f, c_f, c_i, c_i64, c_p, c_i, c_i, c_i, c_p, c_p, c_i, c_i, c_f, c_p, c_i, c_p]),
     'w2l_feature_normalize': (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_p, c_p, c_p, c_p]),
     'w2l_zero_rects': (c_i, [c_p, c_i, c_i, c_i, c_p, c_i, c_p]),
@@ -245,7 +256,8 @@ TRACE_NAMES = {
     'w2l_nct_to_ntc': 'nct_to_ntc_kernel', 'w2l_pad_cast': 'pad_cast_kernel', 'w2l_quantize_e4m3': 'quantize_e4m3',
     'w2l_quantize_e4m3_dyn': 'quantize_e4m3_dyn', 'w2l_dwconv_fwd': 'dw_fwd_kernel', 'w2l_dwconv_dgrad': 'dw_dgrad_kernel',
     'w2l_dwconv_wgrad': 'dw_wgrad_kernel', 'w2l_argmax': 'argmax_kernel', 'w2l_novograd_pack': 'novograd_pack_kernel',
-    'w2l_ctc_beam_search': 'ctc_beam_search_kernel',
+    'w2l_ctc_beam_search': 'ctc_beam_search_kernel', 'w2l_ctc_beam_search_lm': 'ctc_beam_search_kernel<LM>',
+    'w2l_ngram_lm_build': 'ngram_insert_kernel',
 }
 _trace = {'rows': None, 'saved': {}, 'pool': []}
 

@@ -8,7 +8,9 @@ when a word is closed (space or end char) with weight ``alpha``, ranking multipl
 strictly positive masses survive a step, ties keep first-seen order.
 
 prefix_beam_search_gpu / GPUPrefixBeamSearchDecoder run the same recursion without a language model as one HIP launch per
-batch (w2l_ctc_beam_search, csrc/beam_search.hip), in fp64 logs."""
+batch (w2l_ctc_beam_search, csrc/beam_search.hip), in fp64 logs; with an ARPA n-gram model (ngram_lm.ArpaLM: ``lm=`` of
+prefix_beam_search_gpu, GPUPrefixBeamSearchLMDecoder) the same launch scores words on the device (w2l_ctc_beam_search_lm)
+as the host does with ``lm=lambda s: 10 ** arpa.score(s)``."""
 from __future__ import annotations
 
 import ctypes as C
@@ -160,9 +162,10 @@ def _label_info(labels: Sequence[str], blank_index: int, end_char: str):
     return info, first_index.get(end_char, -1)
 
 
-def _beam_search_device(probs, labels, blank_index, k, beta, prune, end_char, sizes, log_probs):
+def _beam_search_device(probs, labels, blank_index, k, beta, prune, end_char, sizes, log_probs, lm=None, alpha=0.3):
     """one launch of w2l_ctc_beam_search for probs [N, T, A] on the current stream; returns the host arrays
-    (scores [N, k], lengths [N, k], labels [N, k, T])"""
+    (scores [N, k], lengths [N, k], labels [N, k, T]).  With ``lm`` (an ngram_lm.ArpaLM) one launch of
+    w2l_ctc_beam_search_lm, and a fourth array: lm_log10 [N, k] float32, the LM total of each result."""
     if probs.dim() != 3:
         raise ValueError('expected [N, T, labels] or [T, labels] posteriors, got shape %s' % (tuple(probs.shape),))
     n, t, a = probs.shape
@@ -187,6 +190,8 @@ def _beam_search_device(probs, labels, blank_index, k, beta, prune, end_char, si
         if bool((host < 2).any()) or bool((host > t).any()):
             raise ValueError('sizes must lie in [2, %d], got %s' % (t, host.tolist()))
         sz = host.to(torch.int32).to(dev, non_blocking=True)
+    if lm is not None:
+        return _beam_search_device_lm(x, sz, labels, info, blank_index, end_index, k, alpha, beta, prune, log_probs, lm)
     ws_bytes = int(lib.w2l_ctc_beam_search_workspace_bytes(n, t, k))
     if ws_bytes < 0:
         raise ValueError('prefix_beam_search_gpu: k=%d with T=%d is out of range' % (k, t))
@@ -206,11 +211,46 @@ def _beam_search_device(probs, labels, blank_index, k, beta, prune, end_char, si
     return scores, lengths, idx
 
 
+def _beam_search_device_lm(x, sz, labels, info, blank_index, end_index, k, alpha, beta, prune, log_probs, lm):
+    """_beam_search_device's launch of w2l_ctc_beam_search_lm (x, sz already on the device)"""
+    from .ngram_lm import ArpaLM
+    if not isinstance(lm, ArpaLM):
+        raise TypeError('lm must be an ngram_lm.ArpaLM, got %s' % type(lm).__name__)
+    odd = [ch for ch in labels if ch.isspace() and ch != ' ']
+    if odd:
+        raise ValueError('prefix_beam_search_gpu: whitespace labels other than a space (%r) cannot be scored by a word LM' % odd)
+    n, t, a = x.shape
+    dev = x.device
+    info = info | np.array([ch.isspace() << 11 for ch in labels], dtype=np.int32)
+    space_index = labels.index(' ') if ' ' in labels else -1
+    tables = lm.to_device(labels, blank_index, dev)
+    ws_bytes = int(lib.w2l_ctc_beam_search_lm_workspace_bytes(n, t, k, lm.order))
+    if ws_bytes < 0:
+        raise ValueError('prefix_beam_search_gpu: k=%d with T=%d (LM order %d) is out of range' % (k, t, lm.order))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    out = torch.empty(12 * n * k + 4 * n + 4 * n * k * t + 4 * n * k, dtype=torch.uint8, device=dev)
+    check(lib.w2l_ctc_beam_search_lm(ptr(x), ptr(sz), n, t, a, info.ctypes.data_as(C.c_void_p), int(blank_index),
+                                     int(end_index), space_index, int(k), float(alpha), float(beta), float(prune),
+                                     int(bool(log_probs)), tables.desc_ref, lm.order, ptr(ws), ws_bytes, ptr(out), stream_ptr()),
+          'w2l_ctc_beam_search_lm')
+    host = out.cpu().numpy()                           # the one copy to the host
+    scores = host[:8 * n * k].view(np.float64).reshape(n, k)
+    rest = host[8 * n * k:].view(np.int32)
+    lengths = rest[:n * k].reshape(n, k)
+    status = rest[n * k:n * k + n]
+    idx = rest[n * k + n:n * k + n + n * k * t].reshape(n, k, t)
+    lm_log10 = rest[n * k + n + n * k * t:].view(np.float32).reshape(n, k)
+    if status.any():
+        raise ValueError('ctc output contains negative numbers (utterances %s)' % np.nonzero(status)[0].tolist())
+    return scores, lengths, idx, lm_log10
+
+
 def prefix_beam_search_gpu(probs, labels: Sequence[str], blank_index: int = 0, k: int = 5, beta: float = 5,
                            prune: float = 0.001, end_char: str = '>', sizes=None, log_probs: bool = False, nbest: int = 1,
-                           return_weights: bool = False):
-    """prefix_beam_search without a language model, on the MI355X: one launch for a whole batch, masses as fp64 logs (no
-    underflow on long utterances; the host function's float32 products do underflow), the host's candidate order and ties.
+                           return_weights: bool = False, lm=None, alpha: float = 0.3):
+    """prefix_beam_search on the MI355X: one launch for a whole batch, masses as fp64 logs (no underflow on long
+    utterances; the host function's float32 products do underflow), the host's candidate order and ties.  ``lm``: an
+    ngram_lm.ArpaLM scored as the host's ``lm=lambda s: 10 ** lm.score(s)`` with weight ``alpha`` (None: no LM).
 
     probs: [T, labels] or [N, T, labels] (numpy or torch, any device; probabilities, or log-probabilities if ``log_probs``);
     ``sizes[n]``: decode only the first sizes[n] frames of utterance n (default: all T).  Per utterance the result is the best
@@ -226,7 +266,11 @@ def prefix_beam_search_gpu(probs, labels: Sequence[str], blank_index: int = 0, k
         x = x.unsqueeze(0)
         if sizes is not None:
             sizes = [int(np.asarray(sizes).reshape(-1)[0])]
-    scores, lengths, idx = _beam_search_device(x, labels, blank_index, k, beta, prune, end_char, sizes, log_probs)
+    if lm is None:
+        scores, lengths, idx = _beam_search_device(x, labels, blank_index, k, beta, prune, end_char, sizes, log_probs)
+    else:
+        scores, lengths, idx, _ = _beam_search_device(x, labels, blank_index, k, beta, prune, end_char, sizes, log_probs,
+                                                      lm=lm, alpha=alpha)
     results = []
     for u in range(scores.shape[0]):
         found = [(''.join(labels[j] for j in idx[u, r, :lengths[u, r]]), float(scores[u, r]))
@@ -262,6 +306,27 @@ class GPUPrefixBeamSearchDecoder(Decoder):
                                '[Frames X Labels]' % str(tuple(probs.shape)))
         return prefix_beam_search_gpu(probs, self.labels, self.blank_index, self.k, self.beta, self.prune, sizes=sizes,
                                       log_probs=self.log_probs)
+
+
+class GPUPrefixBeamSearchLMDecoder(Decoder):
+    """PrefixBeamSearchLMDecoder on the MI355X with an ARPA n-gram model read without kenlm (ngram_lm.ArpaLM, plain or
+    .gz): the reference decoder's constructor (plus ``log_probs``); a falsy ``lm_path`` decodes without an LM."""
+
+    def __init__(self, lm_path, labels, blank_index=0, k=5, alpha=0.3, beta=5, prune=1e-3, log_probs=False):
+        super(GPUPrefixBeamSearchLMDecoder, self).__init__(labels, blank_index)
+        from .ngram_lm import ArpaLM
+        self.lm = ArpaLM(lm_path) if lm_path else None
+        self.k, self.alpha, self.beta, self.prune, self.log_probs = k, alpha, beta, prune, log_probs
+
+    def decode(self, probs, sizes=None, return_offsets=False):
+        """[N, T, labels] -> N strings (utterance n over its first sizes[n] frames); [T, labels] -> one string"""
+        if return_offsets:
+            raise NotImplementedError("Prefix beam search does not support offsets (yet).")
+        if len(probs.shape) not in (2, 3):
+            raise RuntimeError('Decoding with wrong shape: %s, expected either [Batch X Frames X Labels] or '
+                               '[Frames X Labels]' % str(tuple(probs.shape)))
+        return prefix_beam_search_gpu(probs, self.labels, self.blank_index, self.k, self.beta, self.prune, sizes=sizes,
+                                      log_probs=self.log_probs, lm=self.lm, alpha=self.alpha)
 
 
 def get_time_per_word(predictions, offsets, ratio=1.0):

@@ -19,7 +19,12 @@
 //   P3  one thread per live candidate: rank by counting the candidates ahead of it (score, then first insertion);
 //       the k first become the next beam, new members are interned
 // LDS holds two frames of entry masses plus the live-candidate list (see lds_bytes); limits in w2l_hip.h.
+//
+// With a language model (LM = true, w2l_ctc_beam_search_lm): every trie node also carries an LM state (NodeLM, after the
+// intern table in the workspace), computed once by the P3 thread that interns the node from its parent's state and its
+// character.  P2 adds a member's LM weight to the one contribution the host weights (parent_part, a word-closing label).
 #include "common.h"
+#include "../../include/w2l_hip.h"
 #include <math.h>
 
 namespace {
@@ -60,12 +65,123 @@ struct Beam {                         // one frame's beam, slot-indexed
 
 __device__ __forceinline__ uint32_t key_hash(uint64_t key) { return (uint32_t)((key * 0x9E3779B97F4A7C15ull) >> 32); }
 
+// ------------------------------------------------------------------------------------------------------- language model
+constexpr int LM_MAXORDER = 6;
+constexpr int LM_EOS = 2;                     // word ids: <unk> 0, <s> 1, </s> 2
+
+struct LmArgs {                               // w2l_ngram_lm_t on the device, plus the search's LM parameters
+    const float* prob;
+    const float* bo;
+    const uint64_t* nkeys;
+    const int32_t* nvals;
+    const uint64_t* tkeys;
+    const int32_t* tvals;
+    const int32_t* tword;
+    uint32_t nmask, tmask;
+    int order, space;
+    double alpha_ln10;
+    int64_t state_off;                        // byte offset of the NodeLM array in an utterance's workspace
+};
+
+struct NodeLM {                               // 64 bytes per trie node
+    int32_t ctx[LM_MAXORDER - 1];             // the last m words, most recent first
+    float bo[LM_MAXORDER - 1];                // log10 backoff of the context ctx[L-1] .. ctx[0] (0: absent)
+    int32_t m;
+    float done;                               // float32 sum of the closed words' log10 q
+    int32_t trie;                             // spelling-trie node of the partial word: 0 empty, -1 off the trie
+    int32_t nonspace;                         // the string has a character other than ' '
+    float total;                              // log10 of the string's words with </s> (0 if !nonspace)
+    int32_t pad_;
+};
+
+__device__ __forceinline__ int tab_find(const uint64_t* keys, const int32_t* vals, uint32_t mask, uint64_t key) {
+    uint32_t h = key_hash(key) & mask;
+    for (;;) {                                // at most half full: an empty slot ends every probe sequence
+        const uint64_t kk = keys[h];
+        if (kk == key) return vals[h];
+        if (kk == BS_EMPTY) return -1;
+        h = (h + 1) & mask;
+    }
+}
+
+// log10 q(w | s) (ngram_lm.ArpaLM.q) by the reverse-suffix walk w, h_1 w, h_2 h_1 w, ...; with nx, also the state after w
+__device__ float lm_word(const LmArgs& L, const NodeLM& s, int w, NodeLM* nx) {
+    int e = w;
+    float prob = L.prob[e];
+    float nbo[LM_MAXORDER];
+    nbo[0] = L.bo[e];
+    int j = 0, depth = 1;
+    bool alive = true;
+#pragma unroll
+    for (int i = 0; i < LM_MAXORDER - 1; ++i) {
+        if (alive && i < s.m) {
+            const int e2 = tab_find(L.nkeys, L.nvals, L.nmask, ((uint64_t)e << 32) | (uint32_t)s.ctx[i]);
+            if (e2 < 0) {
+                alive = false;
+            } else {
+                e = e2;
+                depth = i + 2;
+                const float p = L.prob[e];
+                if (p == p) { prob = p; j = i + 1; }       // NaN: a context-only entry
+                nbo[i + 1] = L.bo[e];
+            }
+        }
+    }
+    float q = prob;
+#pragma unroll
+    for (int i = 0; i < LM_MAXORDER - 1; ++i)
+        if (i >= j && i < s.m) q += s.bo[i];               // increasing context length, float32
+    if (nx) {
+        const int m2 = min(s.m + 1, L.order - 1);
+#pragma unroll
+        for (int i = LM_MAXORDER - 2; i >= 1; --i) nx->ctx[i] = i < m2 ? s.ctx[i - 1] : 0;
+        nx->ctx[0] = w;
+#pragma unroll
+        for (int i = 0; i < LM_MAXORDER - 1; ++i) nx->bo[i] = i < m2 && i < depth ? nbo[i] : 0.f;
+        nx->m = m2;
+    }
+    return q;
+}
+
+// the LM state of the node (parent state s) + canonical label c
+__device__ NodeLM lm_extend(const LmArgs& L, const NodeLM& s, int c, int endc) {
+    NodeLM ns = s;
+    if (c == L.space || c == endc) {
+        if (s.trie != 0) {                                 // a word closes (a partial word off the trie is <unk>)
+            int wid = s.trie > 0 ? L.tword[s.trie] : -1;
+            const float q = lm_word(L, s, wid < 0 ? 0 : wid, &ns);
+            ns.done = s.done + q;
+            ns.trie = 0;
+        }
+        if (c == endc) ns.nonspace = 1;                    // (a closed string is never extended: this only shows in lm_log10)
+    } else {
+        ns.nonspace = 1;
+        ns.trie = s.trie >= 0 ? tab_find(L.tkeys, L.tvals, L.tmask, ((uint64_t)s.trie << 8) | (uint64_t)c) : -1;
+    }
+    float total = 0.f;
+    if (ns.nonspace) {
+        if (ns.trie == 0) {
+            total = ns.done + lm_word(L, ns, LM_EOS, nullptr);
+        } else {
+            const int wid = ns.trie > 0 ? L.tword[ns.trie] : -1;
+            NodeLM tmp;
+            const float d = ns.done + lm_word(L, ns, wid < 0 ? 0 : wid, &tmp);
+            total = d + lm_word(L, tmp, LM_EOS, nullptr);
+        }
+    }
+    ns.total = total;
+    return ns;
+}
+
+template <bool LM>
 __global__ __launch_bounds__(BS_THREADS) void ctc_beam_search_kernel(
     const float* __restrict__ probs, const int32_t* __restrict__ sizes, int T, int A, LabelInfo info, int blank, int endc,
     int k, double beta, double prune, int log_probs, char* __restrict__ ws, int64_t ws_per_utt, int hash_cap,
     double* __restrict__ out_score, int32_t* __restrict__ out_len, int32_t* __restrict__ out_status,
-    int32_t* __restrict__ out_labels) {
+    int32_t* __restrict__ out_labels, LmArgs lmargs, float* __restrict__ out_lm) {
     __shared__ Beam beams[2];
+    __shared__ double lm_w[2][LM ? BS_KMAX : 1];          // LM weight (natural log) of each beam slot
+    __shared__ int lm_on[2][LM ? BS_KMAX : 1];             // ... and whether it applies (a non-space character)
     __shared__ double lpd[BS_AMAX];
     __shared__ int alph[BS_AMAX], act[BS_AMAX], lab[BS_AMAX];
     __shared__ int s_m[2], s_nalph, s_count, s_bad;
@@ -85,6 +201,7 @@ __global__ __launch_bounds__(BS_THREADS) void ctc_beam_search_kernel(
     int32_t* nd_chr = nd_parent + ((int64_t)k * T + 1);
     uint64_t* hkeys = (uint64_t*)(wsn + (((int64_t)k * T + 1) * 8 + 15) / 16 * 16);
     int32_t* hvals = (int32_t*)(hkeys + hash_cap);
+    NodeLM* nd_lm = (NodeLM*)(wsn + lmargs.state_off);    // LM only
 
     for (int i = tid; i < hash_cap; i += BS_THREADS) hkeys[i] = BS_EMPTY;
     for (int i = tid; i < 2 * k * A; i += BS_THREADS) mem[i] = 0;         // mem and redir: stamp 0 never matches
@@ -95,6 +212,16 @@ __global__ __launch_bounds__(BS_THREADS) void ctc_beam_search_kernel(
         Beam& b0 = beams[0];
         b0.node[0] = 0; b0.parent[0] = -1; b0.chr[0] = -1; b0.words[0] = 0; b0.len[0] = 0; b0.prevslot[0] = -1;
         b0.pb[0] = 0.0; b0.pnb[0] = -INFINITY; b0.score[0] = 0.0;
+        if constexpr (LM) {
+            NodeLM r;                                      // the root: context <s>
+            for (int i = 0; i < LM_MAXORDER - 1; ++i) { r.ctx[i] = 0; r.bo[i] = 0.f; }
+            r.m = min(1, lmargs.order - 1);
+            if (r.m > 0) { r.ctx[0] = 1; r.bo[0] = lmargs.bo[1]; }
+            r.done = 0.f; r.trie = 0; r.nonspace = 0; r.total = 0.f; r.pad_ = 0;
+            nd_lm[0] = r;
+            lm_w[0][0] = 0.0;
+            lm_on[0][0] = 0;
+        }
         s_m[0] = 1;
         s_m[1] = 0;
         s_bad = 0;
@@ -201,7 +328,13 @@ __global__ __launch_bounds__(BS_THREADS) void ctc_beam_search_kernel(
                         for (int q = 0; q < L; ++q) {
                             const int l = alph[q];
                             if ((lab[l] & 0xff) != c || (lab[l] & 0x100)) continue;
-                            acc.add_nb(p + lin, loop_pos(i, A, l, 0));
+                            if constexpr (LM) {        // a word closes: the member's LM weight (decoder.py:210-212)
+                                double v = p + lin;
+                                if (!rep && (c == lmargs.space || c == endc) && lm_on[cur][i]) v += lm_w[cur][i];
+                                acc.add_nb(v, loop_pos(i, A, l, 0));
+                            } else {
+                                acc.add_nb(p + lin, loop_pos(i, A, l, 0));
+                            }
                             if (s < 0) {                   // the extension fell off the beam: last frame's mass joins
                                 acc.add_b(pblank + fb, loop_pos(i, A, l, 2));
                                 acc.add_nb(p + fnb, loop_pos(i, A, l, 3));
@@ -288,6 +421,7 @@ __global__ __launch_bounds__(BS_THREADS) void ctc_beam_search_kernel(
             if (s >= 0) {
                 NB.node[r] = B.node[s]; NB.parent[r] = B.parent[s]; NB.chr[r] = B.chr[s];
                 NB.words[r] = B.words[s]; NB.len[r] = B.len[s]; NB.prevslot[r] = s;
+                if constexpr (LM) { lm_w[cur ^ 1][r] = lm_w[cur][s]; lm_on[cur ^ 1][r] = lm_on[cur][s]; }
             } else {
                 const int par = B.node[i];
                 const uint64_t key = ((uint64_t)par << 8) | (uint64_t)c;
@@ -301,8 +435,18 @@ __global__ __launch_bounds__(BS_THREADS) void ctc_beam_search_kernel(
                         hvals[h] = node;
                         nd_parent[node] = par;
                         nd_chr[node] = c;
+                        if constexpr (LM) {
+                            const NodeLM ns = lm_extend(lmargs, nd_lm[par], c, endc);
+                            nd_lm[node] = ns;
+                            lm_w[cur ^ 1][r] = lmargs.alpha_ln10 * (double)ns.total;
+                            lm_on[cur ^ 1][r] = ns.nonspace;
+                        }
                     } else if (cur_key == key) {           // interned in an earlier frame
                         node = hvals[h];
+                        if constexpr (LM) {
+                            lm_w[cur ^ 1][r] = lmargs.alpha_ln10 * (double)nd_lm[node].total;
+                            lm_on[cur ^ 1][r] = nd_lm[node].nonspace;
+                        }
                     } else {
                         h = (h + 1) & (hash_cap - 1);
                     }
@@ -330,6 +474,7 @@ __global__ __launch_bounds__(BS_THREADS) void ctc_beam_search_kernel(
             const int len = B.len[tid];
             out_score[o] = B.score[tid];
             out_len[o] = len;
+            if constexpr (LM) out_lm[o] = nd_lm[B.node[tid]].total;
             int32_t* lab_out = out_labels + o * T;
             int node = B.node[tid];
             for (int p = len - 1; p >= 0; --p) {
@@ -339,6 +484,7 @@ __global__ __launch_bounds__(BS_THREADS) void ctc_beam_search_kernel(
         } else {
             out_score[o] = -INFINITY;
             out_len[o] = -1;
+            if constexpr (LM) out_lm[o] = 0.f;
         }
     }
     if (tid == 0) out_status[n] = s_bad;
@@ -368,42 +514,140 @@ extern "C" int64_t w2l_ctc_beam_search_workspace_bytes(int N, int T, int k) {
     return (int64_t)N * ws_stride(T, k);
 }
 
-extern "C" int w2l_ctc_beam_search(const float* probs, const int32_t* sizes, int N, int T, int A,
-                                   const int32_t* label_info_host, int blank, int end_index, int k, double beta, double prune,
-                                   int log_probs, void* workspace, int64_t workspace_bytes, void* out, void* stream) {
-    W2L_CHECK_ARG(probs && label_info_host && workspace && out && N > 0 && T > 0, "ctc_beam_search: bad arguments");
-    W2L_CHECK_ARG(A >= 1 && A <= BS_AMAX, "ctc_beam_search: %d labels, supported 1..%d", A, BS_AMAX);
-    W2L_CHECK_ARG(k >= 1 && k <= BS_KMAX, "ctc_beam_search: beam width k=%d, supported 1..%d", k, BS_KMAX);
-    W2L_CHECK_ARG(blank >= 0 && blank < A && end_index >= -1 && end_index < A, "ctc_beam_search: blank %d / end %d outside %d labels",
-                  blank, end_index, A);
-    W2L_CHECK_ARG((int64_t)k * T < (1 << 29) && T < (1 << 24), "ctc_beam_search: k*T = %lld too large", (long long)k * T);
-    const int64_t need = w2l_ctc_beam_search_workspace_bytes(N, T, k);
-    W2L_CHECK_ARG(workspace_bytes >= need, "ctc_beam_search: workspace of %lld bytes, %lld needed", (long long)workspace_bytes,
-                  (long long)need);
+namespace {
+
+// the checks and the launch shared by both entry points (ws_per_utt: the workspace stride of one utterance)
+template <bool LM>
+int launch_search(const char* name, const float* probs, const int32_t* sizes, int N, int T, int A, const int32_t* label_info_host,
+                  int blank, int end_index, int k, double beta, double prune, int log_probs, void* workspace,
+                  int64_t workspace_bytes, int64_t need, int64_t ws_per_utt, void* out, const LmArgs& lm, void* stream) {
+    W2L_CHECK_ARG(probs && label_info_host && workspace && out && N > 0 && T > 0, "%s: bad arguments", name);
+    W2L_CHECK_ARG(A >= 1 && A <= BS_AMAX, "%s: %d labels, supported 1..%d", name, A, BS_AMAX);
+    W2L_CHECK_ARG(k >= 1 && k <= BS_KMAX, "%s: beam width k=%d, supported 1..%d", name, k, BS_KMAX);
+    W2L_CHECK_ARG(blank >= 0 && blank < A && end_index >= -1 && end_index < A, "%s: blank %d / end %d outside %d labels",
+                  name, blank, end_index, A);
+    W2L_CHECK_ARG((int64_t)k * T < (1 << 29) && T < (1 << 24), "%s: k*T = %lld too large", name, (long long)k * T);
+    W2L_CHECK_ARG(need > 0 && workspace_bytes >= need, "%s: workspace of %lld bytes, %lld needed", name,
+                  (long long)workspace_bytes, (long long)need);
+    const void* kern = (const void*)ctc_beam_search_kernel<LM>;
     hipFuncAttributes fa;
-    W2L_CHECK_HIP(hipFuncGetAttributes(&fa, (const void*)ctc_beam_search_kernel));
+    W2L_CHECK_HIP(hipFuncGetAttributes(&fa, kern));
     const int64_t lds = lds_bytes(k, A);
     W2L_CHECK_ARG(lds + (int64_t)fa.sharedSizeBytes <= 160 * 1024,
-                  "ctc_beam_search: k=%d with %d labels needs %lld bytes of LDS, the limit is %d (k*(A+1) <= ~3200)", k, A,
+                  "%s: k=%d with %d labels needs %lld bytes of LDS, the limit is %d (k*(A+1) <= ~3200)", name, k, A,
                   (long long)(lds + fa.sharedSizeBytes), 160 * 1024);
     LabelInfo info;
     for (int i = 0; i < BS_AMAX; ++i) info.v[i] = 0;
     for (int i = 0; i < A; ++i) {
         const int canon = label_info_host[i] & 0xff;
-        W2L_CHECK_ARG(canon <= i && (label_info_host[canon] & 0xff) == canon, "ctc_beam_search: label %d: bad canonical index %d",
+        W2L_CHECK_ARG(canon <= i && (label_info_host[canon] & 0xff) == canon, "%s: label %d: bad canonical index %d", name,
                       i, canon);
         info.v[i] = label_info_host[i];
     }
     if (lds > 64 * 1024)    // (the dynamic share is what the kernel's static state leaves of 160 KiB)
-        W2L_CHECK_HIP(hipFuncSetAttribute((const void*)ctc_beam_search_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                          160 * 1024 - (int)fa.sharedSizeBytes));
+        W2L_CHECK_HIP(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - (int)fa.sharedSizeBytes));
     double* out_score = (double*)out;
     int32_t* out_len = (int32_t*)(out_score + (int64_t)N * k);
     int32_t* out_status = out_len + (int64_t)N * k;
     int32_t* out_labels = out_status + N;
-    hipLaunchKernelGGL(ctc_beam_search_kernel, dim3(N), dim3(BS_THREADS), (size_t)lds, (hipStream_t)stream, probs, sizes, T, A,
-                       info, blank, end_index, k, beta, prune, log_probs, (char*)workspace, ws_stride(T, k),
-                       hash_capacity(T, k), out_score, out_len, out_status, out_labels);
+    float* out_lm = LM ? (float*)(out_labels + (int64_t)N * k * T) : nullptr;
+    hipLaunchKernelGGL(ctc_beam_search_kernel<LM>, dim3(N), dim3(BS_THREADS), (size_t)lds, (hipStream_t)stream, probs, sizes, T,
+                       A, info, blank, end_index, k, beta, prune, log_probs, (char*)workspace, ws_per_utt, hash_capacity(T, k),
+                       out_score, out_len, out_status, out_labels, lm, out_lm);
     W2L_CHECK_LAUNCH();
     return 0;
+}
+
+__global__ void ngram_insert_kernel(const uint64_t* __restrict__ keys, const int32_t* __restrict__ vals, int64_t n,
+                                    uint64_t* __restrict__ tkeys, int32_t* __restrict__ tvals, uint32_t mask,
+                                    int32_t* __restrict__ dups) {
+    for (int64_t x = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; x < n; x += (int64_t)gridDim.x * blockDim.x) {
+        const uint64_t key = keys[x];
+        uint32_t h = key_hash(key) & mask;
+        for (;;) {
+            const uint64_t prev =
+                atomicCAS((unsigned long long*)&tkeys[h], (unsigned long long)BS_EMPTY, (unsigned long long)key);
+            if (prev == BS_EMPTY) { tvals[h] = vals[x]; break; }
+            if (prev == key) { atomicAdd(dups, 1); break; }
+            h = (h + 1) & mask;
+        }
+    }
+}
+
+int64_t lm_state_offset(int T, int k) { return ws_stride(T, k); }
+
+int64_t lm_ws_stride(int T, int k) {
+    const int64_t bytes = lm_state_offset(T, k) + ((int64_t)k * T + 1) * (int64_t)sizeof(NodeLM);
+    return (bytes + 255) / 256 * 256;
+}
+
+bool pow2_cap(int64_t cap) { return cap >= 16 && cap <= (1ll << 31) && (cap & (cap - 1)) == 0; }
+
+}  // namespace
+
+extern "C" int w2l_ctc_beam_search(const float* probs, const int32_t* sizes, int N, int T, int A,
+                                   const int32_t* label_info_host, int blank, int end_index, int k, double beta, double prune,
+                                   int log_probs, void* workspace, int64_t workspace_bytes, void* out, void* stream) {
+    return launch_search<false>("ctc_beam_search", probs, sizes, N, T, A, label_info_host, blank, end_index, k, beta, prune,
+                                log_probs, workspace, workspace_bytes, w2l_ctc_beam_search_workspace_bytes(N, T, k),
+                                ws_stride(T, k), out, LmArgs{}, stream);
+}
+
+extern "C" int w2l_ngram_lm_build(const uint64_t* keys, const int32_t* vals, int64_t n, uint64_t* table_keys, int32_t* table_vals,
+                                  int64_t cap, int32_t* dups, void* stream) {
+    W2L_CHECK_ARG(n >= 0 && table_keys && table_vals && dups && (n == 0 || (keys && vals)), "ngram_lm_build: bad arguments");
+    W2L_CHECK_ARG(pow2_cap(cap) && cap >= 2 * n, "ngram_lm_build: capacity %lld for %lld keys (a power of two in [16, 2^31], "
+                  ">= 2n)", (long long)cap, (long long)n);
+    W2L_CHECK_HIP(hipMemsetAsync(table_keys, 0xff, (size_t)cap * 8, (hipStream_t)stream));
+    W2L_CHECK_HIP(hipMemsetAsync(table_vals, 0xff, (size_t)cap * 4, (hipStream_t)stream));
+    if (n == 0) return 0;
+    const int blocks = (int)std::min<int64_t>((n + 255) / 256, 4096);
+    hipLaunchKernelGGL(ngram_insert_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, keys, vals, n, table_keys,
+                       table_vals, (uint32_t)(cap - 1), dups);
+    W2L_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int64_t w2l_ctc_beam_search_lm_workspace_bytes(int N, int T, int k, int order) {
+    if (N <= 0 || T <= 0 || k <= 0 || (int64_t)k * T >= (1 << 29) || order < 1 || order > LM_MAXORDER) return -1;
+    return (int64_t)N * lm_ws_stride(T, k);
+}
+
+extern "C" int w2l_ctc_beam_search_lm(const float* probs, const int32_t* sizes, int N, int T, int A,
+                                      const int32_t* label_info_host, int blank, int end_index, int space_index, int k,
+                                      double alpha, double beta, double prune, int log_probs, const w2l_ngram_lm_t* lm,
+                                      int order, void* workspace, int64_t workspace_bytes, void* out, void* stream) {
+    W2L_CHECK_ARG(lm && label_info_host && A >= 1 && A <= BS_AMAX, "ctc_beam_search_lm: bad arguments");
+    W2L_CHECK_ARG(order >= 1 && order <= LM_MAXORDER, "ctc_beam_search_lm: order %d, supported 1..%d", order, LM_MAXORDER);
+    W2L_CHECK_ARG(space_index >= -1 && space_index < A && (space_index < 0 || (label_info_host[space_index] & 0xff) == space_index),
+                  "ctc_beam_search_lm: space index %d is not the first index of a label", space_index);
+    for (int i = 0; i < A; ++i)
+        W2L_CHECK_ARG(!(label_info_host[i] & 0x800) || (label_info_host[i] & 0xff) == space_index,
+                      "ctc_beam_search_lm: label %d is whitespace other than ' '", i);
+    W2L_CHECK_ARG(lm->prob && lm->bo && lm->ngram_keys && lm->ngram_vals && lm->trie_keys && lm->trie_vals && lm->trie_word,
+                  "ctc_beam_search_lm: a table pointer is NULL");
+    W2L_CHECK_ARG(lm->n_words >= 3 && lm->n_entries >= lm->n_words && lm->n_entries < (1 << 30) && lm->n_trie_nodes >= 1,
+                  "ctc_beam_search_lm: %d entries, %d words, %d trie nodes (3 <= words <= entries < 2^30)", lm->n_entries,
+                  lm->n_words, lm->n_trie_nodes);
+    W2L_CHECK_ARG(pow2_cap(lm->ngram_cap) && lm->ngram_cap >= 2 * (int64_t)(lm->n_entries - lm->n_words) && pow2_cap(lm->trie_cap)
+                      && lm->trie_cap >= 2 * (int64_t)(lm->n_trie_nodes - 1),
+                  "ctc_beam_search_lm: table capacities %lld / %lld (powers of two in [16, 2^31], at most half full)",
+                  (long long)lm->ngram_cap, (long long)lm->trie_cap);
+    LmArgs a;
+    a.prob = lm->prob;
+    a.bo = lm->bo;
+    a.nkeys = lm->ngram_keys;
+    a.nvals = lm->ngram_vals;
+    a.tkeys = lm->trie_keys;
+    a.tvals = lm->trie_vals;
+    a.tword = lm->trie_word;
+    a.nmask = (uint32_t)(lm->ngram_cap - 1);
+    a.tmask = (uint32_t)(lm->trie_cap - 1);
+    a.order = order;
+    a.space = space_index;
+    a.alpha_ln10 = alpha * 2.302585092994045684;
+    a.state_off = lm_state_offset(T, k);
+    return launch_search<true>("ctc_beam_search_lm", probs, sizes, N, T, A, label_info_host, blank, end_index, k, beta, prune,
+                               log_probs, workspace, workspace_bytes, w2l_ctc_beam_search_lm_workspace_bytes(N, T, k, order),
+                               lm_ws_stride(T, k), out, a, stream);
 }

@@ -152,7 +152,7 @@ class GreedyDecoder(Decoder):
 def __getattr__(name):
     """the device beam-search decoder lives in beam_search.py, which imports this module: resolve it lazily so that
     ``_target_: decoder.GPUPrefixBeamSearchDecoder`` (config.instantiate's alias of ``decoder``) finds it"""
-    if name in ('GPUPrefixBeamSearchDecoder', 'prefix_beam_search_gpu'):
+    if name in ('GPUPrefixBeamSearchDecoder', 'GPUPrefixBeamSearchLMDecoder', 'prefix_beam_search_gpu'):
         from . import beam_search
         return getattr(beam_search, name)
     raise AttributeError(f'module {__name__!r} has no attribute {name!r}')
