@@ -431,6 +431,26 @@ int w2l_ctc_loss(const float* log_probs, const int32_t* targets, const int32_t* 
                  const int32_t* target_lengths, int N, int T, int C, int Smax, int blank, int zero_infinity,
                  float* nll, float* loss, float* grad, void* workspace, void* stream);
 
+/* ---- CTC forced alignment: the offsets decoder.py:238 refuses for beam search, in the format of decoder.py:104-119 ---- */
+/* workspace bytes for w2l_ctc_align: 0 while the back-pointers fit in LDS, else N * ceil(T / 16) * (states rounded up to the
+ * block's) * 4; -1 if out of range */
+int64_t w2l_ctc_align_workspace_bytes(int N, int T, int Smax);
+/* The best CTC path of a given target (Viterbi form of w2l_ctc_loss's recursion), one workgroup per utterance, one launch.
+ * x fp32 [N][T][A] contiguous: log-probabilities, or probabilities if !log_probs (one logf per emission read, log 0 = -inf);
+ * input_lengths int32 [N] (NULL: all T).  Target row n is the int32 row at targets + n * target_stride, its length
+ * target_lengths[n * length_stride] (clamped to [0, Smax]), so rank 0 of w2l_ctc_beam_search's out buffer is aligned in place
+ * (labels: stride k * T; len: stride k, an empty slot's -1 reads as 0).  Over the L = 2 S + 1 extended states, in fp32,
+ * score[t][s] = max(score[t-1][s], score[t-1][s-1], score[t-1][s-2] if ext[s] != ext[s-2] and s odd) + lp[t][ext[s]].  Ties: the
+ * first of s, s-1, s-2 wins; at the end state L-2 wins a tie with L-1; a maximum of -inf stays -inf.  Outputs: score[N] (best
+ * path log-probability, -inf unless status 0); status[N]: 0 ok, 1 no path of finite score, 2 a negative or NaN probability
+ * in the utterance's frames or a target outside [0, A) or equal to blank; path[N][T]: the label emitted at each frame (-1
+ * from input_lengths[n] on, and everywhere unless status 0); starts / ends [N][Smax]: first and last frame of each token's
+ * own state (-1 beyond the target's length, and everywhere unless status 0).  Limits: T <= 32768, Smax <= 4095. */
+int w2l_ctc_align(const float* x, const int32_t* input_lengths, const int32_t* targets, int64_t target_stride,
+                  const int32_t* target_lengths, int64_t length_stride, int N, int T, int A, int Smax, int blank,
+                  int log_probs, void* workspace, int64_t workspace_bytes, float* score, int32_t* status, int32_t* path,
+                  int32_t* starts, int32_t* ends, void* stream);
+
 /* ---- greedy decode (decoder.py:136) + Levenshtein (decoder.py:49,60) ---- */
 /* argmax over the last dim, ties -> lowest index (torch.max): probs fp32 [rows][C] -> idx int32 [rows] */
 int w2l_argmax(const float* probs, int64_t rows, int C, int32_t* idx, void* stream);

@@ -137,6 +137,9 @@ _SIGNATURES = {
     'w2l_ctc_workspace_bytes': (c_i64, [c_i, c_i, c_i]),
     'w2l_ctc_loss': (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p]),
     'w2l_argmax': (c_i, [c_p, c_i64, c_i, c_p, c_p]),
+    'w2l_ctc_align_workspace_bytes': (c_i64, [c_i, c_i, c_i]),
+    'w2l_ctc_align': (c_i, [c_p, c_p, c_p, c_i64, c_p, c_i64, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_i64, c_p, c_p, c_p, c_p, c_p,
+                            c_p]),
     'w2l_ctc_beam_search_workspace_bytes': (c_i64, [c_i, c_i, c_i]),
     'w2l_ctc_beam_search': (c_i, [c_p, c_p, c_i, c_i, c_i, c_p, c_i, c_i, c_i, C.c_double, C.c_double, c_i, c_p, c_i64, c_p,
                                   c_p]),
@@ -257,7 +260,7 @@ TRACE_NAMES = {
     'w2l_quantize_e4m3_dyn': 'quantize_e4m3_dyn', 'w2l_dwconv_fwd': 'dw_fwd_kernel', 'w2l_dwconv_dgrad': 'dw_dgrad_kernel',
     'w2l_dwconv_wgrad': 'dw_wgrad_kernel', 'w2l_argmax': 'argmax_kernel', 'w2l_novograd_pack': 'novograd_pack_kernel',
     'w2l_ctc_beam_search': 'ctc_beam_search_kernel', 'w2l_ctc_beam_search_lm': 'ctc_beam_search_kernel<LM>',
-    'w2l_ngram_lm_build': 'ngram_insert_kernel',
+    'w2l_ngram_lm_build': 'ngram_insert_kernel', 'w2l_ctc_align': 'ctc_align_kernel',
 }
 _trace = {'rows': None, 'saved': {}, 'pool': []}
 

@@ -1,0 +1,263 @@
+"""CTC forced alignment: the best frame path of a GIVEN label sequence (the Viterbi, max-instead-of-sum, form of the CTC
+recursion).  It is what gives a beam-search result character offsets -- a beam result sums over many frame paths and has
+none of its own (the reference stops at decoder.py:238, "Prefix beam search does not support offsets (yet)") -- and what
+aligns a known transcript to the posteriors (segmenting a corpus, word start AND end times).
+
+ctc_forced_align runs one HIP launch for a batch (w2l_ctc_align, csrc/ctc_align.hip); viterbi_align_host is the same recursion
+in NumPy, the model the device tests compare with.  Both keep the same tie rules: among equal predecessors the state itself
+(stay), then s-1, then s-2; at the end the last label's state before the trailing blank's; a state whose best predecessor is
+-inf stays -inf."""
+from __future__ import annotations
+
+import ctypes as C
+from collections import namedtuple
+from typing import Optional, Sequence
+
+import numpy as np
+
+HostAlignment = namedtuple('HostAlignment', 'score path starts ends feasible')
+HostAlignment.__doc__ = """viterbi_align_host's result: ``score`` (best-path log-probability, -inf if infeasible), ``path`` [T] (the label
+emitted at each frame), ``starts`` / ends`` [S] (first / last frame of each target token), ``feasible``.  An infeasible target
+has path, starts and ends filled with -1."""
+
+
+class Alignment(object):
+    """ctc_forced_align's result, host arrays: ``scores`` float32 [N], ``feasible`` bool [N], ``paths`` int32 [N, T] (label per
+    frame, -1 past an utterance's frames), ``starts`` / ``ends`` int32 [N, Smax] (first / last frame of each target token, -1
+    past a target's length).  An infeasible utterance has score -inf and -1 everywhere."""
+    __slots__ = ('scores', 'feasible', 'paths', 'starts', 'ends', 'target_lengths')
+
+    def __init__(self, scores, feasible, paths, starts, ends, target_lengths):
+        self.scores, self.feasible, self.paths, self.starts, self.ends = scores, feasible, paths, starts, ends
+        self.target_lengths = target_lengths
+
+    def __repr__(self):
+        return 'Alignment(N=%d, T=%d, feasible=%d)' % (self.paths.shape[0], self.paths.shape[1], int(self.feasible.sum()))
+
+
+def viterbi_align_host(lp, target, blank: int = 0, dtype=np.float64) -> HostAlignment:
+    """Best CTC path of ``target`` (a sequence of label indices, none equal to ``blank``) over the frames of ``lp`` [T, A]
+    (log-probabilities; -inf allowed), vectorised over the 2 S + 1 extended states, one Python iteration per frame.  With
+    ``dtype=np.float32`` the arithmetic is w2l_ctc_align's, add for add and compare for compare."""
+    dtype = np.dtype(dtype).type
+    lp = np.asarray(lp).astype(dtype, copy=False)
+    if lp.ndim != 2 or lp.shape[0] < 1:
+        raise ValueError('viterbi_align_host: expected [T >= 1, A] log-probabilities, got shape %s' % (lp.shape,))
+    t_n, a = lp.shape
+    tg = np.asarray(target, dtype=np.int64).reshape(-1)
+    if not 0 <= blank < a:
+        raise ValueError('blank %d outside %d labels' % (blank, a))
+    if tg.size and (tg.min() < 0 or tg.max() >= a or (tg == blank).any()):
+        raise ValueError('viterbi_align_host: a target lies outside [0, %d) or equals the blank (%d)' % (a, blank))
+    s_n = tg.size
+    n_st = 2 * s_n + 1
+    ext = np.full(n_st, blank, dtype=np.int64)
+    ext[1::2] = tg
+    skip = np.zeros(n_st, dtype=bool)
+    if s_n > 1:
+        skip[3::2] = tg[1:] != tg[:-1]
+    ninf = dtype(-np.inf)
+    score = np.full(n_st, ninf, dtype=dtype)
+    score[:2] = lp[0, ext[:2]]
+    moves = np.zeros((t_n, n_st), dtype=np.uint8)
+    a1 = np.full(n_st, ninf, dtype=dtype)
+    a2 = np.full(n_st, ninf, dtype=dtype)
+    with np.errstate(invalid='ignore'):
+        for t in range(1, t_n):
+            a1[1:] = score[:-1]
+            if n_st > 2:
+                a2[2:] = score[:-2]
+                a2[~skip] = ninf
+            best = score.copy()
+            mv = moves[t]
+            m = a1 > best                               # ties: stay, then s-1, then s-2
+            best[m] = a1[m]
+            mv[m] = 1
+            m = a2 > best
+            best[m] = a2[m]
+            mv[m] = 2
+            new = best + lp[t, ext]
+            new[best == ninf] = ninf
+            score = new
+    end = n_st - 1
+    if n_st > 1 and score[n_st - 2] >= score[n_st - 1]:  # the last label wins a tie with the trailing blank
+        end = n_st - 2
+    best = score[end]
+    if not best > ninf:
+        none = np.full(s_n, -1, dtype=np.int32)
+        return HostAlignment(dtype(-np.inf), np.full(t_n, -1, dtype=np.int32), none, none.copy(), False)
+    states = np.empty(t_n, dtype=np.int64)
+    s = end
+    for t in range(t_n - 1, 0, -1):
+        states[t] = s
+        s -= int(moves[t, s])
+    states[0] = s
+    path = ext[states].astype(np.int32)
+    starts = np.full(s_n, -1, dtype=np.int32)
+    ends = np.full(s_n, -1, dtype=np.int32)
+    own = (states & 1) == 1
+    first = own & np.concatenate(([True], states[1:] != states[:-1]))
+    last = own & np.concatenate((states[1:] != states[:-1], [True]))
+    starts[states[first] >> 1] = np.nonzero(first)[0]
+    ends[states[last] >> 1] = np.nonzero(last)[0]
+    return HostAlignment(best, path, starts, ends, True)
+
+
+def _first_index(labels):
+    first = {}
+    for i, ch in enumerate(labels):
+        first.setdefault(ch, i)
+    return first
+
+
+def _targets_to_array(targets, target_lengths, labels, n_expected: Optional[int]):
+    """-> (int32 [N, Smax] padded with 0, int32 [N] lengths) on the host"""
+    import torch
+    if torch.is_tensor(targets):
+        targets = targets.detach().cpu().numpy()
+    if isinstance(targets, str):
+        targets = [targets]
+    if isinstance(targets, np.ndarray):
+        if not np.issubdtype(targets.dtype, np.integer):
+            raise ValueError('ctc_forced_align: targets must be integers, got %s' % targets.dtype)
+        rows = targets.reshape(1, -1) if targets.ndim == 1 else targets
+        if rows.ndim != 2:
+            raise ValueError('ctc_forced_align: padded targets must be [N, Smax], got shape %s' % (targets.shape,))
+        if target_lengths is None:
+            lengths = np.full(rows.shape[0], rows.shape[1], dtype=np.int32)
+        else:
+            if torch.is_tensor(target_lengths):
+                target_lengths = target_lengths.detach().cpu().numpy()
+            lengths = np.asarray(target_lengths, dtype=np.int64).reshape(-1)
+            if lengths.size != rows.shape[0]:
+                raise ValueError('target_lengths holds %d lengths for %d targets' % (lengths.size, rows.shape[0]))
+            if lengths.size and (lengths.min() < 0 or lengths.max() > rows.shape[1]):
+                raise ValueError('target_lengths must lie in [0, %d], got %s' % (rows.shape[1], lengths.tolist()))
+            lengths = lengths.astype(np.int32)
+        return np.ascontiguousarray(rows, dtype=np.int32), lengths
+    if target_lengths is not None:
+        raise ValueError('ctc_forced_align: target_lengths goes with padded targets only (a list carries its own lengths)')
+    targets = list(targets)
+    if targets and isinstance(targets[0], (int, np.integer)):          # one utterance's labels
+        targets = [targets]
+    rows = []
+    first = _first_index(labels) if labels is not None else None
+    for row in targets:
+        if isinstance(row, str):
+            if first is None:
+                raise ValueError('ctc_forced_align: string targets need ``labels``')
+            try:
+                rows.append([first[ch] for ch in row])
+            except KeyError as e:
+                raise ValueError('ctc_forced_align: character %r of %r is not in the labels' % (e.args[0], row)) from None
+        else:
+            rows.append([int(v) for v in row])
+    lengths = np.array([len(r) for r in rows], dtype=np.int32)
+    out = np.zeros((len(rows), int(lengths.max()) if len(rows) else 0), dtype=np.int32)
+    for i, r in enumerate(rows):
+        out[i, :len(r)] = r
+    return out, lengths
+
+
+def align_sections(n: int, t: int, smax: int):
+    """byte offsets (score, status, path, starts, ends, total) of w2l_ctc_align's outputs inside one buffer"""
+    o_status = 4 * n
+    o_path = o_status + 4 * n
+    o_starts = o_path + 4 * n * t
+    o_ends = o_starts + 4 * n * smax
+    return 0, o_status, o_path, o_starts, o_ends, o_ends + 4 * n * smax
+
+
+def launch_align(x, sz, tg_ptr: int, tg_stride: int, len_ptr: int, len_stride: int, smax: int, blank: int, log_probs: bool,
+                 out, out_offset: int):
+    """one w2l_ctc_align launch on the current stream: x [N, T, A] float32 contiguous on the device, ``sz`` int32 [N] there or
+    None, targets / lengths by device address and stride (elements), outputs into ``out`` (a uint8 device tensor) from byte
+    ``out_offset`` in align_sections' layout.  -> the workspace tensor (or None): keep it alive until the stream has passed."""
+    import torch
+    from . import _lib
+    from ._lib import check, lib, ptr, stream_ptr
+    n, t, a = x.shape
+    ws_bytes = int(lib.w2l_ctc_align_workspace_bytes(n, t, smax))
+    if ws_bytes < 0:
+        raise _lib.W2LError('ctc_forced_align: T=%d (max 32768) or target length %d (max 4095) is out of range' % (t, smax))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device) if ws_bytes else None
+    base = out.data_ptr() + out_offset
+    o = align_sections(n, t, smax)
+    vp = C.c_void_p
+    check(lib.w2l_ctc_align(ptr(x), ptr(sz), vp(tg_ptr), int(tg_stride), vp(len_ptr), int(len_stride), n, t, a, int(smax),
+                            int(blank), int(bool(log_probs)), ptr(ws), ws_bytes, vp(base + o[0]), vp(base + o[1]),
+                            vp(base + o[2]), vp(base + o[3]), vp(base + o[4]), stream_ptr()), 'w2l_ctc_align')
+    return ws
+
+
+def split_align(host: np.ndarray, n: int, t: int, smax: int):
+    """the host copy of align_sections' bytes -> (scores, status, paths, starts, ends)"""
+    o = align_sections(n, t, smax)
+    scores = host[o[0]:o[1]].view(np.float32)
+    status = host[o[1]:o[2]].view(np.int32)
+    paths = host[o[2]:o[3]].view(np.int32).reshape(n, t)
+    starts = host[o[3]:o[4]].view(np.int32).reshape(n, smax)
+    ends = host[o[4]:o[5]].view(np.int32).reshape(n, smax)
+    return scores, status, paths, starts, ends
+
+
+def ctc_forced_align(probs, targets, input_lengths=None, target_lengths=None, blank: int = 0, log_probs: bool = True,
+                     labels: Optional[Sequence[str]] = None) -> Alignment:
+    """Align each utterance's target to its posteriors on the MI355X: one launch, one copy to the host.
+
+    probs: [N, T, A] or [T, A] (numpy or torch, any device; log-probabilities, or probabilities if not ``log_probs``);
+    targets: padded int tensor / array [N, Smax] with ``target_lengths``, a list of int lists, or -- with ``labels`` -- a list
+    of strings (a character maps to its first index in ``labels``, as in the decoders; an unknown one is a ValueError);
+    input_lengths[n]: the frames of utterance n (default: all T).  An utterance whose target has no path of finite score
+    (more labels, counting one blank between repeated ones, than frames; or a zero probability on every path) does not
+    raise: ``feasible[n]`` is False and ``scores[n]`` -inf.  A negative probability, or a target outside [0, A) or equal to
+    ``blank``, is a ValueError."""
+    import torch
+    from . import _lib
+    x = probs if torch.is_tensor(probs) else torch.from_numpy(np.ascontiguousarray(probs))
+    if x.dim() == 2:
+        x = x.unsqueeze(0)
+        if input_lengths is not None:
+            input_lengths = [int(np.asarray(torch.as_tensor(input_lengths).cpu()).reshape(-1)[0])]
+    if x.dim() != 3:
+        raise ValueError('expected [N, T, labels] or [T, labels] posteriors, got shape %s' % (tuple(x.shape),))
+    n, t, a = x.shape
+    if n < 1 or t < 1 or a < 1:
+        raise ValueError('ctc_forced_align: empty posteriors, shape %s' % (tuple(x.shape),))
+    if labels is not None and len(labels) != a:
+        raise ValueError('ctc size:%d, labels: %d' % (a, len(labels)))
+    if not 0 <= blank < a:
+        raise ValueError('blank %d outside %d labels' % (blank, a))
+    tg, tl = _targets_to_array(targets, target_lengths, labels, n)
+    if tg.shape[0] != n:
+        raise ValueError('%d targets for %d utterances' % (tg.shape[0], n))
+    smax = tg.shape[1]
+    if smax > 4095 or t > 32768:
+        raise ValueError('ctc_forced_align: T=%d (max 32768) or target length %d (max 4095) is out of range' % (t, smax))
+    il = None
+    if input_lengths is not None:
+        il = torch.as_tensor(input_lengths).detach().cpu().to(torch.int64).reshape(-1)
+        if il.numel() != n:
+            raise ValueError('input_lengths holds %d lengths for %d utterances' % (il.numel(), n))
+        if bool((il < 1).any()) or bool((il > t).any()):
+            raise ValueError('input_lengths must lie in [1, %d], got %s' % (t, il.tolist()))
+    if not x.is_cuda:
+        if not torch.cuda.is_available():
+            raise _lib.W2LError('ctc_forced_align needs the MI355X device (there is no CPU fallback; viterbi_align_host is '
+                                'the host model)')
+        x = x.cuda()
+    x = x.detach().float().contiguous()
+    dev = x.device
+    sz = il.to(torch.int32).to(dev, non_blocking=True) if il is not None else None
+    # targets and their lengths travel in one buffer: [N * Smax | N] int32
+    tgt = torch.from_numpy(np.concatenate([tg.reshape(-1), tl])).to(dev, non_blocking=True)
+    out = torch.empty(align_sections(n, t, smax)[5], dtype=torch.uint8, device=dev)
+    ws = launch_align(x, sz, tgt.data_ptr(), max(smax, 1), tgt.data_ptr() + 4 * n * smax, 1, smax, blank, log_probs, out, 0)
+    host = out.cpu().numpy()                           # the one copy to the host (ordered after the launch on this stream)
+    del ws
+    scores, status, paths, starts, ends = split_align(host, n, t, smax)
+    if (status == 2).any():
+        rows = np.nonzero(status == 2)[0].tolist()
+        raise ValueError('ctc_forced_align: a negative probability, or a target outside [0, %d) or equal to the blank (%d), '
+                         'in utterances %s' % (a, blank, rows))
+    return Alignment(scores, status == 0, paths, starts, ends, tl)

@@ -10,7 +10,9 @@ strictly positive masses survive a step, ties keep first-seen order.
 prefix_beam_search_gpu / GPUPrefixBeamSearchDecoder run the same recursion without a language model as one HIP launch per
 batch (w2l_ctc_beam_search, csrc/beam_search.hip), in fp64 logs; with an ARPA n-gram model (ngram_lm.ArpaLM: ``lm=`` of
 prefix_beam_search_gpu, GPUPrefixBeamSearchLMDecoder) the same launch scores words on the device (w2l_ctc_beam_search_lm)
-as the host does with ``lm=lambda s: 10 ** arpa.score(s)``."""
+as the host does with ``lm=lambda s: 10 ** arpa.score(s)``.  With ``return_offsets`` a second launch on the same stream
+(w2l_ctc_align, alignment.py) aligns each best prefix to the posteriors where it lies in the search's device buffer, and the
+character offsets come back in the same copy."""
 from __future__ import annotations
 
 import ctypes as C
@@ -22,6 +24,7 @@ import torch
 
 from . import _lib
 from ._lib import check, lib, ptr, stream_ptr
+from .alignment import align_sections, launch_align, split_align
 from .decoder import Decoder
 
 _WORD_RE = re.compile(r'\w+[\s|>]')
@@ -162,10 +165,29 @@ def _label_info(labels: Sequence[str], blank_index: int, end_char: str):
     return info, first_index.get(end_char, -1)
 
 
-def _beam_search_device(probs, labels, blank_index, k, beta, prune, end_char, sizes, log_probs, lm=None, alpha=0.3):
+def _align_best(x, sz, out, n, t, k, blank_index, log_probs, beam_bytes):
+    """w2l_ctc_align right behind the search on the same stream: rank 0 of every utterance, read in ``out`` where the search
+    wrote it (labels int32 [N, k, T] from byte 12 N k + 4 N, row stride k T; lengths int32 [N, k] from byte 8 N k, stride k;
+    an empty slot's -1 aligns as the empty string), results behind the search's ``beam_bytes``"""
+    return launch_align(x, sz, out.data_ptr() + 12 * n * k + 4 * n, k * t, out.data_ptr() + 8 * n * k, k, t, blank_index,
+                        log_probs, out, beam_bytes)
+
+
+def _align_starts(host, n, t, beam_bytes):
+    """starts [N, T] of _align_best from the host copy of the buffer"""
+    _, status, _, starts, _ = split_align(host[beam_bytes:], n, t, t)
+    if status.any():
+        raise _lib.W2LError('w2l_ctc_align found no path for the decoded prefix of utterances %s (status %s)'
+                            % (np.nonzero(status)[0].tolist(), status[status != 0].tolist()))
+    return starts
+
+
+def _beam_search_device(probs, labels, blank_index, k, beta, prune, end_char, sizes, log_probs, lm=None, alpha=0.3,
+                        offsets=False):
     """one launch of w2l_ctc_beam_search for probs [N, T, A] on the current stream; returns the host arrays
     (scores [N, k], lengths [N, k], labels [N, k, T]).  With ``lm`` (an ngram_lm.ArpaLM) one launch of
-    w2l_ctc_beam_search_lm, and a fourth array: lm_log10 [N, k] float32, the LM total of each result."""
+    w2l_ctc_beam_search_lm, and a fourth array: lm_log10 [N, k] float32, the LM total of each result.  With ``offsets`` a
+    launch of w2l_ctc_align follows and one more array: starts int32 [N, T], the first frame of each label of rank 0."""
     if probs.dim() != 3:
         raise ValueError('expected [N, T, labels] or [T, labels] posteriors, got shape %s' % (tuple(probs.shape),))
     n, t, a = probs.shape
@@ -175,6 +197,8 @@ def _beam_search_device(probs, labels, blank_index, k, beta, prune, end_char, si
         raise ValueError('blank_index %d outside %d labels' % (blank_index, a))
     if t < 2:
         raise ValueError('ctc length: %d was too short' % t)
+    if offsets and t > 4095:
+        raise ValueError('return_offsets: %d frames, w2l_ctc_align takes targets of at most 4095 labels' % t)
     info, end_index = _label_info(labels, blank_index, end_char)
     if not probs.is_cuda:
         if not torch.cuda.is_available():
@@ -191,27 +215,33 @@ def _beam_search_device(probs, labels, blank_index, k, beta, prune, end_char, si
             raise ValueError('sizes must lie in [2, %d], got %s' % (t, host.tolist()))
         sz = host.to(torch.int32).to(dev, non_blocking=True)
     if lm is not None:
-        return _beam_search_device_lm(x, sz, labels, info, blank_index, end_index, k, alpha, beta, prune, log_probs, lm)
+        return _beam_search_device_lm(x, sz, labels, info, blank_index, end_index, k, alpha, beta, prune, log_probs, lm,
+                                      offsets)
     ws_bytes = int(lib.w2l_ctc_beam_search_workspace_bytes(n, t, k))
     if ws_bytes < 0:
         raise ValueError('prefix_beam_search_gpu: k=%d with T=%d is out of range' % (k, t))
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-    out = torch.empty(12 * n * k + 4 * n + 4 * n * k * t, dtype=torch.uint8, device=dev)
+    beam_bytes = 12 * n * k + 4 * n + 4 * n * k * t
+    out = torch.empty(beam_bytes + (align_sections(n, t, t)[5] if offsets else 0), dtype=torch.uint8, device=dev)
     check(lib.w2l_ctc_beam_search(ptr(x), ptr(sz), n, t, a, info.ctypes.data_as(C.c_void_p), int(blank_index), int(end_index),
                                   int(k), float(beta), float(prune), int(bool(log_probs)), ptr(ws), ws_bytes, ptr(out),
                                   stream_ptr()), 'w2l_ctc_beam_search')
-    host = out.cpu().numpy()                           # the one copy to the host (ordered after the launch on this stream)
+    align_ws = _align_best(x, sz, out, n, t, k, blank_index, log_probs, beam_bytes) if offsets else None
+    host = out.cpu().numpy()                           # the one copy to the host (ordered after the launches on this stream)
+    del align_ws
     scores = host[:8 * n * k].view(np.float64).reshape(n, k)
     rest = host[8 * n * k:].view(np.int32)
     lengths = rest[:n * k].reshape(n, k)
     status = rest[n * k:n * k + n]
-    idx = rest[n * k + n:].reshape(n, k, t)
+    idx = rest[n * k + n:n * k + n + n * k * t].reshape(n, k, t)
     if status.any():
         raise ValueError('ctc output contains negative numbers (utterances %s)' % np.nonzero(status)[0].tolist())
+    if offsets:
+        return scores, lengths, idx, _align_starts(host, n, t, beam_bytes)
     return scores, lengths, idx
 
 
-def _beam_search_device_lm(x, sz, labels, info, blank_index, end_index, k, alpha, beta, prune, log_probs, lm):
+def _beam_search_device_lm(x, sz, labels, info, blank_index, end_index, k, alpha, beta, prune, log_probs, lm, offsets=False):
     """_beam_search_device's launch of w2l_ctc_beam_search_lm (x, sz already on the device)"""
     from .ngram_lm import ArpaLM
     if not isinstance(lm, ArpaLM):
@@ -228,26 +258,31 @@ def _beam_search_device_lm(x, sz, labels, info, blank_index, end_index, k, alpha
     if ws_bytes < 0:
         raise ValueError('prefix_beam_search_gpu: k=%d with T=%d (LM order %d) is out of range' % (k, t, lm.order))
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-    out = torch.empty(12 * n * k + 4 * n + 4 * n * k * t + 4 * n * k, dtype=torch.uint8, device=dev)
+    beam_bytes = 12 * n * k + 4 * n + 4 * n * k * t + 4 * n * k
+    out = torch.empty(beam_bytes + (align_sections(n, t, t)[5] if offsets else 0), dtype=torch.uint8, device=dev)
     check(lib.w2l_ctc_beam_search_lm(ptr(x), ptr(sz), n, t, a, info.ctypes.data_as(C.c_void_p), int(blank_index),
                                      int(end_index), space_index, int(k), float(alpha), float(beta), float(prune),
                                      int(bool(log_probs)), tables.desc_ref, lm.order, ptr(ws), ws_bytes, ptr(out), stream_ptr()),
           'w2l_ctc_beam_search_lm')
+    align_ws = _align_best(x, sz, out, n, t, k, blank_index, log_probs, beam_bytes) if offsets else None
     host = out.cpu().numpy()                           # the one copy to the host
+    del align_ws
     scores = host[:8 * n * k].view(np.float64).reshape(n, k)
     rest = host[8 * n * k:].view(np.int32)
     lengths = rest[:n * k].reshape(n, k)
     status = rest[n * k:n * k + n]
     idx = rest[n * k + n:n * k + n + n * k * t].reshape(n, k, t)
-    lm_log10 = rest[n * k + n + n * k * t:].view(np.float32).reshape(n, k)
+    lm_log10 = rest[n * k + n + n * k * t:n * k + n + n * k * t + n * k].view(np.float32).reshape(n, k)
     if status.any():
         raise ValueError('ctc output contains negative numbers (utterances %s)' % np.nonzero(status)[0].tolist())
+    if offsets:
+        return scores, lengths, idx, lm_log10, _align_starts(host, n, t, beam_bytes)
     return scores, lengths, idx, lm_log10
 
 
 def prefix_beam_search_gpu(probs, labels: Sequence[str], blank_index: int = 0, k: int = 5, beta: float = 5,
                            prune: float = 0.001, end_char: str = '>', sizes=None, log_probs: bool = False, nbest: int = 1,
-                           return_weights: bool = False, lm=None, alpha: float = 0.3):
+                           return_weights: bool = False, lm=None, alpha: float = 0.3, return_offsets: bool = False):
     """prefix_beam_search on the MI355X: one launch for a whole batch, masses as fp64 logs (no underflow on long
     utterances; the host function's float32 products do underflow), the host's candidate order and ties.  ``lm``: an
     ngram_lm.ArpaLM scored as the host's ``lm=lambda s: 10 ** lm.score(s)`` with weight ``alpha`` (None: no LM).
@@ -256,21 +291,23 @@ def prefix_beam_search_gpu(probs, labels: Sequence[str], blank_index: int = 0, k
     ``sizes[n]``: decode only the first sizes[n] frames of utterance n (default: all T).  Per utterance the result is the best
     prefix, ``(best, log weight)`` if ``return_weights``, or if ``nbest > 1`` a list of up to ``nbest`` ``(prefix, log weight)``
     pairs, best first (log weight = log(mass * (words + 1) ** beta), the host's ranking weight).  A [T, labels] input gives one
-    result, a batch a list of N."""
+    result, a batch a list of N.  ``return_offsets`` (only with ``nbest == 1``): ``(results, offsets)``, offsets an IntTensor
+    per utterance holding the first frame of each character of its best prefix on that prefix's best frame path (one more
+    launch, w2l_ctc_align, on the same stream; still one copy to the host)."""
     labels = list(labels)
     if not 1 <= nbest <= k:
         raise ValueError('nbest=%d must lie in [1, k=%d]' % (nbest, k))
+    if return_offsets and nbest != 1:
+        raise ValueError('return_offsets aligns the best prefix only: nbest=%d must be 1' % nbest)
     x = probs if torch.is_tensor(probs) else torch.from_numpy(np.ascontiguousarray(probs))
     single = x.dim() == 2
     if single:
         x = x.unsqueeze(0)
         if sizes is not None:
             sizes = [int(np.asarray(sizes).reshape(-1)[0])]
-    if lm is None:
-        scores, lengths, idx = _beam_search_device(x, labels, blank_index, k, beta, prune, end_char, sizes, log_probs)
-    else:
-        scores, lengths, idx, _ = _beam_search_device(x, labels, blank_index, k, beta, prune, end_char, sizes, log_probs,
-                                                      lm=lm, alpha=alpha)
+    got = _beam_search_device(x, labels, blank_index, k, beta, prune, end_char, sizes, log_probs, lm=lm, alpha=alpha,
+                              offsets=return_offsets)
+    scores, lengths, idx = got[:3]
     results = []
     for u in range(scores.shape[0]):
         found = [(''.join(labels[j] for j in idx[u, r, :lengths[u, r]]), float(scores[u, r]))
@@ -283,7 +320,16 @@ def prefix_beam_search_gpu(probs, labels: Sequence[str], blank_index: int = 0, k
             results.append(found[0])
         else:
             results.append(found[0][0])
+    if return_offsets:
+        offs = [torch.IntTensor(got[-1][u, :max(int(lengths[u, 0]), 0)].copy()) for u in range(scores.shape[0])]
+        return (results[0], offs[0]) if single else (results, offs)
     return results[0] if single else results
+
+
+def _nest_offsets(got, single):
+    """prefix_beam_search_gpu's (results, offsets) in GreedyDecoder.decode's nesting: one single-element list per utterance"""
+    results, offs = got
+    return (results, [offs]) if single else (results, [[o] for o in offs])
 
 
 class GPUPrefixBeamSearchDecoder(Decoder):
@@ -298,14 +344,15 @@ class GPUPrefixBeamSearchDecoder(Decoder):
         self.k, self.alpha, self.beta, self.prune, self.log_probs = k, alpha, beta, prune, log_probs
 
     def decode(self, probs, sizes=None, return_offsets=False):
-        """[N, T, labels] -> N strings (utterance n over its first sizes[n] frames); [T, labels] -> one string"""
-        if return_offsets:
-            raise NotImplementedError("Prefix beam search does not support offsets (yet).")
+        """[N, T, labels] -> N strings (utterance n over its first sizes[n] frames); [T, labels] -> one string.  With
+        ``return_offsets``: ``(strings, offsets)`` nested as GreedyDecoder.decode's, ``offsets[n] = [IntTensor]`` (the first frame
+        of each character of strings[n] on its best frame path), so get_time_per_word(strings[n], offsets[n][0]) applies"""
         if len(probs.shape) not in (2, 3):
             raise RuntimeError('Decoding with wrong shape: %s, expected either [Batch X Frames X Labels] or '
                                '[Frames X Labels]' % str(tuple(probs.shape)))
-        return prefix_beam_search_gpu(probs, self.labels, self.blank_index, self.k, self.beta, self.prune, sizes=sizes,
-                                      log_probs=self.log_probs)
+        got = prefix_beam_search_gpu(probs, self.labels, self.blank_index, self.k, self.beta, self.prune, sizes=sizes,
+                                     log_probs=self.log_probs, return_offsets=return_offsets)
+        return _nest_offsets(got, len(probs.shape) == 2) if return_offsets else got
 
 
 class GPUPrefixBeamSearchLMDecoder(Decoder):
@@ -319,33 +366,37 @@ class GPUPrefixBeamSearchLMDecoder(Decoder):
         self.k, self.alpha, self.beta, self.prune, self.log_probs = k, alpha, beta, prune, log_probs
 
     def decode(self, probs, sizes=None, return_offsets=False):
-        """[N, T, labels] -> N strings (utterance n over its first sizes[n] frames); [T, labels] -> one string"""
-        if return_offsets:
-            raise NotImplementedError("Prefix beam search does not support offsets (yet).")
+        """[N, T, labels] -> N strings (utterance n over its first sizes[n] frames); [T, labels] -> one string.  With
+        ``return_offsets``: ``(strings, offsets)`` nested as GreedyDecoder.decode's, ``offsets[n] = [IntTensor]`` (the first frame
+        of each character of strings[n] on its best frame path), so get_time_per_word(strings[n], offsets[n][0]) applies"""
         if len(probs.shape) not in (2, 3):
             raise RuntimeError('Decoding with wrong shape: %s, expected either [Batch X Frames X Labels] or '
                                '[Frames X Labels]' % str(tuple(probs.shape)))
-        return prefix_beam_search_gpu(probs, self.labels, self.blank_index, self.k, self.beta, self.prune, sizes=sizes,
-                                      log_probs=self.log_probs, lm=self.lm, alpha=self.alpha)
+        got = prefix_beam_search_gpu(probs, self.labels, self.blank_index, self.k, self.beta, self.prune, sizes=sizes,
+                                     log_probs=self.log_probs, lm=self.lm, alpha=self.alpha, return_offsets=return_offsets)
+        return _nest_offsets(got, len(probs.shape) == 2) if return_offsets else got
 
 
-def get_time_per_word(predictions, offsets, ratio=1.0):
+def get_time_per_word(predictions, offsets, ratio=1.0, end_offsets=None):
     """(word, start, end) triples from per-character offsets (decoder.py:270-302); the end time of a word is the
-    first frame of its last character."""
+    first frame of its last character -- or, with ``end_offsets`` (the last frame of each character: Decoder.align's second
+    result), the LAST frame of its last character."""
     assert len(predictions) == len(offsets)
+    assert end_offsets is None or len(end_offsets) == len(offsets)
     words = []
     cur, start, end = '', -1, -1
-    for ch, off in zip(predictions, offsets):
+    for i, (ch, off) in enumerate(zip(predictions, offsets)):
         if ch == ' ':
             if cur:
                 words.append((cur, start, end))
                 cur, start, end = '', -1, -1
             continue
         if cur:
-            end = off * ratio
+            end = (off if end_offsets is None else end_offsets[i]) * ratio
             cur += ch
         else:
-            start = end = off * ratio
+            start = off * ratio
+            end = (off if end_offsets is None else end_offsets[i]) * ratio
             cur = ch
     if cur:
         words.append((cur, start, end))

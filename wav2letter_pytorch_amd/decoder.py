@@ -57,6 +57,24 @@ class Decoder(object):
     def decode(self, probs, sizes=None):
         raise NotImplementedError
 
+    def align(self, probs, texts, sizes=None, log_probs=False):
+        """forced alignment of ``texts`` (one string per utterance, or one string for a [T, labels] input) to the posteriors
+        (alignment.ctc_forced_align: a character maps to its first index in the labels) -> ``(offsets, end_offsets)`` in the
+        format of GreedyDecoder.decode(..., return_offsets=True): ``offsets[n] = [IntTensor]``, the first frame of each
+        character of texts[n], ``end_offsets`` its last.  A text that no frame path spells (more characters than frames) is a
+        ValueError."""
+        from .alignment import ctc_forced_align
+        if isinstance(texts, str):
+            texts = [texts]
+        res = ctc_forced_align(probs, list(texts), input_lengths=sizes, blank=self.blank_index, log_probs=log_probs,
+                               labels=list(self.labels))
+        if not res.feasible.all():
+            raise ValueError('Decoder.align: no frame path spells the texts of utterances %s'
+                             % np.nonzero(~res.feasible)[0].tolist())
+        offsets = [[torch.IntTensor(res.starts[n, :len(text)].copy())] for n, text in enumerate(texts)]
+        end_offsets = [[torch.IntTensor(res.ends[n, :len(text)].copy())] for n, text in enumerate(texts)]
+        return offsets, end_offsets
+
 
 def argmax_indices(probs: torch.Tensor) -> torch.Tensor:
     """int32 [N, T] argmax over the label axis on the device (first maximal index)."""
@@ -155,4 +173,7 @@ def __getattr__(name):
     if name in ('GPUPrefixBeamSearchDecoder', 'GPUPrefixBeamSearchLMDecoder', 'prefix_beam_search_gpu'):
         from . import beam_search
         return getattr(beam_search, name)
+    if name in ('ctc_forced_align', 'viterbi_align_host'):
+        from . import alignment
+        return getattr(alignment, name)
     raise AttributeError(f'module {__name__!r} has no attribute {name!r}')
