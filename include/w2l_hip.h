@@ -415,6 +415,50 @@ int w2l_conv1d_dgrad_bnreduce_tune_ws(const void* dy, int64_t dy_rows_total, con
                                       int flat_rows, int Kw, int dil, int reps, void* splitk_ws, int64_t splitk_ws_bytes,
                                       void* stream);
 
+/* ---- inference: one launch per convolution unit --------------------------------------------------------------
+ * nn.Conv1d + nn.BatchNorm1d in eval() (running statistics: a constant per-channel affine map) + the residual sum + the
+ * activation + MaskedConv1d's length mask + the NEXT convolution's padding, all in the implicit GEMM's epilogue
+ * (conv_igemm_kernel, EPI = 2).  On the fp32 accumulators, in this order:
+ *   v = acc + bias[co] (+ acc_in[n][t][co]);  v = v * scale[co] + shift[co]   (scale = gamma * rsqrt(running_var + eps),
+ *       shift = beta - running_mean * scale, as w2l_bn_finalize(partial = NULL) gives them; NULL: identity)
+ *   v += res[n][t][co] (+ res_lo)           dense bf16 [N][Tout][Cout]: the other branch of a Jasper unit, written by a fused
+ *                                           launch of its own with act = 0 and no padding
+ *   v = clamp(v, 0, 20) (act 1) | max(v, 0) (act 2) | v (act 0);   v = 0 for t >= lens[n]
+ *   out[n][pad_l + t][co] = bf16(v) (+ out_lo = bf16(v - hi)), out = [N][out_rows][Cout] with out_rows >= pad_l + Tout + pad_r.
+ * Halo rows: pad_mode 1 (reflect) -- the block that owns frame j (1 <= j <= pad_l) also writes row pad_l - j, the owner of
+ * frame Tout-1-j (1 <= j <= pad_r) row pad_l + Tout - 1 + j; pad_mode 0 -- rows [0, pad_l) and [pad_l + Tout, pad_l + Tout +
+ * pad_r) are written as zeros.  Rows beyond pad_l + Tout + pad_r are not touched.  pad_l, pad_r <= 96.  No y, no statistics,
+ * no mask is written.  acc_in (optional, fp32 dense [N][Tout][Cout]): partial sums of earlier plain launches -- in split-bf16
+ * mode the first two products go through w2l_conv1d_igemm(y_f32 = 1) and the third launch is this one.
+ * With a split-K workspace (the _ws forms; as for w2l_conv1d_igemm_ws) a tile's reduction may be split over 2-8 blocks: the
+ * block that draws the tile's last ticket sums the slabs and runs the epilogue.  Stream-K plans are not candidates.  The _tune form measures the block shapes WITH the epilogue and remembers the fastest under
+ * a key of its own (statistics flag 3 of the plan table), so fused and plain launches of one shape never share a choice.
+ * The key is the problem shape only: it does not tell the epilogue's variants apart (residual operand, lo output, reflect
+ * double stores, mask) -- the first variant measured decides the block shape for all of them -- and a launch with acc_in
+ * (split-bf16 mode) is never measured: it takes the remembered choice or the cost model's.
+ * Replaces, for inference, nn.Conv1d + nn.BatchNorm1d + Hardtanh-style clamp + nn.ReflectionPad1d (wav2letter.py:28-38,
+ * 41-46) and MaskedConv1d + BatchNorm1d + the residual sum + ReLU (jasper.py:96-105,116-119,127,363,376,400-410,448). */
+typedef struct {
+    const float* scale;     /* [Cout] fp32, NULL => identity (a unit without BatchNorm) */
+    const float* shift;
+    const void* res;        /* optional second branch, dense bf16 [N][Tout][Cout] */
+    const void* res_lo;     /* its lo half (split-bf16 mode), NULL otherwise */
+    int32_t act;            /* 0 none, 1 clamp[0,20], 2 ReLU */
+    const int32_t* lens;    /* optional [N] */
+    void* out_hi;           /* [N][out_rows][Cout] bf16 */
+    void* out_lo;           /* optional lo half */
+    int32_t out_rows, pad_l, pad_r, pad_mode;
+} w2l_bnact_epi_t;
+int w2l_conv1d_igemm_bnact(const void* xp, int64_t x_bstride, int64_t x_rows_total, const void* w, const float* acc_in,
+                           const float* bias, const w2l_bnact_epi_t* e, int N, int Cin, int Cout, int Tout, int Kw, int stride,
+                           int dil, void* stream);
+int w2l_conv1d_igemm_bnact_ws(const void* xp, int64_t x_bstride, int64_t x_rows_total, const void* w, const float* acc_in,
+                              const float* bias, const w2l_bnact_epi_t* e, int N, int Cin, int Cout, int Tout, int Kw,
+                              int stride, int dil, void* splitk_ws, int64_t splitk_ws_bytes, void* stream);
+int w2l_conv1d_igemm_bnact_tune_ws(const void* xp, int64_t x_bstride, int64_t x_rows_total, const void* w, const float* bias,
+                                   const w2l_bnact_epi_t* e, int N, int Cin, int Cout, int Tout, int Kw, int stride, int dil,
+                                   int reps, void* splitk_ws, int64_t splitk_ws_bytes, void* stream);
+
 /* ---- log_softmax + CTC (wav2letter.py:86-87, jasper.py:469-473, base_asr_models.py:23,81,90) ---- */
 /* logits fp32 [N][T][CP] (first C valid) -> out fp32 [N][T][C]; mode 0 log_softmax, 1 softmax */
 int w2l_log_softmax_fwd(const float* logits, int N, int T, int C, int CP, int mode, float* out, void* stream);

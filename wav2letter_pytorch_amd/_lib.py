@@ -60,6 +60,13 @@ class LmTables(C.Structure):
                 ('n_words', C.c_int32), ('n_trie_nodes', C.c_int32)]
 
 
+class BnActEpi(C.Structure):
+    """w2l_bnact_epi_t (include/w2l_hip.h): the fused inference epilogue of w2l_conv1d_igemm_bnact."""
+    _fields_ = [('scale', c_p), ('shift', c_p), ('res', c_p), ('res_lo', c_p), ('act', C.c_int32), ('lens', c_p),
+                ('out_hi', c_p), ('out_lo', c_p), ('out_rows', C.c_int32), ('pad_l', C.c_int32), ('pad_r', C.c_int32),
+                ('pad_mode', C.c_int32)]
+
+
 class GradSrc(C.Structure):
     """w2l_gradsrc_t (include/w2l_hip.h)."""
     _fields_ = [('dxp', c_p), ('f32', C.c_int32), ('pad_l', C.c_int32), ('pad_r', C.c_int32),
@@ -83,6 +90,11 @@ _SIGNATURES = {
     'w2l_conv1d_igemm_ws': (c_i, [c_p, c_i64, c_i64, c_p, c_p, c_i, c_i, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_i64, c_p]),
     'w2l_conv1d_igemm_tune_ws': (c_i, [c_p, c_i64, c_i64, c_p, c_p, c_i, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p,
                                        c_i64, c_p]),
+    'w2l_conv1d_igemm_bnact': (c_i, [c_p, c_i64, c_i64, c_p, c_p, c_p, C.POINTER(BnActEpi), c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p]),
+    'w2l_conv1d_igemm_bnact_ws': (c_i, [c_p, c_i64, c_i64, c_p, c_p, c_p, C.POINTER(BnActEpi), c_i, c_i, c_i, c_i, c_i, c_i, c_i,
+                                        c_p, c_i64, c_p]),
+    'w2l_conv1d_igemm_bnact_tune_ws': (c_i, [c_p, c_i64, c_i64, c_p, c_p, C.POINTER(BnActEpi), c_i, c_i, c_i, c_i, c_i, c_i, c_i,
+                                             c_i, c_p, c_i64, c_p]),
     'w2l_conv_splitk_workspace_bytes': (c_i64, [c_i, c_i, c_i]),
     'w2l_conv_streamk_ranges': (c_i, [c_i] * 8 + [c_i64]),
     'w2l_conv_streamk_pieces': (c_i, [c_i, c_i, c_i, c_p, c_i]),
@@ -247,7 +259,9 @@ def require_device(*tensors):
 # tools/timeline.py reads either.  ~10 us of host time per launch; diagnostic only (bench.py --event-trace).
 TRACE_NAMES = {
     'w2l_conv1d_igemm': 'conv_igemm_kernel', 'w2l_conv1d_igemm_ws': 'conv_igemm_kernel',
-    'w2l_conv1d_dgrad_bnreduce_ws': 'conv_igemm_kernel/dgrad+bnreduce', 'w2l_conv1d_igemm_fp8': 'conv_igemm_fp8_kernel',
+    'w2l_conv1d_dgrad_bnreduce_ws': 'conv_igemm_kernel/dgrad+bnreduce',
+    'w2l_conv1d_igemm_bnact': 'conv_igemm_kernel/bnact', 'w2l_conv1d_igemm_bnact_ws': 'conv_igemm_kernel/bnact',
+    'w2l_conv1d_igemm_fp8': 'conv_igemm_fp8_kernel',
     'w2l_conv1d_wgrad': 'conv_wgrad_kernel', 'w2l_conv1d_wgrad_ws': 'conv_wgrad_kernel', 'w2l_conv1d_wgrad_group': 'conv_wgrad_kernel', 'w2l_conv1d_wgrad_fp8': 'conv_wgrad_fp8_kernel',
     'w2l_bn_finalize': 'bn_finalize_kernel', 'w2l_bn_act_fwd': 'bn_act_fwd_kernel', 'w2l_bn_act_fwd_q': 'bn_act_fwd_kernel',
     'w2l_bn_act_fwd_fin': 'bn_act_fwd_kernel', 'w2l_bn_act_bwd_reduce': 'bn_act_bwd_reduce_kernel',

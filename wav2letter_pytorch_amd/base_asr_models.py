@@ -339,13 +339,13 @@ class ConvCTCASR(_Base):
         self.__dict__['_ints_keep'] = host         # alive until the next batch's copy has been enqueued behind it
         return tuple(outs)
 
-    def _step(self, batch, prefix: str, extra: Dict[str, float]):
+    def _step(self, batch, prefix: str, extra: Dict[str, float], forward=None):
         """forward -> CTC -> string metrics -> log_dict; the body of training_step and validation_step
         (base_asr_models.py:78-94).  batch = _collator's 6-tuple (data_loader.py:149-158).  Nothing in here waits for the
         GPU when ``async_metrics`` is on and the step is a training step: the metrics are logged by on_train_batch_end."""
         spect, spect_lens, targets, target_lens, _paths, texts = batch
         x = self._device_batch(spect)
-        out, out_lens = self.forward(x, spect_lens)
+        out, out_lens = (forward or self.forward)(x, spect_lens)
         if x.is_cuda and torch.is_tensor(out_lens) and torch.is_tensor(targets) and torch.is_tensor(target_lens):
             tg_d, ol_d, tl_d = self._device_ints(x.device, targets, out_lens, target_lens)
         else:
@@ -364,3 +364,46 @@ class ConvCTCASR(_Base):
 
     def validation_step(self, batch, batch_idx):
         return self._step(batch, 'val', {})
+
+    def test_step(self, batch, batch_idx):
+        """Lightning's test hook: ``validation_step`` under the prefix ``test``, on the inference forward (``infer``)"""
+        with torch.no_grad():
+            return self._step(batch, 'test', {}, forward=self.infer)
+
+    def infer(self, inputs, input_lengths):
+        raise NotImplementedError()
+
+    def train(self, mode: bool = True):
+        if mode:                             # training forwards move the running statistics that infer() has folded
+            from .engine import drop_infer_state
+            drop_infer_state()
+        return super().train(mode)
+
+    def transcribe(self, paths_or_waveforms, batch_size: int = 8, decoder=None, word_times: bool = False):
+        """audio -> text: files (paths) or 1-D waveforms at the model's sample rate -> the GPU log-mel front end
+        (data_loader.SpectrogramExtractor) -> ``infer`` -> ``decoder`` (default: the model's own) -> one string per input, in
+        order.  ``word_times``: (string, [(word, start s, end s), ...]) pairs instead, by forced alignment of the decoded text.
+        Wav2Letter pads by reflection at the BATCH's padded length and masks nothing, so the last frames of an utterance depend
+        on what it is batched with: ``batch_size=1`` gives batch-independent text."""
+        from .evaluate import decode_batch
+        from .data.data_loader import SpectrogramExtractor, load_audio
+        items = [paths_or_waveforms] if isinstance(paths_or_waveforms, str) else list(paths_or_waveforms)
+        dev = next(self.parameters()).device
+        ext = self.__dict__.get('_transcribe_extractor')
+        if ext is None or ext.fb.device != dev:
+            ext = self.__dict__['_transcribe_extractor'] = SpectrogramExtractor(self.audio_conf, self._cfg.input_size, device=dev)
+        decoder = decoder or self.ctc_decoder
+        was_training = self.training
+        self.eval()
+        results = []
+        try:
+            for i in range(0, len(items), max(1, int(batch_size))):
+                chunk = [load_audio(a) if isinstance(a, str) else a for a in items[i: i + max(1, int(batch_size))]]
+                x, lens = ext.extract_batch(chunk)
+                out, out_lens = self.infer(x, lens)
+                hyps, words = decode_batch(self, decoder, out, out_lens, word_times)
+                results += list(zip(hyps, words)) if word_times else hyps
+        finally:
+            if was_training:
+                self.train()
+        return results

@@ -55,14 +55,26 @@ struct IgemmParams {
     // EPI == 1 (data gradient fused with the BatchNorm-backward reduction of the layer that produced the conv's input):
     // the output tile IS the gradient wrt that layer's padded activation, so the epilogue also forms, per channel,
     // sum g*gate and sum g*gate*xhat over its rows (what bn_act_bwd_reduce_kernel computes in a pass of its own)
-    const bf16_raw* bn_y;     // that layer's conv output [N][T][C] (C = this launch's Cout)
-    const float* bn_scale;    // its BatchNorm scale / shift / mean / invstd
-    const float* bn_shift;
-    const float* bn_mean;
-    const float* bn_invstd;
-    const uint8_t* bn_mask;   // dropout keep bits (one byte per 8 channels) or NULL
-    const int32_t* bn_lens;   // optional [N] valid lengths
-    int bn_T, bn_pad_l, bn_pad_mode, bn_per, bn_Tp, bn_act;
+    // EPI == 2 (inference, w2l_conv1d_igemm_bnact): the whole unit in the epilogue -- BatchNorm as the per-channel affine map
+    // it is with running statistics, the residual branch, the activation, the length mask -- stored as bf16 straight into the
+    // consumer's padded operand, halo rows included; no y, no statistics.  Its fields (fz_*) SHARE the storage of the EPI == 1
+    // fields, which a launch never uses together with them: the struct -- the kernel argument of every instantiation -- keeps
+    // its size and offsets, and with them the code of the EPI == 0 / 1 kernels.
+    union { const bf16_raw* bn_y; const bf16_raw* fz_res; };          // bn_y: that layer's conv output [N][T][C] (C = this launch's Cout)
+                                                                      // fz_res: optional dense [N][Tout][Cout] second branch
+    union { const float* bn_scale; const float* fz_scale; };          // bn_*: its BatchNorm scale / shift / mean / invstd
+    union { const float* bn_shift; const float* fz_shift; };          // fz_scale / fz_shift: the folded affine map, NULL: identity
+    union { const float* bn_mean; const bf16_raw* fz_res_lo; };       // fz_res_lo: the second branch's lo half (split-bf16 mode)
+    union { const float* bn_invstd; bf16_raw* fz_out; };              // fz_out: [N][fz_rows][Cout], frame t at row fz_pad_l + t
+    union { const uint8_t* bn_mask; bf16_raw* fz_out_lo; };           // bn_mask: dropout keep bits (one byte per 8 channels) or NULL
+                                                                      // fz_out_lo: optional lo half of the output
+    union { const int32_t* bn_lens; const int32_t* fz_lens; };        // optional [N] valid lengths (fz: frames beyond are stored as 0)
+    union { int bn_T; int fz_rows; };
+    union { int bn_pad_l; int fz_pad_l; };
+    union { int bn_pad_mode; int fz_pad_mode; };
+    union { int bn_per; int fz_pad_r; };
+    int bn_Tp;
+    union { int bn_act; int fz_act; };
     float bn_gk;              // 1 / (1 - p) with dropout, else 1
 };
 
@@ -111,8 +123,9 @@ __host__ __device__ inline SkPiece sk_piece(int W, int G, int S_, int r, int w_c
 template <int MW, int NW, int MS, int NS, int S, int PIPE, bool F8 = false, int EPI = 0, bool SK = false>
 __global__ __launch_bounds__(64 * MW * NW, 2) void conv_igemm_kernel(IgemmParams p) {
     static_assert(!SK || (!F8 && EPI == 0 && S == 1), "stream-K is built for the plain bf16 stride-1 kernels");
+    static_assert(EPI != 2 || !F8, "the fused inference epilogue is built for bf16 operands");
     static_assert(!(F8 && PIPE != 0), "the e4m3 kernel is built for K-loop structure 0 only");
-    static_assert(EPI == 0 || (!F8 && S == 1), "the fused BatchNorm-backward epilogue belongs to bf16 data gradients");
+    static_assert(EPI != 1 || (!F8 && S == 1), "the fused BatchNorm-backward epilogue belongs to bf16 data gradients");
     constexpr int ESZ = F8 ? 1 : 2;                // bytes per operand element
     constexpr int BKE = ROWB / ESZ;                // channels per K chunk (one 128-byte LDS row)
     constexpr int BM = 16 * MW * MS, BN = 16 * NW * NS, NWAVES = MW * NW, NT = 64 * NWAVES;
@@ -426,6 +439,74 @@ __global__ __launch_bounds__(64 * MW * NW, 2) void conv_igemm_kernel(IgemmParams
     // acc[mi][ni][r] = y[co = m0 + (wm*MS+mi)*16 + fq*4 + r][t = t0 + (wn*NS+ni)*16 + fr]
     const int Cout = p.Cout, Tout = p.Tout;
     const float descale = F8 ? p.descale * (p.descale_dev ? p.descale_dev[0] : 1.f) : 1.f;
+    if constexpr (EPI == 2) {
+        // ---- inference epilogue: v = act((acc + bias [+ y]) * scale + shift [+ residual]), masked, as bf16 into the consumer's
+        // padded buffer.  Halo rows are written by the block that owns the frame they mirror (reflect), or by the first
+        // column tile of the utterance (zeros): every pad is shorter than a tile (checked by the launcher).
+        const int pl = p.fz_pad_l, pr = p.fz_pad_r;
+        const int len_n = p.fz_lens ? p.fz_lens[n] : Tout;
+        bf16_raw* const obase = p.fz_out + (int64_t)n * p.fz_rows * Cout;
+        bf16_raw* const obase_lo = p.fz_out_lo ? p.fz_out_lo + (int64_t)n * p.fz_rows * Cout : nullptr;
+        auto put = [&](int row, int co, u16x4 hi, u16x4 lo) {
+            const int64_t o = (int64_t)row * Cout + co;
+            *reinterpret_cast<u16x4*>(obase + o) = hi;
+            if (obase_lo) *reinterpret_cast<u16x4*>(obase_lo + o) = lo;
+        };
+#pragma unroll
+        for (int mi = 0; mi < MS; ++mi) {
+            const int co = m0 + (wm * MS + mi) * 16 + fq * 4;
+            const bool co_ok = co < Cout;
+            f32x4 bias4 = f32x4{0.f, 0.f, 0.f, 0.f}, sc4 = f32x4{1.f, 1.f, 1.f, 1.f}, sh4 = bias4;
+            if (p.bias && co_ok) bias4 = *reinterpret_cast<const f32x4*>(p.bias + co);
+            if (p.fz_scale && co_ok) {
+                sc4 = *reinterpret_cast<const f32x4*>(p.fz_scale + co);
+                sh4 = *reinterpret_cast<const f32x4*>(p.fz_shift + co);
+            }
+#pragma unroll
+            for (int ni = 0; ni < NS; ++ni) {
+                const int tl = (wn * NS + ni) * 16 + fr;       // column inside the tile
+                const int t = t0 + tl;
+                const bool ok = co_ok && t < Tout;
+                if (ok) {
+                    const int64_t off = ((int64_t)n * Tout + t) * Cout + co;
+                    f32x4 v = acc[mi][ni] + bias4;
+                    if (p.accumulate) v += *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(p.y) + off);
+                    v = v * sc4 + sh4;
+                    if (p.fz_res) {
+                        const u16x4 rv = *reinterpret_cast<const u16x4*>(p.fz_res + off);
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) v[r] += bf16_bits_to_f32(rv[r]);
+                        if (p.fz_res_lo) {
+                            const u16x4 rl = *reinterpret_cast<const u16x4*>(p.fz_res_lo + off);
+#pragma unroll
+                            for (int r = 0; r < 4; ++r) v[r] += bf16_bits_to_f32(rl[r]);
+                        }
+                    }
+                    u16x4 hi, lo = u16x4{0, 0, 0, 0};
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        float a = v[r];
+                        if (p.fz_act == 1) a = fminf(fmaxf(a, 0.f), 20.f);
+                        else if (p.fz_act == 2) a = fmaxf(a, 0.f);
+                        if (t >= len_n) a = 0.f;
+                        hi[r] = f32_to_bf16_bits(a);
+                        if (obase_lo) lo[r] = f32_to_bf16_bits(a - bf16_bits_to_f32(hi[r]));
+                    }
+                    put(pl + t, co, hi, lo);
+                    if (p.fz_pad_mode == 1) {                  // nn.ReflectionPad1d: frame j is row pl - j, frame T-1-j row pl+T-1+j
+                        if (t >= 1 && t <= pl) put(pl - t, co, hi, lo);
+                        const int j = Tout - 1 - t;
+                        if (j >= 1 && j <= pr) put(pl + Tout - 1 + j, co, hi, lo);
+                    }
+                }
+                if (p.fz_pad_mode != 1 && tt == 0 && co_ok) {  // zero halo: the utterance's first tile writes both ends
+                    const u16x4 z = u16x4{0, 0, 0, 0};
+                    if (tl < pl) put(tl, co, z, z);
+                    if (tl < pr) put(pl + Tout + tl, co, z, z);
+                }
+            }
+        }
+    } else {
     float s1[MS][4], s2[MS][4];
 #pragma unroll
     for (int mi = 0; mi < MS; ++mi) {
@@ -609,6 +690,7 @@ __global__ __launch_bounds__(64 * MW * NW, 2) void conv_igemm_kernel(IgemmParams
         }
         }
     }
+    }
     } while (SK && w_cur < w_end);
 }
 
@@ -645,6 +727,25 @@ int launch_cfg1(const IgemmParams& p, int tiles_m, size_t lds, hipStream_t strea
             w2l_set_error("conv1d_igemm: the fused BatchNorm-backward epilogue needs a block shape of 128-column tiles");
             return 1;
         }
+    }
+    if (epi == 2) {
+        if (p.stride == 2) {
+            if constexpr (MW == 2 && NW == 2 && MS == 4 && NS == 4) {
+                auto kernf2 = conv_igemm_kernel<2, 2, 4, 4, 2, PIPE, false, 2>;
+                W2L_CHECK_HIP(w2l_allow_big_lds((const void*)kernf2));
+                hipLaunchKernelGGL(kernf2, dim3(tiles_m * p.ncols), dim3(256), lds, stream, p);
+                W2L_CHECK_LAUNCH();
+                return 0;
+            } else {
+                w2l_set_error("conv1d_igemm_bnact: stride 2 is only built for the 128x128 block shape");
+                return 1;
+            }
+        }
+        auto kernf = conv_igemm_kernel<MW, NW, MS, NS, 1, PIPE, false, 2>;
+        W2L_CHECK_HIP(w2l_allow_big_lds((const void*)kernf));
+        hipLaunchKernelGGL(kernf, dim3(tiles_m * p.ncols), dim3(64 * MW * NW), lds, stream, p);
+        W2L_CHECK_LAUNCH();
+        return 0;
     }
     if (p.stride == 2) {
         if constexpr (MW == 2 && NW == 2 && MS == 4 && NS == 4) {
@@ -736,7 +837,14 @@ static bool cfg_feasible(int idx, int Kw, int stride, int dil, bool need_bn128) 
 // resident blocks on the 256 CUs, larger tiles preferred)
 // statistics flag of a shape key: 0 none, 1 one row per 128-column tile (block shapes of 128 / 256 columns only), 2 added onto
 // slot rows (w2l_conv_stats_mode: every block shape)
-static int stats_flag(const float* stats_partial) { return stats_partial == nullptr ? 0 : (g_stats_slots > 0 ? 2 : 1); }
+// 3: a fused inference launch (w2l_conv1d_igemm_bnact) -- measured, remembered and looked up as itself; split-K forms included
+// (the combining block runs the epilogue), stream-K forms not
+static thread_local const w2l_bnact_epi_t* g_fz = nullptr;      // the fused launch's descriptor (same thread, like g_force_cfg)
+constexpr int kFzMaxPad = 96;                                   // halo rows a tile writes: fewer than the narrowest tile's columns
+static int stats_flag(const float* stats_partial) {
+    if (g_fz != nullptr) return 3;
+    return stats_partial == nullptr ? 0 : (g_stats_slots > 0 ? 2 : 1);
+}
 
 static int choose_cfg(int N, int Cin, int Cout, int Tout, int Kw, int stride, int dil, int sflag) {
     const bool need_bn128 = sflag == 1;
@@ -836,7 +944,8 @@ static int igemm_launch(const void* xp, int64_t x_bstride, int64_t x_rows_total,
                         int accumulate, const float* bias, float* stats_partial, int N, int Cin, int Cout, int Tout, int Kw,
                         int stride, int dil, void* splitk_ws, int64_t splitk_ws_bytes, void* stream, const BnBwdArgs* bb) {
     if (bb == nullptr) bb = g_tune_bb;
-    W2L_CHECK_ARG(xp && w && y, "conv1d_igemm: null pointer");
+    const w2l_bnact_epi_t* fz = g_fz;
+    W2L_CHECK_ARG(xp && w && (y || fz), "conv1d_igemm: null pointer");
     W2L_CHECK_ARG(N > 0 && Tout > 0 && Kw > 0 && (stride == 1 || stride == 2) && dil > 0,
                   "conv1d_igemm: bad sizes (stride must be 1 or 2)");
     W2L_CHECK_ARG(Cin % 64 == 0 && Cin > 0, "conv1d_igemm: Cin=%d must be a positive multiple of 64", Cin);
@@ -876,6 +985,24 @@ static int igemm_launch(const void* xp, int64_t x_bstride, int64_t x_rows_total,
         p.bn_gk = d->drop_p > 0.f ? 1.f / (1.f - d->drop_p) : 1.f;
         epi = 1;
     }
+    if (fz != nullptr) {
+        W2L_CHECK_ARG(bb == nullptr && stats_partial == nullptr && fz->out_hi, "conv1d_igemm_bnact: null output / bad combination");
+        W2L_CHECK_ARG(fz->pad_l >= 0 && fz->pad_r >= 0 && fz->pad_l <= kFzMaxPad && fz->pad_r <= kFzMaxPad &&
+                      fz->out_rows >= fz->pad_l + Tout + fz->pad_r,
+                      "conv1d_igemm_bnact: bad output geometry (pads %d,%d of at most %d; %d rows for %d frames)", fz->pad_l,
+                      fz->pad_r, kFzMaxPad, fz->out_rows, Tout);
+        W2L_CHECK_ARG(fz->pad_mode != 1 || (fz->pad_l < Tout && fz->pad_r < Tout),
+                      "conv1d_igemm_bnact: reflect pad (%d,%d) needs pad < T=%d", fz->pad_l, fz->pad_r, Tout);
+        W2L_CHECK_ARG((fz->scale == nullptr) == (fz->shift == nullptr) && fz->act >= 0 && fz->act <= 2 &&
+                      (fz->res || !fz->res_lo), "conv1d_igemm_bnact: scale/shift come together, act is 0..2, res_lo needs res");
+        p.fz_scale = fz->scale; p.fz_shift = fz->shift;
+        p.fz_res = (const bf16_raw*)fz->res; p.fz_res_lo = (const bf16_raw*)fz->res_lo;
+        p.fz_lens = fz->lens;
+        p.fz_out = (bf16_raw*)fz->out_hi; p.fz_out_lo = (bf16_raw*)fz->out_lo;
+        p.fz_rows = fz->out_rows; p.fz_pad_l = fz->pad_l; p.fz_pad_r = fz->pad_r; p.fz_pad_mode = fz->pad_mode;
+        p.fz_act = fz->act;
+        epi = 2;
+    }
     // the last valid output row must only need rows that exist in the padded buffer
     const int64_t need = (int64_t)(N - 1) * p.x_rows_per_utt + (int64_t)(Tout - 1) * stride + (int64_t)(Kw - 1) * dil;
     W2L_CHECK_ARG(need <= p.x_max_row, "conv1d_igemm: padded input too small (need row %lld, have %lld)",
@@ -891,7 +1018,8 @@ static int igemm_launch(const void* xp, int64_t x_bstride, int64_t x_rows_total,
     p.ncols = N * p.tiles_t;
     p.xrows_lds = cfg_xrows(c, stride, Kw, dil);
     // a split-K choice (measured with a workspace) silently degrades to one block per tile when the caller brings none
-    int splits = kSplits[ci / kBaseCfgs];
+    int splits = kSplits[ci / kBaseCfgs];          // (a fused inference launch may split K: the block that combines the slabs
+                                                   //  holds the whole tile in registers and runs the epilogue; never stream-K)
     p.sk_ranges = 0;
     p.sk_total = 0;
     if (splits == 0) {                                   // stream-K (never with the fused epilogue: cfg_feasible)
@@ -953,6 +1081,42 @@ extern "C" int w2l_conv1d_igemm(const void* xp, int64_t x_bstride, int64_t x_row
                                 int Cout, int Tout, int Kw, int stride, int dil, void* stream) {
     return w2l_conv1d_igemm_ws(xp, x_bstride, x_rows_total, w, y, y_f32, accumulate, bias, stats_partial, N, Cin, Cout, Tout,
                                Kw, stride, dil, nullptr, 0, stream);
+}
+
+// ---- inference: convolution + BatchNorm (running statistics) + residual + activation + mask + the consumer's padding ----
+extern "C" int w2l_conv1d_igemm_bnact_ws(const void* xp, int64_t x_bstride, int64_t x_rows_total, const void* w,
+                                         const float* acc_in, const float* bias, const w2l_bnact_epi_t* e, int N, int Cin,
+                                         int Cout, int Tout, int Kw, int stride, int dil, void* splitk_ws,
+                                         int64_t splitk_ws_bytes, void* stream) {
+    W2L_CHECK_ARG(e != nullptr, "conv1d_igemm_bnact: null descriptor");
+    const w2l_bnact_epi_t* saved = g_fz;
+    g_fz = e;
+    const int rc = igemm_launch(xp, x_bstride, x_rows_total, w, (void*)acc_in, 1, acc_in != nullptr, bias, nullptr, N, Cin, Cout,
+                                Tout, Kw, stride, dil, splitk_ws, splitk_ws_bytes, stream, nullptr);
+    g_fz = saved;
+    return rc;
+}
+
+extern "C" int w2l_conv1d_igemm_bnact(const void* xp, int64_t x_bstride, int64_t x_rows_total, const void* w,
+                                      const float* acc_in, const float* bias, const w2l_bnact_epi_t* e, int N, int Cin, int Cout,
+                                      int Tout, int Kw, int stride, int dil, void* stream) {
+    return w2l_conv1d_igemm_bnact_ws(xp, x_bstride, x_rows_total, w, acc_in, bias, e, N, Cin, Cout, Tout, Kw, stride, dil,
+                                     nullptr, 0, stream);
+}
+
+// measure-and-pick for a fused inference launch: the candidates run with the fused epilogue and are remembered under a key of
+// their own (SYNCHRONISING; warm-up only).  The output is written like a normal launch.
+extern "C" int w2l_conv1d_igemm_bnact_tune_ws(const void* xp, int64_t x_bstride, int64_t x_rows_total, const void* w,
+                                              const float* bias, const w2l_bnact_epi_t* e, int N, int Cin, int Cout, int Tout,
+                                              int Kw, int stride, int dil, int reps, void* splitk_ws, int64_t splitk_ws_bytes,
+                                              void* stream) {
+    W2L_CHECK_ARG(e != nullptr, "conv1d_igemm_bnact_tune: null descriptor");
+    const w2l_bnact_epi_t* saved = g_fz;
+    g_fz = e;
+    const int rc = w2l_conv1d_igemm_tune_ws(xp, x_bstride, x_rows_total, w, nullptr, 1, bias, nullptr, N, Cin, Cout, Tout, Kw,
+                                            stride, dil, reps, splitk_ws, splitk_ws_bytes, stream);
+    g_fz = saved;
+    return rc;
 }
 
 // blocks of the stream-K launch configuration idx would make of this problem with a workspace of ws_bytes; 0: the launch
@@ -1038,6 +1202,7 @@ extern "C" int w2l_conv1d_igemm_tune_ws(const void* xp, int64_t x_bstride, int64
     for (int i = 0; i < kBaseCfgs * kNumSplits; ++i) {
         if (!cfg_feasible(i, Kw, stride, dil, need128)) continue;
         const int ci = i % kNumCfgs, splits = kSplits[i / kBaseCfgs];
+        if (g_fz != nullptr && splits == 0) continue;              // the fused inference epilogue has no stream-K form
         if (splits == 0) {
             // stream-K where one block per tile fills the last round to 85 % or less (and never under the fused epilogue)
             if (g_tune_bb != nullptr || !sk_feasible(ci, N, Cin, Cout, Tout, Kw, stride, dil, splitk_ws, splitk_ws_bytes)) continue;
@@ -1279,7 +1444,8 @@ bool w2l_igemm_fp8_tune_put(const int* v) {      // v[0..7] = key, v[8] = index 
 }
 
 bool w2l_igemm_tune_put(const int* v) {          // v[0..7] = key, v[8] = block-shape index
-    if (v[7] < 0 || v[7] > 2 || !cfg_feasible(v[8], v[4], v[5], v[6], v[7] == 1)) return false;
+    if (v[7] < 0 || v[7] > 3 || !cfg_feasible(v[8], v[4], v[5], v[6], v[7] == 1)) return false;
+    if (v[7] == 3 && kSplits[v[8] / kBaseCfgs] == 0) return false; // (fused inference launches have no stream-K form)
     std::lock_guard<std::mutex> lock(g_tuned_mu);
     g_tuned[ShapeKey(v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7])] = v[8];
     return true;

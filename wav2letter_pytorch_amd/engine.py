@@ -25,7 +25,7 @@ import torch
 
 from . import _lib
 from . import wgrad_groups as WG
-from ._lib import BnActDesc, GradSrc, check, lib, ptr, stream_ptr
+from ._lib import BnActDesc, BnActEpi, GradSrc, check, lib, ptr, stream_ptr
 
 ACT_NONE, ACT_CLAMP20, ACT_RELU = 0, 1, 2
 PAD_ZERO, PAD_REFLECT = 0, 1
@@ -349,6 +349,50 @@ _wev_epoch = [0]
 _in_forward = [False]              # (the backward pass looks packs up too: it has nothing to wait for -- its forward already did)
 
 
+# W2L_FUSED_INFER (default 1): StackEngine.infer runs one fused launch per convolution (w2l_conv1d_igemm_bnact_ws: BatchNorm
+# as a per-channel affine map, residual sum, activation, length mask and the consumer's padding in the convolution's
+# epilogue).  0: infer() calls the evaluation-mode forward (three launches per unit) -- the A/B switch of
+# tools/bench_infer.py, and what an fp8 engine always does (the fused epilogue is built for bf16 operands).
+FUSED_INFER = os.environ.get('W2L_FUSED_INFER', '1') != '0'
+# the folded (scale, shift) vectors of infer() are kept per convolution and dropped whenever this moves: a training-mode
+# forward (running statistics are written through raw pointers), model.train(), invalidate_packed(); version-bumping writes
+# (optimizers, load_state_dict) are seen through the tensors' own versions
+_infer_epoch = [0]
+_infer_warned = [False]
+
+
+def bnact_rows(t: int, T: int, pad_l: int, pad_r: int, reflect: bool) -> List[int]:
+    """host model of the fused epilogue's row map (conv_igemm_kernel, EPI = 2): the padded rows the owner of frame ``t``
+    writes -- its own row pad_l + t, and under reflect padding row pad_l - t if 1 <= t <= pad_l and row pad_l + T - 1 + j if
+    j = T - 1 - t is in [1, pad_r]"""
+    rows = [pad_l + t]
+    if reflect:
+        if 1 <= t <= pad_l:
+            rows.append(pad_l - t)
+        j = T - 1 - t
+        if 1 <= j <= pad_r:
+            rows.append(pad_l + T - 1 + j)
+    return rows
+
+
+def bnact_zero_rows(T: int, pad_l: int, pad_r: int) -> List[int]:
+    """the rows the first column tile of an utterance writes as zeros under zero padding"""
+    return list(range(pad_l)) + [pad_l + T + j for j in range(pad_r)]
+
+
+def fold_bn(gamma, beta, running_mean, running_var, eps: float):
+    """BatchNorm with running statistics as (scale, shift): scale = gamma * rsqrt(var + eps), shift = beta - mean * scale --
+    the host statement of w2l_bn_finalize's eval branch (fp32, same operation order)"""
+    istd = 1.0 / torch.sqrt(running_var.float() + eps)
+    scale = gamma.float() * istd
+    return scale, beta.float() - running_mean.float() * gamma.float() * istd
+
+
+def drop_infer_state():
+    """forget every folded BatchNorm (scale, shift) pair of StackEngine.infer: the next infer() folds again"""
+    _infer_epoch[0] += 1
+
+
 def invalidate_packed(params) -> int:
     """Drop the cached bf16 operand packs of ``params`` (an iterable of Parameters, or a Module).
 
@@ -359,6 +403,7 @@ def invalidate_packed(params) -> int:
     The packs are marked stale, not freed: recorded launch lists (replay.py) name their buffers, and the repack writes into them."""
     if isinstance(params, torch.nn.Module):
         params = params.parameters()
+    drop_infer_state()
     n = 0
     for p in params:
         cache = getattr(p, '_w2l_pack', None)
@@ -717,6 +762,8 @@ class StackEngine:
     def _forward(self, x, lens, training, softmax_mode, want_input_grad):
         _lib.require_device(x)
         global _dropout_calls
+        if training:
+            _infer_epoch[0] += 1            # running statistics move: infer()'s folded BatchNorm vectors are stale
         if self._deferred:
             self.flush_deferred(pos=0)
         precise = self.precise
@@ -861,6 +908,190 @@ class StackEngine:
         for hook in list(AFTER_FORWARD):
             _py(hook)
         return out, ctx
+
+    # ------------------------------------------------------------------ inference
+    def infer(self, x: torch.Tensor, lens: Optional[torch.Tensor], softmax_mode: int = 0):
+        """x fp32 [N, C, T] on device -> (out fp32 [N, T', n_labels], final lengths or None): what ``forward(training=False)``
+        returns, without autograd and without anything kept for a backward pass.  One fused launch per convolution
+        (w2l_conv1d_igemm_bnact_ws), activations in a few reused padded buffers, BatchNorm folded once per weight version."""
+        if self.head is None:
+            raise ValueError('infer() needs a stack with a classifier')
+        if self.fp8 or not FUSED_INFER:
+            if self.fp8 and FUSED_INFER and not _infer_warned[0]:
+                _infer_warned[0] = True
+                import warnings
+                warnings.warn('infer(): the fused inference epilogue is built for bf16 operands; an fp8 engine uses the '
+                              'evaluation-mode forward')
+            with torch.no_grad():
+                out, ctx = self.forward(x, lens, False, softmax_mode)
+            return out, ctx['lens_out']
+        _in_forward[0] = True
+        try:
+            with torch.no_grad():
+                return self._infer(x, lens, softmax_mode)
+        finally:
+            _in_forward[0] = False
+
+    def _infer_affine(self, conv: ConvSpec, cp: int):
+        """(bias, scale, shift) of one convolution for the fused epilogue, fp32 [cp] each or None: scale = gamma *
+        rsqrt(running_var + eps), shift = beta - running_mean * scale through w2l_bn_finalize's eval branch, cached until a
+        tensor's version or the module-level epoch moves"""
+        srcs = (conv.bias, conv.bn_weight, conv.bn_bias, conv.running_mean, conv.running_var)
+        key = (_infer_epoch[0], cp) + tuple((t.data_ptr(), t._version) if t is not None else None for t in srcs)
+        cache = self.__dict__.setdefault('_infer_fold', {})
+        hit = cache.get(id(conv))
+        if hit is not None and hit[0] == key:
+            return hit[1]
+        bias = _padded_vec(conv.bias, cp, 0.0)
+        scale = shift = None
+        if conv.has_bn:
+            scale, shift, _, _ = self._bn_finalize(conv, None, 1, cp, False)
+        self.infer_folds = getattr(self, 'infer_folds', 0) + 1          # (counted: the tests watch the cache)
+        cache[id(conv)] = (key, (bias, scale, shift))
+        return bias, scale, shift
+
+    def _infer_conv(self, conv: ConvSpec, src: Act, epi: BnActEpi, Tout: int):
+        """one fused launch (three in split-bf16 mode: two plain products into an fp32 scratch, then the fused one on top)"""
+        pk = pack_weights(conv, self.precise, need_dgrad=False)
+        if pk.cinp != src.CP:
+            raise ValueError(f'channel mismatch: conv expects {pk.cinp} padded channels, activation has {src.CP}')
+        bias, scale, shift = self._infer_affine(conv, pk.coutp)
+        epi.scale, epi.shift = ptr(scale), ptr(shift)
+        n, cin, cout, kw, stride, dil = src.N, pk.cinp, pk.coutp, conv.kernel, conv.stride, conv.dilation
+        row_off = src.pad_l - conv.pad_l
+        bstride, rows_total = src.rows * src.CP, n * src.rows - row_off
+        st = stream_ptr()
+
+        def xptr(t):
+            return C.c_void_p(t.data_ptr() + row_off * src.CP * 2)
+
+        flops = 2.0 * n * Tout * conv.cout * conv.cin * kw
+        if self.precise:
+            # (one fp32 scratch per shape, kept with the buffer pool: every launch that reads it is behind its writers on the stream)
+            scratch = self.__dict__.setdefault('_infer_acc', {})
+            acc = scratch.get((n, Tout, cout, src.hi.device))
+            if acc is None:
+                acc = scratch[(n, Tout, cout, src.hi.device)] = torch.empty(n, Tout, cout, dtype=torch.float32,
+                                                                            device=src.hi.device)
+                self.infer_buffers = getattr(self, 'infer_buffers', 0) + 1
+            check(lib.w2l_conv1d_igemm(xptr(src.hi), bstride, rows_total, ptr(pk.fwd_hi), ptr(acc), 1, 0, ptr(bias), None, n, cin,
+                                       cout, Tout, kw, stride, dil, st), 'w2l_conv1d_igemm')
+            check(lib.w2l_conv1d_igemm(xptr(src.hi), bstride, rows_total, ptr(pk.fwd_lo), ptr(acc), 1, 1, None, None, n, cin,
+                                       cout, Tout, kw, stride, dil, st), 'w2l_conv1d_igemm')
+            check(lib.w2l_conv1d_igemm_bnact(xptr(src.lo), bstride, rows_total, ptr(pk.fwd_hi), ptr(acc), None, C.byref(epi), n,
+                                             cin, cout, Tout, kw, stride, dil, st), 'w2l_conv1d_igemm_bnact')
+            return
+        ws = _splitk_workspace(src.hi.device, n, cout, Tout)
+        if AUTOTUNE:
+            key = ('bnact', n, cin, cout, Tout, kw, stride, dil, src.hi.device.index)
+            if key not in _tuned_shapes:           # once per shape and device (synchronises)
+                _tuned_shapes.add(key)
+                _tune_state['dirty'] = True
+                check(lib.w2l_conv1d_igemm_bnact_tune_ws(xptr(src.hi), bstride, rows_total, ptr(pk.fwd_hi), ptr(bias),
+                                                         C.byref(epi), n, cin, cout, Tout, kw, stride, dil, TUNE_REPS, ptr(ws),
+                                                         ws.numel(), st), 'w2l_conv1d_igemm_bnact_tune_ws')
+        with _timed('conv_igemm_kernel', flops):
+            check(lib.w2l_conv1d_igemm_bnact_ws(xptr(src.hi), bstride, rows_total, ptr(pk.fwd_hi), None, ptr(bias), C.byref(epi),
+                                                n, cin, cout, Tout, kw, stride, dil, ptr(ws), ws.numel(), st),
+                  'w2l_conv1d_igemm_bnact_ws')
+
+    def _infer(self, x, lens, softmax_mode):
+        _lib.require_device(x)
+        if self._deferred:
+            self.flush_deferred()
+        precise = self.precise
+        N, C0, T0 = x.shape
+        x = x.contiguous().float()
+        dev = x.device
+        n_units = len(self.units)
+        lens_dev, mid_lens, out_lens, lens_final = self._plan_lens(lens, dev)
+        # ---- buffers: an activation's buffer goes back to the free list after its last reader's launch has been enqueued
+        # (one stream: the next writer runs behind it); the list lives on the engine while the input shape stays the same
+        last_use = [0] * (n_units + 1)
+        for ui, u in enumerate(self.units):
+            last_use[u.src] = max(last_use[u.src], ui)
+            if u.res is not None:
+                last_use[u.res_src] = max(last_use[u.res_src], ui)
+        last_use[n_units] = n_units
+        pool = self.__dict__.get('_infer_pool')
+        if pool is None or pool[0] != (N, C0, T0, dev, precise):
+            pool = self.__dict__['_infer_pool'] = ((N, C0, T0, dev, precise), {})
+            self.__dict__.pop('_infer_acc', None)
+        free = pool[1]
+        self.infer_buffers = 0
+
+        def take(rows, cp):
+            lst = free.get((rows, cp))
+            if lst:
+                return lst.pop()
+            self.infer_buffers += 1
+            hi = torch.empty(N, rows, cp, dtype=torch.bfloat16, device=dev)
+            return hi, (torch.empty_like(hi) if precise else None)
+
+        def give(a: Act):
+            free.setdefault((a.hi.shape[1], a.CP), []).append((a.hi, a.lo))
+
+        pl, pr, mode = self._in_pad_for(0)
+        cp0 = padded_channels(C0)
+        a_hi, a_lo = take(pl + T0 + pr, cp0)
+        if lens_dev is not None and not any((u.src == 0 and u.update_lens) for u in self.units):
+            in_mask = None
+        else:
+            in_mask = lens_dev
+        check(lib.w2l_nct_to_ntc(ptr(x), N, C0, T0, cp0, pl, pr, mode, ptr(in_mask), ptr(a_hi), ptr(a_lo), stream_ptr()),
+              'w2l_nct_to_ntc')
+        acts: List[Optional[Act]] = [Act(a_hi, a_lo, N, T0, C0, cp0, pl, pr, mode, in_mask)]
+        for ui, u in enumerate(self.units):
+            src = acts[u.src]
+            conv = u.main
+            mid = None
+            if u.dw is not None:            # separable unit: the depthwise kernel, then the pointwise convolution fused
+                tmid = (src.T + u.dw.pad_l + u.dw.pad_r - (u.dw.kernel - 1) * u.dw.dilation - 1) // u.dw.stride + 1
+                src = mid = self._dw_forward(u.dw, src, mid_lens[ui], out=take(tmid, src.CP))
+            if src.pad_l < conv.pad_l or src.pad_r < conv.pad_r:
+                raise ValueError('activation buffer is not padded enough for its consumer')
+            Tout = (src.T + conv.pad_l + conv.pad_r - (conv.kernel - 1) * conv.dilation - 1) // conv.stride + 1
+            if Tout <= 0:
+                raise ValueError('input too short for this convolution')
+            coutp = padded_channels(conv.cout)
+            res_buf = None
+            epi = BnActEpi()
+            if u.res is not None:           # the second branch first: affine only, dense, read by the main launch's epilogue
+                rsrc = acts[u.res_src]
+                rc = u.res
+                Tres = (rsrc.T + rc.pad_l + rc.pad_r - (rc.kernel - 1) * rc.dilation - 1) // rc.stride + 1
+                if Tres != Tout or padded_channels(rc.cout) != coutp:
+                    raise ValueError('residual branch shape mismatch')
+                res_buf = take(Tout, coutp)
+                e2 = BnActEpi()
+                e2.act, e2.out_hi, e2.out_lo, e2.out_rows = ACT_NONE, ptr(res_buf[0]), ptr(res_buf[1]), Tout
+                e2.pad_l = e2.pad_r = 0
+                e2.pad_mode = PAD_ZERO
+                self._infer_conv(rc, rsrc, e2, Tout)
+                epi.res, epi.res_lo = ptr(res_buf[0]), ptr(res_buf[1])
+            opl, opr, omode = self._in_pad_for(ui + 1)
+            out_hi, out_lo = take(opl + Tout + opr, coutp)
+            lens_out = out_lens[ui]
+            epi.act, epi.lens = u.act, ptr(lens_out)
+            epi.out_hi, epi.out_lo, epi.out_rows = ptr(out_hi), ptr(out_lo), opl + Tout + opr
+            epi.pad_l, epi.pad_r, epi.pad_mode = opl, opr, omode
+            self._infer_conv(conv, src, epi, Tout)
+            acts.append(Act(out_hi, out_lo, N, Tout, conv.cout, coutp, opl, opr, omode, lens_out))
+            if res_buf is not None:
+                free.setdefault((Tout, coutp), []).append(res_buf)
+            if mid is not None:
+                give(mid)
+            for ai in range(ui + 1):
+                if acts[ai] is not None and last_use[ai] == ui:
+                    give(acts[ai])
+                    acts[ai] = None
+        last = acts[-1]
+        logits, _, Th = self._conv_forward(self.head, last, need_stats=False, force_f32=True)
+        give(last)
+        out = torch.empty(N, Th, self.n_labels, dtype=torch.float32, device=dev)
+        check(lib.w2l_log_softmax_fwd(ptr(logits), N, Th, self.n_labels, logits.shape[2], softmax_mode, ptr(out), stream_ptr()),
+              'w2l_log_softmax_fwd')
+        return out, lens_final
 
     def _bump_counters(self, tensors):
         """num_batches_tracked += 1 of every BatchNorm1d that ran in training mode (wav2letter.py:37), one launch: a device
@@ -1014,15 +1245,19 @@ class StackEngine:
         out[:, :c] = km
         return out
 
-    def _dw_forward(self, dwc: ConvSpec, src: Act, lens_mid) -> Act:
+    def _dw_forward(self, dwc: ConvSpec, src: Act, lens_mid, out=None) -> Act:
+        """``out``: optional (hi, lo) buffers [N, Tmid, CP] for the result (infer()'s free list); None: fresh tensors"""
         if src.pad_l < dwc.pad_l or src.pad_r < dwc.pad_r:
             raise ValueError('activation buffer is not padded enough for its depthwise consumer')
         N, cp = src.N, src.CP
         Tp = src.T + dwc.pad_l + dwc.pad_r
         Tmid = (Tp - (dwc.kernel - 1) * dwc.dilation - 1) // dwc.stride + 1
         dev = src.hi.device
-        mid_hi = torch.empty(N, Tmid, cp, dtype=torch.bfloat16, device=dev)
-        mid_lo = torch.empty_like(mid_hi) if self.precise else None
+        if out is not None:
+            mid_hi, mid_lo = out
+        else:
+            mid_hi = torch.empty(N, Tmid, cp, dtype=torch.bfloat16, device=dev)
+            mid_lo = torch.empty_like(mid_hi) if self.precise else None
         row_off = src.pad_l - dwc.pad_l
         off = row_off * cp * 2
         w = self._dw_weight(dwc, cp)

@@ -1,0 +1,94 @@
+"""Evaluation of a finished model over a data loader: the loop behind ``Trainer.test``, the ``test`` command line and
+``ConvCTCASR.transcribe``.  Forward = ``model.infer`` (the fused inference engine), decoding = any decoder of this package,
+metrics = corpus level: errors summed over the set divided by reference lengths summed over the set, with
+``Decoder.cer_ratio`` / ``Decoder.wer_ratio`` arithmetic."""
+from __future__ import annotations
+
+from typing import Dict, List, Optional, Sequence, Tuple
+
+
+def corpus_metrics(decoder, pairs: Sequence[Tuple[str, str]]) -> Dict[str, float]:
+    """(reference, hypothesis) pairs -> test_cer / test_wer / test_len_ratio over the whole set.  CER: character edit
+    distances (spaces removed) summed / reference characters summed; WER: word edit distances summed / reference words
+    summed; length ratio: hypothesis characters / reference characters.  An empty denominator gives 0.0 for an error-free
+    set and inf otherwise."""
+    c_err = c_ref = w_err = w_ref = h_len = r_len = 0
+    for ref, hyp in pairs:
+        e, d = decoder.cer_ratio(ref, hyp)
+        c_err, c_ref = c_err + e, c_ref + d
+        e, d = decoder.wer_ratio(ref, hyp)
+        w_err, w_ref = w_err + e, w_ref + d
+        h_len, r_len = h_len + len(hyp), r_len + len(ref)
+
+    def ratio(a, b):
+        return a / b if b else (0.0 if not a else float('inf'))
+
+    return {'test_cer': ratio(c_err, c_ref), 'test_wer': ratio(w_err, w_ref), 'test_len_ratio': ratio(h_len, r_len)}
+
+
+def frame_seconds(model) -> float:
+    """seconds per output frame: the feature hop times the network's stride product"""
+    return float(model.audio_conf['window_stride']) * float(model.scaling_factor)
+
+
+def decode_batch(model, decoder, out, out_lens, word_times: bool = False):
+    """posteriors of one batch -> (hypotheses, word timings or Nones).  Word timings: forced alignment of each decoded string
+    to the utterance's own frames (``Decoder.align``), then ``get_time_per_word(end_offsets=)``: (word, start s, end s)."""
+    hyps = decoder.decode(out, out_lens)
+    hyps = [h[0] if isinstance(h, (list, tuple)) else h for h in hyps]
+    if not word_times:
+        return hyps, [None] * len(hyps)
+    from .beam_search import get_time_per_word
+    ratio = frame_seconds(model)
+    log_probs = bool(getattr(model, 'infer_log_probs', True))
+    words = []
+    for n, hyp in enumerate(hyps):
+        if not hyp.strip():
+            words.append([])
+            continue
+        size = None if out_lens is None else out_lens[n: n + 1]
+        offs, ends = decoder.align(out[n: n + 1], [hyp], sizes=size, log_probs=log_probs)
+        words.append([(w, float(s), float(e)) for w, s, e in
+                      get_time_per_word(hyp, offs[0][0].tolist(), ratio, end_offsets=ends[0][0].tolist())])
+    return hyps, words
+
+
+def evaluate(model, dataloader, decoder=None, word_times: bool = False) -> Tuple[Dict[str, float], List[dict]]:
+    """``model.infer`` over every batch of ``dataloader`` (the 6-tuples of data_loader._collator) -> (metrics, records):
+    metrics = test_loss (batch-size-weighted mean of the batch losses, as the validation epoch mean is formed), test_cer,
+    test_wer, test_len_ratio (corpus_metrics); one record per utterance with path, text, hypothesis, char_errors, char_ref,
+    word_errors, word_ref (and words with ``word_times``)."""
+    import torch
+    decoder = decoder or model.ctc_decoder
+    was_training = model.training
+    model.eval()
+    records: List[dict] = []
+    loss_sum, n_sum = 0.0, 0
+    try:
+        with torch.no_grad():
+            for batch in dataloader:
+                spect, spect_lens, targets, target_lens, paths, texts = batch
+                x = model._device_batch(spect)
+                out, out_lens = model.infer(x, spect_lens)
+                if x.is_cuda and all(torch.is_tensor(t) for t in (out_lens, targets, target_lens)):
+                    tg_d, ol_d, tl_d = model._device_ints(x.device, targets, out_lens, target_lens)
+                else:
+                    tg_d, ol_d, tl_d = targets, out_lens, target_lens
+                loss = model.criterion(out.transpose(0, 1), tg_d, ol_d, tl_d)
+                hyps, words = decode_batch(model, decoder, out, out_lens, word_times)
+                loss_sum += float(loss) * len(texts)
+                n_sum += len(texts)
+                for path, text, hyp, w in zip(paths, texts, hyps, words):
+                    ce, cr = decoder.cer_ratio(text, hyp)
+                    we, wr = decoder.wer_ratio(text, hyp)
+                    rec = {'path': path, 'text': text, 'hypothesis': hyp, 'char_errors': int(ce), 'char_ref': int(cr),
+                           'word_errors': int(we), 'word_ref': int(wr)}
+                    if word_times:
+                        rec['words'] = [{'word': a, 'start': s, 'end': e} for a, s, e in w]
+                    records.append(rec)
+    finally:
+        if was_training:
+            model.train()
+    metrics = {'test_loss': loss_sum / n_sum if n_sum else float('nan')}
+    metrics.update(corpus_metrics(decoder, [(r['text'], r['hypothesis']) for r in records]))
+    return metrics, records

@@ -321,3 +321,15 @@ class Jasper(ConvCTCASR):
         if self.check_nan:
             assert not bool(torch.isnan(out).any())          # is there any NaN in the result?
         return out, output_lengths
+
+    infer_log_probs = False         # infer() returns probabilities: eval() takes softmax (reference quirk, jasper.py:470-473)
+
+    def infer(self, xs, input_lengths):
+        """what ``forward`` returns in ``eval()`` -- (softmax [batch, time', labels], lengths) -- through the inference
+        engine: one fused launch per convolution (the depthwise half of a separable unit keeps its kernel), no autograd."""
+        from .layers import run_infer
+        out, lens_f = run_infer(self.engine(), xs, input_lengths, softmax_mode=1)
+        output_lengths = lens_f.to(dtype=torch.int64).cpu() if lens_f is not None else None
+        if self.check_nan:
+            assert not bool(torch.isnan(out).any())
+        return out, output_lengths

@@ -224,6 +224,17 @@ def run_stack(engine: StackEngine, x, lens, training: bool, softmax_mode: int = 
     return out, holder.get('lens_out')
 
 
+def run_infer(engine: StackEngine, x, lens, softmax_mode: int = 0):
+    """(out, final lengths) of ``engine.infer``: the inference forward (one fused launch per convolution, no autograd).  What a
+    recorded training step still holds back is launched first, as in front of any eager pass."""
+    from . import replay
+    rp = replay.replayer_for(engine) if x.is_cuda else None
+    if rp is not None:
+        rp.before_eager()
+        rp.flush_pending()
+    return engine.infer(x, lens, softmax_mode)
+
+
 def solo_engine(owner: nn.Module, units_fn: Callable[[], list]) -> StackEngine:
     """Open (head-less) engine for a module called on its own -- Conv1dBlock, MaskedConv1d, JasperBlock, Conv1d --
     cached on the module and rebuilt when a parameter / buffer object, its device or the precision changes."""

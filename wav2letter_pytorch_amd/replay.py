@@ -497,6 +497,7 @@ def _replay_forward(rp, engine, rset, x, lens):
         engine.flush_deferred(pos=0)
     rp.sync_counter(x.device, len(engine.units) + 1)
     rset.F.replay()
+    E.drop_infer_state()                               # a training forward: the running statistics moved (through raw pointers)
     g = rset.group()
     if g is not None:
         g.replays += 1
@@ -651,6 +652,8 @@ def optimizer_step(opt, eager_body) -> bool:
             if have != want:
                 return False                           # someone replaced a gradient tensor: the eager step takes what is there
         rset.O.replay()
+        from .engine import drop_infer_state
+        drop_infer_state()                             # gamma / beta / bias moved without a version bump: infer() folds again
         # (an eager forward after it: the conv weights O updated in the small-parameter launch -- the classifier -- get the
         # version bump the eager step gives them, so that their operand packs are rebuilt; recorded F repacks them anyway)
         for w in rp._conv_weights(engine):

@@ -1,0 +1,113 @@
+"""Command-line evaluation of a checkpoint, the ``test.py`` the reference's README promises (README.md:46-56) and never
+shipped:
+
+    python -m wav2letter_pytorch_amd.test [--config-dir /path/to/configuration] model_path=run/epoch=4-step=900.ckpt \\
+           data.test_manifest=test.csv [model=jasper] [model.mid_layers=20] [decoder=greedy|beam|beam_lm] [lm_path=lm.arpa] \\
+           [beam.k=5] [beam.alpha=0.3] [beam.beta=5] [beam.prune=1e-3] [print_samples=K | print_all=true] \\
+           [output=hyps.jsonl] [word_times=true]
+
+``train.py``'s override syntax and config tree.  The forward pass is ``model.infer`` (one fused launch per convolution);
+``test_loss``, corpus-level ``test_cer`` / ``test_wer`` and ``test_len_ratio`` are printed and returned.  ``output=`` writes one
+JSON line per utterance: path, text, hypothesis, character and word errors (and each word's start / end seconds with
+``word_times=true``, by forced alignment of the hypothesis)."""
+from __future__ import annotations
+
+import json
+import sys
+
+from .train import build_config as _train_config
+
+DECODERS = ('greedy', 'beam', 'beam_lm')
+BEAM_DEFAULTS = dict(k=5, alpha=0.3, beta=5, prune=1e-3)
+
+
+def _truth(v) -> bool:
+    return v is True or (isinstance(v, str) and v.lower() in ('1', 'true', 'yes'))
+
+
+def build_config(argv):
+    """the config tree of ``train.build_config`` plus the evaluation keys, checked: ``model_path`` and
+    ``data.test_manifest`` are required (SystemExit naming the key), ``decoder`` is one of greedy / beam / beam_lm,
+    ``lm_path`` belongs to ``decoder=beam_lm`` only (and that decoder needs it)."""
+    cfg = _train_config(argv)
+    if cfg.get('model_path') in (None, '???', ''):
+        raise SystemExit('model_path is required (e.g. model_path=/path/to/epoch=0-step=100.ckpt)')
+    if cfg.data.get('test_manifest') in (None, '???', ''):
+        raise SystemExit('data.test_manifest is required (e.g. data.test_manifest=/path/to/manifest.csv)')
+    cfg.setdefault('decoder', 'greedy')
+    if cfg.decoder not in DECODERS:
+        raise SystemExit(f'decoder={cfg.decoder!r} is not one of {", ".join(DECODERS)}')
+    lm = cfg.get('lm_path')
+    if lm and cfg.decoder != 'beam_lm':
+        raise SystemExit(f'lm_path is given but decoder={cfg.decoder}: a language model needs decoder=beam_lm')
+    if cfg.decoder == 'beam_lm' and not lm:
+        raise SystemExit('decoder=beam_lm needs lm_path=/path/to/model.arpa')
+    beam = dict(BEAM_DEFAULTS)
+    beam.update(cfg.get('beam') or {})
+    unknown = sorted(set(beam) - set(BEAM_DEFAULTS))
+    if unknown:
+        raise SystemExit(f'unknown beam option(s) {unknown}: beam.k, beam.alpha, beam.beta, beam.prune')
+    cfg['beam'] = type(cfg)(beam)
+    cfg['print_samples'] = int(cfg.get('print_samples') or 0)
+    cfg['print_all'] = _truth(cfg.get('print_all', False))
+    cfg['word_times'] = _truth(cfg.get('word_times', False))
+    cfg.setdefault('output', None)
+    return cfg
+
+
+def decoder_spec(cfg, log_probs: bool):
+    """(class name, constructor keywords) of the decoder the config selects -- no device needed to form it"""
+    labels = cfg.model.labels
+    if cfg.decoder == 'greedy':
+        return 'GreedyDecoder', dict(labels=labels)
+    kw = dict(labels=labels, k=int(cfg.beam.k), alpha=float(cfg.beam.alpha), beta=float(cfg.beam.beta),
+              prune=float(cfg.beam.prune), log_probs=log_probs)
+    if cfg.decoder == 'beam':
+        return 'GPUPrefixBeamSearchDecoder', dict(lm_path=None, **kw)
+    return 'GPUPrefixBeamSearchLMDecoder', dict(lm_path=cfg.lm_path, **kw)
+
+
+def build_decoder(cfg, log_probs: bool):
+    from . import beam_search, decoder
+    name, kw = decoder_spec(cfg, log_probs)
+    return getattr(decoder if name == 'GreedyDecoder' else beam_search, name)(**kw)
+
+
+def main(argv=None):
+    argv = sys.argv[1:] if argv is None else list(argv)
+    cfg = build_config(argv)
+    import torch
+    from .data import label_sets
+    from .data.data_loader import BatchAudioDataLoader, SpectrogramDataset
+    from .evaluate import evaluate
+    from .train import name_to_model
+    if type(cfg.model.labels) is str:
+        cfg.model.labels = list(label_sets.labels_map[cfg.model.labels])
+    if isinstance(cfg.model.get('decoder'), dict):
+        cfg.model.decoder.labels = cfg.model.labels
+    if not torch.cuda.is_available():
+        raise RuntimeError('wav2letter_pytorch_amd runs on MI355X only (no CPU path)')
+    torch.cuda.set_device(0)
+    model = name_to_model[cfg.model.name](cfg.model).cuda()
+    ck = torch.load(cfg.model_path, map_location='cpu')
+    model.load_state_dict(ck['state_dict'] if 'state_dict' in ck else ck)
+    from .engine import invalidate_packed
+    invalidate_packed(model)
+    ds = SpectrogramDataset(cfg.data.test_manifest, cfg.data.audio_conf, cfg.model.labels, mel_spec=cfg.data.mel_spec)
+    loader = BatchAudioDataLoader(ds, batch_size=cfg.data.batch_size)
+    dec = build_decoder(cfg, bool(getattr(model, 'infer_log_probs', True)))
+    metrics, records = evaluate(model, loader, decoder=dec, word_times=cfg.word_times)
+    shown = len(records) if cfg.print_all else min(cfg.print_samples, len(records))
+    for r in records[:shown]:
+        print(f'reference : {r["text"]}')
+        print(f'hypothesis: {r["hypothesis"]}')
+    if cfg.output:
+        with open(cfg.output, 'w') as f:
+            for r in records:
+                f.write(json.dumps(r) + '\n')
+    print('test ' + ' '.join(f'{k}={v:.6g}' for k, v in metrics.items()) + f' utterances={len(records)}', flush=True)
+    return metrics, records
+
+
+if __name__ == '__main__':
+    main()

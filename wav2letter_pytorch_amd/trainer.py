@@ -90,6 +90,26 @@ class Trainer:
         self.global_step = int(ck.get('global_step', 0))
         return int(ck.get('epoch', -1)) + 1          # the checkpoint is written at the END of its epoch
 
+    def test(self, model, dataloader, ckpt_path: Optional[str] = None):
+        """``Trainer.test`` of Lightning: load ``ckpt_path`` (its ``state_dict``), run ``model.infer`` over the loader and
+        return (and print) ``test_loss`` (batch-size-weighted epoch mean, as validation forms it), corpus-level ``test_cer`` /
+        ``test_wer`` (errors summed over the set / reference lengths summed over the set) and ``test_len_ratio``."""
+        if not torch.cuda.is_available():
+            raise RuntimeError('wav2letter_pytorch_amd runs on MI355X only (no CPU path)')
+        from .evaluate import evaluate
+        model = model.cuda()
+        if ckpt_path:
+            ck = torch.load(ckpt_path, map_location='cpu')
+            model.load_state_dict(ck['state_dict'])
+            from .engine import invalidate_packed
+            invalidate_packed(model)
+        metrics, records = evaluate(model, dataloader)
+        self.test_records = records
+        if hasattr(model, '_logged'):
+            model._logged.update(metrics)
+        self._say('test ' + ' '.join(f'{k}={v:.4g}' for k, v in metrics.items()))
+        return metrics
+
     def _clip(self, model, opt):
         hook = getattr(model, 'configure_gradient_clipping', None)
         if hook is not None:

@@ -9,7 +9,7 @@ import torch.nn as nn
 
 from .base_asr_models import ConvCTCASR, feature_size
 from .engine import ACT_CLAMP20, ACT_NONE, PAD_REFLECT, StackEngine, UnitSpec
-from .layers import BatchNorm1d, Conv1d, conv_spec, default_precision, run_stack, solo_engine
+from .layers import BatchNorm1d, Conv1d, conv_spec, default_precision, run_infer, run_stack, solo_engine
 
 
 def same_pad_amounts(rows: int, kernel: int, stride: int, dilation: int) -> Tuple[int, int, int]:
@@ -101,3 +101,12 @@ class Wav2Letter(ConvCTCASR):
         if keep:
             self._last_ctx = res[2]
         return res[0], (None if input_lengths is None else self.compute_output_lengths(input_lengths))
+
+    infer_log_probs = True          # infer() returns log-probabilities (log_softmax, wav2letter.py:86)
+
+    def infer(self, x, input_lengths=None):
+        """what ``forward`` returns in ``eval()`` -- (log_probs [N, T', n_labels], output_lengths or None) -- through the
+        inference engine: one fused launch per convolution, no autograd, nothing kept (``W2L_FUSED_INFER=0``: the evaluation
+        forward itself).  The network reflects at the batch's padded length and masks nothing (wav2letter.py:84-92)."""
+        out, _ = run_infer(self.engine(), x, None, softmax_mode=0)
+        return out, (None if input_lengths is None else self.compute_output_lengths(input_lengths))
