@@ -445,7 +445,7 @@ typedef struct {
     const void* res_lo;     /* its lo half (split-bf16 mode), NULL otherwise */
     int32_t act;            /* 0 none, 1 clamp[0,20], 2 ReLU */
     const int32_t* lens;    /* optional [N] */
-    void* out_hi;           /* [N][out_rows][Cout] bf16 */
+    void* out_hi;           /* [N][out_rows][Cout] bf16 (w2l_conv1d_igemm_bnact_fp8: NULL with an e4m3 output alone) */
     void* out_lo;           /* optional lo half */
     int32_t out_rows, pad_l, pad_r, pad_mode;
 } w2l_bnact_epi_t;
@@ -458,6 +458,29 @@ int w2l_conv1d_igemm_bnact_ws(const void* xp, int64_t x_bstride, int64_t x_rows_
 int w2l_conv1d_igemm_bnact_tune_ws(const void* xp, int64_t x_bstride, int64_t x_rows_total, const void* w, const float* bias,
                                    const w2l_bnact_epi_t* e, int N, int Cin, int Cout, int Tout, int Kw, int stride, int dil,
                                    int reps, void* splitk_ws, int64_t splitk_ws_bytes, void* stream);
+
+/* ---- inference on e4m3 operands: the same unit in the epilogue of the e4m3 implicit GEMM (conv_igemm_kernel, F8, EPI = 2) ----
+ * xq / wq / descale as for w2l_conv1d_igemm_fp8 (stride 1, Cin % 128 == 0, Cout % 64 == 0); on the fp32 accumulators
+ *   v = acc * descale + bias[co],  then the sequence of w2l_conv1d_igemm_bnact: scale / shift, + res (dense bf16), the
+ *       activation, the length mask -- giving a, which is never rounded to bf16 on the way to the e4m3 copy
+ *   out_q[n][pad_l + t][co] = e4m3(a * q_scale)   OCP e4m3 bytes [N][e->out_rows][Cout], round to nearest even, saturating at
+ *                                                 +-448: the conversion of w2l_bn_act_fwd_q's out_q.  Optional; 16-byte aligned
+ *   e->out_hi[n][pad_l + t][co] = bf16(a)         optional here (NULL when nothing reads the bf16 copy); one of the two is needed
+ * Halo rows of both outputs follow e->pad_mode / pad_l / pad_r exactly as above (reflect: byte copies of the mirrored row; zero:
+ * zero bytes), rows beyond pad_l + Tout + pad_r stay untouched, pad_l, pad_r <= 96.  e->out_lo, e->res_lo must be NULL (no
+ * split-bf16 form), there is no acc_in, no split-K and no stream-K.  q_clipped (optional, device int64): the number of
+ * elements with |a| > 448 / q_scale (frames only, halo copies not counted) is added to it, one atomic per block that saw any.
+ * A lane's 4 channels are 4 bytes: 4 (2) consecutive 16-channel tiles are transposed among the 4 lanes of a frame so that the
+ * stores are 16 (8) bytes per lane.  The _tune form measures the e4m3 block shapes WITH the epilogue and remembers the fastest
+ * under statistics flag 3 of the e4m3 plan table ("igemmf8" lines of the tune file); it does not count saturations.  Four of the
+ * e4m3 kernel's block shapes are not built in this form (their epilogue spills): 2x4x6x4, 2x4x8x4, 2x3x5x6, 2x3x6x6.
+ * Replaces, for inference with precision='fp8', w2l_conv1d_igemm_fp8 + w2l_bn_finalize + w2l_bn_act_fwd_q. */
+int w2l_conv1d_igemm_bnact_fp8(const void* xq, int64_t x_bstride, int64_t x_rows_total, const void* wq, float descale,
+                               const float* bias, const w2l_bnact_epi_t* e, void* out_q, float q_scale, int64_t* q_clipped,
+                               int N, int Cin, int Cout, int Tout, int Kw, int dil, void* stream);
+int w2l_conv1d_igemm_bnact_fp8_tune(const void* xq, int64_t x_bstride, int64_t x_rows_total, const void* wq, const float* bias,
+                                    const w2l_bnact_epi_t* e, void* out_q, float q_scale, int N, int Cin, int Cout, int Tout,
+                                    int Kw, int dil, int reps, void* stream);
 
 /* ---- log_softmax + CTC (wav2letter.py:86-87, jasper.py:469-473, base_asr_models.py:23,81,90) ---- */
 /* logits fp32 [N][T][CP] (first C valid) -> out fp32 [N][T][C]; mode 0 log_softmax, 1 softmax */

@@ -3,7 +3,10 @@
 after warming (and tuning) both.  Reports ms per forward, frames / s, library launches per forward, peak allocated memory of
 each leg and the spread of the repeated legs.
 
-    python tools/bench_infer.py [--legs 5] [--seconds 1.0] [--out profiles/infer_ab.txt]"""
+    python tools/bench_infer.py [--legs 5] [--seconds 1.0] [--out profiles/infer_ab.txt]
+
+``--precision fp8``: the two legs are the fused fp8 ``infer`` and the fp8 evaluation-mode forward of one ``precision='fp8'``
+model, and a third leg is the bf16 ``infer`` of the same network."""
 import argparse
 import os
 import sys
@@ -60,15 +63,27 @@ def main():
     ap.add_argument('--legs', type=int, default=5)
     ap.add_argument('--seconds', type=float, default=1.0)
     ap.add_argument('--out', default=None)
+    ap.add_argument('--precision', choices=('bf16', 'fp8'), default='bf16')
     args = ap.parse_args()
     torch.cuda.set_device(0)
-    lines = [f'# tools/bench_infer.py --legs {args.legs} --seconds {args.seconds}: infer (fused) vs eval() forward under no_grad, '
-             f'bf16, alternating legs in one process; {torch.cuda.get_device_name(0)} '
+    fp8 = args.precision == 'fp8'
+    lines = [f'# tools/bench_infer.py --legs {args.legs} --seconds {args.seconds}' + (' --precision fp8' if fp8 else '') +
+             ': infer (fused) vs eval() forward under no_grad, '
+             f'{args.precision}' + (' (third leg: bf16 infer of the same network)' if fp8 else '') +
+             f', alternating legs in one process; {torch.cuda.get_device_name(0)} '
              f'({getattr(torch.cuda.get_device_properties(0), "gcnArchName", "?")})']
-    shapes = [('wav2letter mid_layers=20', Wav2Letter(defaults.wav2letter_model(mid_layers=20, dropout=False)), 32, 1000),
-              ('jasper 10x5', Jasper(defaults.jasper10x5_model()), 16, 1000)]
-    for name, model, n, t in shapes:
-        model = model.cuda().eval()
+    def build(which, precision):
+        cfg = (defaults.wav2letter_model(mid_layers=20, dropout=False, precision=precision) if which == 'w2l'
+               else defaults.jasper10x5_model(precision=precision))
+        return (Wav2Letter if which == 'w2l' else Jasper)(cfg)
+    shapes = [('wav2letter mid_layers=20', 'w2l', 32, 1000), ('jasper 10x5', 'jasper', 16, 1000)]
+    for name, which, n, t in shapes:
+        model = build(which, args.precision).cuda().eval()
+        ref = None
+        if fp8:                                          # the same network (same weights) with bf16 operands
+            ref = build(which, 'bf16')
+            ref.load_state_dict(model.state_dict())
+            ref = ref.cuda().eval()
         x, il, _, _ = defaults.synthetic_batch(n, t)
         xd = x.cuda()
         frames = n * t // model.scaling_factor
@@ -79,20 +94,24 @@ def main():
         def plain():
             with torch.no_grad():
                 return model(xd, il)
-        for _ in range(3):                           # warm both (the first call of each measures its block shapes)
-            fused()
-            plain()
+
+        def bf16():
+            return ref.infer(xd, il)
+        fns = [('infer', fused), ('eval', plain)] + ([('bf16', bf16)] if fp8 else [])
+        for _ in range(3):                           # warm all (the first call of each measures its block shapes)
+            for _, fn in fns:
+                fn()
         torch.cuda.synchronize()
-        nl = {'infer': count_launches(fused)[0], 'eval': count_launches(plain)[0]}
-        res = {'infer': [], 'eval': []}
+        nl = {key: count_launches(fn)[0] for key, fn in fns}
+        res = {key: [] for key, _ in fns}
         mem = {}
         for _ in range(args.legs):
-            for key, fn in (('infer', fused), ('eval', plain)):
+            for key, fn in fns:
                 ms, reps, peak = leg(fn, args.seconds)
                 res[key].append(ms)
                 mem[key] = peak
         lines.append(f'{name} N={n} T={t} ({frames} output frames per forward)')
-        for key in ('infer', 'eval'):
+        for key, _ in fns:
             v = sorted(res[key])
             med = v[len(v) // 2]
             lines.append(f'  {key:5s}: median {med:.3f} ms  min {v[0]:.3f}  max {v[-1]:.3f}  spread {(v[-1] - v[0]) / med * 100:.1f} %  '
@@ -100,7 +119,11 @@ def main():
                          + ' '.join(f'{a:.3f}' for a in res[key]))
         mi, me = sorted(res['infer'])[len(res['infer']) // 2], sorted(res['eval'])[len(res['eval']) // 2]
         lines.append(f'  infer / eval = {mi / me:.3f} ({(1 - mi / me) * 100:+.1f} % time saved)')
-        del model
+        if fp8:
+            mb = sorted(res['bf16'])[len(res['bf16']) // 2]
+            lines.append(f'  fp8 infer / bf16 infer = {mi / mb:.3f}')
+            lines.append(f'  fp8_saturated() after all legs: {model.engine().fp8_saturated()}')
+        del model, ref
         torch.cuda.empty_cache()
     text = '\n'.join(lines)
     print(text)

@@ -132,6 +132,10 @@ _SIGNATURES = {
     'w2l_bn_act_bwd_apply_amax': (c_i, [C.POINTER(BnActDesc), C.POINTER(GradSrc), C.POINTER(GradSrc), c_p, c_p, c_p, c_i,
                                         c_p, c_p, c_i, c_p, c_p]),
     'w2l_conv1d_igemm_fp8': (c_i, [c_p, c_i64, c_i64, c_p, c_p, c_i, c_f, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p]),
+    'w2l_conv1d_igemm_bnact_fp8': (c_i, [c_p, c_i64, c_i64, c_p, c_f, c_p, C.POINTER(BnActEpi), c_p, c_f, c_p, c_i, c_i, c_i, c_i,
+                                         c_i, c_i, c_p]),
+    'w2l_conv1d_igemm_bnact_fp8_tune': (c_i, [c_p, c_i64, c_i64, c_p, c_p, C.POINTER(BnActEpi), c_p, c_f, c_i, c_i, c_i, c_i, c_i,
+                                              c_i, c_i, c_p]),
     'w2l_conv1d_igemm_fp8_tune': (c_i, [c_p, c_i64, c_i64, c_p, c_p, c_i, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p]),
     'w2l_bn_bwd_blocks': (c_i, [c_i, c_i, c_i]),
     'w2l_bn_act_bwd_reduce': (c_i, [C.POINTER(BnActDesc), C.POINTER(GradSrc), C.POINTER(GradSrc), c_p, c_p]),
@@ -261,7 +265,7 @@ TRACE_NAMES = {
     'w2l_conv1d_igemm': 'conv_igemm_kernel', 'w2l_conv1d_igemm_ws': 'conv_igemm_kernel',
     'w2l_conv1d_dgrad_bnreduce_ws': 'conv_igemm_kernel/dgrad+bnreduce',
     'w2l_conv1d_igemm_bnact': 'conv_igemm_kernel/bnact', 'w2l_conv1d_igemm_bnact_ws': 'conv_igemm_kernel/bnact',
-    'w2l_conv1d_igemm_fp8': 'conv_igemm_fp8_kernel',
+    'w2l_conv1d_igemm_fp8': 'conv_igemm_fp8_kernel', 'w2l_conv1d_igemm_bnact_fp8': 'conv_igemm_fp8_kernel/bnact',
     'w2l_conv1d_wgrad': 'conv_wgrad_kernel', 'w2l_conv1d_wgrad_ws': 'conv_wgrad_kernel', 'w2l_conv1d_wgrad_group': 'conv_wgrad_kernel', 'w2l_conv1d_wgrad_fp8': 'conv_wgrad_fp8_kernel',
     'w2l_bn_finalize': 'bn_finalize_kernel', 'w2l_bn_act_fwd': 'bn_act_fwd_kernel', 'w2l_bn_act_fwd_q': 'bn_act_fwd_kernel',
     'w2l_bn_act_fwd_fin': 'bn_act_fwd_kernel', 'w2l_bn_act_bwd_reduce': 'bn_act_bwd_reduce_kernel',

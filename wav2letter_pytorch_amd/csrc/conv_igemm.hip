@@ -22,6 +22,7 @@
 #include <vector>
 #include <mutex>
 #include <tuple>
+#include <type_traits>
 
 namespace {
 
@@ -33,7 +34,7 @@ struct IgemmParams {
     const bf16_raw* w;
     void* y;
     const float* bias;
-    float* stats;
+    union { float* stats; uint8_t* fz_q; };       // fz_q (EPI == 2, which writes no statistics): the e4m3 copy of the output
     int stats_slots;          // 0: one statistics row per 128-column tile (plain stores); S: added onto row (tile mod S) with fp32 atomics
     int64_t x_rows_per_utt;   // x_bstride / Cin
     int64_t x_max_row;        // last readable flat row
@@ -51,7 +52,9 @@ struct IgemmParams {
     // of one tile are consecutive), a whole tile inside one range goes straight to the epilogue
     int sk_ranges, sk_total;
     float descale;            // F8 kernels: y = acc * descale (+ bias), descale = 1 / (activation scale * weight scale)
-    const float* descale_dev; // optional further factor in device memory (scale derived from a device-side amax)
+    // descale_dev: optional further factor in device memory (scale derived from a device-side amax), EPI != 2 only
+    // fz_clip (EPI == 2): optional counter of the elements that saturate the e4m3 copy
+    union { const float* descale_dev; unsigned long long* fz_clip; };
     // EPI == 1 (data gradient fused with the BatchNorm-backward reduction of the layer that produced the conv's input):
     // the output tile IS the gradient wrt that layer's padded activation, so the epilogue also forms, per channel,
     // sum g*gate and sum g*gate*xhat over its rows (what bn_act_bwd_reduce_kernel computes in a pass of its own)
@@ -60,6 +63,8 @@ struct IgemmParams {
     // consumer's padded operand, halo rows included; no y, no statistics.  Its fields (fz_*) SHARE the storage of the EPI == 1
     // fields, which a launch never uses together with them: the struct -- the kernel argument of every instantiation -- keeps
     // its size and offsets, and with them the code of the EPI == 0 / 1 kernels.
+    // F8 && EPI == 2 (w2l_conv1d_igemm_bnact_fp8): the same epilogue on e4m3 operands, v = acc * descale + bias first; the
+    // output is written as e4m3 bytes (fz_q, value * fz_qscale, from the fp32 value) and / or as bf16 (fz_out may be NULL).
     union { const bf16_raw* bn_y; const bf16_raw* fz_res; };          // bn_y: that layer's conv output [N][T][C] (C = this launch's Cout)
                                                                       // fz_res: optional dense [N][Tout][Cout] second branch
     union { const float* bn_scale; const float* fz_scale; };          // bn_*: its BatchNorm scale / shift / mean / invstd
@@ -75,7 +80,7 @@ struct IgemmParams {
     union { int bn_per; int fz_pad_r; };
     int bn_Tp;
     union { int bn_act; int fz_act; };
-    float bn_gk;              // 1 / (1 - p) with dropout, else 1
+    union { float bn_gk; float fz_qscale; };   // bn_gk: 1 / (1 - p) with dropout, else 1; fz_qscale: scale of the e4m3 copy
 };
 
 typedef int v4i __attribute__((ext_vector_type(4)));
@@ -106,6 +111,10 @@ __device__ __forceinline__ void glds16(const void* gsrc, void* lds_dst_wave_base
 // how many ranges share the tile (nsplit), this range's place among them (split) and the first of the tile's consecutive slab ids.
 // Range r owns steps [W r / G, W (r + 1) / G) of the tile-major space, W = tiles * S_; the range holding step w is
 // ceil((w + 1) G / W) - 1.  Host and device run this same function (w2l_conv_streamk_pieces: the CPU test of the decomposition).
+// G e4m3 dwords of one lane as one store (the fused e4m3 epilogue)
+template <int G> struct QVec { typedef unsigned type __attribute__((ext_vector_type(G))); };
+template <> struct QVec<1> { typedef unsigned type; };
+
 struct SkPiece { int tile, s_begin, s_end, nsplit, split; int64_t slab_base; };
 __host__ __device__ inline SkPiece sk_piece(int W, int G, int S_, int r, int w_cur, int w_end) {
     SkPiece q;
@@ -123,7 +132,6 @@ __host__ __device__ inline SkPiece sk_piece(int W, int G, int S_, int r, int w_c
 template <int MW, int NW, int MS, int NS, int S, int PIPE, bool F8 = false, int EPI = 0, bool SK = false>
 __global__ __launch_bounds__(64 * MW * NW, 2) void conv_igemm_kernel(IgemmParams p) {
     static_assert(!SK || (!F8 && EPI == 0 && S == 1), "stream-K is built for the plain bf16 stride-1 kernels");
-    static_assert(EPI != 2 || !F8, "the fused inference epilogue is built for bf16 operands");
     static_assert(!(F8 && PIPE != 0), "the e4m3 kernel is built for K-loop structure 0 only");
     static_assert(EPI != 1 || (!F8 && S == 1), "the fused BatchNorm-backward epilogue belongs to bf16 data gradients");
     constexpr int ESZ = F8 ? 1 : 2;                // bytes per operand element
@@ -438,8 +446,141 @@ __global__ __launch_bounds__(64 * MW * NW, 2) void conv_igemm_kernel(IgemmParams
     // ---- epilogue: bias, optional accumulate, store, BatchNorm partial statistics ----
     // acc[mi][ni][r] = y[co = m0 + (wm*MS+mi)*16 + fq*4 + r][t = t0 + (wn*NS+ni)*16 + fr]
     const int Cout = p.Cout, Tout = p.Tout;
-    const float descale = F8 ? p.descale * (p.descale_dev ? p.descale_dev[0] : 1.f) : 1.f;
-    if constexpr (EPI == 2) {
+    const float descale = F8 ? p.descale * (EPI != 2 && p.descale_dev ? p.descale_dev[0] : 1.f) : 1.f;
+    if constexpr (EPI == 2 && F8) {
+        // ---- inference epilogue on e4m3 operands: the sequence of the bf16 form below on v = acc * descale + bias, stored as
+        // e4m3 bytes a * fz_qscale (round to nearest even, saturating: quant8_e4m3's conversion, from the fp32 a) and, where
+        // something reads it, as bf16.  A lane holds 4 channels of one frame = 4 bytes; the 4 lanes that share a frame (fq = 0..3)
+        // hold the 16 channels of one MFMA tile, and G = 4 consecutive tiles (mi) are transposed among them with two lane
+        // exchanges, so that lane fq stores the 16 bytes of tile mi0 + fq: 64 contiguous bytes per frame and store
+        // instruction instead of 16 (G = 2, the remainder of MS = 6 / 3: 8 bytes per lane; G = 1: the plain dword).
+        const int pl = p.fz_pad_l, pr = p.fz_pad_r;
+        const int len_n = p.fz_lens ? p.fz_lens[n] : Tout;
+        bf16_raw* const obase = p.fz_out ? p.fz_out + (int64_t)n * p.fz_rows * Cout : nullptr;
+        uint8_t* const qbase = p.fz_q ? p.fz_q + (int64_t)n * p.fz_rows * Cout : nullptr;
+        const float qs = p.fz_qscale, q_limit = 448.f / qs;
+        unsigned clipped = 0;
+        auto put = [&](int row, int co, u16x4 hi) { *reinterpret_cast<u16x4*>(obase + (int64_t)row * Cout + co) = hi; };
+        auto group = [&](auto gc, const int mi0) {
+            constexpr int G = decltype(gc)::value;
+            typedef typename QVec<G>::type qvec;
+            f32x4 bias4[G], sc4[G], sh4[G];
+            bool co_ok[G];
+#pragma unroll
+            for (int g = 0; g < G; ++g) {
+                const int co = m0 + (wm * MS + mi0 + g) * 16 + fq * 4;
+                co_ok[g] = co < Cout;
+                bias4[g] = f32x4{0.f, 0.f, 0.f, 0.f};
+                sc4[g] = f32x4{1.f, 1.f, 1.f, 1.f};
+                sh4[g] = bias4[g];
+                if (p.bias && co_ok[g]) bias4[g] = *reinterpret_cast<const f32x4*>(p.bias + co);
+                if (p.fz_scale && co_ok[g]) {
+                    sc4[g] = *reinterpret_cast<const f32x4*>(p.fz_scale + co);
+                    sh4[g] = *reinterpret_cast<const f32x4*>(p.fz_shift + co);
+                }
+            }
+            // after the exchanges this lane holds G * 4 bytes of tile mi0 + (fq mod G), from byte (fq / G) * G * 4 of its 16
+            const int co_q = m0 + (wm * MS + mi0 + (fq & (G - 1))) * 16 + (fq / G) * (G * 4);
+            const bool coq_ok = co_q < Cout;
+            auto putq = [&](int row, qvec v) { *reinterpret_cast<qvec*>(qbase + (int64_t)row * Cout + co_q) = v; };
+#pragma unroll
+            for (int ni = 0; ni < NS; ++ni) {
+                const int tl = (wn * NS + ni) * 16 + fr;       // column inside the tile
+                const int t = t0 + tl;
+                unsigned q[G];
+#pragma unroll
+                for (int g = 0; g < G; ++g) {
+                    const int co = m0 + (wm * MS + mi0 + g) * 16 + fq * 4;
+                    const bool ok = co_ok[g] && t < Tout;
+                    f32x4 v = acc[mi0 + g][ni] * descale + bias4[g];
+                    v = v * sc4[g] + sh4[g];
+                    if (p.fz_res && ok) {
+                        const u16x4 rv = *reinterpret_cast<const u16x4*>(p.fz_res + ((int64_t)n * Tout + t) * Cout + co);
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) v[r] += bf16_bits_to_f32(rv[r]);
+                    }
+                    u16x4 hi;
+                    float a[4];
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        a[r] = v[r];
+                        if (p.fz_act == 1) a[r] = fminf(fmaxf(a[r], 0.f), 20.f);
+                        else if (p.fz_act == 2) a[r] = fmaxf(a[r], 0.f);
+                        if (t >= len_n) a[r] = 0.f;
+                        hi[r] = f32_to_bf16_bits(a[r]);
+                        if (ok && fabsf(a[r]) > q_limit) ++clipped;
+                        a[r] = fminf(fmaxf(a[r] * qs, -448.f), 448.f);
+                    }
+                    int w = __builtin_amdgcn_cvt_pk_fp8_f32(a[0], a[1], 0, false);
+                    w = __builtin_amdgcn_cvt_pk_fp8_f32(a[2], a[3], w, true);
+                    q[g] = (unsigned)w;
+                    if (obase && ok) {
+                        put(pl + t, co, hi);
+                        if (p.fz_pad_mode == 1) {              // nn.ReflectionPad1d: frame j is row pl - j, frame T-1-j row pl+T-1+j
+                            if (t >= 1 && t <= pl) put(pl - t, co, hi);
+                            const int j = Tout - 1 - t;
+                            if (j >= 1 && j <= pr) put(pl + Tout - 1 + j, co, hi);
+                        }
+                    }
+                    if (obase && p.fz_pad_mode != 1 && tt == 0 && co_ok[g]) {   // zero halo: the utterance's first tile
+                        const u16x4 z = u16x4{0, 0, 0, 0};
+                        if (tl < pl) put(tl, co, z);
+                        if (tl < pr) put(pl + Tout + tl, co, z);
+                    }
+                }
+                // transpose the G x G dwords among the lanes fq = 0..G-1 of this frame (every lane takes part: no branch here)
+#pragma unroll
+                for (int b = 1; b < G; b <<= 1) {
+                    const bool up = (fq & b) != 0;
+#pragma unroll
+                    for (int i = 0; i < G; ++i) {
+                        if (i & b) continue;
+                        const unsigned send = up ? q[i] : q[i | b];
+                        const unsigned recv = (unsigned)__shfl_xor((int)send, 16 * b, 64);
+                        if (up) q[i] = recv; else q[i | b] = recv;
+                    }
+                }
+                if (qbase) {
+                    qvec qv = {}, z = {};
+                    if constexpr (G == 1) {
+                        qv = q[0];
+                    } else {
+#pragma unroll
+                        for (int g = 0; g < G; ++g) qv[g] = q[g];
+                    }
+                    if (coq_ok && t < Tout) {
+                        putq(pl + t, qv);
+                        if (p.fz_pad_mode == 1) {
+                            if (t >= 1 && t <= pl) putq(pl - t, qv);
+                            const int j = Tout - 1 - t;
+                            if (j >= 1 && j <= pr) putq(pl + Tout - 1 + j, qv);
+                        }
+                    }
+                    if (p.fz_pad_mode != 1 && tt == 0 && coq_ok) {
+                        if (tl < pl) putq(tl, z);
+                        if (tl < pr) putq(pl + Tout + tl, z);
+                    }
+                }
+            }
+        };
+#pragma unroll
+        for (int g4 = 0; g4 < MS / 4; ++g4) group(std::integral_constant<int, 4>{}, g4 * 4);
+        if constexpr ((MS & 3) >= 2) group(std::integral_constant<int, 2>{}, (MS / 4) * 4);
+        if constexpr (MS & 1) group(std::integral_constant<int, 1>{}, MS - 1);
+        if (p.fz_clip) {                               // one atomic per block, and only from a block that saw a saturation
+#pragma unroll
+            for (int m = 1; m < 64; m <<= 1) clipped += __shfl_xor(clipped, m, 64);
+            __syncthreads();                           // main-loop LDS is dead from here
+            unsigned* red = reinterpret_cast<unsigned*>(smem);
+            if (lane == 0) red[wave] = clipped;
+            __syncthreads();
+            if (tid == 0) {
+                unsigned total = 0;
+                for (int w = 0; w < NWAVES; ++w) total += red[w];
+                if (total) atomicAdd(p.fz_clip, (unsigned long long)total);
+            }
+        }
+    } else if constexpr (EPI == 2) {
         // ---- inference epilogue: v = act((acc + bias [+ y]) * scale + shift [+ residual]), masked, as bf16 into the consumer's
         // padded buffer.  Halo rows are written by the block that owns the frame they mirror (reflect), or by the first
         // column tile of the utterance (zeros): every pad is shorter than a tile (checked by the launcher).
@@ -784,8 +925,24 @@ constexpr int kF8Cfgs[] = {2, 5, 12, 14, 16, 1, 3, 8, 9, 11, 13, 18, 19, 21, 24}
                                                                               //  21 / 24: the 384- / 448-column shapes, round 3)
 constexpr int kNumF8Cfgs = sizeof(kF8Cfgs) / sizeof(kF8Cfgs[0]);
 
+// block shapes the fused e4m3 form (EPI = 2) is built for: all of kF8Cfgs but the four whose epilogue spills next to 96 or more
+// accumulator registers -- 2x4x6x4 (2 VGPRs), 2x4x8x4 (35), 2x3x5x6 (68), 2x3x6x6 (85)
+constexpr bool f8_fused_built(int nw, int ms, int ns) { return !((ms == 6 && ns == 4) || ms == 8 || (nw == 3 && ns == 6)); }
+
 template <int MW, int NW, int MS, int NS>
-int launch_f8(const IgemmParams& p, int tiles_m, size_t lds, hipStream_t stream) {
+int launch_f8(const IgemmParams& p, int tiles_m, size_t lds, hipStream_t stream, bool fused = false) {
+    if (fused) {
+        if constexpr (f8_fused_built(NW, MS, NS)) {
+            auto kernf = conv_igemm_kernel<MW, NW, MS, NS, 1, 0, true, 2>;
+            W2L_CHECK_HIP(w2l_allow_big_lds((const void*)kernf));
+            hipLaunchKernelGGL(kernf, dim3(tiles_m * p.ncols), dim3(64 * MW * NW), lds, stream, p);
+            W2L_CHECK_LAUNCH();
+            return 0;
+        } else {
+            w2l_set_error("conv1d_igemm_bnact_fp8: block shape not built for the fused epilogue");
+            return 1;
+        }
+    }
     auto kern = conv_igemm_kernel<MW, NW, MS, NS, 1, 0, true>;
     W2L_CHECK_HIP(w2l_allow_big_lds((const void*)kern));
     hipLaunchKernelGGL(kern, dim3(tiles_m * p.ncols), dim3(64 * MW * NW), lds, stream, p);
@@ -1284,25 +1441,30 @@ static thread_local int g_force_f8 = -1;
 // testing / profiling hook (per calling thread): pin the e4m3 kernel's block shape (index into kF8Cfgs), -1 = automatic
 extern "C" void w2l_conv_force_fp8_config(int idx) { g_force_f8 = idx; }
 
-static bool f8_feasible(int k, int Kw, int dil, bool need_bn128) {
+// statistics flag of an e4m3 shape key: 0 none, 1 one row per 128-column tile, 3 the fused inference launch
+// (w2l_conv1d_igemm_bnact_fp8): measured, remembered and looked up as itself, like flag 3 of the bf16 table
+static bool f8_feasible(int k, int Kw, int dil, int sflag) {
     if (k < 0 || k >= kNumF8Cfgs) return false;
+    const bool need_bn128 = sflag == 1;
     const TileCfg& c = kCfgs[kF8Cfgs[k]];
+    if (sflag == 3 && (!f8_fused_built(c.nw, c.ms, c.ns) || 16 * c.nw * c.ns <= kFzMaxPad)) return false;   // (a tile writes the
+                                                                                // halo rows: every pad is shorter than it)
     if (need_bn128 && ((16 * c.nw * c.ns) % 128 != 0 || 16 * c.nw * c.ns > 256)) return false;
     const size_t lds = 2 * (size_t)(16 * c.mw * c.ms) * ROWB + 2 * (size_t)cfg_xrows(c, 1, Kw, dil) * ROWB;
     return lds <= 160 * 1024;
 }
 
-static int choose_f8(int N, int Cin, int Cout, int Tout, int Kw, int dil, bool need_bn128) {
-    if (g_force_f8 >= 0) return f8_feasible(g_force_f8, Kw, dil, need_bn128) ? g_force_f8 : -1;
+static int choose_f8(int N, int Cin, int Cout, int Tout, int Kw, int dil, int sflag) {
+    if (g_force_f8 >= 0) return f8_feasible(g_force_f8, Kw, dil, sflag) ? g_force_f8 : -1;
     {
         std::lock_guard<std::mutex> lock(g_tuned_mu);
-        auto it = g_tuned_f8.find(ShapeKey(N, Cin, Cout, Tout, Kw, 1, dil, need_bn128 ? 1 : 0));
+        auto it = g_tuned_f8.find(ShapeKey(N, Cin, Cout, Tout, Kw, 1, dil, sflag));
         if (it != g_tuned_f8.end()) return it->second;
     }
     int best = -1;
     double best_cost = 1e30;
     for (int k = 0; k < kNumF8Cfgs; ++k) {            // cost model: whole rounds of resident blocks, larger tiles preferred
-        if (!f8_feasible(k, Kw, dil, need_bn128)) continue;
+        if (!f8_feasible(k, Kw, dil, sflag)) continue;
         const TileCfg& c = kCfgs[kF8Cfgs[k]];
         const int bm = 16 * c.mw * c.ms, bn = 16 * c.nw * c.ns, waves = c.mw * c.nw;
         const size_t lds = 2 * (size_t)bm * ROWB + 2 * (size_t)cfg_xrows(c, 1, Kw, dil) * ROWB;
@@ -1317,10 +1479,18 @@ static int choose_f8(int N, int Cin, int Cout, int Tout, int Kw, int dil, bool n
     return best;
 }
 
-extern "C" int w2l_conv1d_igemm_fp8(const void* xq, int64_t x_bstride, int64_t x_rows_total, const void* wq, void* y, int y_f32,
-                                    float descale, const float* descale_dev, const float* bias, float* stats_partial, int N,
-                                    int Cin, int Cout, int Tout, int Kw, int dil, void* stream) {
-    W2L_CHECK_ARG(xq && wq && y, "conv1d_igemm_fp8: null pointer");
+// the fused form's outputs (w2l_conv1d_igemm_bnact_fp8); NULL: the plain launch
+struct F8Fused {
+    const w2l_bnact_epi_t* e;
+    void* out_q;
+    float q_scale;
+    int64_t* q_clipped;
+};
+
+static int f8_launch(const void* xq, int64_t x_bstride, int64_t x_rows_total, const void* wq, void* y, int y_f32,
+                     float descale, const float* descale_dev, const float* bias, float* stats_partial, int N,
+                     int Cin, int Cout, int Tout, int Kw, int dil, void* stream, const F8Fused* fz) {
+    W2L_CHECK_ARG(xq && wq && (y || fz), "conv1d_igemm_fp8: null pointer");
     W2L_CHECK_ARG(N > 0 && Tout > 0 && Kw > 0 && dil > 0, "conv1d_igemm_fp8: bad sizes");
     W2L_CHECK_ARG(Cin % 128 == 0 && Cin > 0, "conv1d_igemm_fp8: Cin=%d must be a positive multiple of 128", Cin);
     W2L_CHECK_ARG(Cout % 64 == 0 && Cout > 0, "conv1d_igemm_fp8: Cout=%d must be a positive multiple of 64", Cout);
@@ -1341,10 +1511,35 @@ extern "C" int w2l_conv1d_igemm_fp8(const void* xq, int64_t x_bstride, int64_t x
     p.sk_ranges = 0; p.sk_total = 0;
     p.descale = descale;
     p.descale_dev = descale_dev;
+    if (fz != nullptr) {
+        const w2l_bnact_epi_t* e = fz->e;
+        W2L_CHECK_ARG(e && (e->out_hi || fz->out_q) && !e->out_lo && !e->res_lo && !y && !stats_partial && !descale_dev,
+                      "conv1d_igemm_bnact_fp8: needs an e4m3 or a bf16 output and takes no lo halves");
+        W2L_CHECK_ARG(!fz->out_q || (fz->q_scale > 0.f && ((uintptr_t)fz->out_q & 15) == 0),
+                      "conv1d_igemm_bnact_fp8: the e4m3 output needs a positive scale and 16-byte alignment");
+        W2L_CHECK_ARG(e->pad_l >= 0 && e->pad_r >= 0 && e->pad_l <= kFzMaxPad && e->pad_r <= kFzMaxPad &&
+                      e->out_rows >= e->pad_l + Tout + e->pad_r,
+                      "conv1d_igemm_bnact_fp8: bad output geometry (pads %d,%d of at most %d; %d rows for %d frames)", e->pad_l,
+                      e->pad_r, kFzMaxPad, e->out_rows, Tout);
+        W2L_CHECK_ARG(e->pad_mode != 1 || (e->pad_l < Tout && e->pad_r < Tout),
+                      "conv1d_igemm_bnact_fp8: reflect pad (%d,%d) needs pad < T=%d", e->pad_l, e->pad_r, Tout);
+        W2L_CHECK_ARG((e->scale == nullptr) == (e->shift == nullptr) && e->act >= 0 && e->act <= 2,
+                      "conv1d_igemm_bnact_fp8: scale/shift come together, act is 0..2");
+        p.stats_slots = 0;
+        p.fz_q = (uint8_t*)fz->out_q;
+        p.fz_qscale = fz->out_q ? fz->q_scale : 1.f;
+        p.fz_clip = fz->out_q ? (unsigned long long*)fz->q_clipped : nullptr;
+        p.fz_scale = e->scale; p.fz_shift = e->shift;
+        p.fz_res = (const bf16_raw*)e->res; p.fz_res_lo = nullptr;
+        p.fz_lens = e->lens;
+        p.fz_out = (bf16_raw*)e->out_hi; p.fz_out_lo = nullptr;
+        p.fz_rows = e->out_rows; p.fz_pad_l = e->pad_l; p.fz_pad_r = e->pad_r; p.fz_pad_mode = e->pad_mode;
+        p.fz_act = e->act;
+    }
     const int64_t need = (int64_t)(N - 1) * p.x_rows_per_utt + (int64_t)(Tout - 1) + (int64_t)(Kw - 1) * dil;
     W2L_CHECK_ARG(need <= p.x_max_row, "conv1d_igemm_fp8: padded input too small (need row %lld, have %lld)",
                   (long long)need, (long long)p.x_max_row);
-    const int k = choose_f8(N, Cin, Cout, Tout, Kw, dil, stats_partial != nullptr);
+    const int k = choose_f8(N, Cin, Cout, Tout, Kw, dil, fz ? 3 : (stats_partial != nullptr ? 1 : 0));
     W2L_CHECK_ARG(k >= 0, "conv1d_igemm_fp8: no block shape fits LDS (Kw=%d dil=%d)", Kw, dil);
     const TileCfg& c = kCfgs[kF8Cfgs[k]];
     const int bm = 16 * c.mw * c.ms, bn = 16 * c.nw * c.ns;
@@ -1355,30 +1550,48 @@ extern "C" int w2l_conv1d_igemm_fp8(const void* xq, int64_t x_bstride, int64_t x
     const size_t lds = 2 * (size_t)bm * ROWB + 2 * (size_t)p.xrows_lds * ROWB;
     hipStream_t st = (hipStream_t)stream;
     switch (kF8Cfgs[k]) {                       // block shapes of kCfgs
-        case 2: return launch_f8<2, 2, 4, 4>(p, tiles_m, lds, st);
-        case 5: return launch_f8<4, 2, 4, 4>(p, tiles_m, lds, st);
-        case 12: return launch_f8<2, 4, 4, 4>(p, tiles_m, lds, st);
-        case 14: return launch_f8<2, 4, 6, 4>(p, tiles_m, lds, st);
-        case 16: return launch_f8<2, 4, 8, 4>(p, tiles_m, lds, st);
-        case 1: return launch_f8<2, 2, 3, 4>(p, tiles_m, lds, st);
-        case 3: return launch_f8<2, 2, 5, 4>(p, tiles_m, lds, st);
-        case 8: return launch_f8<2, 3, 4, 3>(p, tiles_m, lds, st);
-        case 9: return launch_f8<2, 3, 5, 3>(p, tiles_m, lds, st);
-        case 11: return launch_f8<2, 4, 3, 4>(p, tiles_m, lds, st);
-        case 13: return launch_f8<2, 4, 5, 4>(p, tiles_m, lds, st);
-        case 18: return launch_f8<2, 3, 5, 6>(p, tiles_m, lds, st);
-        case 19: return launch_f8<2, 3, 6, 6>(p, tiles_m, lds, st);
-        case 21: return launch_f8<2, 4, 4, 6>(p, tiles_m, lds, st);
-        default: return launch_f8<2, 4, 4, 7>(p, tiles_m, lds, st);
+        case 2: return launch_f8<2, 2, 4, 4>(p, tiles_m, lds, st, fz != nullptr);
+        case 5: return launch_f8<4, 2, 4, 4>(p, tiles_m, lds, st, fz != nullptr);
+        case 12: return launch_f8<2, 4, 4, 4>(p, tiles_m, lds, st, fz != nullptr);
+        case 14: return launch_f8<2, 4, 6, 4>(p, tiles_m, lds, st, fz != nullptr);
+        case 16: return launch_f8<2, 4, 8, 4>(p, tiles_m, lds, st, fz != nullptr);
+        case 1: return launch_f8<2, 2, 3, 4>(p, tiles_m, lds, st, fz != nullptr);
+        case 3: return launch_f8<2, 2, 5, 4>(p, tiles_m, lds, st, fz != nullptr);
+        case 8: return launch_f8<2, 3, 4, 3>(p, tiles_m, lds, st, fz != nullptr);
+        case 9: return launch_f8<2, 3, 5, 3>(p, tiles_m, lds, st, fz != nullptr);
+        case 11: return launch_f8<2, 4, 3, 4>(p, tiles_m, lds, st, fz != nullptr);
+        case 13: return launch_f8<2, 4, 5, 4>(p, tiles_m, lds, st, fz != nullptr);
+        case 18: return launch_f8<2, 3, 5, 6>(p, tiles_m, lds, st, fz != nullptr);
+        case 19: return launch_f8<2, 3, 6, 6>(p, tiles_m, lds, st, fz != nullptr);
+        case 21: return launch_f8<2, 4, 4, 6>(p, tiles_m, lds, st, fz != nullptr);
+        default: return launch_f8<2, 4, 4, 7>(p, tiles_m, lds, st, fz != nullptr);
     }
 }
 
+extern "C" int w2l_conv1d_igemm_fp8(const void* xq, int64_t x_bstride, int64_t x_rows_total, const void* wq, void* y, int y_f32,
+                                    float descale, const float* descale_dev, const float* bias, float* stats_partial, int N,
+                                    int Cin, int Cout, int Tout, int Kw, int dil, void* stream) {
+    W2L_CHECK_ARG(y, "conv1d_igemm_fp8: null pointer");
+    return f8_launch(xq, x_bstride, x_rows_total, wq, y, y_f32, descale, descale_dev, bias, stats_partial, N, Cin, Cout, Tout, Kw,
+                     dil, stream, nullptr);
+}
+
+// ---- inference on e4m3 operands: the whole unit in the e4m3 kernel's epilogue (conv_igemm_kernel<F8, EPI = 2>) ----
+extern "C" int w2l_conv1d_igemm_bnact_fp8(const void* xq, int64_t x_bstride, int64_t x_rows_total, const void* wq, float descale,
+                                          const float* bias, const w2l_bnact_epi_t* e, void* out_q, float q_scale,
+                                          int64_t* q_clipped, int N, int Cin, int Cout, int Tout, int Kw, int dil, void* stream) {
+    W2L_CHECK_ARG(e != nullptr, "conv1d_igemm_bnact_fp8: null descriptor");
+    const F8Fused fz{e, out_q, q_scale, q_clipped};
+    return f8_launch(xq, x_bstride, x_rows_total, wq, nullptr, 0, descale, nullptr, bias, nullptr, N, Cin, Cout, Tout, Kw, dil,
+                     stream, &fz);
+}
+
 // measure the e4m3 block shapes for this problem and remember the fastest (SYNCHRONISING: warm-up only)
-extern "C" int w2l_conv1d_igemm_fp8_tune(const void* xq, int64_t x_bstride, int64_t x_rows_total, const void* wq, void* y,
-                                         int y_f32, const float* bias, float* stats_partial, int N, int Cin, int Cout, int Tout,
-                                         int Kw, int dil, int reps, void* stream) {
-    const bool need128 = stats_partial != nullptr;
-    const ShapeKey key(N, Cin, Cout, Tout, Kw, 1, dil, need128 ? 1 : 0);
+static int f8_tune(const void* xq, int64_t x_bstride, int64_t x_rows_total, const void* wq, void* y, int y_f32, const float* bias,
+                   float* stats_partial, int N, int Cin, int Cout, int Tout, int Kw, int dil, int reps, void* stream,
+                   const F8Fused* fz) {
+    const int need128 = fz ? 3 : (stats_partial != nullptr ? 1 : 0);          // the key's statistics flag
+    const ShapeKey key(N, Cin, Cout, Tout, Kw, 1, dil, need128);
     {
         std::lock_guard<std::mutex> lock(g_tuned_mu);
         if (g_tuned_f8.count(key)) return 0;
@@ -1394,13 +1607,13 @@ extern "C" int w2l_conv1d_igemm_fp8_tune(const void* xq, int64_t x_bstride, int6
     for (int k = 0; k < kNumF8Cfgs; ++k) {
         if (!f8_feasible(k, Kw, dil, need128)) continue;
         g_force_f8 = k;
-        if (w2l_conv1d_igemm_fp8(xq, x_bstride, x_rows_total, wq, y, y_f32, 1.f, nullptr, bias, stats_partial, N, Cin, Cout, Tout, Kw,
-                                 dil, stream) != 0)
+        if (f8_launch(xq, x_bstride, x_rows_total, wq, y, y_f32, 1.f, nullptr, bias, stats_partial, N, Cin, Cout, Tout, Kw, dil,
+                      stream, fz) != 0)
             continue;
         (void)hipEventRecord(e0, st);
         for (int r = 0; r < reps; ++r)
-            w2l_conv1d_igemm_fp8(xq, x_bstride, x_rows_total, wq, y, y_f32, 1.f, nullptr, bias, stats_partial, N, Cin, Cout, Tout, Kw,
-                                 dil, stream);
+            f8_launch(xq, x_bstride, x_rows_total, wq, y, y_f32, 1.f, nullptr, bias, stats_partial, N, Cin, Cout, Tout, Kw, dil,
+                      stream, fz);
         (void)hipEventRecord(e1, st);
         if (hipEventSynchronize(e1) != hipSuccess) continue;
         float ms = 0.f;
@@ -1414,6 +1627,23 @@ extern "C" int w2l_conv1d_igemm_fp8_tune(const void* xq, int64_t x_bstride, int6
     std::lock_guard<std::mutex> lock(g_tuned_mu);
     g_tuned_f8[key] = best;
     return 0;
+}
+
+extern "C" int w2l_conv1d_igemm_fp8_tune(const void* xq, int64_t x_bstride, int64_t x_rows_total, const void* wq, void* y,
+                                         int y_f32, const float* bias, float* stats_partial, int N, int Cin, int Cout, int Tout,
+                                         int Kw, int dil, int reps, void* stream) {
+    return f8_tune(xq, x_bstride, x_rows_total, wq, y, y_f32, bias, stats_partial, N, Cin, Cout, Tout, Kw, dil, reps, stream, nullptr);
+}
+
+// measure-and-pick for the fused e4m3 launch: the candidates run WITH the epilogue (descale 1: the time does not depend on it) and
+// are remembered under flag 3 of the e4m3 table (SYNCHRONISING; warm-up only).  The saturation counter is not passed on: the
+// measuring launches must not count.  The outputs are written like a normal launch's, to be overwritten by the one that follows.
+extern "C" int w2l_conv1d_igemm_bnact_fp8_tune(const void* xq, int64_t x_bstride, int64_t x_rows_total, const void* wq,
+                                               const float* bias, const w2l_bnact_epi_t* e, void* out_q, float q_scale, int N,
+                                               int Cin, int Cout, int Tout, int Kw, int dil, int reps, void* stream) {
+    W2L_CHECK_ARG(e != nullptr, "conv1d_igemm_bnact_fp8_tune: null descriptor");
+    const F8Fused fz{e, out_q, q_scale, nullptr};
+    return f8_tune(xq, x_bstride, x_rows_total, wq, nullptr, 0, bias, nullptr, N, Cin, Cout, Tout, Kw, dil, reps, stream, &fz);
 }
 
 // Tuning-cache (de)serialisation used by w2l_tune_save / w2l_tune_load (runtime.hip).
@@ -1437,9 +1667,10 @@ void w2l_igemm_fp8_tune_dump(FILE* f) {
 }
 
 bool w2l_igemm_fp8_tune_put(const int* v) {      // v[0..7] = key, v[8] = index into kF8Cfgs
-    if (v[5] != 1 || v[0] < 1 || v[3] < 1 || !f8_feasible(v[8], v[4], v[6], v[7] != 0)) return false;
+    const int sflag = v[7] == 3 ? 3 : (v[7] != 0 ? 1 : 0);
+    if (v[5] != 1 || v[0] < 1 || v[3] < 1 || !f8_feasible(v[8], v[4], v[6], sflag)) return false;
     std::lock_guard<std::mutex> lock(g_tuned_mu);
-    g_tuned_f8[ShapeKey(v[0], v[1], v[2], v[3], v[4], 1, v[6], v[7] != 0 ? 1 : 0)] = v[8];
+    g_tuned_f8[ShapeKey(v[0], v[1], v[2], v[3], v[4], 1, v[6], sflag)] = v[8];
     return true;
 }
 

@@ -19,7 +19,7 @@ import ctypes as C
 import math
 import os
 from dataclasses import dataclass, field
-from typing import Callable, List, Optional, Sequence
+from typing import Callable, List, Optional, Sequence, Tuple
 
 import torch
 
@@ -349,16 +349,33 @@ _wev_epoch = [0]
 _in_forward = [False]              # (the backward pass looks packs up too: it has nothing to wait for -- its forward already did)
 
 
-# W2L_FUSED_INFER (default 1): StackEngine.infer runs one fused launch per convolution (w2l_conv1d_igemm_bnact_ws: BatchNorm
-# as a per-channel affine map, residual sum, activation, length mask and the consumer's padding in the convolution's
-# epilogue).  0: infer() calls the evaluation-mode forward (three launches per unit) -- the A/B switch of
-# tools/bench_infer.py, and what an fp8 engine always does (the fused epilogue is built for bf16 operands).
+# W2L_FUSED_INFER (default 1): StackEngine.infer runs one fused launch per convolution (w2l_conv1d_igemm_bnact_ws, or
+# w2l_conv1d_igemm_bnact_fp8 where an fp8 engine's convolution reads e4m3 operands: BatchNorm as a per-channel affine map,
+# residual sum, activation, length mask and the consumer's padding in the convolution's epilogue).  0: infer() calls the
+# evaluation-mode forward (three launches per unit) -- the A/B switch of tools/bench_infer.py.
 FUSED_INFER = os.environ.get('W2L_FUSED_INFER', '1') != '0'
 # the folded (scale, shift) vectors of infer() are kept per convolution and dropped whenever this moves: a training-mode
 # forward (running statistics are written through raw pointers), model.train(), invalidate_packed(); version-bumping writes
 # (optimizers, load_state_dict) are seen through the tensors' own versions
 _infer_epoch = [0]
-_infer_warned = [False]
+
+
+def infer_copies(units: Sequence['UnitSpec'], has_head: bool, fp8: bool, cp0: int) -> List[Tuple[bool, bool]]:
+    """Which copies of each activation infer() writes: [(bf16, e4m3)] for activation 0 (the input, ``cp0`` padded channels)
+    .. len(units).  The e4m3 copy follows the forward pass's rule (fp8 engine, padded channels % 128 == 0, some stride-1 dense
+    convolution reads the activation -- StackEngine._fp8_consumers; never the input of a network with a classifier), and
+    every such convolution then reads it.  The bf16 copy exists only if something reads it: a depthwise kernel, a strided
+    convolution, any convolution while there is no e4m3 copy, or the classifier.  (The residual operand of a unit is the
+    dense buffer its second branch writes, not an activation of this list.)"""
+    out = []
+    for ai in range(len(units) + 1):
+        cp = cp0 if ai == 0 else padded_channels(units[ai - 1].main.cout)
+        dense1 = [u.dw is None and u.main.stride == 1 for u in units if u.src == ai]
+        dense1 += [u.res.stride == 1 for u in units if u.res is not None and u.res_src == ai]
+        q = bool(fp8 and ai > 0 and cp % 128 == 0 and any(dense1))
+        hi = (has_head and ai == len(units)) or any(not (q and d) for d in dense1)
+        out.append((bool(hi or not q), q))
+    return out
 
 
 def bnact_rows(t: int, T: int, pad_l: int, pad_r: int, reflect: bool) -> List[int]:
@@ -913,15 +930,11 @@ class StackEngine:
     def infer(self, x: torch.Tensor, lens: Optional[torch.Tensor], softmax_mode: int = 0):
         """x fp32 [N, C, T] on device -> (out fp32 [N, T', n_labels], final lengths or None): what ``forward(training=False)``
         returns, without autograd and without anything kept for a backward pass.  One fused launch per convolution
-        (w2l_conv1d_igemm_bnact_ws), activations in a few reused padded buffers, BatchNorm folded once per weight version."""
+        (w2l_conv1d_igemm_bnact_ws; w2l_conv1d_igemm_bnact_fp8 where an fp8 engine's convolution reads e4m3 operands),
+        activations in a few reused padded buffers, BatchNorm folded once per weight version."""
         if self.head is None:
             raise ValueError('infer() needs a stack with a classifier')
-        if self.fp8 or not FUSED_INFER:
-            if self.fp8 and FUSED_INFER and not _infer_warned[0]:
-                _infer_warned[0] = True
-                import warnings
-                warnings.warn('infer(): the fused inference epilogue is built for bf16 operands; an fp8 engine uses the '
-                              'evaluation-mode forward')
+        if not FUSED_INFER:
             with torch.no_grad():
                 out, ctx = self.forward(x, lens, False, softmax_mode)
             return out, ctx['lens_out']
@@ -950,8 +963,11 @@ class StackEngine:
         cache[id(conv)] = (key, (bias, scale, shift))
         return bias, scale, shift
 
-    def _infer_conv(self, conv: ConvSpec, src: Act, epi: BnActEpi, Tout: int):
-        """one fused launch (three in split-bf16 mode: two plain products into an fp32 scratch, then the fused one on top)"""
+    def _infer_conv(self, conv: ConvSpec, src: Act, epi: BnActEpi, Tout: int, out_q=None, q_scale: float = 1.0):
+        """one fused launch (three in split-bf16 mode: two plain products into an fp32 scratch, then the fused one on top).
+        fp8 engine: a stride-1 convolution whose source carries an e4m3 copy runs on e4m3 operands -- the condition of
+        _conv_forward -- and writes ``out_q`` (optional e4m3 copy of the output at ``q_scale``) itself, epi.out_hi may then be
+        NULL; after a bf16-operand launch ``out_q`` is filled by one w2l_quantize_e4m3 launch over the bf16 output."""
         pk = pack_weights(conv, self.precise, need_dgrad=False)
         if pk.cinp != src.CP:
             raise ValueError(f'channel mismatch: conv expects {pk.cinp} padded channels, activation has {src.CP}')
@@ -961,6 +977,35 @@ class StackEngine:
         row_off = src.pad_l - conv.pad_l
         bstride, rows_total = src.rows * src.CP, n * src.rows - row_off
         st = stream_ptr()
+        if self.fp8 and src.q is not None and stride == 1 and cin % 128 == 0:
+            wq, w_scale = _fp8_weights(conv, pk)
+            xq = C.c_void_p(src.q.data_ptr() + row_off * src.CP)
+            dev = src.q.device
+            if out_q is not None and (self._q_clipped is None or self._q_clipped.device != dev):
+                self._q_clipped = torch.zeros(1, dtype=torch.int64, device=dev)
+            if AUTOTUNE:
+                key = ('bnact_fp8', n, cin, cout, Tout, kw, dil, dev.index)
+                if key not in _tuned_shapes:           # once per shape and device (synchronises)
+                    _tuned_shapes.add(key)
+                    _tune_state['dirty'] = True
+                    check(lib.w2l_conv1d_igemm_bnact_fp8_tune(xq, bstride, rows_total, ptr(wq), ptr(bias), C.byref(epi), ptr(out_q),
+                                                              q_scale, n, cin, cout, Tout, kw, dil, TUNE_REPS, st),
+                          'w2l_conv1d_igemm_bnact_fp8_tune')
+            with _timed('conv_igemm_fp8_kernel', 2.0 * n * Tout * conv.cout * conv.cin * kw):
+                check(lib.w2l_conv1d_igemm_bnact_fp8(xq, bstride, rows_total, ptr(wq), 1.0 / (src.q_scale * w_scale), ptr(bias),
+                                                     C.byref(epi), ptr(out_q), q_scale,
+                                                     ptr(self._q_clipped) if out_q is not None else None, n, cin, cout, Tout, kw,
+                                                     dil, st), 'w2l_conv1d_igemm_bnact_fp8')
+            return
+        if src.hi is None or not epi.out_hi:
+            raise RuntimeError('infer(): a bf16-operand launch without its bf16 buffers (buffer plan out of step)')
+        self._infer_conv_bf16(conv, src, epi, Tout, pk, bias, row_off, bstride, rows_total, st)
+        if out_q is not None:
+            check(lib.w2l_quantize_e4m3(C.c_void_p(epi.out_hi), 0, n * epi.out_rows * cout, q_scale, ptr(out_q), st),
+                  'w2l_quantize_e4m3')
+
+    def _infer_conv_bf16(self, conv, src, epi, Tout, pk, bias, row_off, bstride, rows_total, st):
+        n, cin, cout, kw, stride, dil = src.N, pk.cinp, pk.coutp, conv.kernel, conv.stride, conv.dilation
 
         def xptr(t):
             return C.c_void_p(t.data_ptr() + row_off * src.CP * 2)
@@ -1021,15 +1066,25 @@ class StackEngine:
         self.infer_buffers = 0
 
         def take(rows, cp):
-            lst = free.get((rows, cp))
+            lst = free.get((rows, cp, 2))
             if lst:
                 return lst.pop()
             self.infer_buffers += 1
             hi = torch.empty(N, rows, cp, dtype=torch.bfloat16, device=dev)
             return hi, (torch.empty_like(hi) if precise else None)
 
+        def take_q(rows, cp):           # (the free list is keyed by element size: an e4m3 buffer is half a bf16 buffer)
+            lst = free.get((rows, cp, 1))
+            if lst:
+                return lst.pop()
+            self.infer_buffers += 1
+            return torch.empty(N, rows, cp, dtype=torch.uint8, device=dev)
+
         def give(a: Act):
-            free.setdefault((a.hi.shape[1], a.CP), []).append((a.hi, a.lo))
+            if a.hi is not None:
+                free.setdefault((a.hi.shape[1], a.CP, 2), []).append((a.hi, a.lo))
+            if a.q is not None:
+                free.setdefault((a.q.shape[1], a.CP, 1), []).append(a.q)
 
         pl, pr, mode = self._in_pad_for(0)
         cp0 = padded_channels(C0)
@@ -1041,6 +1096,7 @@ class StackEngine:
         check(lib.w2l_nct_to_ntc(ptr(x), N, C0, T0, cp0, pl, pr, mode, ptr(in_mask), ptr(a_hi), ptr(a_lo), stream_ptr()),
               'w2l_nct_to_ntc')
         acts: List[Optional[Act]] = [Act(a_hi, a_lo, N, T0, C0, cp0, pl, pr, mode, in_mask)]
+        copies = infer_copies(self.units, True, self.fp8, cp0)
         for ui, u in enumerate(self.units):
             src = acts[u.src]
             conv = u.main
@@ -1070,15 +1126,24 @@ class StackEngine:
                 self._infer_conv(rc, rsrc, e2, Tout)
                 epi.res, epi.res_lo = ptr(res_buf[0]), ptr(res_buf[1])
             opl, opr, omode = self._in_pad_for(ui + 1)
-            out_hi, out_lo = take(opl + Tout + opr, coutp)
+            want_hi, want_q = copies[ui + 1]
+            # an e4m3-operand launch writes either copy itself; a bf16-operand launch always writes bf16 (its e4m3 copy, where
+            # one is wanted, is quantised from that by a launch of its own, and the bf16 buffer goes straight back if unread)
+            e4m3_in = self.fp8 and src.q is not None and conv.stride == 1 and src.CP % 128 == 0
+            out_hi, out_lo = take(opl + Tout + opr, coutp) if (want_hi or not e4m3_in) else (None, None)
+            out_q = take_q(opl + Tout + opr, coutp) if want_q else None
+            q_scale = FP8_ACT_SCALE[u.act] if want_q else 1.0
             lens_out = out_lens[ui]
             epi.act, epi.lens = u.act, ptr(lens_out)
             epi.out_hi, epi.out_lo, epi.out_rows = ptr(out_hi), ptr(out_lo), opl + Tout + opr
             epi.pad_l, epi.pad_r, epi.pad_mode = opl, opr, omode
-            self._infer_conv(conv, src, epi, Tout)
-            acts.append(Act(out_hi, out_lo, N, Tout, conv.cout, coutp, opl, opr, omode, lens_out))
+            self._infer_conv(conv, src, epi, Tout, out_q, q_scale)
+            if out_hi is not None and not want_hi:
+                free.setdefault((out_hi.shape[1], coutp, 2), []).append((out_hi, out_lo))
+                out_hi = out_lo = None
+            acts.append(Act(out_hi, out_lo, N, Tout, conv.cout, coutp, opl, opr, omode, lens_out, out_q, q_scale))
             if res_buf is not None:
-                free.setdefault((Tout, coutp), []).append(res_buf)
+                free.setdefault((Tout, coutp, 2), []).append(res_buf)
             if mid is not None:
                 give(mid)
             for ai in range(ui + 1):
