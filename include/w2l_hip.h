@@ -143,6 +143,16 @@ void w2l_conv_force_tile_config(int idx);
 /* likewise for the e4m3 kernel: idx = index into its list of 13 block shapes; an infeasible one (statistics need 128-row
  * tiles, LDS) makes w2l_conv1d_igemm_fp8 fail with a message */
 void w2l_conv_force_fp8_config(int idx);
+/* Host-only plan query: what a launch of this problem would be given, decided by the very function the launches go through
+ * -- no stream, no buffer, no GPU.  stats_flag as in the tune cache's key: 0 none, 1 statistics rows per 128-column tile, 2
+ * statistics added onto slot rows (w2l_conv_stats_mode), 3 the fused inference epilogue.  ws_bytes: the split-K workspace the
+ * launch would bring (0: none).  forced_idx < 0: the remembered (tuned / loaded) choice, else the cost model's; >= 0: as under
+ * w2l_conv_force_tile_config / w2l_conv_force_fp8_config.  out[8] = configuration index, K-loop structure, blocks per tile,
+ * stream-K blocks (0: one block per tile and split), grid blocks, block threads, LDS bytes, feasible.  Returns 0 with
+ * out[7] = 1, or nonzero with out = {-1, 0, ...} and the reason in w2l_last_error. */
+int w2l_conv_plan(int N, int Cin, int Cout, int Tout, int Kw, int stride, int dil, int stats_flag, int64_t ws_bytes,
+                  int forced_idx, int* out);
+int w2l_conv_plan_fp8(int N, int Cin, int Cout, int Tout, int Kw, int dil, int stats_flag, int forced_idx, int* out);
 
 /* Conv1d weight gradient (autograd of the same call sites):
  * dw[kw][co][ci] (+)= sum_{n,t} dy[n][t][co] * xp[n][t*stride + kw*dil][ci]

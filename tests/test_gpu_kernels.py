@@ -362,6 +362,102 @@ def test_conv_igemm_every_configuration(L, with_stats):
     assert split_ran >= 100, split_ran
 
 
+def test_conv_plan_query_is_what_the_launch_runs(L):
+    """w2l_conv_plan / w2l_conv_plan_fp8 against the launches themselves, one launch form after the other: plain, statistics
+    rows, fused bf16 inference (reflect pad 2, a residual), fused e4m3 inference with an e4m3 output.  After the form's tuner
+    has measured the shape, the query names the remembered configuration; the unforced launch and the launch with exactly that
+    index forced write the same bits; and a launch after w2l_conv_force_tile_config(-1) / w2l_conv_force_fp8_config(-1) still
+    does -- the tuner forces its candidates by argument and leaves no per-thread state behind.  No workspace: one block per
+    tile, no atomics, so every launch of one configuration is bit-reproducible."""
+    from wav2letter_pytorch_amd._lib import BnActEpi
+    lib, ptr, st = L.lib, L.ptr, L.stream_ptr()
+    N, Cin, Cout, Tout, Kw = 2, 128, 128, 300, 5
+    rows = Tout + Kw - 1
+    g = torch.Generator().manual_seed(31)
+    x = torch.randn(N, rows, Cin, generator=g)
+    w = torch.randn(Kw, Cout, Cin, generator=g) / (Cin * Kw) ** 0.5
+    xb, wb = x.to(torch.bfloat16).cuda(), w.to(torch.bfloat16).cuda()
+    xq = (x * 16).to(torch.float8_e4m3fn).view(torch.uint8).cuda()
+    wq = (w * 64).to(torch.float8_e4m3fn).view(torch.uint8).cuda()
+    bias, scale, shift = (torch.randn(Cout, generator=g).cuda() for _ in range(3))
+    res = torch.randn(N, Tout, Cout, generator=g).to(torch.bfloat16).cuda()
+    tiles = lib.w2l_conv_stat_tiles(N, Tout)
+    shape = (N, Cin, Cout, Tout, Kw, 1, 1)
+    head = (rows * Cin, N * rows)
+
+    def outputs():
+        return {'y': torch.full((N, Tout, Cout), float('nan'), dtype=torch.bfloat16, device='cuda'),
+                'stats': torch.full((tiles, 2, Cout), float('nan'), device='cuda'),
+                'out': torch.full((N, Tout + 4, Cout), float('nan'), dtype=torch.bfloat16, device='cuda'),
+                'q': torch.full((N, Tout + 4, Cout), 0x7F, dtype=torch.uint8, device='cuda'),
+                'clip': torch.zeros(1, dtype=torch.int64, device='cuda')}
+
+    def epi(o):
+        e = BnActEpi()
+        e.scale, e.shift, e.res, e.act = ptr(scale), ptr(shift), ptr(res), 1
+        e.out_hi, e.out_rows, e.pad_l, e.pad_r, e.pad_mode = ptr(o['out']), Tout + 4, 2, 2, 1
+        return e
+
+    def plain(o, tune):
+        if tune:
+            return lib.w2l_conv1d_igemm_tune_ws(ptr(xb), *head, ptr(wb), ptr(o['y']), 0, ptr(bias), None, *shape, 1, None, 0, st)
+        return lib.w2l_conv1d_igemm_ws(ptr(xb), *head, ptr(wb), ptr(o['y']), 0, 0, ptr(bias), None, *shape, None, 0, st)
+
+    def with_stats(o, tune):
+        if tune:
+            return lib.w2l_conv1d_igemm_tune_ws(ptr(xb), *head, ptr(wb), ptr(o['y']), 0, ptr(bias), ptr(o['stats']), *shape, 1,
+                                                None, 0, st)
+        return lib.w2l_conv1d_igemm_ws(ptr(xb), *head, ptr(wb), ptr(o['y']), 0, 0, ptr(bias), ptr(o['stats']), *shape, None, 0, st)
+
+    def fused(o, tune):
+        e = epi(o)
+        if tune:
+            return lib.w2l_conv1d_igemm_bnact_tune_ws(ptr(xb), *head, ptr(wb), ptr(bias), C.byref(e), *shape, 1, None, 0, st)
+        return lib.w2l_conv1d_igemm_bnact_ws(ptr(xb), *head, ptr(wb), None, ptr(bias), C.byref(e), *shape, None, 0, st)
+
+    def fused_fp8(o, tune):
+        e = epi(o)
+        if tune:
+            return lib.w2l_conv1d_igemm_bnact_fp8_tune(ptr(xq), *head, ptr(wq), ptr(bias), C.byref(e), ptr(o['q']), 4.0,
+                                                       N, Cin, Cout, Tout, Kw, 1, 1, st)
+        return lib.w2l_conv1d_igemm_bnact_fp8(ptr(xq), *head, ptr(wq), 1.0 / (16 * 64), ptr(bias), C.byref(e), ptr(o['q']), 4.0,
+                                              ptr(o['clip']), N, Cin, Cout, Tout, Kw, 1, st)
+
+    def query(fp8, flag, forced):
+        out = (C.c_int * 8)()
+        if fp8:
+            L.check(lib.w2l_conv_plan_fp8(N, Cin, Cout, Tout, Kw, 1, flag, forced, out), 'w2l_conv_plan_fp8')
+        else:
+            L.check(lib.w2l_conv_plan(*shape, flag, 0, forced, out), 'w2l_conv_plan')
+        return list(out)
+
+    for name, form, fp8, flag, written in (('plain', plain, False, 0, ('y',)), ('statistics', with_stats, False, 1, ('y', 'stats')),
+                                           ('fused', fused, False, 3, ('out',)), ('fused e4m3', fused_fp8, True, 3, ('out', 'q', 'clip'))):
+        force = lib.w2l_conv_force_fp8_config if fp8 else lib.w2l_conv_force_tile_config
+        L.check(form(outputs(), True), name + ' tune')
+        chosen = query(fp8, flag, -1)
+        assert chosen[7] == 1 and chosen[2] == 1 and chosen[3] == 0, (name, chosen)     # no workspace: one block per tile
+        assert query(fp8, flag, chosen[0]) == chosen, name
+        runs = []
+        for forced in (None, chosen[0], -1):         # straight after the tuner; that index forced; the hook released
+            if forced is not None:
+                force(forced)
+            o = outputs()
+            try:
+                L.check(form(o, False), name)
+            finally:
+                force(-1)
+            torch.cuda.synchronize()
+            runs.append(o)
+        for k in written:
+            assert not (runs[0][k] != runs[0][k]).any() and not (k == 'q' and (runs[0][k] == 0x7F).all()), (name, k)
+            assert torch.equal(runs[0][k], runs[1][k]) and torch.equal(runs[0][k], runs[2][k]), (name, k, chosen)
+        # a forced index is an argument of the query too
+        assert (query(fp8, flag, 1)[0] == 1) if not fp8 else (query(fp8, flag, 0)[0] == 0), name
+    out = (C.c_int * 8)()                            # the statistics rows refuse a 144-column tile
+    assert lib.w2l_conv_plan(*shape, 1, 0, 6, out) != 0 and list(out) == [-1, 0, 0, 0, 0, 0, 0, 0]
+
+
 @pytest.mark.parametrize('Kw,s,d', [(5, 1, 2), (6, 1, 1), (7, 1, 2), (8, 1, 1), (11, 2, 1), (7, 1, 3), (7, 1, 4), (7, 1, 5)])
 def test_conv_wgrad_every_plan(L, Kw, s, d):
     """split counts x both block orders x {one tap group, two tap groups, 32x32x16 MFMA fragments (order bit 3; stride 1),

@@ -100,6 +100,8 @@ _SIGNATURES = {
     'w2l_conv_streamk_pieces': (c_i, [c_i, c_i, c_i, c_p, c_i]),
     'w2l_conv_force_tile_config': (None, [c_i]),
     'w2l_conv_force_fp8_config': (None, [c_i]),
+    'w2l_conv_plan': (c_i, [c_i] * 8 + [c_i64, c_i, c_p]),
+    'w2l_conv_plan_fp8': (c_i, [c_i] * 8 + [c_p]),
     'w2l_wgrad_force_plan': (None, [c_i, c_i]),
     'w2l_wgrad_deterministic': (None, [c_i]),
     'w2l_wgrad_needs_zero': (c_i, [c_i, c_i, c_i, c_i, c_i]),

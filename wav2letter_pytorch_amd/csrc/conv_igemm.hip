@@ -18,11 +18,13 @@
 #include "common.h"
 #include "../../include/w2l_hip.h"
 #include <algorithm>
+#include <array>
 #include <map>
 #include <vector>
 #include <mutex>
 #include <tuple>
 #include <type_traits>
+#include <utility>
 
 namespace {
 
@@ -853,74 +855,155 @@ constexpr TileCfg kCfgs[] = {
     {2, 4, 4, 7, 1.00f}, {2, 4, 5, 7, 1.00f},                                               // BN 448, 8 waves
 };
 constexpr int kNumCfgs = sizeof(kCfgs) / sizeof(kCfgs[0]);
+constexpr int kSpillCfg = 20;                           // 2x3x7x6 spills: never chosen, kept only for index stability
 
-template <int MW, int NW, int MS, int NS, int PIPE>
-int launch_cfg1(const IgemmParams& p, int tiles_m, size_t lds, hipStream_t stream, int epi = 0) {
-    if (epi == 1) {
-        // statistics rows are per 128-column tile -- unless the sums are added onto slot rows (w2l_conv_stats_mode): any shape then
-        if ((16 * NW * NS) % 128 == 0 && 16 * NW * NS <= 256 ? true : p.stats_slots > 0) {
-            auto kern1 = conv_igemm_kernel<MW, NW, MS, NS, 1, PIPE, false, 1>;
-            W2L_CHECK_HIP(w2l_allow_big_lds((const void*)kern1));
-            hipLaunchKernelGGL(kern1, dim3(tiles_m * p.ncols), dim3(64 * MW * NW), lds, stream, p);
-            W2L_CHECK_LAUNCH();
-            return 0;
-        } else {
-            w2l_set_error("conv1d_igemm: the fused BatchNorm-backward epilogue needs a block shape of 128-column tiles");
-            return 1;
-        }
-    }
-    if (epi == 2) {
-        if (p.stride == 2) {
-            if constexpr (MW == 2 && NW == 2 && MS == 4 && NS == 4) {
-                auto kernf2 = conv_igemm_kernel<2, 2, 4, 4, 2, PIPE, false, 2>;
-                W2L_CHECK_HIP(w2l_allow_big_lds((const void*)kernf2));
-                hipLaunchKernelGGL(kernf2, dim3(tiles_m * p.ncols), dim3(256), lds, stream, p);
-                W2L_CHECK_LAUNCH();
-                return 0;
-            } else {
-                w2l_set_error("conv1d_igemm_bnact: stride 2 is only built for the 128x128 block shape");
-                return 1;
-            }
-        }
-        auto kernf = conv_igemm_kernel<MW, NW, MS, NS, 1, PIPE, false, 2>;
-        W2L_CHECK_HIP(w2l_allow_big_lds((const void*)kernf));
-        hipLaunchKernelGGL(kernf, dim3(tiles_m * p.ncols), dim3(64 * MW * NW), lds, stream, p);
-        W2L_CHECK_LAUNCH();
-        return 0;
-    }
-    if (p.stride == 2) {
-        if constexpr (MW == 2 && NW == 2 && MS == 4 && NS == 4) {
-            auto kern2 = conv_igemm_kernel<2, 2, 4, 4, 2, PIPE>;
-            W2L_CHECK_HIP(w2l_allow_big_lds((const void*)kern2));
-            hipLaunchKernelGGL(kern2, dim3(tiles_m * p.ncols), dim3(256), lds, stream, p);
-            W2L_CHECK_LAUNCH();
-            return 0;
-        } else {
-            w2l_set_error("conv1d_igemm: stride 2 is only built for the 128x128 block shape");
-            return 1;
-        }
-    }
-    if (p.sk_ranges > 0) {
-        auto kern_sk = conv_igemm_kernel<MW, NW, MS, NS, 1, PIPE, false, 0, true>;
-        W2L_CHECK_HIP(w2l_allow_big_lds((const void*)kern_sk));
-        hipLaunchKernelGGL(kern_sk, dim3(p.sk_ranges), dim3(64 * MW * NW), lds, stream, p);
-        W2L_CHECK_LAUNCH();
-        return 0;
-    }
-    auto kern = conv_igemm_kernel<MW, NW, MS, NS, 1, PIPE>;
+constexpr size_t kLdsBytes = 160 * 1024;                // LDS of a CU
+constexpr int kCUs = 256;
+constexpr size_t kTicketBytes = 64 * 1024;              // head of the split-K workspace: one counter per output tile
+constexpr int kFzMaxPad = 96;                           // halo rows a fused tile writes: fewer than the narrowest tile's columns
+// waves a CU holds of these kernels: <= 16 at their VGPR budget -- what the cost model and the tuner's split-K filter count
+// with; a stream-K launch sizes its grid with eight (what two 4-wave blocks hold), one or two blocks per CU
+constexpr int kWaveCap = 16, kSkWaveCap = 8;
+
+// ---- what a launch is asked to do: the problem, and the epilogue fused onto it ----
+struct ConvProblem {                                    // (in the order of the entry points' arguments)
+    const void* x;
+    int64_t x_bstride, x_rows_total;
+    const void* w;
+    void* y;
+    int y_f32, accumulate;
+    const float* bias;
+    float* stats;
+    int N, Cin, Cout, Tout, Kw, stride, dil;
+    void* ws;                                           // split-K workspace or NULL
+    int64_t ws_bytes;
+    hipStream_t stream;
+    bool f8 = false;                                    // e4m3 operands: stride 1, no workspace
+    float descale = 1.f;
+    const float* descale_dev = nullptr;
+    int stats_slots = 0;                                // w2l_conv_stats_mode, where stats is given (set by run())
+};
+
+enum EpiKind { kEpiNone = 0, kEpiBnReduce, kEpiInfer, kEpiInferF8 };
+struct Epilogue {
+    EpiKind kind;
+    struct { const w2l_bnact_t* d; int pad_l, pad_r, pad_mode, per; } bn;       // kEpiBnReduce (w2l_conv1d_dgrad_bnreduce_ws)
+    const w2l_bnact_epi_t* fz;                                                  // kEpiInfer / kEpiInferF8
+    void* out_q;                                                                // kEpiInferF8: the e4m3 output ...
+    float q_scale;
+    int64_t* q_clipped;                                                         // ... and its saturation counter
+};
+constexpr Epilogue kNoEpilogue{};
+static inline bool is_infer(const Epilogue* ep) { return ep->kind == kEpiInfer || ep->kind == kEpiInferF8; }
+
+// statistics flag of a shape key: 0 none, 1 one row per 128-column tile (block shapes of 128 / 256 columns only), 2 added onto
+// slot rows (w2l_conv_stats_mode: every block shape; bf16 only)
+// 3: a fused inference launch (w2l_conv1d_igemm_bnact[_fp8]) -- measured, remembered and looked up as itself; split-K forms
+// included (the combining block runs the epilogue), stream-K forms not
+static int stats_flag(const ConvProblem& pr, const Epilogue* ep) {
+    if (is_infer(ep)) return 3;
+    return pr.stats == nullptr ? 0 : (!pr.f8 && pr.stats_slots > 0 ? 2 : 1);
+}
+
+// ---- the geometry of one block shape on one problem ----
+struct TileGeom {
+    int bm, bn, xrows, waves, tiles_m, tiles_t;
+    size_t lds;
+    int64_t blocks;                                     // one block per output tile
+};
+static TileGeom tile_geom(const TileCfg& c, const ConvProblem& pr) {
+    TileGeom g;
+    g.bm = 16 * c.mw * c.ms;
+    g.bn = 16 * c.nw * c.ns;
+    g.xrows = ((g.bn - 1) * pr.stride + (pr.Kw - 1) * pr.dil + 1 + 7) & ~7;
+    g.waves = c.mw * c.nw;
+    g.tiles_m = (pr.Cout + g.bm - 1) / g.bm;
+    g.tiles_t = (pr.Tout + g.bn - 1) / g.bn;
+    g.lds = 2 * (size_t)g.bm * ROWB + 2 * (size_t)g.xrows * ROWB;
+    g.blocks = (int64_t)g.tiles_m * pr.N * g.tiles_t;
+    return g;
+}
+// a problem of which only the window matters (feasibility of a block shape)
+static ConvProblem window_only(int Kw, int stride, int dil) {
+    ConvProblem pr{};
+    pr.Kw = Kw; pr.stride = stride; pr.dil = dil;
+    return pr;
+}
+static int blocks_per_cu(const TileGeom& g, int wave_cap) {
+    const int by_lds = (int)(kLdsBytes / g.lds), by_waves = wave_cap / g.waves;
+    const int per_cu = by_lds < by_waves ? by_lds : by_waves;
+    return per_cu < 1 ? 1 : per_cu;
+}
+// fill of the last round when `blocks` blocks run `slots` at a time
+static double last_round_fill(int64_t blocks, int64_t slots) {
+    return (double)blocks / (double)(((blocks + slots - 1) / slots) * slots);
+}
+// BatchNorm partial statistics are per 128-column tile: the epilogue assumes whole waves per tile
+static bool bn128_ok(const TileGeom& g) { return g.bn % 128 == 0 && g.bn <= 256; }
+
+// the cost model: time ~ rounds of resident blocks on the CUs x (work per block) x (blocks sharing a CU) / efficiency, larger
+// tiles preferred.  low_occ: factor on the efficiency with fewer than 8 waves per CU; tie: stable tie-break
+static double tile_cost(const TileGeom& g, float eff, double low_occ, int tie) {
+    const int per_cu = blocks_per_cu(g, kWaveCap);
+    const int64_t slots = (int64_t)kCUs * per_cu, rounds = (g.blocks + slots - 1) / slots;
+    const double e = eff * (per_cu * g.waves >= 8 ? 1.0 : low_occ);
+    double cost = (double)rounds * g.bm * g.bn * per_cu / e;
+    cost *= 1.0 + 1e-3 * tie;
+    return cost;
+}
+
+// ---- a planned launch: everything host arithmetic decides, and the kernel's argument ----
+struct ConvPlan {
+    int idx;                                            // configuration index (bf16: see kSplits; e4m3: into kF8Cfgs)
+    int shape, pipe, splits, sk_ranges;                 // kCfgs row, K-loop structure, blocks per tile, stream-K blocks or 0
+    int epi;                                            // the kernel's EPI
+    bool f8;
+    unsigned grid, threads;
+    size_t lds;
+    hipStream_t stream;
+    IgemmParams p;
+};
+
+template <typename K>
+int launch_kernel(K kern, const ConvPlan& pl) {
     W2L_CHECK_HIP(w2l_allow_big_lds((const void*)kern));
-    hipLaunchKernelGGL(kern, dim3(tiles_m * p.ncols), dim3(64 * MW * NW), lds, stream, p);
+    hipLaunchKernelGGL(kern, dim3(pl.grid), dim3(pl.threads), pl.lds, pl.stream, pl.p);
     W2L_CHECK_LAUNCH();
     return 0;
 }
 
-template <int MW, int NW, int MS, int NS>
-int launch_cfg(const IgemmParams& p, int tiles_m, size_t lds, hipStream_t stream, int pipe, int epi = 0) {
-    return pipe ? launch_cfg1<MW, NW, MS, NS, 1>(p, tiles_m, lds, stream, epi)
-                : launch_cfg1<MW, NW, MS, NS, 0>(p, tiles_m, lds, stream, epi);
+template <int MW, int NW, int MS, int NS, int PIPE>
+int launch_cfg1(const ConvPlan& pl) {
+    constexpr bool k128x128 = MW == 2 && NW == 2 && MS == 4 && NS == 4;          // the one shape with stride-2 forms
+    if (pl.epi == 1) {
+        // statistics rows are per 128-column tile -- unless the sums are added onto slot rows (w2l_conv_stats_mode): any shape then
+        if ((16 * NW * NS) % 128 == 0 && 16 * NW * NS <= 256 ? true : pl.p.stats_slots > 0)
+            return launch_kernel(conv_igemm_kernel<MW, NW, MS, NS, 1, PIPE, false, 1>, pl);
+        w2l_set_error("conv1d_igemm: the fused BatchNorm-backward epilogue needs a block shape of 128-column tiles");
+        return 1;
+    }
+    if (pl.p.stride == 2 && !k128x128) {
+        w2l_set_error("conv1d_igemm: stride 2 is only built for the 128x128 block shape");
+        return 1;
+    }
+    if (pl.epi == 2) {
+        if constexpr (k128x128)
+            if (pl.p.stride == 2) return launch_kernel(conv_igemm_kernel<2, 2, 4, 4, 2, PIPE, false, 2>, pl);
+        return launch_kernel(conv_igemm_kernel<MW, NW, MS, NS, 1, PIPE, false, 2>, pl);
+    }
+    if constexpr (k128x128)
+        if (pl.p.stride == 2) return launch_kernel(conv_igemm_kernel<2, 2, 4, 4, 2, PIPE>, pl);
+    if (pl.sk_ranges > 0) return launch_kernel(conv_igemm_kernel<MW, NW, MS, NS, 1, PIPE, false, 0, true>, pl);
+    return launch_kernel(conv_igemm_kernel<MW, NW, MS, NS, 1, PIPE>, pl);
 }
 
-// e4m3 launches: K-loop structure 0, stride 1, a subset of the block shapes (indices into kCfgs)
+template <int MW, int NW, int MS, int NS>
+int launch_cfg(const ConvPlan& pl) {
+    return pl.pipe ? launch_cfg1<MW, NW, MS, NS, 1>(pl) : launch_cfg1<MW, NW, MS, NS, 0>(pl);
+}
+
+// e4m3 launches: K-loop structure 0, stride 1, a subset of the block shapes (indices into kCfgs); a configuration index of the
+// e4m3 kernel is an index into this list
 constexpr int kF8Cfgs[] = {2, 5, 12, 14, 16, 1, 3, 8, 9, 11, 13, 18, 19, 21, 24};     // (the first five were round 2's first set;
                                                                               //  21 / 24: the 384- / 448-column shapes, round 3)
 constexpr int kNumF8Cfgs = sizeof(kF8Cfgs) / sizeof(kF8Cfgs[0]);
@@ -930,25 +1013,30 @@ constexpr int kNumF8Cfgs = sizeof(kF8Cfgs) / sizeof(kF8Cfgs[0]);
 constexpr bool f8_fused_built(int nw, int ms, int ns) { return !((ms == 6 && ns == 4) || ms == 8 || (nw == 3 && ns == 6)); }
 
 template <int MW, int NW, int MS, int NS>
-int launch_f8(const IgemmParams& p, int tiles_m, size_t lds, hipStream_t stream, bool fused = false) {
-    if (fused) {
+int launch_f8(const ConvPlan& pl) {
+    if (pl.epi == 2) {
         if constexpr (f8_fused_built(NW, MS, NS)) {
-            auto kernf = conv_igemm_kernel<MW, NW, MS, NS, 1, 0, true, 2>;
-            W2L_CHECK_HIP(w2l_allow_big_lds((const void*)kernf));
-            hipLaunchKernelGGL(kernf, dim3(tiles_m * p.ncols), dim3(64 * MW * NW), lds, stream, p);
-            W2L_CHECK_LAUNCH();
-            return 0;
+            return launch_kernel(conv_igemm_kernel<MW, NW, MS, NS, 1, 0, true, 2>, pl);
         } else {
             w2l_set_error("conv1d_igemm_bnact_fp8: block shape not built for the fused epilogue");
             return 1;
         }
     }
-    auto kern = conv_igemm_kernel<MW, NW, MS, NS, 1, 0, true>;
-    W2L_CHECK_HIP(w2l_allow_big_lds((const void*)kern));
-    hipLaunchKernelGGL(kern, dim3(tiles_m * p.ncols), dim3(64 * MW * NW), lds, stream, p);
-    W2L_CHECK_LAUNCH();
-    return 0;
+    return launch_kernel(conv_igemm_kernel<MW, NW, MS, NS, 1, 0, true>, pl);
 }
+
+// index -> instantiation, generated from kCfgs (and kF8Cfgs) themselves: a row of the table IS the template arguments
+typedef int (*LaunchFn)(const ConvPlan&);
+template <int I> constexpr LaunchFn kLaunchCfg = &launch_cfg<kCfgs[I].mw, kCfgs[I].nw, kCfgs[I].ms, kCfgs[I].ns>;
+template <int I> constexpr LaunchFn kLaunchF8 = &launch_f8<kCfgs[I].mw, kCfgs[I].nw, kCfgs[I].ms, kCfgs[I].ns>;
+template <size_t... I>
+constexpr std::array<LaunchFn, sizeof...(I)> cfg_launchers(std::index_sequence<I...>) { return {{kLaunchCfg<(int)I>...}}; }
+template <size_t... K>
+constexpr std::array<LaunchFn, sizeof...(K)> f8_launchers(std::index_sequence<K...>) { return {{kLaunchF8<kF8Cfgs[K]>...}}; }
+constexpr auto kCfgLaunchers = cfg_launchers(std::make_index_sequence<kNumCfgs>{});
+constexpr auto kF8Launchers = f8_launchers(std::make_index_sequence<kNumF8Cfgs>{});
+
+int launch(const ConvPlan& pl) { return (pl.f8 ? kF8Launchers[pl.idx] : kCfgLaunchers[pl.shape])(pl); }
 
 }  // namespace
 
@@ -959,278 +1047,349 @@ constexpr int kNumSplits = sizeof(kSplits) / sizeof(kSplits[0]);
 constexpr int kMaxSplit = 8;
 constexpr int kSkMinSteps = 8;                          // a stream-K range is at least this many steps
 constexpr int kBaseCfgs = 2 * kNumCfgs;
-constexpr size_t kTicketBytes = 64 * 1024;              // head of the split-K workspace: one counter per output tile
-// thread-local: the tuner (and the test hook below) force a configuration for launches made by the CALLING thread only --
-// a backward running on an autograd worker thread while another thread tunes never sees a forced index
+// the three per-thread hooks of the ABI, each read in one place (run()).  thread-local: a forced configuration holds for
+// launches made by the CALLING thread only -- a backward running on an autograd worker thread never sees another thread's
 static thread_local int g_force_cfg = -1;
-static thread_local int g_stats_slots = 0;      // w2l_conv_stats_mode
+static thread_local int g_force_f8 = -1;
+static thread_local int g_stats_slots = 0;
 extern "C" void w2l_conv_stats_mode(int slots) { g_stats_slots = slots < 0 ? 0 : (slots > 64 ? 64 : slots); }
 extern "C" void w2l_conv_force_tile_config(int idx) { g_force_cfg = idx; }
+// testing / profiling hook (per calling thread): pin the e4m3 kernel's block shape (index into kF8Cfgs), -1 = automatic
+extern "C" void w2l_conv_force_fp8_config(int idx) { g_force_f8 = idx; }
 W2L_DIAG_IGEMM_EXPORTS
 
-static inline int cfg_xrows(const TileCfg& c, int stride, int Kw, int dil) {
-    const int bn = 16 * c.nw * c.ns;
-    return ((bn - 1) * stride + (Kw - 1) * dil + 1 + 7) & ~7;
+// measured choices (the _tune entry points): shape -> configuration index; the e4m3 kernel's in a table of its own (same key,
+// stride always 1, value = index into kF8Cfgs)
+typedef std::tuple<int, int, int, int, int, int, int, int> ShapeKey;
+static std::map<ShapeKey, int> g_tuned, g_tuned_f8;
+static std::mutex g_tuned_mu;
+static ShapeKey shape_key(const ConvProblem& pr, int sflag) {
+    return ShapeKey(pr.N, pr.Cin, pr.Cout, pr.Tout, pr.Kw, pr.stride, pr.dil, sflag);
 }
 
-// measured choices (w2l_conv1d_igemm_tune): shape -> block-shape index
-typedef std::tuple<int, int, int, int, int, int, int, int> ShapeKey;
-static std::map<ShapeKey, int> g_tuned;
-static std::mutex g_tuned_mu;
-
-static bool cfg_feasible(int idx, int Kw, int stride, int dil, bool need_bn128) {
+static bool cfg_feasible(int idx, const ConvProblem& pr, int sflag) {
     if (idx < 0 || idx >= kBaseCfgs * kNumSplits) return false;
     const int i = idx % kNumCfgs;
-    const TileCfg& c = kCfgs[i];
-    const int bm = 16 * c.mw * c.ms, bn = 16 * c.nw * c.ns;
-    if (need_bn128 && (bn % 128 != 0 || bn > 256)) return false;   // the statistics epilogue assumes whole waves per 128-column tile
-    if (stride != 1 && i != 2) return false;
-    if (i == 20) return false;                               // spills (kept only for index stability)
-    const size_t lds = 2 * (size_t)bm * ROWB + 2 * (size_t)cfg_xrows(c, stride, Kw, dil) * ROWB;
-    return lds <= 160 * 1024;
+    const TileGeom g = tile_geom(kCfgs[i], pr);
+    if (sflag == 1 && !bn128_ok(g)) return false;
+    if (pr.stride != 1 && i != 2) return false;             // strided convs (first layer only) use the 128x128 shape
+    if (i == kSpillCfg) return false;
+    return g.lds <= kLdsBytes;
 }
 
-// pick the block shape: a measured choice if this shape was tuned, else a cost model (whole rounds of
-// resident blocks on the 256 CUs, larger tiles preferred)
-// statistics flag of a shape key: 0 none, 1 one row per 128-column tile (block shapes of 128 / 256 columns only), 2 added onto
-// slot rows (w2l_conv_stats_mode: every block shape)
-// 3: a fused inference launch (w2l_conv1d_igemm_bnact) -- measured, remembered and looked up as itself; split-K forms included
-// (the combining block runs the epilogue), stream-K forms not
-static thread_local const w2l_bnact_epi_t* g_fz = nullptr;      // the fused launch's descriptor (same thread, like g_force_cfg)
-constexpr int kFzMaxPad = 96;                                   // halo rows a tile writes: fewer than the narrowest tile's columns
-static int stats_flag(const float* stats_partial) {
-    if (g_fz != nullptr) return 3;
-    return stats_partial == nullptr ? 0 : (g_stats_slots > 0 ? 2 : 1);
+static bool f8_feasible(int k, const ConvProblem& pr, int sflag) {
+    if (k < 0 || k >= kNumF8Cfgs) return false;
+    const TileCfg& c = kCfgs[kF8Cfgs[k]];
+    const TileGeom g = tile_geom(c, pr);
+    if (sflag == 3 && (!f8_fused_built(c.nw, c.ms, c.ns) || g.bn <= kFzMaxPad)) return false;   // (a tile writes the halo
+                                                                                // rows: every pad is shorter than it)
+    if (sflag == 1 && !bn128_ok(g)) return false;
+    return g.lds <= kLdsBytes;
 }
 
-static int choose_cfg(int N, int Cin, int Cout, int Tout, int Kw, int stride, int dil, int sflag) {
-    const bool need_bn128 = sflag == 1;
-    if (g_force_cfg < 0) {
+// pick the configuration: the forced one, else a measured choice if this shape was tuned, else the cost model (which only
+// ranks the PIPE = 0, one-block-per-tile variants).  -1: nothing fits
+static int choose_cfg(const ConvProblem& pr, int sflag, int forced) {
+    if (forced >= 0) return (pr.f8 ? f8_feasible(forced, pr, sflag) : cfg_feasible(forced, pr, sflag)) ? forced : -1;
+    {
         std::lock_guard<std::mutex> lock(g_tuned_mu);
-        auto it = g_tuned.find(ShapeKey(N, Cin, Cout, Tout, Kw, stride, dil, sflag));
-        if (it != g_tuned.end()) return it->second;
+        const auto& tuned = pr.f8 ? g_tuned_f8 : g_tuned;
+        auto it = tuned.find(shape_key(pr, sflag));
+        if (it != tuned.end()) return it->second;
     }
-    if (g_force_cfg >= 0) return cfg_feasible(g_force_cfg, Kw, stride, dil, need_bn128) ? g_force_cfg : -1;
-    int best = -1;                                     // the cost model only ranks the PIPE = 0 variants
+    int best = -1;
     double best_cost = 1e30;
-    for (int i = 0; i < kNumCfgs; ++i) {
-        const TileCfg& c = kCfgs[i];
-        const int bm = 16 * c.mw * c.ms, bn = 16 * c.nw * c.ns;
-        if (need_bn128 && (bn % 128 != 0 || bn > 256)) continue;     // BatchNorm partial statistics are per 128-column tile
-        if (stride != 1 && i != 2) continue;          // strided convs (first layer only) use the 128x128 shape
-        if (i == 20) continue;
-        const size_t lds = 2 * (size_t)bm * ROWB + 2 * (size_t)cfg_xrows(c, stride, Kw, dil) * ROWB;
-        if (lds > 160 * 1024) continue;
-        const int waves = c.mw * c.nw;
-        int per_cu = (int)((160 * 1024) / lds);
-        const int wave_cap = 16 / waves;                 // <= 16 waves per CU at the VGPR budget of these kernels
-        if (per_cu > wave_cap) per_cu = wave_cap;
-        if (per_cu < 1) continue;
-        const long blocks = (long)((Cout + bm - 1) / bm) * N * ((Tout + bn - 1) / bn);
-        const long slots = 256L * per_cu;
-        const long rounds = (blocks + slots - 1) / slots;
-        // time ~ rounds x (work per block) x (blocks sharing a CU) / efficiency
-        double eff = c.eff * (per_cu * waves >= 8 ? 1.0 : 0.75);
-        double cost = (double)rounds * bm * bn * per_cu / eff;
-        cost *= 1.0 + 1e-3 * i;                          // stable tie-break
-        if (cost < best_cost) { best_cost = cost; best = i; }
+    for (int k = 0; k < (pr.f8 ? kNumF8Cfgs : kNumCfgs); ++k) {
+        if (!(pr.f8 ? f8_feasible(k, pr, sflag) : cfg_feasible(k, pr, sflag))) continue;
+        const TileCfg& c = kCfgs[pr.f8 ? kF8Cfgs[k] : k];
+        const double cost = tile_cost(tile_geom(c, pr), c.eff, pr.f8 ? 1.0 : 0.75, k);
+        if (cost < best_cost) { best_cost = cost; best = k; }
     }
     return best;
 }
 
 extern "C" int w2l_conv_stat_tiles(int N, int Tout) { return N * ((Tout + 127) / 128); }
 
-// bytes of split-K workspace that let every configuration of this problem run (slabs of the largest split + the tickets)
-static size_t splitk_bytes(int cfg_i, int splits, int N, int Cout, int Tout) {
-    const TileCfg& c = kCfgs[cfg_i];
-    const int bm = 16 * c.mw * c.ms, bn = 16 * c.nw * c.ns;
-    const size_t tiles = (size_t)((Cout + bm - 1) / bm) * N * ((Tout + bn - 1) / bn);
-    return kTicketBytes + tiles * splits * bm * bn * sizeof(float);
+// bytes of split-K workspace for `splits` slabs per tile (+ the tickets)
+static size_t splitk_bytes(const TileGeom& g, int splits) {
+    return kTicketBytes + (size_t)g.blocks * splits * g.bm * g.bn * sizeof(float);
 }
 
 // blocks of a stream-K launch of this shape: the slots the chip has for it (one or two blocks per CU)
-static int sk_ranges(const TileCfg& c, int stride, int Kw, int dil) {
-    const size_t lds = 2 * (size_t)(16 * c.mw * c.ms) * ROWB + 2 * (size_t)cfg_xrows(c, stride, Kw, dil) * ROWB;
-    int per_cu = (int)((160 * 1024) / lds);
-    if (per_cu > 8 / (c.mw * c.nw)) per_cu = 8 / (c.mw * c.nw);          // (eight waves per CU: what two 4-wave blocks hold)
-    return 256 * (per_cu < 1 ? 1 : (per_cu > 2 ? 2 : per_cu));
-}
+static int sk_ranges(const TileGeom& g) { return kCUs * blocks_per_cu(g, kSkWaveCap); }
 
-static bool sk_feasible(int cfg_i, int N, int Cin, int Cout, int Tout, int Kw, int stride, int dil, const void* ws, int64_t ws_bytes) {
-    if (ws == nullptr || stride != 1) return false;
-    const TileCfg& c = kCfgs[cfg_i];
-    const int bm = 16 * c.mw * c.ms, bn = 16 * c.nw * c.ns;
-    const int64_t tiles = (int64_t)((Cout + bm - 1) / bm) * N * ((Tout + bn - 1) / bn);
-    const int64_t steps = (int64_t)(Cin / BK) * Kw, G = sk_ranges(c, stride, Kw, dil);
+static bool sk_feasible(const TileGeom& g, const ConvProblem& pr) {
+    if (pr.ws == nullptr || pr.stride != 1) return false;
+    const int64_t tiles = g.blocks, steps = (int64_t)(pr.Cin / BK) * pr.Kw, G = sk_ranges(g);
     if (tiles * steps / G < kSkMinSteps || (tiles * steps + steps) * G >= (1LL << 31)) return false;
     return tiles * (int64_t)sizeof(unsigned) <= (int64_t)kTicketBytes &&
-           (int64_t)kTicketBytes + (tiles + G) * bm * bn * (int64_t)sizeof(float) <= ws_bytes;
+           (int64_t)kTicketBytes + (tiles + G) * g.bm * g.bn * (int64_t)sizeof(float) <= pr.ws_bytes;
 }
 
-static bool split_feasible(int cfg_i, int splits, int N, int Cin, int Cout, int Tout, int Kw, const void* ws, int64_t ws_bytes) {
+static bool split_feasible(const TileGeom& g, int splits, const ConvProblem& pr) {
     if (splits == 1) return true;
-    if (ws == nullptr || (Cin / BK) * Kw < 2 * splits) return false;
-    const TileCfg& c = kCfgs[cfg_i];
-    const int bm = 16 * c.mw * c.ms, bn = 16 * c.nw * c.ns;
-    const size_t tiles = (size_t)((Cout + bm - 1) / bm) * N * ((Tout + bn - 1) / bn);
-    return tiles * sizeof(unsigned) <= kTicketBytes && splitk_bytes(cfg_i, splits, N, Cout, Tout) <= (size_t)ws_bytes;
+    if (pr.ws == nullptr || (pr.Cin / BK) * pr.Kw < 2 * splits) return false;
+    return (size_t)g.blocks * sizeof(unsigned) <= kTicketBytes && splitk_bytes(g, splits) <= (size_t)pr.ws_bytes;
 }
 
-// the BatchNorm-backward side of a fused data-gradient launch (w2l_conv1d_dgrad_bnreduce_ws); NULL: plain launch
-struct BnBwdArgs {
-    const w2l_bnact_t* d;
-    int pad_l, pad_r, pad_mode, per;
-};
-
-static int igemm_launch(const void* xp, int64_t x_bstride, int64_t x_rows_total, const void* w, void* y, int y_f32,
-                        int accumulate, const float* bias, float* stats_partial, int N, int Cin, int Cout, int Tout, int Kw,
-                        int stride, int dil, void* splitk_ws, int64_t splitk_ws_bytes, void* stream, const BnBwdArgs* bb);
-
-extern "C" int w2l_conv1d_igemm_ws(const void* xp, int64_t x_bstride, int64_t x_rows_total, const void* w, void* y,
-                                   int y_f32, int accumulate, const float* bias, float* stats_partial, int N, int Cin,
-                                   int Cout, int Tout, int Kw, int stride, int dil, void* splitk_ws, int64_t splitk_ws_bytes,
-                                   void* stream) {
-    return igemm_launch(xp, x_bstride, x_rows_total, w, y, y_f32, accumulate, bias, stats_partial, N, Cin, Cout, Tout, Kw,
-                        stride, dil, splitk_ws, splitk_ws_bytes, stream, nullptr);
+// the fused inference descriptor, as the bf16 and the e4m3 launch both need it
+static int check_infer_epi(const w2l_bnact_epi_t* e, int Tout, const char* who) {
+    W2L_CHECK_ARG(e->pad_l >= 0 && e->pad_r >= 0 && e->pad_l <= kFzMaxPad && e->pad_r <= kFzMaxPad &&
+                  e->out_rows >= e->pad_l + Tout + e->pad_r,
+                  "%s: bad output geometry (pads %d,%d of at most %d; %d rows for %d frames)", who, e->pad_l, e->pad_r,
+                  kFzMaxPad, e->out_rows, Tout);
+    W2L_CHECK_ARG(e->pad_mode != 1 || (e->pad_l < Tout && e->pad_r < Tout), "%s: reflect pad (%d,%d) needs pad < T=%d", who,
+                  e->pad_l, e->pad_r, Tout);
+    W2L_CHECK_ARG((e->scale == nullptr) == (e->shift == nullptr) && e->act >= 0 && e->act <= 2 && (e->res || !e->res_lo),
+                  "%s: scale/shift come together, act is 0..2, res_lo needs res", who);
+    return 0;
 }
 
-// thread-local hand-over of the fused launch's descriptor to the tuner's inner launches (same thread, see g_force_cfg)
-static thread_local const BnBwdArgs* g_tune_bb = nullptr;
-
-static int igemm_launch(const void* xp, int64_t x_bstride, int64_t x_rows_total, const void* w, void* y, int y_f32,
-                        int accumulate, const float* bias, float* stats_partial, int N, int Cin, int Cout, int Tout, int Kw,
-                        int stride, int dil, void* splitk_ws, int64_t splitk_ws_bytes, void* stream, const BnBwdArgs* bb) {
-    if (bb == nullptr) bb = g_tune_bb;
-    const w2l_bnact_epi_t* fz = g_fz;
-    W2L_CHECK_ARG(xp && w && (y || fz), "conv1d_igemm: null pointer");
-    W2L_CHECK_ARG(N > 0 && Tout > 0 && Kw > 0 && (stride == 1 || stride == 2) && dil > 0,
-                  "conv1d_igemm: bad sizes (stride must be 1 or 2)");
-    W2L_CHECK_ARG(Cin % 64 == 0 && Cin > 0, "conv1d_igemm: Cin=%d must be a positive multiple of 64", Cin);
-    W2L_CHECK_ARG(Cout % 64 == 0 && Cout > 0, "conv1d_igemm: Cout=%d must be a positive multiple of 64", Cout);
-    W2L_CHECK_ARG(x_bstride % Cin == 0, "conv1d_igemm: x_bstride must be a multiple of Cin");
-    W2L_CHECK_ARG(!(accumulate && !y_f32), "conv1d_igemm: accumulate needs fp32 output");
-    IgemmParams p;
-    p.x = (const bf16_raw*)xp;
-    p.w = (const bf16_raw*)w;
-    p.y = y;
-    p.bias = bias;
-    p.stats = stats_partial;
-    p.stats_slots = stats_partial ? g_stats_slots : 0;
-    p.x_rows_per_utt = x_bstride / Cin;
-    p.x_max_row = x_rows_total - 1;
-    p.N = N; p.Cin = Cin; p.Cout = Cout; p.Tout = Tout; p.Kw = Kw; p.stride = stride; p.dil = dil;
-    p.y_f32 = y_f32; p.accumulate = accumulate;
-    p.descale = 1.f;
-    p.descale_dev = nullptr;
-    int epi = 0;
-    if (bb != nullptr) {
-        const w2l_bnact_t* d = bb->d;
-        W2L_CHECK_ARG(d && d->y && !d->y_f32 && !d->y2 && stats_partial && !y_f32 && !accumulate && !bias && N == 1 && stride == 1,
+// Everything a launch decides on the host: checks the problem and its epilogue, picks the configuration (`forced` >= 0: that
+// one or an error), sizes the grid and fills the kernel's argument.  No HIP call, no state but the table of measured choices.
+static int plan(const ConvProblem& pr, const Epilogue* ep, int forced, ConvPlan& pl) {
+    const char* who = pr.f8 ? "conv1d_igemm_fp8" : "conv1d_igemm";
+    W2L_CHECK_ARG(pr.x && pr.w && (pr.y || is_infer(ep)), "%s: null pointer", who);
+    W2L_CHECK_ARG(pr.f8 ? ep->kind == kEpiNone || ep->kind == kEpiInferF8 : ep->kind != kEpiInferF8,
+                  "%s: epilogue of the other operand type", who);
+    W2L_CHECK_ARG(pr.N > 0 && pr.Tout > 0 && pr.Kw > 0 && (pr.stride == 1 || (pr.stride == 2 && !pr.f8)) && pr.dil > 0,
+                  "%s: bad sizes (stride must be 1 or 2; e4m3: 1)", who);
+    const int cin_unit = pr.f8 ? 128 : 64;
+    W2L_CHECK_ARG(pr.Cin % cin_unit == 0 && pr.Cin > 0, "%s: Cin=%d must be a positive multiple of %d", who, pr.Cin, cin_unit);
+    W2L_CHECK_ARG(pr.Cout % 64 == 0 && pr.Cout > 0, "%s: Cout=%d must be a positive multiple of 64", who, pr.Cout);
+    W2L_CHECK_ARG(pr.x_bstride % pr.Cin == 0, "%s: x_bstride must be a multiple of Cin", who);
+    W2L_CHECK_ARG(!(pr.accumulate && !pr.y_f32), "%s: accumulate needs fp32 output", who);
+    W2L_CHECK_ARG(pr.descale > 0.f, "%s: descale must be positive", who);
+    IgemmParams& p = pl.p;
+    p.x = (const bf16_raw*)pr.x;
+    p.w = (const bf16_raw*)pr.w;
+    p.y = pr.y;
+    p.bias = pr.bias;
+    p.stats = pr.stats;
+    p.stats_slots = pr.stats ? pr.stats_slots : 0;
+    p.x_rows_per_utt = pr.x_bstride / pr.Cin;
+    p.x_max_row = pr.x_rows_total - 1;
+    p.N = pr.N; p.Cin = pr.Cin; p.Cout = pr.Cout; p.Tout = pr.Tout; p.Kw = pr.Kw; p.stride = pr.stride; p.dil = pr.dil;
+    p.y_f32 = pr.y_f32; p.accumulate = pr.accumulate;
+    p.descale = pr.descale;
+    p.descale_dev = pr.descale_dev;
+    pl.epi = 0;
+    if (ep->kind == kEpiBnReduce) {
+        const w2l_bnact_t* d = ep->bn.d;
+        const int pad_l = ep->bn.pad_l, pad_r = ep->bn.pad_r, per = ep->bn.per;
+        W2L_CHECK_ARG(d && d->y && !d->y_f32 && !d->y2 && pr.stats && !pr.y_f32 && !pr.accumulate && !pr.bias && pr.N == 1 &&
+                      pr.stride == 1,
                       "conv1d_dgrad_bnreduce: needs a bf16 single-branch layer, a statistics buffer and a flat bf16 output");
-        W2L_CHECK_ARG(d->C == Cout && bb->per > 0 && bb->pad_l >= 0 && bb->pad_r >= 0 &&
-                      (int64_t)d->N * bb->per <= Tout && bb->per >= bb->pad_l + d->T + bb->pad_r,
-                      "conv1d_dgrad_bnreduce: geometry mismatch (C=%d vs %d, per=%d, N=%d, rows=%d)", d->C, Cout, bb->per,
-                      d->N, Tout);
+        W2L_CHECK_ARG(d->C == pr.Cout && per > 0 && pad_l >= 0 && pad_r >= 0 && (int64_t)d->N * per <= pr.Tout &&
+                      per >= pad_l + d->T + pad_r,
+                      "conv1d_dgrad_bnreduce: geometry mismatch (C=%d vs %d, per=%d, N=%d, rows=%d)", d->C, pr.Cout, per, d->N,
+                      pr.Tout);
         W2L_CHECK_ARG(d->drop_p == 0.f || d->mask, "conv1d_dgrad_bnreduce: dropout needs the recorded mask");
         p.bn_y = (const bf16_raw*)d->y;
         p.bn_scale = d->scale; p.bn_shift = d->shift; p.bn_mean = d->mean; p.bn_invstd = d->invstd;
         p.bn_mask = d->drop_p > 0.f ? d->mask : nullptr;
         p.bn_lens = d->lens;
-        p.bn_T = d->T; p.bn_pad_l = bb->pad_l; p.bn_pad_mode = bb->pad_mode; p.bn_per = bb->per;
-        p.bn_Tp = bb->pad_l + d->T + bb->pad_r;
+        p.bn_T = d->T; p.bn_pad_l = pad_l; p.bn_pad_mode = ep->bn.pad_mode; p.bn_per = per;
+        p.bn_Tp = pad_l + d->T + pad_r;
         p.bn_act = d->act;
         p.bn_gk = d->drop_p > 0.f ? 1.f / (1.f - d->drop_p) : 1.f;
-        epi = 1;
-    }
-    if (fz != nullptr) {
-        W2L_CHECK_ARG(bb == nullptr && stats_partial == nullptr && fz->out_hi, "conv1d_igemm_bnact: null output / bad combination");
-        W2L_CHECK_ARG(fz->pad_l >= 0 && fz->pad_r >= 0 && fz->pad_l <= kFzMaxPad && fz->pad_r <= kFzMaxPad &&
-                      fz->out_rows >= fz->pad_l + Tout + fz->pad_r,
-                      "conv1d_igemm_bnact: bad output geometry (pads %d,%d of at most %d; %d rows for %d frames)", fz->pad_l,
-                      fz->pad_r, kFzMaxPad, fz->out_rows, Tout);
-        W2L_CHECK_ARG(fz->pad_mode != 1 || (fz->pad_l < Tout && fz->pad_r < Tout),
-                      "conv1d_igemm_bnact: reflect pad (%d,%d) needs pad < T=%d", fz->pad_l, fz->pad_r, Tout);
-        W2L_CHECK_ARG((fz->scale == nullptr) == (fz->shift == nullptr) && fz->act >= 0 && fz->act <= 2 &&
-                      (fz->res || !fz->res_lo), "conv1d_igemm_bnact: scale/shift come together, act is 0..2, res_lo needs res");
-        p.fz_scale = fz->scale; p.fz_shift = fz->shift;
-        p.fz_res = (const bf16_raw*)fz->res; p.fz_res_lo = (const bf16_raw*)fz->res_lo;
-        p.fz_lens = fz->lens;
-        p.fz_out = (bf16_raw*)fz->out_hi; p.fz_out_lo = (bf16_raw*)fz->out_lo;
-        p.fz_rows = fz->out_rows; p.fz_pad_l = fz->pad_l; p.fz_pad_r = fz->pad_r; p.fz_pad_mode = fz->pad_mode;
-        p.fz_act = fz->act;
-        epi = 2;
+        pl.epi = 1;
+    } else if (is_infer(ep)) {
+        const w2l_bnact_epi_t* e = ep->fz;
+        const bool q = ep->kind == kEpiInferF8 && ep->out_q != nullptr;
+        const char* who_fz = pr.f8 ? "conv1d_igemm_bnact_fp8" : "conv1d_igemm_bnact";
+        if (pr.f8) {                                    // the e4m3-only conditions
+            W2L_CHECK_ARG(e && (e->out_hi || q) && !e->out_lo && !e->res_lo && !pr.y && !pr.stats && !pr.descale_dev,
+                          "conv1d_igemm_bnact_fp8: needs an e4m3 or a bf16 output and takes no lo halves");
+            W2L_CHECK_ARG(!q || (ep->q_scale > 0.f && ((uintptr_t)ep->out_q & 15) == 0),
+                          "conv1d_igemm_bnact_fp8: the e4m3 output needs a positive scale and 16-byte alignment");
+        } else {
+            W2L_CHECK_ARG(e && pr.stats == nullptr && e->out_hi, "conv1d_igemm_bnact: null output / bad combination");
+        }
+        if (int rc = check_infer_epi(e, pr.Tout, who_fz)) return rc;
+        p.stats_slots = 0;
+        p.fz_q = q ? (uint8_t*)ep->out_q : nullptr;     // (shares storage with stats / descale_dev, both NULL here)
+        p.fz_qscale = q ? ep->q_scale : 1.f;
+        p.fz_clip = q ? (unsigned long long*)ep->q_clipped : nullptr;
+        p.fz_scale = e->scale; p.fz_shift = e->shift;
+        p.fz_res = (const bf16_raw*)e->res; p.fz_res_lo = (const bf16_raw*)e->res_lo;
+        p.fz_lens = e->lens;
+        p.fz_out = (bf16_raw*)e->out_hi; p.fz_out_lo = (bf16_raw*)e->out_lo;
+        p.fz_rows = e->out_rows; p.fz_pad_l = e->pad_l; p.fz_pad_r = e->pad_r; p.fz_pad_mode = e->pad_mode;
+        p.fz_act = e->act;
+        pl.epi = 2;
     }
     // the last valid output row must only need rows that exist in the padded buffer
-    const int64_t need = (int64_t)(N - 1) * p.x_rows_per_utt + (int64_t)(Tout - 1) * stride + (int64_t)(Kw - 1) * dil;
-    W2L_CHECK_ARG(need <= p.x_max_row, "conv1d_igemm: padded input too small (need row %lld, have %lld)",
-                  (long long)need, (long long)p.x_max_row);
-    // BatchNorm partial statistics are laid out per 128-row column tile (w2l_conv_stat_tiles)
-    const int ci = choose_cfg(N, Cin, Cout, Tout, Kw, stride, dil, stats_flag(stats_partial));     // (a fused data gradient
-    // shares the table with forward launches: its N = 1, Tout = flat rows shape never coincides with one of theirs)
-    W2L_CHECK_ARG(ci >= 0, "conv1d_igemm: no block shape fits LDS (Kw=%d dil=%d stride=%d)", Kw, dil, stride);
-    const int pipe = (ci % kBaseCfgs) / kNumCfgs;
-    const TileCfg& c = kCfgs[ci % kNumCfgs];
-    const int bm = 16 * c.mw * c.ms, bn = 16 * c.nw * c.ns;
-    p.tiles_t = (Tout + bn - 1) / bn;
-    p.ncols = N * p.tiles_t;
-    p.xrows_lds = cfg_xrows(c, stride, Kw, dil);
-    // a split-K choice (measured with a workspace) silently degrades to one block per tile when the caller brings none
-    int splits = kSplits[ci / kBaseCfgs];          // (a fused inference launch may split K: the block that combines the slabs
-                                                   //  holds the whole tile in registers and runs the epilogue; never stream-K)
+    const int64_t need = (int64_t)(pr.N - 1) * p.x_rows_per_utt + (int64_t)(pr.Tout - 1) * pr.stride + (int64_t)(pr.Kw - 1) * pr.dil;
+    W2L_CHECK_ARG(need <= p.x_max_row, "%s: padded input too small (need row %lld, have %lld)", who, (long long)need,
+                  (long long)p.x_max_row);
+    // (a fused data gradient shares the table with forward launches: its N = 1, Tout = flat rows shape never coincides with
+    // one of theirs)
+    pl.idx = choose_cfg(pr, stats_flag(pr, ep), forced);
+    W2L_CHECK_ARG(pl.idx >= 0, "%s: no block shape fits LDS (Kw=%d dil=%d stride=%d)", who, pr.Kw, pr.dil, pr.stride);
+    pl.f8 = pr.f8;
+    pl.shape = pr.f8 ? kF8Cfgs[pl.idx] : pl.idx % kNumCfgs;
+    pl.pipe = pr.f8 ? 0 : (pl.idx % kBaseCfgs) / kNumCfgs;
+    const TileCfg& c = kCfgs[pl.shape];
+    const TileGeom g = tile_geom(c, pr);
+    p.tiles_t = g.tiles_t;
+    p.ncols = pr.N * g.tiles_t;
+    p.xrows_lds = g.xrows;
+    // a split-K choice (measured with a workspace) silently degrades to one block per tile when the caller brings none.
+    // (A fused inference launch may split K: the block that combines the slabs holds the whole tile in registers and runs
+    // the epilogue; the fused epilogues never run stream-K)
+    int splits = pr.f8 ? 1 : kSplits[pl.idx / kBaseCfgs];
     p.sk_ranges = 0;
     p.sk_total = 0;
-    if (splits == 0) {                                   // stream-K (never with the fused epilogue: cfg_feasible)
-        if (epi == 0 && sk_feasible(ci % kNumCfgs, N, Cin, Cout, Tout, Kw, stride, dil, splitk_ws, splitk_ws_bytes)) {
-            p.sk_ranges = sk_ranges(c, stride, Kw, dil);
-            p.sk_total = ((Cout + bm - 1) / bm) * p.ncols * ((Cin / BK) * Kw);
+    if (splits == 0) {
+        if (pl.epi == 0 && sk_feasible(g, pr)) {
+            p.sk_ranges = sk_ranges(g);
+            p.sk_total = g.tiles_m * p.ncols * ((pr.Cin / BK) * pr.Kw);
         }
         splits = 1;
     }
-    if (!split_feasible(ci % kNumCfgs, splits, N, Cin, Cout, Tout, Kw, splitk_ws, splitk_ws_bytes)) splits = 1;
+    if (!split_feasible(g, splits, pr)) splits = 1;
     p.splits = splits;
-    p.tickets = (unsigned*)splitk_ws;
-    p.slabs = splitk_ws ? (float*)((char*)splitk_ws + kTicketBytes) : nullptr;
-    const int tiles_m = ((Cout + bm - 1) / bm) * splits;        // grid = tiles x splits (launch_cfg multiplies by ncols)
-    const size_t lds = 2 * (size_t)bm * ROWB + 2 * (size_t)p.xrows_lds * ROWB;
-    hipStream_t st = (hipStream_t)stream;
-    switch (ci % kNumCfgs) {
-        case 0: return launch_cfg<2, 2, 2, 4>(p, tiles_m, lds, st, pipe, epi);
-        case 1: return launch_cfg<2, 2, 3, 4>(p, tiles_m, lds, st, pipe, epi);
-        case 2: return launch_cfg<2, 2, 4, 4>(p, tiles_m, lds, st, pipe, epi);
-        case 3: return launch_cfg<2, 2, 5, 4>(p, tiles_m, lds, st, pipe, epi);
-        case 4: return launch_cfg<4, 2, 3, 4>(p, tiles_m, lds, st, pipe, epi);
-        case 5: return launch_cfg<4, 2, 4, 4>(p, tiles_m, lds, st, pipe, epi);
-        case 6: return launch_cfg<2, 3, 2, 3>(p, tiles_m, lds, st, pipe, epi);
-        case 7: return launch_cfg<2, 3, 3, 3>(p, tiles_m, lds, st, pipe, epi);
-        case 8: return launch_cfg<2, 3, 4, 3>(p, tiles_m, lds, st, pipe, epi);
-        case 9: return launch_cfg<2, 3, 5, 3>(p, tiles_m, lds, st, pipe, epi);
-        case 10: return launch_cfg<2, 4, 2, 4>(p, tiles_m, lds, st, pipe, epi);
-        case 11: return launch_cfg<2, 4, 3, 4>(p, tiles_m, lds, st, pipe, epi);
-        case 12: return launch_cfg<2, 4, 4, 4>(p, tiles_m, lds, st, pipe, epi);
-        case 13: return launch_cfg<2, 4, 5, 4>(p, tiles_m, lds, st, pipe, epi);
-        case 14: return launch_cfg<2, 4, 6, 4>(p, tiles_m, lds, st, pipe, epi);
-        case 15: return launch_cfg<2, 4, 7, 4>(p, tiles_m, lds, st, pipe, epi);
-        case 16: return launch_cfg<2, 4, 8, 4>(p, tiles_m, lds, st, pipe, epi);
-        case 17: return launch_cfg<2, 3, 4, 6>(p, tiles_m, lds, st, pipe, epi);
-        case 18: return launch_cfg<2, 3, 5, 6>(p, tiles_m, lds, st, pipe, epi);
-        case 19: return launch_cfg<2, 3, 6, 6>(p, tiles_m, lds, st, pipe, epi);
-        case 20: return launch_cfg<2, 3, 7, 6>(p, tiles_m, lds, st, pipe, epi);
-        case 21: return launch_cfg<2, 4, 4, 6>(p, tiles_m, lds, st, pipe, epi);
-        case 22: return launch_cfg<2, 4, 5, 6>(p, tiles_m, lds, st, pipe, epi);
-        case 23: return launch_cfg<2, 4, 6, 6>(p, tiles_m, lds, st, pipe, epi);
-        case 24: return launch_cfg<2, 4, 4, 7>(p, tiles_m, lds, st, pipe, epi);
-        default: return launch_cfg<2, 4, 5, 7>(p, tiles_m, lds, st, pipe, epi);
-    }
+    p.tickets = (unsigned*)pr.ws;
+    p.slabs = pr.ws ? (float*)((char*)pr.ws + kTicketBytes) : nullptr;
+    pl.splits = splits;
+    pl.sk_ranges = p.sk_ranges;
+    pl.grid = p.sk_ranges > 0 ? (unsigned)p.sk_ranges : (unsigned)(g.tiles_m * splits * p.ncols);
+    pl.threads = 64 * g.waves;
+    pl.lds = g.lds;
+    pl.stream = pr.stream;
+    return 0;
 }
 
+// ---- measure-and-pick (the _tune entry points; EXPLICITLY synchronising: warm-up only) ----
+struct EventPair {                                      // destroyed on every return path
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    ~EventPair() {
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+    }
+};
+
+// one launch of the plan `make` yields (which also validates it), then `n` launches timed between the two events;
+// < 0: the candidate did not run
+template <typename MakePlan>
+static float time_candidate(const MakePlan& make, int n, const EventPair& ev) {
+    ConvPlan pl;
+    if (make(pl) != 0 || launch(pl) != 0) return -1.f;
+    (void)hipEventRecord(ev.e0, pl.stream);
+    for (int r = 0; r < n; ++r) launch(pl);
+    (void)hipEventRecord(ev.e1, pl.stream);
+    if (hipEventSynchronize(ev.e1) != hipSuccess) return -1.f;
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, ev.e0, ev.e1) != hipSuccess) return -1.f;
+    return ms;
+}
+
+// Measure every feasible configuration for this problem on the caller's device and remember the fastest.  Call it once per
+// shape during warm-up, never inside a captured / latency-critical region.  The output is simply rewritten (accumulate == 0).
+static int tune(const ConvProblem& pr, const Epilogue* ep, int reps) {
+    const int sflag = stats_flag(pr, ep);
+    const ShapeKey key = shape_key(pr, sflag);
+    auto& table = pr.f8 ? g_tuned_f8 : g_tuned;
+    {
+        std::lock_guard<std::mutex> lock(g_tuned_mu);
+        if (table.count(key)) return 0;
+    }
+    EventPair ev;
+    W2L_CHECK_HIP(hipEventCreate(&ev.e0));
+    W2L_CHECK_HIP(hipEventCreate(&ev.e1));
+    if (reps < 1) reps = 1;
+    if (pr.ws) (void)hipMemsetAsync(pr.ws, 0, kTicketBytes, pr.stream);      // tickets start from zero whatever ran before
+    auto time_cfg = [&](int i, int n) -> float {
+        float ms = time_candidate([&](ConvPlan& pl) { return plan(pr, ep, i, pl); }, n, ev);
+        // a stream-K form has to win by 3 %: level with the best one-block-per-tile form it buys the step nothing (plan files
+        // with and without it: 12.79 / 12.82 ms) and moves 40-45 MB more per launch through its slabs
+        if (!pr.f8 && kSplits[i / kBaseCfgs] == 0) ms *= 1.03f;
+        return ms;
+    };
+    int best = -1;
+    if (pr.f8) {                                        // the e4m3 kernel's few shapes: a single pass
+        float best_ms = 1e30f;
+        for (int k = 0; k < kNumF8Cfgs; ++k) {
+            if (!f8_feasible(k, pr, sflag)) continue;
+            const float ms = time_cfg(k, reps);
+            if (ms >= 0.f && ms < best_ms) { best_ms = ms; best = k; }
+        }
+    } else {
+        std::vector<std::pair<float, int>> timed;
+        for (int i = 0; i < kBaseCfgs * kNumSplits; ++i) {
+            if (!cfg_feasible(i, pr, sflag)) continue;
+            const int splits = kSplits[i / kBaseCfgs];
+            const TileGeom g = tile_geom(kCfgs[i % kNumCfgs], pr);
+            if (splits == 0) {
+                // stream-K where one block per tile fills the last round to 85 % or less (and never under a fused epilogue)
+                if (ep->kind != kEpiNone || !sk_feasible(g, pr)) continue;
+                const int64_t slots = sk_ranges(g);
+                if (last_round_fill(g.blocks, slots) > 0.85 || g.blocks > 4 * slots) continue;   // (at 92 % fill it measured 3 % ahead alone and level in the step,
+                                                                       //  for 48 MB more traffic per launch: every finisher's acquire empties its XCD's L2)
+            } else if (splits > 1) {
+                // split-K is only a candidate where one block per tile leaves CUs idle (a partly filled last round, or fewer
+                // tiles than CUs) and where it does not flood the chip with short blocks
+                if (!split_feasible(g, splits, pr)) continue;
+                const int64_t slots = (int64_t)kCUs * blocks_per_cu(g, kWaveCap);
+                if (last_round_fill(g.blocks, slots) > 0.92 || g.blocks * splits > 6 * slots ||
+                    (pr.Cin / BK) * pr.Kw / splits < 8)
+                    continue;
+            }
+            const float ms = time_cfg(i, reps);
+            if (ms >= 0.f) timed.emplace_back(ms, i);
+        }
+        // the first pass ranks ~50 candidates on `reps` launches each -- the clock the chip holds drifts over such a sweep by
+        // more than the best candidates differ --, so the kFinalists fastest are timed again, interleaved (common.h)
+        std::sort(timed.begin(), timed.end());
+        best = timed.empty() ? -1 : timed[0].second;
+        const int finalists = timed.size() < kFinalists ? (int)timed.size() : kFinalists;
+        if (finalists > 1) {
+            float total[kFinalists] = {};
+            for (int round = 0; round < kFinalRounds; ++round)
+                for (int k = 0; k < finalists; ++k) {
+                    const float ms = time_cfg(timed[k].second, 4 * reps);
+                    total[k] += ms >= 0.f ? ms : 1e30f;
+                }
+            int kb = 0;
+            for (int k = 1; k < finalists; ++k)
+                if (total[k] < total[kb]) kb = k;
+            best = timed[kb].second;
+        }
+    }
+    W2L_CHECK_ARG(best >= 0, "%s_tune: no feasible block shape", pr.f8 ? "conv1d_igemm_fp8" : "conv1d_igemm");
+    std::lock_guard<std::mutex> lock(g_tuned_mu);
+    table[key] = best;
+    return 0;
+}
+
+// what every entry point ends in -- reps == 0: plan and launch; reps > 0: measure and remember.  The one reader of the hooks.
+static int run(ConvProblem pr, const Epilogue* ep, int reps = 0) {
+    pr.stats_slots = pr.stats ? g_stats_slots : 0;
+    if (reps != 0) return tune(pr, ep, reps);
+    ConvPlan pl;
+    if (int rc = plan(pr, ep, pr.f8 ? g_force_f8 : g_force_cfg, pl)) return rc;
+    return launch(pl);
+}
+
+extern "C" int w2l_conv1d_igemm_ws(const void* xp, int64_t x_bstride, int64_t x_rows_total, const void* w, void* y,
+                                   int y_f32, int accumulate, const float* bias, float* stats_partial, int N, int Cin,
+                                   int Cout, int Tout, int Kw, int stride, int dil, void* splitk_ws, int64_t splitk_ws_bytes,
+                                   void* stream) {
+    return run({xp, x_bstride, x_rows_total, w, y, y_f32, accumulate, bias, stats_partial, N, Cin, Cout, Tout, Kw, stride, dil,
+                splitk_ws, splitk_ws_bytes, (hipStream_t)stream}, &kNoEpilogue);
+}
+
+// the flat data gradient with the BatchNorm-backward reduction in its epilogue, and its measure-and-pick (the candidates run
+// with the fused epilogue)
 extern "C" int w2l_conv1d_dgrad_bnreduce_ws(const void* dy, int64_t dy_rows_total, const void* w_dgr, void* dxp, float* partial,
                                             const w2l_bnact_t* d, int pad_l, int pad_r, int pad_mode, int per, int Cconv_out,
                                             int flat_rows, int Kw, int dil, void* splitk_ws, int64_t splitk_ws_bytes,
                                             void* stream) {
     W2L_CHECK_ARG(d != nullptr, "conv1d_dgrad_bnreduce: null descriptor");
-    const BnBwdArgs bb{d, pad_l, pad_r, pad_mode, per};
-    return igemm_launch(dy, dy_rows_total * Cconv_out, dy_rows_total, w_dgr, dxp, 0, 0, nullptr, partial, 1, Cconv_out, d->C,
-                        flat_rows, Kw, 1, dil, splitk_ws, splitk_ws_bytes, stream, &bb);
+    const Epilogue ep{kEpiBnReduce, {d, pad_l, pad_r, pad_mode, per}};
+    return run({dy, dy_rows_total * Cconv_out, dy_rows_total, w_dgr, dxp, 0, 0, nullptr, partial, 1, Cconv_out, d->C, flat_rows,
+                Kw, 1, dil, splitk_ws, splitk_ws_bytes, (hipStream_t)stream}, &ep);
 }
 
 extern "C" int w2l_conv1d_igemm(const void* xp, int64_t x_bstride, int64_t x_rows_total, const void* w, void* y,
@@ -1246,12 +1405,9 @@ extern "C" int w2l_conv1d_igemm_bnact_ws(const void* xp, int64_t x_bstride, int6
                                          int Cout, int Tout, int Kw, int stride, int dil, void* splitk_ws,
                                          int64_t splitk_ws_bytes, void* stream) {
     W2L_CHECK_ARG(e != nullptr, "conv1d_igemm_bnact: null descriptor");
-    const w2l_bnact_epi_t* saved = g_fz;
-    g_fz = e;
-    const int rc = igemm_launch(xp, x_bstride, x_rows_total, w, (void*)acc_in, 1, acc_in != nullptr, bias, nullptr, N, Cin, Cout,
-                                Tout, Kw, stride, dil, splitk_ws, splitk_ws_bytes, stream, nullptr);
-    g_fz = saved;
-    return rc;
+    const Epilogue ep{kEpiInfer, {}, e};
+    return run({xp, x_bstride, x_rows_total, w, (void*)acc_in, 1, acc_in != nullptr, bias, nullptr, N, Cin, Cout, Tout, Kw,
+                stride, dil, splitk_ws, splitk_ws_bytes, (hipStream_t)stream}, &ep);
 }
 
 extern "C" int w2l_conv1d_igemm_bnact(const void* xp, int64_t x_bstride, int64_t x_rows_total, const void* w,
@@ -1268,21 +1424,20 @@ extern "C" int w2l_conv1d_igemm_bnact_tune_ws(const void* xp, int64_t x_bstride,
                                               int Kw, int stride, int dil, int reps, void* splitk_ws, int64_t splitk_ws_bytes,
                                               void* stream) {
     W2L_CHECK_ARG(e != nullptr, "conv1d_igemm_bnact_tune: null descriptor");
-    const w2l_bnact_epi_t* saved = g_fz;
-    g_fz = e;
-    const int rc = w2l_conv1d_igemm_tune_ws(xp, x_bstride, x_rows_total, w, nullptr, 1, bias, nullptr, N, Cin, Cout, Tout, Kw,
-                                            stride, dil, reps, splitk_ws, splitk_ws_bytes, stream);
-    g_fz = saved;
-    return rc;
+    const Epilogue ep{kEpiInfer, {}, e};
+    return run({xp, x_bstride, x_rows_total, w, nullptr, 1, 0, bias, nullptr, N, Cin, Cout, Tout, Kw, stride, dil, splitk_ws,
+                splitk_ws_bytes, (hipStream_t)stream}, &ep, reps < 1 ? 1 : reps);
 }
 
 // blocks of the stream-K launch configuration idx would make of this problem with a workspace of ws_bytes; 0: the launch
 // falls back to one block per tile (no stream-K form of that configuration, ranges too short, workspace too small)
 extern "C" int w2l_conv_streamk_ranges(int idx, int N, int Cin, int Cout, int Tout, int Kw, int stride, int dil, int64_t ws_bytes) {
-    if (!cfg_feasible(idx, Kw, stride, dil, false) || kSplits[idx / kBaseCfgs] != 0) return 0;
-    static const char dummy = 0;
-    if (!sk_feasible(idx % kNumCfgs, N, Cin, Cout, Tout, Kw, stride, dil, &dummy, ws_bytes)) return 0;
-    return sk_ranges(kCfgs[idx % kNumCfgs], stride, Kw, dil);
+    static char dummy;
+    ConvProblem pr = window_only(Kw, stride, dil);
+    pr.N = N; pr.Cin = Cin; pr.Cout = Cout; pr.Tout = Tout; pr.ws = &dummy; pr.ws_bytes = ws_bytes;
+    if (!cfg_feasible(idx, pr, 0) || kSplits[idx / kBaseCfgs] != 0) return 0;
+    const TileGeom g = tile_geom(kCfgs[idx % kNumCfgs], pr);
+    return sk_feasible(g, pr) ? sk_ranges(g) : 0;
 }
 
 // the pieces of a stream-K launch of `tiles` tiles x `steps` steps over G ranges, in range order, as the kernel walks them:
@@ -1307,124 +1462,31 @@ extern "C" int w2l_conv_streamk_pieces(int tiles, int steps, int G, int* out, in
     return n;
 }
 
+// bytes of split-K workspace that let every configuration of this problem run (slabs of the largest split + the tickets)
 extern "C" int64_t w2l_conv_splitk_workspace_bytes(int N, int Cout, int Tout) {
+    ConvProblem pr{};
+    pr.N = N; pr.Cout = Cout; pr.Tout = Tout;
     size_t need = 0;
-    for (int i = 0; i < kNumCfgs; ++i) {
-        const size_t b = splitk_bytes(i, kMaxSplit, N, Cout, Tout);
-        if (b > need) need = b;
-    }
+    for (int i = 0; i < kNumCfgs; ++i) need = std::max(need, splitk_bytes(tile_geom(kCfgs[i], pr), kMaxSplit));
     return (int64_t)need;
 }
 
-// Measure every feasible block shape for this problem on the caller's device and remember the fastest.
-// EXPLICITLY synchronising (hipEventSynchronize): call it once per shape during warm-up, never inside a
-// captured / latency-critical region.  Only for accumulate == 0 launches (the output is simply rewritten).
 extern "C" int w2l_conv1d_igemm_tune_ws(const void* xp, int64_t x_bstride, int64_t x_rows_total, const void* w, void* y,
                                         int y_f32, const float* bias, float* stats_partial, int N, int Cin, int Cout, int Tout,
                                         int Kw, int stride, int dil, int reps, void* splitk_ws, int64_t splitk_ws_bytes,
                                         void* stream) {
-    const bool need128 = stats_flag(stats_partial) == 1;
-    const ShapeKey key(N, Cin, Cout, Tout, Kw, stride, dil, stats_flag(stats_partial));
-    {
-        std::lock_guard<std::mutex> lock(g_tuned_mu);
-        if (g_tuned.count(key)) return 0;
-    }
-    hipEvent_t e0, e1;
-    W2L_CHECK_HIP(hipEventCreate(&e0));
-    W2L_CHECK_HIP(hipEventCreate(&e1));
-    hipStream_t st = (hipStream_t)stream;
-    const int saved = g_force_cfg;
-    if (reps < 1) reps = 1;
-    if (splitk_ws) (void)hipMemsetAsync(splitk_ws, 0, kTicketBytes, st);     // tickets start from zero whatever ran before
-    // time `n` back-to-back launches of candidate i after one warm-up launch (which also validates it); < 0: it did not run
-    auto time_cfg = [&](int i, int n) -> float {
-        g_force_cfg = i;
-        int rc = w2l_conv1d_igemm_ws(xp, x_bstride, x_rows_total, w, y, y_f32, 0, bias, stats_partial, N, Cin, Cout, Tout, Kw,
-                                     stride, dil, splitk_ws, splitk_ws_bytes, stream);
-        if (rc != 0) return -1.f;
-        (void)hipEventRecord(e0, st);
-        for (int r = 0; r < n; ++r)
-            w2l_conv1d_igemm_ws(xp, x_bstride, x_rows_total, w, y, y_f32, 0, bias, stats_partial, N, Cin, Cout, Tout, Kw,
-                                stride, dil, splitk_ws, splitk_ws_bytes, stream);
-        (void)hipEventRecord(e1, st);
-        if (hipEventSynchronize(e1) != hipSuccess) return -1.f;
-        float ms = 0.f;
-        if (hipEventElapsedTime(&ms, e0, e1) != hipSuccess) return -1.f;
-        // a stream-K form has to win by 3 %: level with the best one-block-per-tile form it buys the step nothing (plan files
-        // with and without it: 12.79 / 12.82 ms) and moves 40-45 MB more per launch through its slabs
-        if (kSplits[i / kBaseCfgs] == 0) ms *= 1.03f;
-        return ms;
-    };
-    std::vector<std::pair<float, int>> timed;
-    for (int i = 0; i < kBaseCfgs * kNumSplits; ++i) {
-        if (!cfg_feasible(i, Kw, stride, dil, need128)) continue;
-        const int ci = i % kNumCfgs, splits = kSplits[i / kBaseCfgs];
-        if (g_fz != nullptr && splits == 0) continue;              // the fused inference epilogue has no stream-K form
-        if (splits == 0) {
-            // stream-K where one block per tile fills the last round to 85 % or less (and never under the fused epilogue)
-            if (g_tune_bb != nullptr || !sk_feasible(ci, N, Cin, Cout, Tout, Kw, stride, dil, splitk_ws, splitk_ws_bytes)) continue;
-            const TileCfg& c = kCfgs[ci];
-            const int bm = 16 * c.mw * c.ms, bn = 16 * c.nw * c.ns;
-            const long slots = sk_ranges(c, stride, Kw, dil);
-            const long blocks = (long)((Cout + bm - 1) / bm) * N * ((Tout + bn - 1) / bn);
-            const double util = (double)blocks / (double)(((blocks + slots - 1) / slots) * slots);
-            if (util > 0.85 || blocks > 4 * slots) continue;       // (at 92 % fill it measured 3 % ahead alone and level in the step,
-                                                                   //  for 48 MB more traffic per launch: every finisher's acquire empties its XCD's L2)
-        } else if (splits > 1) {
-            // split-K is only a candidate where one block per tile leaves CUs idle (a partly filled last round, or fewer
-            // tiles than CUs) and where it does not flood the chip with short blocks
-            if (!split_feasible(ci, splits, N, Cin, Cout, Tout, Kw, splitk_ws, splitk_ws_bytes)) continue;
-            const TileCfg& c = kCfgs[ci];
-            const int bm = 16 * c.mw * c.ms, bn = 16 * c.nw * c.ns;
-            const size_t lds = 2 * (size_t)bm * ROWB + 2 * (size_t)cfg_xrows(c, stride, Kw, dil) * ROWB;
-            int per_cu = (int)((160 * 1024) / lds);
-            if (per_cu > 16 / (c.mw * c.nw)) per_cu = 16 / (c.mw * c.nw);
-            const long slots = 256L * (per_cu < 1 ? 1 : per_cu);
-            const long blocks = (long)((Cout + bm - 1) / bm) * N * ((Tout + bn - 1) / bn);
-            const double util = (double)blocks / (double)(((blocks + slots - 1) / slots) * slots);
-            if (util > 0.92 || blocks * splits > 6 * slots || (Cin / BK) * Kw / splits < 8) continue;
-        }
-        const float ms = time_cfg(i, reps);
-        if (ms >= 0.f) timed.emplace_back(ms, i);
-    }
-    // the first pass ranks ~50 candidates on `reps` launches each -- the clock the chip holds drifts over such a sweep by more
-    // than the best candidates differ --, so the kFinalists fastest are timed again, interleaved (common.h)
-    std::sort(timed.begin(), timed.end());
-    int best = timed.empty() ? -1 : timed[0].second;
-    const int finalists = timed.size() < kFinalists ? (int)timed.size() : kFinalists;
-    if (finalists > 1) {
-        float total[kFinalists] = {};
-        for (int round = 0; round < kFinalRounds; ++round)
-            for (int k = 0; k < finalists; ++k) {
-                const float ms = time_cfg(timed[k].second, 4 * reps);
-                total[k] += ms >= 0.f ? ms : 1e30f;
-            }
-        int kb = 0;
-        for (int k = 1; k < finalists; ++k)
-            if (total[k] < total[kb]) kb = k;
-        best = timed[kb].second;
-    }
-    g_force_cfg = saved;
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    W2L_CHECK_ARG(best >= 0, "conv1d_igemm_tune: no feasible block shape");
-    std::lock_guard<std::mutex> lock(g_tuned_mu);
-    g_tuned[key] = best;
-    return 0;
+    return run({xp, x_bstride, x_rows_total, w, y, y_f32, 0, bias, stats_partial, N, Cin, Cout, Tout, Kw, stride, dil, splitk_ws,
+                splitk_ws_bytes, (hipStream_t)stream}, &kNoEpilogue, reps < 1 ? 1 : reps);
 }
 
-// measure-and-pick for a fused data gradient: the candidates run with the fused epilogue (SYNCHRONISING; warm-up only)
 extern "C" int w2l_conv1d_dgrad_bnreduce_tune_ws(const void* dy, int64_t dy_rows_total, const void* w_dgr, void* dxp,
                                                  float* partial, const w2l_bnact_t* d, int pad_l, int pad_r, int pad_mode,
                                                  int per, int Cconv_out, int flat_rows, int Kw, int dil, int reps,
                                                  void* splitk_ws, int64_t splitk_ws_bytes, void* stream) {
     W2L_CHECK_ARG(d != nullptr, "conv1d_dgrad_bnreduce_tune: null descriptor");
-    const BnBwdArgs bb{d, pad_l, pad_r, pad_mode, per};
-    g_tune_bb = &bb;
-    const int rc = w2l_conv1d_igemm_tune_ws(dy, dy_rows_total * Cconv_out, dy_rows_total, w_dgr, dxp, 0, nullptr, partial, 1,
-                                            Cconv_out, d->C, flat_rows, Kw, 1, dil, reps, splitk_ws, splitk_ws_bytes, stream);
-    g_tune_bb = nullptr;
-    return rc;
+    const Epilogue ep{kEpiBnReduce, {d, pad_l, pad_r, pad_mode, per}};
+    return run({dy, dy_rows_total * Cconv_out, dy_rows_total, w_dgr, dxp, 0, 0, nullptr, partial, 1, Cconv_out, d->C, flat_rows,
+                Kw, 1, dil, splitk_ws, splitk_ws_bytes, (hipStream_t)stream}, &ep, reps < 1 ? 1 : reps);
 }
 
 extern "C" int w2l_conv1d_igemm_tune(const void* xp, int64_t x_bstride, int64_t x_rows_total, const void* w, void* y,
@@ -1434,146 +1496,13 @@ extern "C" int w2l_conv1d_igemm_tune(const void* xp, int64_t x_bstride, int64_t 
                                     stride, dil, reps, nullptr, 0, stream);
 }
 
-// ---- e4m3 operands (BASELINE config 5: fp8 MFMA) -------------------------------------------------------------------
-// measured choices of the e4m3 kernel: shape -> index into kF8Cfgs
-static std::map<ShapeKey, int> g_tuned_f8;
-static thread_local int g_force_f8 = -1;
-// testing / profiling hook (per calling thread): pin the e4m3 kernel's block shape (index into kF8Cfgs), -1 = automatic
-extern "C" void w2l_conv_force_fp8_config(int idx) { g_force_f8 = idx; }
-
-// statistics flag of an e4m3 shape key: 0 none, 1 one row per 128-column tile, 3 the fused inference launch
-// (w2l_conv1d_igemm_bnact_fp8): measured, remembered and looked up as itself, like flag 3 of the bf16 table
-static bool f8_feasible(int k, int Kw, int dil, int sflag) {
-    if (k < 0 || k >= kNumF8Cfgs) return false;
-    const bool need_bn128 = sflag == 1;
-    const TileCfg& c = kCfgs[kF8Cfgs[k]];
-    if (sflag == 3 && (!f8_fused_built(c.nw, c.ms, c.ns) || 16 * c.nw * c.ns <= kFzMaxPad)) return false;   // (a tile writes the
-                                                                                // halo rows: every pad is shorter than it)
-    if (need_bn128 && ((16 * c.nw * c.ns) % 128 != 0 || 16 * c.nw * c.ns > 256)) return false;
-    const size_t lds = 2 * (size_t)(16 * c.mw * c.ms) * ROWB + 2 * (size_t)cfg_xrows(c, 1, Kw, dil) * ROWB;
-    return lds <= 160 * 1024;
-}
-
-static int choose_f8(int N, int Cin, int Cout, int Tout, int Kw, int dil, int sflag) {
-    if (g_force_f8 >= 0) return f8_feasible(g_force_f8, Kw, dil, sflag) ? g_force_f8 : -1;
-    {
-        std::lock_guard<std::mutex> lock(g_tuned_mu);
-        auto it = g_tuned_f8.find(ShapeKey(N, Cin, Cout, Tout, Kw, 1, dil, sflag));
-        if (it != g_tuned_f8.end()) return it->second;
-    }
-    int best = -1;
-    double best_cost = 1e30;
-    for (int k = 0; k < kNumF8Cfgs; ++k) {            // cost model: whole rounds of resident blocks, larger tiles preferred
-        if (!f8_feasible(k, Kw, dil, sflag)) continue;
-        const TileCfg& c = kCfgs[kF8Cfgs[k]];
-        const int bm = 16 * c.mw * c.ms, bn = 16 * c.nw * c.ns, waves = c.mw * c.nw;
-        const size_t lds = 2 * (size_t)bm * ROWB + 2 * (size_t)cfg_xrows(c, 1, Kw, dil) * ROWB;
-        int per_cu = (int)((160 * 1024) / lds);
-        if (per_cu > 16 / waves) per_cu = 16 / waves;
-        if (per_cu < 1) continue;
-        const long blocks = (long)((Cout + bm - 1) / bm) * N * ((Tout + bn - 1) / bn);
-        const long rounds = (blocks + 256L * per_cu - 1) / (256L * per_cu);
-        const double cost = (double)rounds * bm * bn * per_cu / c.eff * (1.0 + 1e-3 * k);
-        if (cost < best_cost) { best_cost = cost; best = k; }
-    }
-    return best;
-}
-
-// the fused form's outputs (w2l_conv1d_igemm_bnact_fp8); NULL: the plain launch
-struct F8Fused {
-    const w2l_bnact_epi_t* e;
-    void* out_q;
-    float q_scale;
-    int64_t* q_clipped;
-};
-
-static int f8_launch(const void* xq, int64_t x_bstride, int64_t x_rows_total, const void* wq, void* y, int y_f32,
-                     float descale, const float* descale_dev, const float* bias, float* stats_partial, int N,
-                     int Cin, int Cout, int Tout, int Kw, int dil, void* stream, const F8Fused* fz) {
-    W2L_CHECK_ARG(xq && wq && (y || fz), "conv1d_igemm_fp8: null pointer");
-    W2L_CHECK_ARG(N > 0 && Tout > 0 && Kw > 0 && dil > 0, "conv1d_igemm_fp8: bad sizes");
-    W2L_CHECK_ARG(Cin % 128 == 0 && Cin > 0, "conv1d_igemm_fp8: Cin=%d must be a positive multiple of 128", Cin);
-    W2L_CHECK_ARG(Cout % 64 == 0 && Cout > 0, "conv1d_igemm_fp8: Cout=%d must be a positive multiple of 64", Cout);
-    W2L_CHECK_ARG(x_bstride % Cin == 0, "conv1d_igemm_fp8: x_bstride must be a multiple of Cin");
-    W2L_CHECK_ARG(descale > 0.f, "conv1d_igemm_fp8: descale must be positive");
-    IgemmParams p;
-    p.x = (const bf16_raw*)xq;
-    p.w = (const bf16_raw*)wq;
-    p.y = y;
-    p.bias = bias;
-    p.stats = stats_partial;
-    p.stats_slots = stats_partial ? g_stats_slots : 0;
-    p.x_rows_per_utt = x_bstride / Cin;
-    p.x_max_row = x_rows_total - 1;
-    p.N = N; p.Cin = Cin; p.Cout = Cout; p.Tout = Tout; p.Kw = Kw; p.stride = 1; p.dil = dil;
-    p.y_f32 = y_f32; p.accumulate = 0;
-    p.splits = 1; p.slabs = nullptr; p.tickets = nullptr;
-    p.sk_ranges = 0; p.sk_total = 0;
-    p.descale = descale;
-    p.descale_dev = descale_dev;
-    if (fz != nullptr) {
-        const w2l_bnact_epi_t* e = fz->e;
-        W2L_CHECK_ARG(e && (e->out_hi || fz->out_q) && !e->out_lo && !e->res_lo && !y && !stats_partial && !descale_dev,
-                      "conv1d_igemm_bnact_fp8: needs an e4m3 or a bf16 output and takes no lo halves");
-        W2L_CHECK_ARG(!fz->out_q || (fz->q_scale > 0.f && ((uintptr_t)fz->out_q & 15) == 0),
-                      "conv1d_igemm_bnact_fp8: the e4m3 output needs a positive scale and 16-byte alignment");
-        W2L_CHECK_ARG(e->pad_l >= 0 && e->pad_r >= 0 && e->pad_l <= kFzMaxPad && e->pad_r <= kFzMaxPad &&
-                      e->out_rows >= e->pad_l + Tout + e->pad_r,
-                      "conv1d_igemm_bnact_fp8: bad output geometry (pads %d,%d of at most %d; %d rows for %d frames)", e->pad_l,
-                      e->pad_r, kFzMaxPad, e->out_rows, Tout);
-        W2L_CHECK_ARG(e->pad_mode != 1 || (e->pad_l < Tout && e->pad_r < Tout),
-                      "conv1d_igemm_bnact_fp8: reflect pad (%d,%d) needs pad < T=%d", e->pad_l, e->pad_r, Tout);
-        W2L_CHECK_ARG((e->scale == nullptr) == (e->shift == nullptr) && e->act >= 0 && e->act <= 2,
-                      "conv1d_igemm_bnact_fp8: scale/shift come together, act is 0..2");
-        p.stats_slots = 0;
-        p.fz_q = (uint8_t*)fz->out_q;
-        p.fz_qscale = fz->out_q ? fz->q_scale : 1.f;
-        p.fz_clip = fz->out_q ? (unsigned long long*)fz->q_clipped : nullptr;
-        p.fz_scale = e->scale; p.fz_shift = e->shift;
-        p.fz_res = (const bf16_raw*)e->res; p.fz_res_lo = nullptr;
-        p.fz_lens = e->lens;
-        p.fz_out = (bf16_raw*)e->out_hi; p.fz_out_lo = nullptr;
-        p.fz_rows = e->out_rows; p.fz_pad_l = e->pad_l; p.fz_pad_r = e->pad_r; p.fz_pad_mode = e->pad_mode;
-        p.fz_act = e->act;
-    }
-    const int64_t need = (int64_t)(N - 1) * p.x_rows_per_utt + (int64_t)(Tout - 1) + (int64_t)(Kw - 1) * dil;
-    W2L_CHECK_ARG(need <= p.x_max_row, "conv1d_igemm_fp8: padded input too small (need row %lld, have %lld)",
-                  (long long)need, (long long)p.x_max_row);
-    const int k = choose_f8(N, Cin, Cout, Tout, Kw, dil, fz ? 3 : (stats_partial != nullptr ? 1 : 0));
-    W2L_CHECK_ARG(k >= 0, "conv1d_igemm_fp8: no block shape fits LDS (Kw=%d dil=%d)", Kw, dil);
-    const TileCfg& c = kCfgs[kF8Cfgs[k]];
-    const int bm = 16 * c.mw * c.ms, bn = 16 * c.nw * c.ns;
-    p.tiles_t = (Tout + bn - 1) / bn;
-    p.ncols = N * p.tiles_t;
-    p.xrows_lds = cfg_xrows(c, 1, Kw, dil);
-    const int tiles_m = (Cout + bm - 1) / bm;
-    const size_t lds = 2 * (size_t)bm * ROWB + 2 * (size_t)p.xrows_lds * ROWB;
-    hipStream_t st = (hipStream_t)stream;
-    switch (kF8Cfgs[k]) {                       // block shapes of kCfgs
-        case 2: return launch_f8<2, 2, 4, 4>(p, tiles_m, lds, st, fz != nullptr);
-        case 5: return launch_f8<4, 2, 4, 4>(p, tiles_m, lds, st, fz != nullptr);
-        case 12: return launch_f8<2, 4, 4, 4>(p, tiles_m, lds, st, fz != nullptr);
-        case 14: return launch_f8<2, 4, 6, 4>(p, tiles_m, lds, st, fz != nullptr);
-        case 16: return launch_f8<2, 4, 8, 4>(p, tiles_m, lds, st, fz != nullptr);
-        case 1: return launch_f8<2, 2, 3, 4>(p, tiles_m, lds, st, fz != nullptr);
-        case 3: return launch_f8<2, 2, 5, 4>(p, tiles_m, lds, st, fz != nullptr);
-        case 8: return launch_f8<2, 3, 4, 3>(p, tiles_m, lds, st, fz != nullptr);
-        case 9: return launch_f8<2, 3, 5, 3>(p, tiles_m, lds, st, fz != nullptr);
-        case 11: return launch_f8<2, 4, 3, 4>(p, tiles_m, lds, st, fz != nullptr);
-        case 13: return launch_f8<2, 4, 5, 4>(p, tiles_m, lds, st, fz != nullptr);
-        case 18: return launch_f8<2, 3, 5, 6>(p, tiles_m, lds, st, fz != nullptr);
-        case 19: return launch_f8<2, 3, 6, 6>(p, tiles_m, lds, st, fz != nullptr);
-        case 21: return launch_f8<2, 4, 4, 6>(p, tiles_m, lds, st, fz != nullptr);
-        default: return launch_f8<2, 4, 4, 7>(p, tiles_m, lds, st, fz != nullptr);
-    }
-}
-
+// ---- e4m3 operands (BASELINE config 5: fp8 MFMA) ----
 extern "C" int w2l_conv1d_igemm_fp8(const void* xq, int64_t x_bstride, int64_t x_rows_total, const void* wq, void* y, int y_f32,
                                     float descale, const float* descale_dev, const float* bias, float* stats_partial, int N,
                                     int Cin, int Cout, int Tout, int Kw, int dil, void* stream) {
     W2L_CHECK_ARG(y, "conv1d_igemm_fp8: null pointer");
-    return f8_launch(xq, x_bstride, x_rows_total, wq, y, y_f32, descale, descale_dev, bias, stats_partial, N, Cin, Cout, Tout, Kw,
-                     dil, stream, nullptr);
+    return run({xq, x_bstride, x_rows_total, wq, y, y_f32, 0, bias, stats_partial, N, Cin, Cout, Tout, Kw, 1, dil, nullptr, 0,
+                (hipStream_t)stream, true, descale, descale_dev}, &kNoEpilogue);
 }
 
 // ---- inference on e4m3 operands: the whole unit in the e4m3 kernel's epilogue (conv_igemm_kernel<F8, EPI = 2>) ----
@@ -1581,58 +1510,17 @@ extern "C" int w2l_conv1d_igemm_bnact_fp8(const void* xq, int64_t x_bstride, int
                                           const float* bias, const w2l_bnact_epi_t* e, void* out_q, float q_scale,
                                           int64_t* q_clipped, int N, int Cin, int Cout, int Tout, int Kw, int dil, void* stream) {
     W2L_CHECK_ARG(e != nullptr, "conv1d_igemm_bnact_fp8: null descriptor");
-    const F8Fused fz{e, out_q, q_scale, q_clipped};
-    return f8_launch(xq, x_bstride, x_rows_total, wq, nullptr, 0, descale, nullptr, bias, nullptr, N, Cin, Cout, Tout, Kw, dil,
-                     stream, &fz);
+    const Epilogue ep{kEpiInferF8, {}, e, out_q, q_scale, q_clipped};
+    return run({xq, x_bstride, x_rows_total, wq, nullptr, 0, 0, bias, nullptr, N, Cin, Cout, Tout, Kw, 1, dil, nullptr, 0,
+                (hipStream_t)stream, true, descale}, &ep);
 }
 
 // measure the e4m3 block shapes for this problem and remember the fastest (SYNCHRONISING: warm-up only)
-static int f8_tune(const void* xq, int64_t x_bstride, int64_t x_rows_total, const void* wq, void* y, int y_f32, const float* bias,
-                   float* stats_partial, int N, int Cin, int Cout, int Tout, int Kw, int dil, int reps, void* stream,
-                   const F8Fused* fz) {
-    const int need128 = fz ? 3 : (stats_partial != nullptr ? 1 : 0);          // the key's statistics flag
-    const ShapeKey key(N, Cin, Cout, Tout, Kw, 1, dil, need128);
-    {
-        std::lock_guard<std::mutex> lock(g_tuned_mu);
-        if (g_tuned_f8.count(key)) return 0;
-    }
-    hipEvent_t e0, e1;
-    W2L_CHECK_HIP(hipEventCreate(&e0));
-    W2L_CHECK_HIP(hipEventCreate(&e1));
-    hipStream_t st = (hipStream_t)stream;
-    int best = -1;
-    float best_ms = 1e30f;
-    const int saved = g_force_f8;
-    if (reps < 1) reps = 1;
-    for (int k = 0; k < kNumF8Cfgs; ++k) {
-        if (!f8_feasible(k, Kw, dil, need128)) continue;
-        g_force_f8 = k;
-        if (f8_launch(xq, x_bstride, x_rows_total, wq, y, y_f32, 1.f, nullptr, bias, stats_partial, N, Cin, Cout, Tout, Kw, dil,
-                      stream, fz) != 0)
-            continue;
-        (void)hipEventRecord(e0, st);
-        for (int r = 0; r < reps; ++r)
-            f8_launch(xq, x_bstride, x_rows_total, wq, y, y_f32, 1.f, nullptr, bias, stats_partial, N, Cin, Cout, Tout, Kw, dil,
-                      stream, fz);
-        (void)hipEventRecord(e1, st);
-        if (hipEventSynchronize(e1) != hipSuccess) continue;
-        float ms = 0.f;
-        if (hipEventElapsedTime(&ms, e0, e1) != hipSuccess) continue;
-        if (ms < best_ms) { best_ms = ms; best = k; }
-    }
-    g_force_f8 = saved;
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    W2L_CHECK_ARG(best >= 0, "conv1d_igemm_fp8_tune: no feasible block shape");
-    std::lock_guard<std::mutex> lock(g_tuned_mu);
-    g_tuned_f8[key] = best;
-    return 0;
-}
-
 extern "C" int w2l_conv1d_igemm_fp8_tune(const void* xq, int64_t x_bstride, int64_t x_rows_total, const void* wq, void* y,
                                          int y_f32, const float* bias, float* stats_partial, int N, int Cin, int Cout, int Tout,
                                          int Kw, int dil, int reps, void* stream) {
-    return f8_tune(xq, x_bstride, x_rows_total, wq, y, y_f32, bias, stats_partial, N, Cin, Cout, Tout, Kw, dil, reps, stream, nullptr);
+    return run({xq, x_bstride, x_rows_total, wq, y, y_f32, 0, bias, stats_partial, N, Cin, Cout, Tout, Kw, 1, dil, nullptr, 0,
+                (hipStream_t)stream, true}, &kNoEpilogue, reps < 1 ? 1 : reps);
 }
 
 // measure-and-pick for the fused e4m3 launch: the candidates run WITH the epilogue (descale 1: the time does not depend on it) and
@@ -1642,40 +1530,68 @@ extern "C" int w2l_conv1d_igemm_bnact_fp8_tune(const void* xq, int64_t x_bstride
                                                const float* bias, const w2l_bnact_epi_t* e, void* out_q, float q_scale, int N,
                                                int Cin, int Cout, int Tout, int Kw, int dil, int reps, void* stream) {
     W2L_CHECK_ARG(e != nullptr, "conv1d_igemm_bnact_fp8_tune: null descriptor");
-    const F8Fused fz{e, out_q, q_scale, nullptr};
-    return f8_tune(xq, x_bstride, x_rows_total, wq, nullptr, 0, bias, nullptr, N, Cin, Cout, Tout, Kw, dil, reps, stream, &fz);
+    const Epilogue ep{kEpiInferF8, {}, e, out_q, q_scale, nullptr};
+    return run({xq, x_bstride, x_rows_total, wq, nullptr, 0, 0, bias, nullptr, N, Cin, Cout, Tout, Kw, 1, dil, nullptr, 0,
+                (hipStream_t)stream, true}, &ep, reps < 1 ? 1 : reps);
 }
 
-// Tuning-cache (de)serialisation used by w2l_tune_save / w2l_tune_load (runtime.hip).
-void w2l_igemm_tune_dump(FILE* f) {
+// ---- host-only queries ----
+// The plan a launch of this problem would get, without a stream or a buffer: out = configuration index, K-loop structure,
+// blocks per tile, stream-K blocks, grid blocks, block threads, LDS bytes, feasible.  stats_flag as in the shape key;
+// forced_idx < 0: the tuned choice or the cost model.  Returns 0 and out[7] = 1, or 1 with out = {-1, 0...} and the error set.
+static int plan_query(bool f8, int N, int Cin, int Cout, int Tout, int Kw, int stride, int dil, int sflag, int64_t ws_bytes,
+                      int forced_idx, int* out) {
+    static char dummy[16];
+    w2l_bnact_epi_t e{};
+    e.out_hi = dummy;
+    e.out_rows = Tout;
+    const Epilogue ep{sflag == 3 ? (f8 ? kEpiInferF8 : kEpiInfer) : kEpiNone, {}, &e};
+    const int64_t rows = (int64_t)(Tout - 1) * stride + (int64_t)(Kw - 1) * dil + 1;
+    ConvProblem pr{dummy, Cin > 0 ? rows * Cin : 0, rows * N, dummy, sflag == 3 ? nullptr : dummy, 1, 0, nullptr,
+                   sflag == 1 || sflag == 2 ? (float*)dummy : nullptr, N, Cin, Cout, Tout, Kw, stride, dil,
+                   ws_bytes > 0 ? dummy : nullptr, ws_bytes, nullptr, f8};
+    pr.stats_slots = sflag == 2 ? 1 : 0;
+    ConvPlan pl;
+    out[0] = -1;
+    for (int i = 1; i < 8; ++i) out[i] = 0;
+    W2L_CHECK_ARG(sflag >= 0 && sflag <= 3 && !(f8 && sflag == 2), "conv_plan: stats_flag is 0..3 (e4m3: 0, 1 or 3)");
+    if (int rc = plan(pr, &ep, forced_idx, pl)) return rc;
+    const int v[8] = {pl.idx, pl.pipe, pl.splits, pl.sk_ranges, (int)pl.grid, (int)pl.threads, (int)pl.lds, 1};
+    for (int i = 0; i < 8; ++i) out[i] = v[i];
+    return 0;
+}
+
+extern "C" int w2l_conv_plan(int N, int Cin, int Cout, int Tout, int Kw, int stride, int dil, int stats_flag, int64_t ws_bytes,
+                             int forced_idx, int* out) {
+    return plan_query(false, N, Cin, Cout, Tout, Kw, stride, dil, stats_flag, ws_bytes, forced_idx, out);
+}
+
+extern "C" int w2l_conv_plan_fp8(int N, int Cin, int Cout, int Tout, int Kw, int dil, int stats_flag, int forced_idx, int* out) {
+    return plan_query(true, N, Cin, Cout, Tout, Kw, 1, dil, stats_flag, 0, forced_idx, out);
+}
+
+// Tuning-cache (de)serialisation used by w2l_tune_save / w2l_tune_load (runtime.hip): "<tag> <the 8 key fields> <index>"
+static void tune_dump(FILE* f, const char* tag, const std::map<ShapeKey, int>& table) {
     std::lock_guard<std::mutex> lock(g_tuned_mu);
-    for (const auto& kv : g_tuned) {
+    for (const auto& kv : table) {
         const ShapeKey& k = kv.first;
-        fprintf(f, "igemm %d %d %d %d %d %d %d %d %d\n", std::get<0>(k), std::get<1>(k), std::get<2>(k), std::get<3>(k),
+        fprintf(f, "%s %d %d %d %d %d %d %d %d %d\n", tag, std::get<0>(k), std::get<1>(k), std::get<2>(k), std::get<3>(k),
                 std::get<4>(k), std::get<5>(k), std::get<6>(k), std::get<7>(k), kv.second);
     }
 }
-
-// the e4m3 kernel's choices: same key (stride always 1), value = index into kF8Cfgs
-void w2l_igemm_fp8_tune_dump(FILE* f) {
-    std::lock_guard<std::mutex> lock(g_tuned_mu);
-    for (const auto& kv : g_tuned_f8) {
-        const ShapeKey& k = kv.first;
-        fprintf(f, "igemmf8 %d %d %d %d %d %d %d %d %d\n", std::get<0>(k), std::get<1>(k), std::get<2>(k), std::get<3>(k),
-                std::get<4>(k), std::get<5>(k), std::get<6>(k), std::get<7>(k), kv.second);
-    }
-}
+void w2l_igemm_tune_dump(FILE* f) { tune_dump(f, "igemm", g_tuned); }
+void w2l_igemm_fp8_tune_dump(FILE* f) { tune_dump(f, "igemmf8", g_tuned_f8); }
 
 bool w2l_igemm_fp8_tune_put(const int* v) {      // v[0..7] = key, v[8] = index into kF8Cfgs
     const int sflag = v[7] == 3 ? 3 : (v[7] != 0 ? 1 : 0);
-    if (v[5] != 1 || v[0] < 1 || v[3] < 1 || !f8_feasible(v[8], v[4], v[6], sflag)) return false;
+    if (v[5] != 1 || v[0] < 1 || v[3] < 1 || !f8_feasible(v[8], window_only(v[4], 1, v[6]), sflag)) return false;
     std::lock_guard<std::mutex> lock(g_tuned_mu);
     g_tuned_f8[ShapeKey(v[0], v[1], v[2], v[3], v[4], 1, v[6], sflag)] = v[8];
     return true;
 }
 
-bool w2l_igemm_tune_put(const int* v) {          // v[0..7] = key, v[8] = block-shape index
-    if (v[7] < 0 || v[7] > 3 || !cfg_feasible(v[8], v[4], v[5], v[6], v[7] == 1)) return false;
+bool w2l_igemm_tune_put(const int* v) {          // v[0..7] = key, v[8] = configuration index
+    if (v[7] < 0 || v[7] > 3 || !cfg_feasible(v[8], window_only(v[4], v[5], v[6]), v[7])) return false;
     if (v[7] == 3 && kSplits[v[8] / kBaseCfgs] == 0) return false; // (fused inference launches have no stream-K form)
     std::lock_guard<std::mutex> lock(g_tuned_mu);
     g_tuned[ShapeKey(v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7])] = v[8];

@@ -115,6 +115,10 @@ class ConvSpec:
     def has_bn(self) -> bool:
         return self.bn_weight is not None
 
+    def out_len(self, T: int) -> int:
+        """frames this convolution makes of T input frames (its own padding included)"""
+        return (T + self.pad_l + self.pad_r - (self.kernel - 1) * self.dilation - 1) // self.stride + 1
+
     @property
     def cout(self) -> int:
         return self.weight.shape[0]
@@ -215,6 +219,18 @@ TUNE_REPS = int(os.environ.get('W2L_TUNE_REPS', '2'))      # timed launches per 
 # measured new shapes, so later processes (and the other DP ranks) skip the measuring launches.
 TUNE_CACHE = os.environ.get('W2L_TUNE_CACHE') or None
 _tune_state = {'dirty': False}
+
+
+def _tune_once(key, why=None) -> bool:
+    """True the first time a shape key is seen: the caller then measures it (the tune cache has to be written back, and a
+    recording under way is poisoned where `why` says the measuring launches must not be replayed)"""
+    if key in _tuned_shapes:
+        return False
+    _tuned_shapes.add(key)
+    _tune_state['dirty'] = True
+    if why is not None:
+        _lib.poison(why)
+    return True
 _wgroup_plans = {}                 # (convolutions of a backward pass, W2L_WGRAD_GROUPS) -> groups (wgrad_groups.plan)
 _wgroup_forms = {}                 # group signature -> measured block form of its launch, -1: one by one
 
@@ -570,10 +586,7 @@ def _igemm(x: Act, row_off: int, w_hi, w_lo, y, bias, stats, Cin, Cout, Tout, Kw
         ws = _splitk_workspace(x.hi.device, n, Cout, Tout)
         if AUTOTUNE:
             key = (n, Cin, Cout, Tout, Kw, stride, dil, stats is not None, x.hi.device.index)
-            if key not in _tuned_shapes:       # once per shape and device, during the first (warm-up) step
-                _tuned_shapes.add(key)
-                _tune_state['dirty'] = True
-                _lib.poison('measuring launches')
+            if _tune_once(key, 'measuring launches'):       # once per shape and device, during the first (warm-up) step
                 check(lib.w2l_conv1d_igemm_tune_ws(xptr(x.hi), bstride, rows_total, ptr(w_hi), ptr(y),
                                                    int(y.dtype == torch.float32), ptr(bias), ptr(stats), n, Cin, Cout, Tout,
                                                    Kw, stride, dil, TUNE_REPS, ptr(ws), ws.numel(), st), 'w2l_conv1d_igemm_tune_ws')
@@ -985,9 +998,7 @@ class StackEngine:
                 self._q_clipped = torch.zeros(1, dtype=torch.int64, device=dev)
             if AUTOTUNE:
                 key = ('bnact_fp8', n, cin, cout, Tout, kw, dil, dev.index)
-                if key not in _tuned_shapes:           # once per shape and device (synchronises)
-                    _tuned_shapes.add(key)
-                    _tune_state['dirty'] = True
+                if _tune_once(key):           # once per shape and device (synchronises)
                     check(lib.w2l_conv1d_igemm_bnact_fp8_tune(xq, bstride, rows_total, ptr(wq), ptr(bias), C.byref(epi), ptr(out_q),
                                                               q_scale, n, cin, cout, Tout, kw, dil, TUNE_REPS, st),
                           'w2l_conv1d_igemm_bnact_fp8_tune')
@@ -1029,9 +1040,7 @@ class StackEngine:
         ws = _splitk_workspace(src.hi.device, n, cout, Tout)
         if AUTOTUNE:
             key = ('bnact', n, cin, cout, Tout, kw, stride, dil, src.hi.device.index)
-            if key not in _tuned_shapes:           # once per shape and device (synchronises)
-                _tuned_shapes.add(key)
-                _tune_state['dirty'] = True
+            if _tune_once(key):           # once per shape and device (synchronises)
                 check(lib.w2l_conv1d_igemm_bnact_tune_ws(xptr(src.hi), bstride, rows_total, ptr(pk.fwd_hi), ptr(bias),
                                                          C.byref(epi), n, cin, cout, Tout, kw, stride, dil, TUNE_REPS, ptr(ws),
                                                          ws.numel(), st), 'w2l_conv1d_igemm_bnact_tune_ws')
@@ -1102,11 +1111,11 @@ class StackEngine:
             conv = u.main
             mid = None
             if u.dw is not None:            # separable unit: the depthwise kernel, then the pointwise convolution fused
-                tmid = (src.T + u.dw.pad_l + u.dw.pad_r - (u.dw.kernel - 1) * u.dw.dilation - 1) // u.dw.stride + 1
+                tmid = u.dw.out_len(src.T)
                 src = mid = self._dw_forward(u.dw, src, mid_lens[ui], out=take(tmid, src.CP))
             if src.pad_l < conv.pad_l or src.pad_r < conv.pad_r:
                 raise ValueError('activation buffer is not padded enough for its consumer')
-            Tout = (src.T + conv.pad_l + conv.pad_r - (conv.kernel - 1) * conv.dilation - 1) // conv.stride + 1
+            Tout = conv.out_len(src.T)
             if Tout <= 0:
                 raise ValueError('input too short for this convolution')
             coutp = padded_channels(conv.cout)
@@ -1115,7 +1124,7 @@ class StackEngine:
             if u.res is not None:           # the second branch first: affine only, dense, read by the main launch's epilogue
                 rsrc = acts[u.res_src]
                 rc = u.res
-                Tres = (rsrc.T + rc.pad_l + rc.pad_r - (rc.kernel - 1) * rc.dilation - 1) // rc.stride + 1
+                Tres = rc.out_len(rsrc.T)
                 if Tres != Tout or padded_channels(rc.cout) != coutp:
                     raise ValueError('residual branch shape mismatch')
                 res_buf = take(Tout, coutp)
@@ -1248,8 +1257,7 @@ class StackEngine:
         if pk.cinp != src.CP:
             raise ValueError(f'channel mismatch: conv expects {pk.cinp} padded channels, activation has {src.CP}')
         N = src.N
-        Tp = src.T + conv.pad_l + conv.pad_r
-        Tout = (Tp - (conv.kernel - 1) * conv.dilation - 1) // conv.stride + 1
+        Tout = conv.out_len(src.T)
         if Tout <= 0:
             raise ValueError('input too short for this convolution')
         f32 = self.precise or force_f32
@@ -1284,9 +1292,7 @@ class StackEngine:
         st = stream_ptr()
         if AUTOTUNE:
             key = ('fp8', N, cin, cout, Tout, conv.kernel, conv.dilation, stats is not None, src.q.device.index)
-            if key not in _tuned_shapes:
-                _tuned_shapes.add(key)
-                _tune_state['dirty'] = True
+            if _tune_once(key):
                 check(lib.w2l_conv1d_igemm_fp8_tune(xq, bstride, rows_total, ptr(wq), ptr(y), y_f32, ptr(bias), ptr(stats), N,
                                                     cin, cout, Tout, conv.kernel, conv.dilation, TUNE_REPS, st),
                       'w2l_conv1d_igemm_fp8_tune')
@@ -1315,8 +1321,7 @@ class StackEngine:
         if src.pad_l < dwc.pad_l or src.pad_r < dwc.pad_r:
             raise ValueError('activation buffer is not padded enough for its depthwise consumer')
         N, cp = src.N, src.CP
-        Tp = src.T + dwc.pad_l + dwc.pad_r
-        Tmid = (Tp - (dwc.kernel - 1) * dwc.dilation - 1) // dwc.stride + 1
+        Tmid = dwc.out_len(src.T)
         dev = src.hi.device
         if out is not None:
             mid_hi, mid_lo = out
@@ -2148,9 +2153,7 @@ class StackEngine:
         if f8 is not None:
             if AUTOTUNE:
                 key = ('wgrad_fp8', N, pk.cinp, pk.coutp, Tout, kw, conv.dilation, dev.index)
-                if key not in _tuned_shapes:
-                    _tuned_shapes.add(key)
-                    _tune_state['dirty'] = True
+                if _tune_once(key):
                     scratch = torch.empty(kw, pk.coutp, pk.cinp, dtype=torch.float32, device=dev)
                     check(lib.w2l_conv1d_wgrad_fp8_tune(C.c_void_p(f8[0].data_ptr() + halo * pk.coutp), dy_bstride,
                                                         C.c_void_p(src.q.data_ptr() + row_off * src.CP), x_bstride, x_rows_total,
@@ -2158,9 +2161,7 @@ class StackEngine:
                                                         stream_ptr()), 'w2l_conv1d_wgrad_fp8_tune')
         elif AUTOTUNE and not self.precise:
             key = ('wgrad', N, pk.cinp, pk.coutp, Tout, kw, conv.stride, conv.dilation, dev.index)
-            if key not in _tuned_shapes:       # once per shape and device, during the first (warm-up) step
-                _tuned_shapes.add(key)
-                _tune_state['dirty'] = True
+            if _tune_once(key):       # once per shape and device, during the first (warm-up) step
                 scratch = torch.empty(kw, pk.coutp, pk.cinp, dtype=torch.float32, device=dev)
                 if self._side is not None:         # the workspace is shared with gradients still running on the side stream
                     torch.cuda.current_stream(dev).wait_stream(self._side)
@@ -2274,9 +2275,7 @@ class StackEngine:
         args = (dy_ptr, rows_total, ptr(pk.dgr_hi), ptr(dxp), ptr(partial)) + tail
         if AUTOTUNE:
             key = ('dgrad+bn', pk.coutp, pk.cinp, flat_rows, conv.kernel, conv.dilation, dev.index)
-            if key not in _tuned_shapes:
-                _tuned_shapes.add(key)
-                _tune_state['dirty'] = True
+            if _tune_once(key):
                 # the measuring launches ADD to slot rows: they get rows of their own -- the step's rows may already hold the
                 # sums another consumer of the same activation (a residual branch) has added
                 scratch = torch.zeros_like(partial) if slots else partial
@@ -2329,9 +2328,7 @@ class StackEngine:
             st_ = stream_ptr()
             if AUTOTUNE:
                 key = ('fp8', 1, pk.coutp, pk.cinp, flat_rows, conv.kernel, conv.dilation, False, dev.index)
-                if key not in _tuned_shapes:
-                    _tuned_shapes.add(key)
-                    _tune_state['dirty'] = True
+                if _tune_once(key):
                     check(lib.w2l_conv1d_igemm_fp8_tune(xq, rows_total * pk.coutp, rows_total, ptr(wq), ptr(dxp), 0, None, None, 1,
                                                         pk.coutp, pk.cinp, flat_rows, conv.kernel, conv.dilation, TUNE_REPS, st_),
                           'w2l_conv1d_igemm_fp8_tune')
