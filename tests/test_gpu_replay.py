@@ -449,7 +449,7 @@ def test_eager_forward_after_a_replayed_phase_x_waits_for_its_updates(monkeypatc
         if i == 6:
             # a validation forward between replayed steps: it consumes the ready flags the recording of X (an eager
             # opt.apply()) left on the packs -- from here on only what a replayed X sets orders an eager forward after it
-            held = [r['conv'] for r in model.engine()._deferred]
+            held = [r.conv for r in model.engine()._deferred]
             model.eval()
             with torch.no_grad():
                 model(batches[0][0], batches[0][1])
@@ -461,7 +461,7 @@ def test_eager_forward_after_a_replayed_phase_x_waits_for_its_updates(monkeypatc
             return
         eng = model.engine()
         assert eng._deferred and eng._side is not None
-        convs = [r['conv'] for r in eng._deferred]
+        convs = [r.conv for r in eng._deferred]
         with torch.cuda.stream(eng._side):
             torch.cuda._sleep(20_000_000)                            # a few milliseconds: the updates land late
         if st['replay_on']:

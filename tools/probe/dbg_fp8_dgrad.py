@@ -36,8 +36,9 @@ def fw(conv, pk, dgrad=False):
     return q, scale
 E._fp8_weights = fw
 real_wg = E.StackEngine._wgrad_now
-def wg(self, conv, pk, dy_hi, dy_lo, halo, Tout, src, grads, fork=None, f8=None, sink=None):
-    r = real_wg(self, conv, pk, dy_hi, dy_lo, halo, Tout, src, grads, fork=fork, f8=f8, sink=sink)
+def wg(self, job, grads, fork=None, sink=None):
+    conv, dy_hi, src, f8 = job.conv, job.dy_hi, job.src, job.f8
+    r = real_wg(self, job, grads, fork=fork, sink=sink)
     torch.cuda.synchronize()
     g = grads.get(id(conv.weight)) if isinstance(grads, dict) else None
     LOG.append({'name': conv.name + '/dW', 'dy': cs(dy_hi), 'x': cs(src.hi), 'xq': cs(src.q), 'f8': f8 is not None, 'dw': cs(g) if g is not None else None})

@@ -38,8 +38,8 @@ def main():
   torch.cuda.synchronize()
   eng = ma.engine()
   for r in eng._deferred:
-      print('deferred', r['conv'].name, 'dy finite', torch.isfinite(r['dy_hi'].float()).all().item(), 'src finite', torch.isfinite(r['src'].hi.float()).all().item(),
-            r['dy_hi'].shape, r['halo'], r['Tout'])
+      print('deferred', r.conv.name, 'dy finite', torch.isfinite(r.dy_hi.float()).all().item(), 'src finite', torch.isfinite(r.src.hi.float()).all().item(),
+            r.dy_hi.shape, r.halo, r.Tout)
   oa.join()
   torch.cuda.synchronize()
   for n, p in ma.named_parameters():

@@ -19,7 +19,7 @@ import ctypes as C
 import math
 import os
 from dataclasses import dataclass, field
-from typing import Callable, List, Optional, Sequence, Tuple
+from typing import Callable, List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
@@ -207,6 +207,81 @@ class _UnitCtx:
     lens_out: Optional[torch.Tensor] = None
     mid: Optional['Act'] = None           # depthwise output = pointwise input (separable units)
     keep: list = field(default_factory=list)
+
+
+class _GradSource(NamedTuple):
+    """the gradient wrt one activation as its consumer left it: ``buf`` [N][per][CP] in that consumer's padded coordinates,
+    ``partial`` the BatchNorm-backward sums a fused data gradient formed beside it (_dgrad_fused)"""
+    buf: torch.Tensor
+    pad_l: int
+    pad_r: int
+    pad_mode: int
+    per: int
+    partial: Optional[torch.Tensor] = None
+
+
+def _row_ptr(t: torch.Tensor, rows: int, width: int, esize: int) -> C.c_void_p:
+    """``t``'s address ``rows`` rows of ``width`` elements in; ``esize`` bytes per element: 2 for bf16, 1 for e4m3"""
+    return C.c_void_p(t.data_ptr() + rows * width * esize)
+
+
+@dataclass(eq=False, slots=True)
+class _WgradJob:
+    """one weight gradient still to be computed: dW of ``conv`` from its dy and its padded input ``src``"""
+    conv: ConvSpec
+    pk: _PackedW
+    dy_hi: torch.Tensor
+    dy_lo: Optional[torch.Tensor]
+    halo: int
+    Tout: int
+    src: Act
+    f8: Optional[tuple] = None            # fp8 mode: (dy's e4m3 copy, the device-side 1/scale) of StackEngine._dy_e4m3
+    token: Optional[int] = None           # held-back jobs only: the optimizer's token of the backward pass that left it,
+    order: int = 0                        # its place in the flush, and the unit in front of which the forward launches it
+    at: Optional[int] = None
+
+    # shared-halo layout (include/w2l_hip.h): dy is [halo zero rows][utt 0: Tout rows][halo zero rows][utt 1] ..., so utterance
+    # n starts at row halo + n*(Tout+halo); x is [N][src.rows][CP], entered src.pad_l - conv.pad_l rows in (the conv's own padding)
+    @property
+    def N(self) -> int:
+        return self.src.N
+
+    @property
+    def row_off(self) -> int:
+        return self.src.pad_l - self.conv.pad_l
+
+    @property
+    def x_bstride(self) -> int:
+        return self.src.rows * self.src.CP
+
+    @property
+    def x_rows_total(self) -> int:
+        return self.src.N * self.src.rows - self.row_off
+
+    @property
+    def dy_bstride(self) -> int:
+        return (self.Tout + self.halo) * self.pk.coutp
+
+    @property
+    def dw_shape(self) -> Tuple[int, int, int]:
+        return (self.conv.kernel, self.pk.coutp, self.pk.cinp)
+
+    @property
+    def flops(self) -> float:
+        return 2.0 * self.src.N * self.Tout * self.conv.cout * self.conv.cin * self.conv.kernel
+
+    def dy_ptr(self, t: torch.Tensor, esize: int) -> C.c_void_p:
+        """row 0 of utterance 0 in ``t``, a dy buffer (dy_hi, dy_lo or the e4m3 copy)"""
+        return _row_ptr(t, self.halo, self.pk.coutp, esize)
+
+    def x_ptr(self, t: torch.Tensor, esize: int) -> C.c_void_p:
+        """the convolution's first input row in ``t``, a buffer of ``src`` (hi, lo or q)"""
+        return _row_ptr(t, self.row_off, self.src.CP, esize)
+
+    def held(self) -> tuple:
+        """the tensors a side-stream launch of this job reads: alive until the streams join"""
+        ts = (self.dy_hi, self.dy_lo, self.src.hi, self.src.lo) + ((self.src.q,) + self.f8 if self.f8 else ())
+        return tuple(t for t in ts if t is not None)
 
 
 _dropout_calls = 0
@@ -1339,15 +1414,14 @@ class StackEngine:
 
     def _dw_backward(self, dwc: ConvSpec, dmid, src: Act, mid: Act, need_dx: bool, grads):
         """depthwise weight gradient (+ data gradient) from the gradient wrt the pointwise conv's input"""
-        g, _, _, _, per = dmid[:5]
+        g, per = dmid.buf, dmid.per
         N, cp = src.N, src.CP
         dev = g.device
         row_off = src.pad_l - dwc.pad_l
-        off = row_off * cp * 2
         k = dwc.kernel
         dwg = zeros((k, cp), torch.float32, dev)
-        check(lib.w2l_dwconv_wgrad(ptr(g), int(g.dtype == torch.float32), per, C.c_void_p(src.hi.data_ptr() + off),
-                                   C.c_void_p(src.lo.data_ptr() + off) if src.lo is not None else None, src.rows, ptr(dwg), N,
+        check(lib.w2l_dwconv_wgrad(ptr(g), int(g.dtype == torch.float32), per, _row_ptr(src.hi, row_off, cp, 2),
+                                   _row_ptr(src.lo, row_off, cp, 2) if src.lo is not None else None, src.rows, ptr(dwg), N,
                                    mid.T, cp, k, dwc.stride, dwc.dilation, ptr(mid.lens), stream_ptr()), 'w2l_dwconv_wgrad')
         c = dwc.cout
         gw = dwg.view(k, cp, 1).permute(1, 2, 0)          # logical [CP, 1, K] in the parameter's tap-major layout
@@ -1370,7 +1444,7 @@ class StackEngine:
         check(lib.w2l_dwconv_dgrad(ptr(g), int(g.dtype == torch.float32), per, ptr(w), ptr(dxp),
                                    int(dxp.dtype == torch.float32), N, Tp, tmid, cp, k, dwc.dilation, ptr(lens_mid),
                                    stream_ptr()), 'w2l_dwconv_dgrad')
-        return (dxp, dwc.pad_l, dwc.pad_r, dwc.pad_mode, Tp)
+        return _GradSource(dxp, dwc.pad_l, dwc.pad_r, dwc.pad_mode, Tp)
 
     def _bn_finalize(self, conv: ConvSpec, stats, count, cp, training):
         dev = conv.weight.device
@@ -1496,14 +1570,14 @@ class StackEngine:
         self._zero_pool = [zbuf[pool_elems + slot_need:], 0] if bias_need else None
         lib.w2l_conv_stats_mode(STAT_SLOTS if self._slot_pool is not None else 0)
         lib.w2l_wgrad_deterministic(int(DETERMINISTIC_WGRAD))
-        act_grads: List[List[tuple]] = [[] for _ in acts]
+        act_grads: List[List[_GradSource]] = [[] for _ in acts]
         if self.head is None:
             # open stack: the caller's gradient wrt the fp32 [N, C, T'] result becomes the (unpadded, fp32) gradient source
             last = acts[-1]
             _lib.poison('open stack')
             gp = torch.zeros(N, last.T, last.CP, dtype=torch.float32, device=dev)
             gp[:, :, :last.C] = g_out.float().transpose(1, 2)
-            act_grads[len(acts) - 1].append((gp, 0, 0, PAD_ZERO, last.T))
+            act_grads[len(acts) - 1].append(_GradSource(gp, 0, 0, PAD_ZERO, last.T))
         else:
             self._plan_wgrad_groups(ctx)
             pool_off = self._head_backward(ctx, g_out, small_pool, grads, act_grads)
@@ -1609,7 +1683,7 @@ class StackEngine:
             fold = fast = False
             if u.main.has_bn or (u.res is not None and u.res.has_bn):
                 ncomp = 4 if u.res is not None else 2
-                fused = [s_[5] for s_ in srcs if len(s_) > 5 and s_[5] is not None]
+                fused = [s_.partial for s_ in srcs if s_.partial is not None]
                 fast = False
                 if len(fused) == len(srcs) and ncomp == 2:
                     # every gradient source was a data-gradient convolution that formed the sums in its epilogue
@@ -1737,8 +1811,9 @@ class StackEngine:
         a0 = ctx['acts'][0]
         _lib.poison('spectrogram gradient')
         total = None
-        for (g, pl, pr, mode, per, *_) in srcs:
-            gv = g.view(N, per, a0.CP)[:, :pl + T0 + pr, :C0].float()
+        for s_ in srcs:
+            pl, pr, mode = s_.pad_l, s_.pad_r, s_.pad_mode
+            gv = s_.buf.view(N, s_.per, a0.CP)[:, :pl + T0 + pr, :C0].float()
             core = gv[:, pl:pl + T0].clone()
             if mode == PAD_REFLECT:
                 if pl:
@@ -1784,12 +1859,11 @@ class StackEngine:
         grads[id(param)] = grad
         self._notify(param, grad, storage)
 
-    def _gsrc(self, s) -> GradSrc:
-        t, pl, pr, mode, rows = s[:5]
+    def _gsrc(self, s: _GradSource) -> GradSrc:
         g = GradSrc()
-        g.dxp = t.data_ptr()
-        g.f32 = int(t.dtype == torch.float32)
-        g.pad_l, g.pad_r, g.pad_mode, g.rows = pl, pr, mode, rows
+        g.dxp = s.buf.data_ptr()
+        g.f32 = int(s.buf.dtype == torch.float32)
+        g.pad_l, g.pad_r, g.pad_mode, g.rows = s.pad_l, s.pad_r, s.pad_mode, s.per
         return g
 
     def _dy_e4m3(self, dy_hi, amax):
@@ -1819,7 +1893,7 @@ class StackEngine:
         # a gradient that autograd would ADD to an existing .grad (accumulation steps) is computed now; so is a second
         # gradient of a weight whose first one is still held back (two backward passes before one step(): the optimizer
         # adds the held one to .grad at step() -- one update with the sum, as torch.optim.SGD would make)
-        if any(r['conv'].weight is w for r in self._deferred):
+        if any(r.conv.weight is w for r in self._deferred):
             return False
         return (w.is_cuda and w.grad is None and not torch.cuda.is_current_stream_capturing() and opt.accepts(w))
 
@@ -1833,10 +1907,7 @@ class StackEngine:
         the layer whose update it carries (just in time, with margin); 'even' = evenly over the units in front of
         the first deferred layer.  A gradient is always launched strictly before its own layer's convolution."""
         mode = DEFER_SPREAD
-        uis = []
-        for r in recs:
-            conv = r['conv']
-            uis.append(next((i for i, u in enumerate(self.units) if u.main is conv or u.res is conv or u.dw is conv), 0))
+        uis = [next((i for i, u in enumerate(self.units) if any(r.conv is c for c in (u.main, u.res, u.dw))), 0) for r in recs]
         first = min(uis) if uis else 0
         for j, (r, ui) in enumerate(zip(recs, uis)):
             if mode == 'start':
@@ -1845,7 +1916,7 @@ class StackEngine:
                 at = ui - int(mode[3:])
             else:
                 at = (j * max(first - 1, 0)) // max(len(recs), 1)
-            r['at'] = max(0, min(at, ui - 1))
+            r.at = max(0, min(at, ui - 1))
 
     def flush_deferred(self, pos=None):
         """launch the weight gradients held back by the last backward pass -- on the weight-gradient stream, in forward order,
@@ -1858,78 +1929,65 @@ class StackEngine:
         recs, self._deferred = self._deferred, []
         if not recs:
             return
-        recs.sort(key=lambda r: r['order'])
+        recs.sort(key=lambda r: r.order)
         opt = self.deferred
         if pos is not None:
-            if any('at' not in r for r in recs):
-                self._defer_positions([r for r in recs if opt is not None and opt.stepped(r['token'])])
-            later = [r for r in recs if r.get('at', 0) > pos and opt is not None and opt.stepped(r['token'])]
+            if any(r.at is None for r in recs):
+                self._defer_positions([r for r in recs if self._stepped(r)])
+            later = [r for r in recs if (r.at or 0) > pos and self._stepped(r)]
             if later:
                 self._deferred = later
                 recs = [r for r in recs if not any(r is q for q in later)]
                 if not recs:
                     return
-        dev = recs[0]['dy_hi'].device
-        main = torch.cuda.current_stream(dev)
-        pending = []
-
-        def sink(w, g, storage):
-            pending.append((w, g, storage, self.grad_reduce_start(storage) if self.grad_reduce_start is not None else None))
-
-        live = [r for r in recs if opt is not None and opt.stepped(r['token'])]
-        stale = [r for r in recs if not (opt is not None and opt.stepped(r['token']))]
-        self._materialize(stale)           # nobody stepped (and nobody called zero_grad): plain gradients, accumulated
+        live = [r for r in recs if self._stepped(r)]
+        # nobody stepped (and nobody called zero_grad): plain gradients, accumulated
+        self._materialize([r for r in recs if not self._stepped(r)])
         if not live:
             return
-        fork = None
-        if self.overlap_wgrad:
-            if self._side is None or self._side.device != dev:
-                self._side = _side_stream(dev, main)
-            fork = (main, self._side)
+        fork = self._fork(live[0].dy_hi.device, current=True)
+        pending = []
+        # one GPU: wgrad_i, update_i, wgrad_i+1, ... on one stream (the sink runs where the gradient was written)
+        sink = self._reduce_sink(pending) if self.grad_reduce_start is not None else (lambda w, g, storage: opt.apply(w, g))
         for r in live:
-            self._wgrad_now(r['conv'], r['pk'], r['dy_hi'], r['dy_lo'], r['halo'], r['Tout'], r['src'], {}, fork=fork,
-                            f8=r['f8'], sink=sink)
-            if self.grad_reduce_start is None:           # one GPU: wgrad_i, update_i, wgrad_i+1, ... on one stream
-                w, g, _, _ = pending.pop()
-                with torch.cuda.stream(fork[1]) if fork else _nullctx():
-                    opt.apply(w, g)
-            if fork is not None:
-                self._held.extend(t for t in (r['dy_hi'], r['dy_lo'], r['src'].hi, r['src'].lo) +
-                                  ((r['src'].q,) + r['f8'] if r['f8'] else ()) if t is not None)
+            self._wgrad_now(r, {}, fork=fork, sink=sink)
         if pending:                        # data parallel: every all-reduce is in flight before the first update waits for one
             with torch.cuda.stream(fork[1]) if fork else _nullctx():
                 for w, g, _, work in pending:
                     work.finish()
                     opt.apply(w, g)
-        if fork is not None:
-            self._side_used = True
 
     def _materialize(self, recs):
         """held-back gradients computed NOW, on the caller's stream, and added to ``param.grad`` as autograd would have"""
         pending = []
-
-        def sink(w, g, storage):
-            pending.append((w, g, storage, self.grad_reduce_start(storage) if self.grad_reduce_start is not None else None))
-
+        sink = self._reduce_sink(pending)
         for r in recs:
-            self._wgrad_now(r['conv'], r['pk'], r['dy_hi'], r['dy_lo'], r['halo'], r['Tout'], r['src'], {}, f8=r['f8'], sink=sink)
+            self._wgrad_now(r, {}, sink=sink)
             w, g, _, work = pending.pop()
             if work is not None:
                 work.finish()
             w.grad = g if w.grad is None else w.grad + g
 
+    def _stepped(self, job: _WgradJob) -> bool:
+        """has the optimizer taken the step of the backward pass that held ``job`` back?"""
+        return self.deferred is not None and self.deferred.stepped(job.token)
+
+    def _reduce_sink(self, pending):
+        """a held-back gradient's way out: (weight, gradient, storage, its all-reduce in flight or None) joins ``pending``"""
+        def sink(w, g, storage):
+            pending.append((w, g, storage, self.grad_reduce_start(storage) if self.grad_reduce_start is not None else None))
+        return sink
+
     def drop_unstepped(self):
         """optimizer.zero_grad(): gradients held back by a backward pass that no step() followed are discarded with the
         rest (a skipped step must not resurface in the next one); those of a stepped batch stay -- they are that step's
         update, still to be applied"""
-        opt = self.deferred
-        self._deferred = [r for r in self._deferred if opt is not None and opt.stepped(r['token'])]
+        self._deferred = [r for r in self._deferred if self._stepped(r)]
 
     def settle_before_step(self):
         """optimizer.step(): a held-back gradient whose weight ALSO has a ``.grad`` (a second backward pass ran before this
         step) joins it now, so that the weight gets ONE update with the summed gradient"""
-        opt = self.deferred
-        both = [r for r in self._deferred if r['conv'].weight.grad is not None and not (opt is not None and opt.stepped(r['token']))]
+        both = [r for r in self._deferred if r.conv.weight.grad is not None and not self._stepped(r)]
         if both:
             self._deferred = [r for r in self._deferred if not any(r is b for b in both)]
             self._materialize(both)
@@ -1951,31 +2009,44 @@ class StackEngine:
         if (self.fp8 and not DETERMINISTIC_WGRAD and amax is not None and src.q is not None and conv.stride == 1 and pk.coutp % 128 == 0
                 and src.CP == pk.cinp and pk.cinp % 128 == 0 and (min(conv.kernel, 2) - 1) * conv.dilation <= 32):
             f8 = self._dy_e4m3(dy_hi, amax)          # on the current (main) stream, before the fork
+        job = _WgradJob(conv, pk, dy_hi, dy_lo, halo, Tout, src, f8)
         if defer:
-            self._deferred.append({'conv': conv, 'pk': pk, 'dy_hi': dy_hi, 'dy_lo': dy_lo, 'halo': halo, 'Tout': Tout, 'src': src,
-                                   'f8': f8, 'order': len(self._deferred) * -1, 'token': self.deferred.token()})
+            job.order, job.token = len(self._deferred) * -1, self.deferred.token()
+            self._deferred.append(job)
             return
         grp = self._wg_of.get(id(conv)) if self._wg_of else None
         if grp is not None and f8 is None and dy_hi.is_cuda:
             recs = self._wg_pending.setdefault(grp[0], [])
-            recs.append({'conv': conv, 'pk': pk, 'dy_hi': dy_hi, 'dy_lo': dy_lo, 'halo': halo, 'Tout': Tout, 'src': src})
+            recs.append(job)
             if len(recs) == grp[1]:
                 del self._wg_pending[grp[0]]
                 self._wgrad_group_now(recs, grads)
             return
-        if not self.overlap_wgrad or not dy_hi.is_cuda:
-            return self._wgrad_now(conv, pk, dy_hi, dy_lo, halo, Tout, src, grads, f8=f8)
-        main = self._main_stream or torch.cuda.current_stream(dy_hi.device)
-        if self._side is None or self._side.device != dy_hi.device:
+        self._wgrad_now(job, grads, fork=self._fork(dy_hi.device))
+
+    def _fork(self, dev, current=False):
+        """(main, side): the stream the weight gradients fork from and the one they run on -- or None, when they stay on the
+        caller's stream (overlap_wgrad off, no GPU).  ``current``: fork from the current stream, not from the backward pass's"""
+        if not self.overlap_wgrad or dev.type != 'cuda':
+            return None
+        main = (None if current else self._main_stream) or torch.cuda.current_stream(dev)
+        if self._side is None or self._side.device != dev:
             # ONE stream per device for the life of the process (engines are rebuilt per forward).  HIP multiplexes streams
             # onto 4 hardware queues round-robin: a fresh pool stream per step lands on the main stream's queue every fourth
             # step and that step loses the overlap (14.8 instead of 13.8 ms; Jasper 23.4 instead of 19.7).  Default priority:
             # streams created with hipStreamCreateWithPriority (lowest OR highest) made the whole step 30 % slower.
-            self._side = _side_stream(dy_hi.device, main)
-        side = self._side
-        self._wgrad_now(conv, pk, dy_hi, dy_lo, halo, Tout, src, grads, fork=(main, side), f8=f8)
-        self._held.extend(t for t in (dy_hi, dy_lo, src.hi, src.lo) + ((src.q,) + f8 if f8 else ()) if t is not None)
+            self._side = _side_stream(dev, main)
+        return main, self._side
+
+    def _on_side(self, fork, held=()):
+        """the context of a launch at a fork: the side stream waits for everything enqueued so far on main and becomes current;
+        ``held`` -- every tensor the launch touches -- stays alive in self._held until backward() joins the streams"""
+        if fork is None:
+            return _nullctx()
+        _lib.stream_wait_stream(fork[1], fork[0])
+        self._held.extend(held)
         self._side_used = True
+        return torch.cuda.stream(fork[1])
 
     # ------------------------------------------------------------------ grouped weight gradients
     def _plan_wgrad_groups(self, ctx):
@@ -2026,22 +2097,13 @@ class StackEngine:
 
     def _wgrad_single(self, r, grads, sink=None):
         """one member of a group through the ordinary path (its own measured plan)"""
-        conv, dy_hi = r['conv'], r['dy_hi']
-        if not self.overlap_wgrad or sink is not None:
-            return self._wgrad_now(conv, r['pk'], dy_hi, r['dy_lo'], r['halo'], r['Tout'], r['src'], grads, sink=sink)
-        main = self._main_stream or torch.cuda.current_stream(dy_hi.device)
-        if self._side is None or self._side.device != dy_hi.device:
-            self._side = _side_stream(dy_hi.device, main)
-        self._wgrad_now(conv, r['pk'], dy_hi, r['dy_lo'], r['halo'], r['Tout'], r['src'], grads, fork=(main, self._side))
-        self._held.extend(t for t in (dy_hi, r['dy_lo'], r['src'].hi, r['src'].lo) if t is not None)
-        self._side_used = True
+        return self._wgrad_now(r, grads, fork=None if sink is not None else self._fork(r.dy_hi.device), sink=sink)
 
     def _wgrad_group_now(self, recs, grads):
         """the weight gradients of ``recs`` (same N, Tout, dilation; stride 1) in ONE launch (w2l_conv1d_wgrad_group) -- or one
         by one, if that measured faster for this group (decided once per group signature, during warm-up)"""
-        dev = recs[0]['dy_hi'].device
-        N, Tout, dil = recs[0]['src'].N, recs[0]['Tout'], recs[0]['conv'].dilation
-        key = (tuple((r['pk'].cinp, r['pk'].coutp, r['conv'].kernel) for r in recs), N, Tout, dil)
+        N, Tout, dil = recs[0].N, recs[0].Tout, recs[0].conv.dilation
+        key = (tuple((r.pk.cinp, r.pk.coutp, r.conv.kernel) for r in recs), N, Tout, dil)
         form = _wgroup_forms.get(key)
         if form is None:
             form = self._wgrad_group_measure(recs, key) if AUTOTUNE and not torch.cuda.is_current_stream_capturing() else \
@@ -2051,61 +2113,38 @@ class StackEngine:
             for r in recs:
                 self._wgrad_single(r, grads)
             return
-        main = self._main_stream or torch.cuda.current_stream(dev)
-        fork = None
-        if self.overlap_wgrad:
-            if self._side is None or self._side.device != dev:
-                self._side = _side_stream(dev, main)
-            fork = (main, self._side)
-        dws = self._wgrad_group_launch(recs, form, fork)
-        # the gradients are handed over ON THE STREAM THAT WROTE THEM: a data-parallel reducer (distributed.GradReducer.on_grad)
-        # orders its all-reduce behind an event it records on the current stream -- on the caller's stream that event would
-        # say nothing about the group kernel, and the collective could read (and overwrite in place) dW while it is written
-        with torch.cuda.stream(fork[1]) if fork is not None else _nullctx():
-            for r, dw in zip(recs, dws):
-                w = r['conv'].weight
-                cout, cin, kw = w.shape
-                g = dw.permute(1, 2, 0)                     # logical [CoutP, CinP, Kw]
-                if not (r['pk'].coutp == cout and r['pk'].cinp == cin):
-                    g = g[:cout, :cin, :]
-                self._set(grads, w, g, storage=dw)
+        self._wgrad_group_launch(recs, form, self._fork(recs[0].dy_hi.device), grads)
 
-    def _wgrad_group_launch(self, recs, form, fork):
-        dev = recs[0]['dy_hi'].device
-        N, Tout, dil = recs[0]['src'].N, recs[0]['Tout'], recs[0]['conv'].dilation
+    def _wgrad_group_launch(self, recs, form, fork, grads=None):
+        """the launch itself; with ``grads``, the gradients are then handed over (without: a measuring launch)"""
+        N, Tout, dil = recs[0].N, recs[0].Tout, recs[0].conv.dilation
         items = (_lib.WgradItem * len(recs))()
         dws = []
         for it, r in zip(items, recs):
-            conv, pk, src, halo = r['conv'], r['pk'], r['src'], r['halo']
-            row_off = src.pad_l - conv.pad_l
             # (a group launch stores whole tiles: a zero-filled buffer optim.FusedSGD left on the weight is of no use here --
             # dropped, so that it does not stay alive beside the gradient)
-            conv.weight.__dict__.pop('_w2l_dw_zeroed', None)
-            dw = torch.empty(conv.kernel, pk.coutp, pk.cinp, dtype=torch.float32, device=dev)      # (on the caller's stream)
+            r.conv.weight.__dict__.pop('_w2l_dw_zeroed', None)
+            dw = torch.empty(r.dw_shape, dtype=torch.float32, device=r.dy_hi.device)      # (on the caller's stream)
             dws.append(dw)
-            it.dy = r['dy_hi'].data_ptr() + halo * pk.coutp * 2
-            it.dy_bstride = (Tout + halo) * pk.coutp
-            it.xp = src.hi.data_ptr() + row_off * src.CP * 2
-            it.x_bstride = src.rows * src.CP
-            it.x_rows_total = N * src.rows - row_off
+            it.dy, it.dy_bstride = r.dy_ptr(r.dy_hi, 2), r.dy_bstride
+            it.xp, it.x_bstride, it.x_rows_total = r.x_ptr(r.src.hi, 2), r.x_bstride, r.x_rows_total
             it.dw = dw.data_ptr()
-            it.Cin, it.Cout, it.Kw = pk.cinp, pk.coutp, conv.kernel
-        flops = sum(2.0 * N * Tout * r['pk'].coutp * r['pk'].cinp * r['conv'].kernel for r in recs)
-        if fork is not None:
-            _lib.stream_wait_stream(fork[1], fork[0])
-            self._held.extend(dws)
-            self._held.extend(t for r in recs for t in (r['dy_hi'], r['src'].hi) if t is not None)
-            self._side_used = True
-        with torch.cuda.stream(fork[1]) if fork is not None else _nullctx():
+            it.Cin, it.Cout, it.Kw = r.pk.cinp, r.pk.coutp, r.conv.kernel
+        flops = sum(2.0 * N * Tout * r.pk.coutp * r.pk.cinp * r.conv.kernel for r in recs)      # (of the padded problem)
+        with self._on_side(fork, dws + [t for r in recs for t in r.held()]):
             with _timed('conv_wgrad3_kernel' if form & 16 else 'conv_wgrad_kernel', flops):
                 check(lib.w2l_conv1d_wgrad_group(items, len(recs), N, Tout, dil, form, stream_ptr()), 'w2l_conv1d_wgrad_group')
-        return dws
+            # the gradients are handed over ON THE STREAM THAT WROTE THEM: a data-parallel reducer (distributed.GradReducer.on_grad)
+            # orders its all-reduce behind an event it records on the current stream -- on the caller's stream that event would
+            # say nothing about the group kernel, and the collective could read (and overwrite in place) dW while it is written
+            if grads is not None:
+                for r, dw in zip(recs, dws):
+                    self._hand_over(r, dw, grads)
 
     def _wgrad_group_measure(self, recs, key) -> int:
         """SYNCHRONISING, warm-up only: the group in every block form against its members one by one with their own measured
         plans (zero fills included); returns the fastest form, or -1 for 'one by one'"""
-        dev = recs[0]['dy_hi'].device
-        main = torch.cuda.current_stream(dev)
+        main = torch.cuda.current_stream(recs[0].dy_hi.device)
         if self._side is not None:
             main.wait_stream(self._side)
 
@@ -2136,40 +2175,32 @@ class StackEngine:
         _tune_state['dirty'] = True
         return best[1]
 
-    def _wgrad_now(self, conv: ConvSpec, pk: _PackedW, dy_hi, dy_lo, halo, Tout, src: Act, grads, fork=None, f8=None, sink=None):
+    def _wgrad_now(self, job: _WgradJob, grads, fork=None, sink=None):
         """dW through w2l_conv1d_wgrad, written in the parameter's own physical layout when possible.
         fork=(main, side): allocate on main, launch on side after an event recorded on main."""
-        w = conv.weight
-        cout, cin, kw = w.shape
-        dev = w.device
-        N = src.N
-        direct = (pk.coutp == cout and pk.cinp == cin)
-        row_off = src.pad_l - conv.pad_l
-        x_bstride = src.rows * src.CP
-        x_rows_total = N * src.rows - row_off
-        dy_bstride = (Tout + halo) * pk.coutp          # shared-halo layout: utterance n starts at row halo + n*(Tout+halo)
+        conv, pk, src, f8, Tout = job.conv, job.pk, job.src, job.f8, job.Tout
+        w, dev = conv.weight, conv.weight.device
+        N, kw = job.N, conv.kernel
         ws = _wgrad_workspace(dev, pk.cinp, pk.coutp, kw) if f8 is None and (DETERMINISTIC_WGRAD or DEALT_WGRAD) else None
         ws_bytes = ws.numel() if ws is not None else 0
         if f8 is not None:
             if AUTOTUNE:
                 key = ('wgrad_fp8', N, pk.cinp, pk.coutp, Tout, kw, conv.dilation, dev.index)
                 if _tune_once(key):
-                    scratch = torch.empty(kw, pk.coutp, pk.cinp, dtype=torch.float32, device=dev)
-                    check(lib.w2l_conv1d_wgrad_fp8_tune(C.c_void_p(f8[0].data_ptr() + halo * pk.coutp), dy_bstride,
-                                                        C.c_void_p(src.q.data_ptr() + row_off * src.CP), x_bstride, x_rows_total,
-                                                        ptr(scratch), N, pk.cinp, pk.coutp, Tout, kw, conv.dilation, TUNE_REPS,
-                                                        stream_ptr()), 'w2l_conv1d_wgrad_fp8_tune')
+                    scratch = torch.empty(job.dw_shape, dtype=torch.float32, device=dev)
+                    check(lib.w2l_conv1d_wgrad_fp8_tune(job.dy_ptr(f8[0], 1), job.dy_bstride, job.x_ptr(src.q, 1), job.x_bstride,
+                                                        job.x_rows_total, ptr(scratch), N, pk.cinp, pk.coutp, Tout, kw,
+                                                        conv.dilation, TUNE_REPS, stream_ptr()), 'w2l_conv1d_wgrad_fp8_tune')
         elif AUTOTUNE and not self.precise:
             key = ('wgrad', N, pk.cinp, pk.coutp, Tout, kw, conv.stride, conv.dilation, dev.index)
             if _tune_once(key):       # once per shape and device, during the first (warm-up) step
-                scratch = torch.empty(kw, pk.coutp, pk.cinp, dtype=torch.float32, device=dev)
+                scratch = torch.empty(job.dw_shape, dtype=torch.float32, device=dev)
                 if self._side is not None:         # the workspace is shared with gradients still running on the side stream
                     torch.cuda.current_stream(dev).wait_stream(self._side)
-                check(lib.w2l_conv1d_wgrad_tune_x(C.c_void_p(dy_hi.data_ptr() + halo * pk.coutp * 2), dy_bstride,
-                                                  C.c_void_p(src.hi.data_ptr() + row_off * src.CP * 2), x_bstride, x_rows_total,
-                                                  ptr(scratch), N, pk.cinp, pk.coutp, Tout, kw, conv.stride, conv.dilation, TUNE_REPS,
-                                                  ptr(ws), ws_bytes, 0 if DETERMINISTIC_WGRAD else 1, stream_ptr()),
-                      'w2l_conv1d_wgrad_tune_x')
+                check(lib.w2l_conv1d_wgrad_tune_x(job.dy_ptr(job.dy_hi, 2), job.dy_bstride, job.x_ptr(src.hi, 2), job.x_bstride,
+                                                  job.x_rows_total, ptr(scratch), N, pk.cinp, pk.coutp, Tout, kw, conv.stride,
+                                                  conv.dilation, TUNE_REPS, ptr(ws), ws_bytes, 0 if DETERMINISTIC_WGRAD else 1,
+                                                  stream_ptr()), 'w2l_conv1d_wgrad_tune_x')
         # with a workspace, split reductions end in plain stores by the last block of a tile: no zero fill, no atomics
         if f8 is not None:
             need_zero = bool(lib.w2l_wgrad_fp8_needs_zero(N, pk.cinp, pk.coutp, Tout, kw))
@@ -2177,68 +2208,56 @@ class StackEngine:
             need_zero = bool(lib.w2l_wgrad_needs_zero_x(N, pk.cinp, pk.coutp, Tout, kw, conv.stride, conv.dilation, ws_bytes)) or self.precise
         # optim.FusedSGD leaves last step's gradient buffer zero-filled on the parameter: take it as this step's dW (only
         # when zero_grad(set_to_none=True) dropped p.grad -- otherwise autograd is about to ADD into that very tensor)
-        recycled = w.__dict__.pop('_w2l_dw_zeroed', None)
-        if (recycled is not None and need_zero and w.grad is None and recycled.device == dev and recycled.is_contiguous()
-                and tuple(recycled.shape) == (kw, pk.coutp, pk.cinp)):
-            if fork is not None:
-                _lib.stream_wait_stream(fork[1], fork[0])
-                self._held.append(recycled)
-                with torch.cuda.stream(fork[1]):
-                    return self._wgrad_launch(conv, pk, recycled, dy_hi, dy_lo, halo, Tout, src, grads, x_bstride,
-                                              x_rows_total, dy_bstride, row_off, direct, ws, f8, sink)
-            return self._wgrad_launch(conv, pk, recycled, dy_hi, dy_lo, halo, Tout, src, grads, x_bstride, x_rows_total,
-                                      dy_bstride, row_off, direct, ws, f8, sink)
-        if fork is not None:
+        dw = w.__dict__.pop('_w2l_dw_zeroed', None)
+        if (dw is not None and need_zero and w.grad is None and dw.device == dev and dw.is_contiguous()
+                and tuple(dw.shape) == job.dw_shape):
+            need_zero = False
+        else:
             # allocated on the main stream (the caching allocator then owns it there), zero-filled on the side stream:
             # the fill of a split-K gradient is as far off the critical path as the kernel that accumulates into it
-            dw = torch.empty(kw, pk.coutp, pk.cinp, dtype=torch.float32, device=dev)
-            _lib.stream_wait_stream(fork[1], fork[0])
-            self._held.append(dw)
-            with torch.cuda.stream(fork[1]):
-                if need_zero:
-                    zero_(dw)
-                return self._wgrad_launch(conv, pk, dw, dy_hi, dy_lo, halo, Tout, src, grads, x_bstride, x_rows_total,
-                                          dy_bstride, row_off, direct, ws, f8, sink)
-        dw = (zeros if need_zero else (lambda shape, dtype, device: torch.empty(shape, dtype=dtype, device=device)))(
-            (kw, pk.coutp, pk.cinp), torch.float32, dev)
-        return self._wgrad_launch(conv, pk, dw, dy_hi, dy_lo, halo, Tout, src, grads, x_bstride, x_rows_total, dy_bstride,
-                                  row_off, direct, ws, f8, sink)
+            dw = torch.empty(job.dw_shape, dtype=torch.float32, device=dev)
+        with self._on_side(fork, (dw,) + job.held()):
+            if need_zero:
+                zero_(dw)
+            self._wgrad_launch(job, dw, ws)
+            return self._hand_over(job, dw, grads, sink)
 
-    def _wgrad_launch(self, conv, pk, dw, dy_hi, dy_lo, halo, Tout, src, grads, x_bstride, x_rows_total, dy_bstride, row_off,
-                      direct, ws, f8=None, sink=None):
-        w = conv.weight
-        cout, cin, kw = w.shape
-        N = src.N
+    def _wgrad_launch(self, job: _WgradJob, dw, ws):
+        conv, pk, src, f8 = job.conv, job.pk, job.src, job.f8
+        N, kw = job.N, conv.kernel
         st = stream_ptr()
 
         def run(dy, x, acc):
-            check(lib.w2l_conv1d_wgrad_ws(C.c_void_p(dy.data_ptr() + halo * pk.coutp * 2), dy_bstride,
-                                          C.c_void_p(x.data_ptr() + row_off * src.CP * 2), x_bstride, x_rows_total,
-                                          ptr(dw), N, pk.cinp, pk.coutp, Tout, kw, conv.stride, conv.dilation, acc, ptr(ws),
+            check(lib.w2l_conv1d_wgrad_ws(job.dy_ptr(dy, 2), job.dy_bstride, job.x_ptr(x, 2), job.x_bstride, job.x_rows_total,
+                                          ptr(dw), N, pk.cinp, pk.coutp, job.Tout, kw, conv.stride, conv.dilation, acc, ptr(ws),
                                           ws.numel() if ws is not None else 0, st), 'w2l_conv1d_wgrad_ws')
 
         if f8 is not None:
             # fp8 mode: dy's e4m3 copy x the input's e4m3 copy (the operand of the forward convolution), fp32 result
-            with _timed('conv_wgrad_fp8_kernel', 2.0 * N * Tout * cout * cin * kw):
-                check(lib.w2l_conv1d_wgrad_fp8(C.c_void_p(f8[0].data_ptr() + halo * pk.coutp), dy_bstride,
-                                               C.c_void_p(src.q.data_ptr() + row_off * src.CP), x_bstride, x_rows_total, ptr(dw), N,
-                                               pk.cinp, pk.coutp, Tout, kw, conv.dilation, 1.0 / src.q_scale, ptr(f8[1]), 0, st),
-                      'w2l_conv1d_wgrad_fp8')
+            with _timed('conv_wgrad_fp8_kernel', job.flops):
+                check(lib.w2l_conv1d_wgrad_fp8(job.dy_ptr(f8[0], 1), job.dy_bstride, job.x_ptr(src.q, 1), job.x_bstride,
+                                               job.x_rows_total, ptr(dw), N, pk.cinp, pk.coutp, job.Tout, kw, conv.dilation,
+                                               1.0 / src.q_scale, ptr(f8[1]), 0, st), 'w2l_conv1d_wgrad_fp8')
         elif not self.precise:
             # (which kernel family: the three-tap AGPR code object -- plan order bit 4 on a stride-1, dilation <= 4 layer -- or the
             # two-tap kernels; bench.py reports the two populations side by side)
             label = 'conv_wgrad_kernel'
             if KERNEL_TIMER is not None and conv.stride == 1 and conv.dilation <= 4 and kw >= 3 and \
-                    lib.w2l_wgrad_plan(N, pk.cinp, pk.coutp, Tout, kw) & 16:
+                    lib.w2l_wgrad_plan(N, pk.cinp, pk.coutp, job.Tout, kw) & 16:
                 label = 'conv_wgrad3_kernel'
-            with _timed(label, 2.0 * N * Tout * cout * cin * kw):
-                run(dy_hi, src.hi, 0)
+            with _timed(label, job.flops):
+                run(job.dy_hi, src.hi, 0)
         else:
-            run(dy_hi, src.hi, 1)
-            run(dy_hi, src.lo, 1)
-            run(dy_lo, src.hi, 1)
+            run(job.dy_hi, src.hi, 1)
+            run(job.dy_hi, src.lo, 1)
+            run(job.dy_lo, src.hi, 1)
+
+    def _hand_over(self, job: _WgradJob, dw, grads, sink=None):
+        """dW [Kw][CoutP][CinP] as the parameter's gradient, on the stream that wrote it"""
+        w = job.conv.weight
+        cout, cin, _ = w.shape
         g = dw.permute(1, 2, 0)                     # logical [CoutP, CinP, Kw]
-        if not direct:
+        if not (job.pk.coutp == cout and job.pk.cinp == cin):
             g = g[:cout, :cin, :]
         if sink is not None:                        # a deferred gradient: reduced / applied by flush_deferred, not by autograd
             return sink(w, g, dw)
@@ -2267,7 +2286,7 @@ class StackEngine:
             tiles = lib.w2l_conv_stat_tiles(1, flat_rows)
             partial = torch.empty(tiles, 2, src.CP, dtype=torch.float32, device=dev)
         row_off = halo - hb
-        dy_ptr = C.c_void_p(dy_hi.data_ptr() + row_off * pk.coutp * 2)
+        dy_ptr = _row_ptr(dy_hi, row_off, pk.coutp, 2)
         rows_total = total - row_off
         ws = _splitk_workspace(dev, 1, pk.cinp, flat_rows)
         st = stream_ptr()
@@ -2323,7 +2342,7 @@ class StackEngine:
             dyq, inv = self._dy_e4m3(dy_hi, amax)
             wq, w_scale = _fp8_weights(conv, pk, dgrad=True)
             row_off = halo - hb
-            xq = C.c_void_p(dyq.data_ptr() + row_off * pk.coutp)
+            xq = _row_ptr(dyq, row_off, pk.coutp, 1)
             rows_total = total - row_off
             st_ = stream_ptr()
             if AUTOTUNE:
@@ -2336,10 +2355,10 @@ class StackEngine:
                 check(lib.w2l_conv1d_igemm_fp8(xq, rows_total * pk.coutp, rows_total, ptr(wq), ptr(dxp), 0, 1.0 / w_scale, ptr(inv),
                                                None, None, 1, pk.coutp, pk.cinp, flat_rows, conv.kernel, conv.dilation, st_),
                       'w2l_conv1d_igemm_fp8')
-            return (dxp, conv.pad_l, conv.pad_r, conv.pad_mode, per)
+            return _GradSource(dxp, conv.pad_l, conv.pad_r, conv.pad_mode, per)
         if producer is not None and conv.stride == 1 and per >= Tp and src.CP == pk.cinp:
             partial = self._dgrad_fused(conv, pk, dy_hi, halo, hb, per, flat_rows, total, dxp, src, producer, flops)
-            return (dxp, conv.pad_l, conv.pad_r, conv.pad_mode, per, partial)
+            return _GradSource(dxp, conv.pad_l, conv.pad_r, conv.pad_mode, per, partial)
         dyact = Act(dy_hi, dy_lo, 1, total, pk.coutp, pk.coutp, 0, 0, PAD_ZERO)
         _igemm(dyact, halo - hb, pk.dgr_hi, pk.dgr_lo, dxp, None, None, pk.coutp, pk.cinp, flat_rows, conv.kernel, 1,
                conv.dilation, self.precise, alg_flops=flops)
@@ -2347,5 +2366,5 @@ class StackEngine:
             _lib.poison('strided data gradient')
             full = torch.zeros(N, Tp, pk.cinp, dtype=dxp.dtype, device=dev)
             full[:, :per] = dxp.view(N, per, pk.cinp)
-            return (full, conv.pad_l, conv.pad_r, conv.pad_mode, Tp)
-        return (dxp, conv.pad_l, conv.pad_r, conv.pad_mode, per)
+            return _GradSource(full, conv.pad_l, conv.pad_r, conv.pad_mode, Tp)
+        return _GradSource(dxp, conv.pad_l, conv.pad_r, conv.pad_mode, per)

@@ -10,7 +10,7 @@ from typing import Callable, Optional
 import torch
 import torch.nn as nn
 
-from .engine import ACT_NONE, PAD_ZERO, ConvSpec, StackEngine, UnitSpec
+from .engine import ACT_NONE, PAD_ZERO, ConvSpec, StackEngine, UnitSpec, _GradSource
 
 
 def default_precision(cfg=None) -> str:
@@ -144,8 +144,8 @@ class _DepthwiseFn(torch.autograd.Function):
         gp = torch.zeros(n, mid.T, cp, dtype=torch.float32, device=g.device)
         gp[:, :, :c] = g.float().transpose(1, 2)
         grads = {}
-        gsrc = eng._dw_backward(spec, (gp, 0, 0, PAD_ZERO, mid.T), src, mid, True, grads)
-        dxp, pl, _, _, per = gsrc[:5]
+        gsrc = eng._dw_backward(spec, _GradSource(gp, 0, 0, PAD_ZERO, mid.T), src, mid, True, grads)
+        dxp, pl, per = gsrc.buf, gsrc.pad_l, gsrc.per
         dx = dxp.view(n, per, cp)[:, pl:pl + t, :c].float()
         if src.lens is not None:                             # masked_fill on the input (jasper.py:116-119)
             dx = dx * (torch.arange(t, device=dx.device)[None, :, None] < src.lens.long()[:, None, None])

@@ -54,7 +54,7 @@ def materialize_held_back(engines, opt=None):
     that no step() has consumed yet, into ``p.grad`` -- and drop their records, so that nothing applies them a second time"""
     for eng in engines:
         dopt = eng.deferred if opt is None else opt
-        recs = [r for r in eng._deferred if not (dopt is not None and dopt.stepped(r['token']))]
+        recs = [r for r in eng._deferred if not (dopt is not None and dopt.stepped(r.token))]
         if recs:
             eng._deferred = [r for r in eng._deferred if not any(r is q for q in recs)]
             eng._materialize(recs)

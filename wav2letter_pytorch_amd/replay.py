@@ -329,13 +329,13 @@ class StepReplayer:
             self.pending = None
             return
         opt = eng.deferred
-        if opt is None or not all(opt.stepped(r['token']) for r in eng._deferred) or s.B is None:
+        if opt is None or not all(eng._stepped(r) for r in eng._deferred) or s.B is None:
             self.pending = None
             return                                     # eager flush_deferred sorts it out (stale gradients, no optimizer)
         # what the held-back updates are applied with: the hyper-parameters of the LAST step() call (optim.FusedSGD.apply), by
         # value in the record -- not necessarily the optimizer's current ones (a scheduler may have stepped since)
         hp = opt._deferred_state()['hp']
-        sig = tuple(hp[id(r['conv'].weight)][2] for r in eng._deferred) + (opt.__dict__.get('_w2l_state_epoch', 0),)
+        sig = tuple(hp[id(r.conv.weight)][2] for r in eng._deferred) + (opt.__dict__.get('_w2l_state_epoch', 0),)
         if s.X is not None and s.X_sig != sig:
             s.X = None
         if s.X is not None:
@@ -343,7 +343,7 @@ class StepReplayer:
             # (the eager forward after a replayed X: its packs carry the weight events X recorded, as opt.apply() sets them)
             from . import engine as E
             for r in eng._deferred:
-                w = r['conv'].weight
+                w = r.conv.weight
                 for pk in (getattr(w, '_w2l_pack', None) or {}).values():
                     pk.ready, pk.version = E.weight_event(w), w._version
             eng._deferred = []
@@ -604,7 +604,7 @@ def _replay_backward(rp, engine, rset, g):
         opt = engine.deferred
         tok = opt.token() if opt is not None else 0
         for r in rset.deferred:
-            r['token'] = tok
+            r.token = tok
         engine._deferred = list(rset.deferred)
         rp.pending = rset
     else:
