@@ -634,6 +634,26 @@ int w2l_feature_normalize(const float* logmel, const int32_t* n_samples, int hop
  * the masked_fill of SpecAugment.forward / SpecCutout.forward (data/augmentations.py:56,97); x fp32 [N][C][T]. */
 int w2l_zero_rects(float* x, int N, int C, int T, const int32_t* rects, int R, void* stream);
 
+/* ---- sample-rate conversion in front of w2l_logmel (data/resample.py; no reference counterpart: the reference asserts the
+ * rate of the first manifest row and has no speed perturbation) --------------------------------------------------------
+ * x [N][in_stride] -> out [N][out_stride], fp32, device, one launch.  Row n has rows[n] = {n_in, n_out, P, Q, bank}:
+ *   P/Q (reduced) = input samples advanced per output sample; n_out = ceil(n_in * Q / P);
+ *   out[m] = sum_{j < K} x~[i0 - H + j] * h[phase][j],  i0 = (m P) div Q, phase = (m P) mod Q in 64-bit integers,
+ *   x~ = x inside [0, n_in) and 0 outside, fp32 accumulation;  out[m] = 0 for n_out <= m < out_stride.
+ * A row with P == Q is copied bit for bit (its bank is not looked at).  banks[b] = {offset, K, H, Q}: the polyphase filter
+ * h[Q][K] of bank b is taps[offset ... offset + Q*K), row-major, K = 2H + 2, offset even.  The row and bank tables are passed
+ * twice, the same int32 values in host memory (checked here, before anything is launched) and in device memory (read by
+ * the kernel).  Rejected: null pointers, P or Q <= 0, n_in > in_stride, n_out != ceil(n_in Q / P) or > out_stride, a bank
+ * index or range outside its table, a bank whose Q differs from the row's, K > W2L_RESAMPLE_MAX_K, and a ratio whose tile
+ * of W2L_RESAMPLE_TILE outputs needs more than W2L_RESAMPLE_MAX_SPAN input floats in LDS ((TILE-1) P/Q + K + 4).
+ * Call site: data_loader.SpectrogramExtractor.extract_batch(rates= / speeds=), data/resample.resample_batch. */
+#define W2L_RESAMPLE_TILE 512
+#define W2L_RESAMPLE_MAX_K 512
+#define W2L_RESAMPLE_MAX_SPAN 8192
+int w2l_resample(const float* x, int64_t in_stride, float* out, int64_t out_stride, int N, const int32_t* rows_host,
+                 const int32_t* rows_dev, const int32_t* banks_host, const int32_t* banks_dev, int n_banks, const float* taps,
+                 int64_t n_taps, void* stream);
+
 /* ---- stream concurrency probe -----------------------------------------------------------------------------------------
  * Launches a chip-filling spin kernel (`rounds` waves of 2 blocks per CU, `spin_us` each) on stream_a, then a one-wave
  * kernel on stream_b that records when it started.  stamps_dev: 3 x int64, zero before the call (caller synchronises

@@ -380,26 +380,37 @@ class ConvCTCASR(_Base):
         return super().train(mode)
 
     def transcribe(self, paths_or_waveforms, batch_size: int = 8, decoder=None, word_times: bool = False):
-        """audio -> text: files (paths) or 1-D waveforms at the model's sample rate -> the GPU log-mel front end
+        """audio -> text: files (paths; any sample rate, channels are averaged), 1-D waveforms at the model's sample rate, or
+        ``(waveform, sample_rate)`` tuples -> resampled to the model's rate on the GPU where the rates differ
+        (data/resample.py; inputs already at the model's rate take the launches they always took) -> the GPU log-mel front end
         (data_loader.SpectrogramExtractor) -> ``infer`` -> ``decoder`` (default: the model's own) -> one string per input, in
         order.  ``word_times``: (string, [(word, start s, end s), ...]) pairs instead, by forced alignment of the decoded text.
         Wav2Letter pads by reflection at the BATCH's padded length and masks nothing, so the last frames of an utterance depend
         on what it is batched with: ``batch_size=1`` gives batch-independent text."""
         from .evaluate import decode_batch
-        from .data.data_loader import SpectrogramExtractor, load_audio
+        from .data.data_loader import SpectrogramExtractor, read_audio
         items = [paths_or_waveforms] if isinstance(paths_or_waveforms, str) else list(paths_or_waveforms)
         dev = next(self.parameters()).device
         ext = self.__dict__.get('_transcribe_extractor')
         if ext is None or ext.fb.device != dev:
             ext = self.__dict__['_transcribe_extractor'] = SpectrogramExtractor(self.audio_conf, self._cfg.input_size, device=dev)
         decoder = decoder or self.ctc_decoder
+        model_rate = int(self.audio_conf['sample_rate'])
+
+        def read(a):
+            if isinstance(a, str):
+                return read_audio(a)
+            return (a[0], int(a[1])) if isinstance(a, tuple) and len(a) == 2 else (a, model_rate)
+
         was_training = self.training
         self.eval()
         results = []
         try:
             for i in range(0, len(items), max(1, int(batch_size))):
-                chunk = [load_audio(a) if isinstance(a, str) else a for a in items[i: i + max(1, int(batch_size))]]
-                x, lens = ext.extract_batch(chunk)
+                chunk = [read(a) for a in items[i: i + max(1, int(batch_size))]]
+                rates = [r for _, r in chunk]
+                # a chunk that is at the model's rate throughout takes the launches it always took
+                x, lens = ext.extract_batch([a for a, _ in chunk], rates=None if all(r == model_rate for r in rates) else rates)
                 out, out_lens = self.infer(x, lens)
                 hyps, words = decode_batch(self, decoder, out, out_lens, word_times)
                 results += list(zip(hyps, words)) if word_times else hyps

@@ -5,7 +5,7 @@ import importlib
 
 from . import label_sets  # noqa: F401
 
-_LAZY = ('data_loader', 'augmentations', 'mel')
+_LAZY = ('data_loader', 'augmentations', 'mel', 'resample')
 
 
 def __getattr__(name):

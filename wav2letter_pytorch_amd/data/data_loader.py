@@ -21,6 +21,7 @@ from torch.utils.data import DataLoader, Dataset
 
 from .._lib import check, lib, ptr, stream_ptr
 from .mel import mel_filterbank
+from .resample import BankCache, SpeedPerturb, plan_rows, resample_device
 
 _TORCH_WINDOWS = {'hann': torch.hann_window, 'hamming': torch.hamming_window, 'blackman': torch.blackman_window,
                   'bartlett': torch.bartlett_window, 'none': None}
@@ -44,6 +45,29 @@ def load_audio(path, duration=-1, offset=0):
     start = int(offset * sr) if offset > 0 else 0
     stop = start + int(duration * sr) if duration > 0 else None
     return samples[start:stop].transpose()
+
+
+def read_audio(path, duration=-1, offset=0):
+    """(mono float32 samples, sample rate): ``load_audio`` that keeps the file's rate and averages the channels -- what
+    the resampling paths read (soundfile when it is installed, otherwise the standard-library WAV reader)."""
+    try:
+        import soundfile as sf
+    except ImportError:
+        sf = None
+    if sf is not None:
+        with sf.SoundFile(path, 'r') as f:
+            sr = f.samplerate
+            if offset > 0:
+                f.seek(int(offset * sr))
+            samples = f.read(int(duration * sr), dtype='float32') if duration > 0 else f.read(dtype='float32')
+    else:
+        samples, sr = _read_wav(path)
+        start = int(offset * sr) if offset > 0 else 0
+        stop = start + int(duration * sr) if duration > 0 else None
+        samples = samples[start:stop]
+    if samples.ndim > 1:
+        samples = samples.mean(axis=1, dtype=np.float32)
+    return np.ascontiguousarray(samples, dtype=np.float32), int(sr)
 
 
 def _read_wav(path):
@@ -74,6 +98,11 @@ def _sample_rate(path) -> int:
         import soundfile as sf
         return sf.info(path).samplerate
     except ImportError:
+        pass
+    try:
+        with wave.open(path, 'rb') as w:                  # the header only
+            return w.getframerate()
+    except wave.Error:
         return _read_wav(path)[1]
 
 
@@ -89,6 +118,8 @@ class SpectrogramExtractor(torch.nn.Module):
     def __init__(self, audio_conf, mel_spec=64, use_cuda=False, device=None):
         super().__init__()
         sr = audio_conf['sample_rate']
+        self.sample_rate = int(sr)
+        self._banks = BankCache()                         # resampling filter banks per (P, Q), uploaded once
         self.win_length = int(sr * audio_conf['window_size'])
         self.hop_length = int(sr * audio_conf['window_stride'])
         self.n_fft = 2 ** math.ceil(math.log2(self.win_length))
@@ -125,19 +156,29 @@ class SpectrogramExtractor(torch.nn.Module):
                              float(self.log_zero_guard_value), ptr(out), tmax, stream_ptr()), 'w2l_logmel')
         return out, tmax
 
-    def _stage(self, signals: Sequence, noise):
+    def _stage(self, signals: Sequence, noise, rates=None, speeds=None):
         dev = self.fb.device
         if dev.type != 'cuda':
             raise RuntimeError('SpectrogramExtractor runs on MI355X only (HIP kernels, no CPU path)')
         arrs = [np.asarray(s.detach().cpu() if torch.is_tensor(s) else s, dtype=np.float32).reshape(-1) for s in signals]
         lens = np.array([a.shape[0] for a in arrs], dtype=np.int32)
+        rows = None
+        if rates is not None or speeds is not None:
+            # per-row ratio speed * rate / model rate; a batch whose rows are all 1/1 takes the plain path (same launches)
+            rows = plan_rows(lens, rates, self.sample_rate, speeds, self._banks)
+            if (rows[:, 2] == rows[:, 3]).all():
+                rows = None
+            else:
+                lens = rows[:, 1].copy()
         if lens.min() <= self.n_fft // 2:
             raise ValueError(f'an utterance of {int(lens.min())} samples is shorter than the STFT reflect padding '
                              f'({self.n_fft // 2}); torch.stft rejects it in the reference too')
-        host = torch.zeros(len(arrs), int(lens.max()), dtype=torch.float32).pin_memory()
+        host = torch.zeros(len(arrs), max(a.shape[0] for a in arrs), dtype=torch.float32).pin_memory()
         for i, a in enumerate(arrs):
             host[i, :a.shape[0]] = torch.from_numpy(a)
         audio = host.to(dev, non_blocking=True)
+        if rows is not None:
+            audio = resample_device(audio, rows, self._banks)         # [N, max n_out], zero past each row's n_out
         lens_d = torch.from_numpy(lens).to(dev, non_blocking=True)
         if noise is None:
             noise_d = torch.randn(audio.shape, dtype=torch.float32, device=dev) if self.dithering > 0 else None
@@ -150,11 +191,14 @@ class SpectrogramExtractor(torch.nn.Module):
                 noise_d[i, :z.shape[0]] = z.to(dev)
         return audio, lens_d, noise_d, lens
 
-    def extract_batch(self, signals: Sequence, noise=None):
+    def extract_batch(self, signals: Sequence, noise=None, rates=None, speeds=None):
         """signals: N 1-D float arrays (any lengths).  noise: None = draw the dither on the device, False = no dither, or N
         arrays of N(0,1) draws (parity tests inject the reference's).  Returns (inputs fp32 [N, n_mels, T_max] on the
-        device, zero beyond each utterance's frames; input_lengths IntTensor [N] on the host) -- _collator's layout."""
-        audio, lens_d, noise_d, lens = self._stage(signals, noise)
+        device, zero beyond each utterance's frames; input_lengths IntTensor [N] on the host) -- _collator's layout.
+        rates (the signals' sample rates) / speeds (speed factors), either one given: the staged batch goes through
+        w2l_resample (data/resample.py) first; lengths, the dither and the returned input_lengths are those of the resampled
+        rows (noise arrays, if given, are at the resampled lengths).  Both None, or every row at 1/1: the plain path's launches."""
+        audio, lens_d, noise_d, lens = self._stage(signals, noise, rates, speeds)
         logmel, tmax = self._launch(audio, lens_d, noise_d, True)
         n = audio.shape[0]
         mean = torch.empty(n, self.n_mels, dtype=torch.float32, device=audio.device)
@@ -180,9 +224,12 @@ class SpectrogramExtractor(torch.nn.Module):
 class SpectrogramDataset(Dataset):
     """Manifest dataset (data_loader.py:90-147): a .csv (first column = index; columns audio_filepath, text[, offset,
     duration]) or JSON lines.  ``dataset[i]`` -> (spect [n_mels, T], target ids, path, transcript) as in the reference;
-    ``dataset.raw(i)`` -> the same with the raw samples instead of features (what BatchAudioDataLoader batches)."""
+    ``dataset.raw(i)`` -> the same with the raw samples instead of features (what BatchAudioDataLoader batches).
+    ``resample=True`` (not in the reference): files of any rate and channel count; every row is read with ``read_audio`` and
+    converted to ``audio_conf['sample_rate']`` on the GPU, instead of the assertion on the first row's rate.
+    ``speed_perturb``: a ``SpeedPerturb`` (or its factors), applied per utterance by BatchAudioDataLoader's batches only."""
 
-    def __init__(self, manifest_filepath, audio_conf, labels, mel_spec=None, use_cuda=False):
+    def __init__(self, manifest_filepath, audio_conf, labels, mel_spec=None, use_cuda=False, resample=False, speed_perturb=None):
         super().__init__()
         rows = self._read_manifest(manifest_filepath)
         self.rows = rows
@@ -193,7 +240,13 @@ class SpectrogramDataset(Dataset):
         self.use_cuda = use_cuda
         self.mel_spec = mel_spec
         self.labels_map = dict([(labels[i], i) for i in range(len(labels))])
-        self.validate_sample_rate()
+        self.resample = bool(resample)
+        if speed_perturb is not None and not isinstance(speed_perturb, SpeedPerturb):
+            speed_perturb = SpeedPerturb(speed_perturb)
+        self.speed_perturb = speed_perturb
+        self._rates = {}
+        if not self.resample:
+            self.validate_sample_rate()
         self.extractor = SpectrogramExtractor(audio_conf, mel_spec, use_cuda)
 
     @staticmethod
@@ -213,16 +266,33 @@ class SpectrogramDataset(Dataset):
         # filter(None, ...) drops unknown characters AND label 0, the blank (data_loader.py:127)
         return list(filter(None, [self.labels_map.get(c) for c in list(transcript)]))
 
+    def rate(self, index) -> int:
+        """sample rate of row ``index``: the model's unless ``resample``, else the file's (read once per row)"""
+        if not self.resample:
+            return self.sample_rate
+        sr = self._rates.get(index)
+        if sr is None:
+            sr = self._rates[index] = int(_sample_rate(self.rows[index]['audio_filepath']))
+        return sr
+
     def raw(self, index):
         r = self.rows[index]
-        audio = load_audio(r['audio_filepath'], r['duration'], r['offset'])
+        if self.resample:
+            audio, self._rates[index] = read_audio(r['audio_filepath'], r['duration'], r['offset'])
+        else:
+            audio = load_audio(r['audio_filepath'], r['duration'], r['offset'])
         return audio, self._target(r['text']), r['audio_filepath'], r['text']
 
     def __getitem__(self, index):
         audio, target, path, text = self.raw(index)
+        if self.resample:
+            return self.extractor.extract_batch([audio], rates=[self.rate(index)])[0][0], target, path, text
         return self.extractor.extract(audio), target, path, text
 
     def parse_audio(self, audio_path, duration, offset):
+        if self.resample:
+            audio, sr = read_audio(audio_path, duration, offset)
+            return self.extractor.extract_batch([audio], rates=[sr])[0][0]
         return self.extractor.extract(load_audio(audio_path, duration, offset))
 
     def validate_sample_rate(self):
@@ -269,7 +339,8 @@ class _RawItems(Dataset):
         return len(self.ds)
 
     def __getitem__(self, i):
-        return self.ds.raw(i)
+        item = self.ds.raw(i)
+        return item + (self.ds.rate(i),) if self.ds.resample else item
 
 
 class BatchAudioDataLoader(DataLoader):
@@ -288,7 +359,13 @@ class BatchAudioDataLoader(DataLoader):
             self.collate_fn = _collator
 
     def _device_collate(self, batch):
-        audio, targets, file_paths, texts = zip(*batch)
-        inputs, input_lengths = self._spect_ds.extractor.extract_batch(audio)
+        ds = self._spect_ds
+        rates = None
+        if ds.resample:
+            audio, targets, file_paths, texts, rates = zip(*batch)
+        else:
+            audio, targets, file_paths, texts = zip(*batch)
+        speeds = ds.speed_perturb.draw(len(audio)) if ds.speed_perturb is not None else None
+        inputs, input_lengths = ds.extractor.extract_batch(audio, rates=rates, speeds=speeds)
         tg, target_lengths = _pad_targets(targets)
         return inputs, input_lengths, tg, target_lengths, file_paths, texts

@@ -55,7 +55,7 @@ def root_config(model: str = 'wav2letter', **model_kw):
     """The whole tree of configuration/config.yaml: data / model / trainer"""
     m = {'wav2letter': wav2letter_model, 'jasper': jasper_model, 'jasper10x5': jasper10x5_model}[model](**model_kw)
     return to_cfg(dict(data=dict(train_manifest='???', val_manifest='???', batch_size=4, mel_spec=m['input_size'],
-                                 audio_conf=dict(m['audio_conf'])),
+                                 audio_conf=dict(m['audio_conf']), resample=False, speed_perturb=None),
                        model=m, trainer=dict(default_root_dir='.', max_epochs=5, max_steps=None, gpus=0)))
 
 

@@ -4,7 +4,7 @@ shipped:
     python -m wav2letter_pytorch_amd.test [--config-dir /path/to/configuration] model_path=run/epoch=4-step=900.ckpt \\
            data.test_manifest=test.csv [model=jasper] [model.mid_layers=20] [decoder=greedy|beam|beam_lm] [lm_path=lm.arpa] \\
            [beam.k=5] [beam.alpha=0.3] [beam.beta=5] [beam.prune=1e-3] [print_samples=K | print_all=true] \\
-           [output=hyps.jsonl] [word_times=true]
+           [output=hyps.jsonl] [word_times=true] [data.resample=true]
 
 ``train.py``'s override syntax and config tree.  The forward pass is ``model.infer`` (one fused launch per convolution);
 ``test_loss``, corpus-level ``test_cer`` / ``test_wer`` and ``test_len_ratio`` are printed and returned.  ``output=`` writes one
@@ -93,7 +93,8 @@ def main(argv=None):
     model.load_state_dict(ck['state_dict'] if 'state_dict' in ck else ck)
     from .engine import invalidate_packed
     invalidate_packed(model)
-    ds = SpectrogramDataset(cfg.data.test_manifest, cfg.data.audio_conf, cfg.model.labels, mel_spec=cfg.data.mel_spec)
+    ds = SpectrogramDataset(cfg.data.test_manifest, cfg.data.audio_conf, cfg.model.labels, mel_spec=cfg.data.mel_spec,
+                            resample=_truth(cfg.data.get('resample', False)))
     loader = BatchAudioDataLoader(ds, batch_size=cfg.data.batch_size)
     dec = build_decoder(cfg, bool(getattr(model, 'infer_log_probs', True)))
     metrics, records = evaluate(model, loader, decoder=dec, word_times=cfg.word_times)

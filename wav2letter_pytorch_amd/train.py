@@ -2,13 +2,16 @@
 Hydra / Lightning:
 
     python -m wav2letter_pytorch_amd.train [--config-dir /path/to/configuration] data.train_manifest=train.csv \\
-           data.val_manifest=val.csv [model=jasper] [model.mid_layers=20] [trainer.max_epochs=1] ...
+           data.val_manifest=val.csv [model=jasper] [model.mid_layers=20] [trainer.max_epochs=1] \\
+           [data.resample=true] [data.speed_perturb=0.9,1.0,1.1] ...
 
 Same override syntax and config keys as ``python train.py ...``; without ``--config-dir`` the built-in copy of the
 hyper-parameters (defaults.py) is used.  Manifests, labels, feature extraction and batching are data/data_loader.py's;
 the fit loop is trainer.Trainer.  ``trainer.gpus=N`` (the reference's Lightning flag, README.md:40) starts N ranks of this
 command line (launch.py), one per GPU; ``python -m torch.distributed.run --nproc-per-node N`` works too.  Every rank trains
-on its own shard of the manifest and gradients are averaged with RCCL (distributed.GradReducer)."""
+on its own shard of the manifest and gradients are averaged with RCCL (distributed.GradReducer).  ``data.resample=true``:
+manifests may mix sample rates and channel counts (converted on the GPU, data/resample.py); ``data.speed_perturb=`` draws one
+speed factor per training utterance."""
 from __future__ import annotations
 
 import os
@@ -73,14 +76,21 @@ def get_data_loaders(labels, cfg, rank: int = 0, world: int = 1):
     injects into the reference's loaders."""
     from torch.utils.data.distributed import DistributedSampler
     from .data.data_loader import BatchAudioDataLoader, SpectrogramDataset
+    from .data.resample import parse_speed_factors
     loaders = []
-    for manifest in (cfg.train_manifest, cfg.val_manifest):
-        ds = SpectrogramDataset(manifest, cfg.audio_conf, labels, mel_spec=cfg.mel_spec)
+    resample = _truth(cfg.get('resample', False))
+    factors = parse_speed_factors(cfg.get('speed_perturb'))         # the train loader only: validation is never perturbed
+    for manifest, perturb in ((cfg.train_manifest, factors), (cfg.val_manifest, None)):
+        ds = SpectrogramDataset(manifest, cfg.audio_conf, labels, mel_spec=cfg.mel_spec, resample=resample, speed_perturb=perturb)
         kw = {}
         if world > 1:
             kw['sampler'] = DistributedSampler(range(len(ds)), num_replicas=world, rank=rank, shuffle=False)
         loaders.append(BatchAudioDataLoader(ds, batch_size=cfg.batch_size, **kw))
     return loaders[0], loaders[1]
+
+
+def _truth(v) -> bool:
+    return v is True or (isinstance(v, str) and v.lower() in ('1', 'true', 'yes'))
 
 
 def build_config(argv):
