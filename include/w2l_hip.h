@@ -528,6 +528,34 @@ int w2l_ctc_align(const float* x, const int32_t* input_lengths, const int32_t* t
                   int log_probs, void* workspace, int64_t workspace_bytes, float* score, int32_t* status, int32_t* path,
                   int32_t* starts, int32_t* ends, void* stream);
 
+/* ---- Auto Segmentation criterion: the loss of the Wav2Letter paper, which the reference replaces by CTC (its README,
+ *      "Differences from article"; call site: base_asr_models.py:23,81,90 with model.criterion=asg, asg.ASGLoss) ---- */
+/* workspace bytes for w2l_asg_loss (alpha and beta tables of both recursions, encoded targets, gradient slabs); -1 if out of
+ * range: A > 64, Smax > 4095, T > 2^20 */
+int64_t w2l_asg_workspace_bytes(int N, int T, int A, int Smax);
+/* ASG loss and gradients.  x fp32 [N][T][A] (any real scores; batch-major), transitions fp32 [A][A] (g[i][j]: label j at frame t
+ * after label i at frame t-1), targets int32 [N][Smax] RAW transcripts (padded), lengths int32 [N].  The targets are
+ * repeat-encoded on the device: within a run of equal labels the 2nd, 4th, ... member becomes repeat_index.
+ * loss_n = Z_full - Z_tgt: Z_full = logsumexp over all A^T frame paths of sum_t x[t][pi_t] + sum_{t>=1} g[pi_{t-1}][pi_t], Z_tgt
+ * the same over the paths that read the encoded target with every label held for at least one frame.  An utterance with S = 0
+ * or S > input_lengths[n] is infeasible: loss and gradient 0.  Outputs: nll[N]; loss[1] = mean_n(nll_n / max(S_n, 1))
+ * (reduction 0) or sum_n nll_n (reduction 1); grad_x [N][T][A] and grad_trans [A][A] = d loss / d x, d loss / d transitions
+ * (both or neither; NULL: the loss only), zero for t >= input_lengths[n], bit-reproducible (fixed summation order, no atomics);
+ * status[N]: 0 ok, 1 infeasible, 2 a raw target equal to repeat_index or outside [0, A) (treated as infeasible; asg.ASGLoss
+ * raises ValueError).  Three launches, no host synchronisation. */
+int w2l_asg_loss(const float* x, const float* transitions, const int32_t* targets, const int32_t* input_lengths,
+                 const int32_t* target_lengths, int N, int T, int A, int Smax, int repeat_index, int reduction, float* nll,
+                 float* loss, float* grad_x, float* grad_trans, int32_t* status, void* workspace, int64_t workspace_bytes,
+                 void* stream);
+/* workspace bytes for w2l_asg_viterbi: one byte of back-pointer per (frame, label padded to 32 or 64); -1 if out of range */
+int64_t w2l_asg_viterbi_workspace_bytes(int N, int T, int A);
+/* The best frame path under the score of Z_full (max instead of logsumexp; asg.ASGDecoder.decode, in the place of
+ * decoder.py:136's argmax): ties go to the lowest predecessor and to the lowest final label; with zero transitions it is the
+ * per-frame argmax.  input_lengths int32 [N] (NULL: all T).  path int32 [N][T] (-1 from input_lengths[n] on), score[N] the
+ * path's score (0 for an utterance without frames).  One launch, one wave per utterance. */
+int w2l_asg_viterbi(const float* x, const float* transitions, const int32_t* input_lengths, int N, int T, int A,
+                    void* workspace, int64_t workspace_bytes, int32_t* path, float* score, void* stream);
+
 /* ---- greedy decode (decoder.py:136) + Levenshtein (decoder.py:49,60) ---- */
 /* argmax over the last dim, ties -> lowest index (torch.max): probs fp32 [rows][C] -> idx int32 [rows] */
 int w2l_argmax(const float* probs, int64_t rows, int C, int32_t* idx, void* stream);

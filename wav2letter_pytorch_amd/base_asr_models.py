@@ -10,7 +10,7 @@ from typing import Callable, Dict, Sequence
 import torch
 import torch.nn as nn
 
-from .config import instantiate
+from .config import criterion_name, instantiate
 from .ctc_loss import CTCLoss
 
 try:  # PyTorch-Lightning is optional: absent in the build image
@@ -89,8 +89,20 @@ class ConvCTCASR(_Base):
         self._cfg = cfg
         self.audio_conf = cfg.audio_conf
         self.labels = cfg.labels
-        self.ctc_decoder = instantiate(cfg.decoder)
-        self.criterion = CTCLoss(blank=0, reduction='mean', zero_infinity=True)      # base_asr_models.py:23
+        if criterion_name(cfg) == 'asg':
+            # the criterion of the paper (asg.py): label 0 is "repeat the previous letter", the decoder is Viterbi over the
+            # criterion's learned transitions; cfg.decoder (a CTC decoder) is not instantiated
+            from .asg import ASGDecoder, ASGLoss
+            if not getattr(type(self), 'infer_log_probs', True):
+                # (Jasper: infer() returns probabilities while training scores are log-probabilities; transitions learned on
+                # one scale would silently decode the other badly)
+                raise NotImplementedError(f'model.criterion=asg with {type(self).__name__}: its infer() returns probabilities, not '
+                                          'the log-probabilities the transitions are trained on; asg is implemented for Wav2Letter')
+            self.criterion = ASGLoss(len(self.labels))
+            self.ctc_decoder = ASGDecoder(self.labels, transitions=self.criterion)
+        else:
+            self.ctc_decoder = instantiate(cfg.decoder)
+            self.criterion = CTCLoss(blank=0, reduction='mean', zero_infinity=True)      # base_asr_models.py:23
         self.print_decoded_prob = cfg.get('print_decoded_prob', 0)
         self.example_input_array = self.create_example_input_array()
         # load_state_dict(assign=True) swaps Parameter OBJECTS under the engine's specs: rebuild after any load
@@ -193,7 +205,21 @@ class ConvCTCASR(_Base):
         from .decoder import argmax_indices
         if len(out.shape) == 2:
             out = out.unsqueeze(0)
+        if getattr(self.criterion, 'is_asg', False):
+            return self._score_strings(self.ctc_decoder.decode(out.detach(), output_lengths), texts, prefix)
         return self._score_indices(argmax_indices(out).cpu(), output_lengths, texts, prefix)
+
+    def _score_strings(self, hyps, texts, prefix) -> Dict[str, float]:
+        """the three logged ratios from decoded strings (criterion asg: the Viterbi decoder's; the CTC collapse rule of
+        _score_indices does not apply)"""
+        dec = self.ctc_decoder
+        char_err, char_ref = map(sum, zip(*(dec.cer_ratio(ref, hyp) for ref, hyp in zip(texts, hyps))))
+        word_err, word_ref = map(sum, zip(*(dec.wer_ratio(ref, hyp) for ref, hyp in zip(texts, hyps))))
+        if random.random() < self.print_decoded_prob:
+            print(f'reference: {texts[0]}')
+            print(f'decoded  : {hyps[0]}')
+        return {f'{prefix}_cer': char_err / char_ref, f'{prefix}_wer': word_err / word_ref,
+                f'{prefix}_len_ratio': sum(len(h) for h in hyps) / sum(len(t) for t in texts)}
 
     def enqueue_string_metrics(self, out, output_lengths, texts, prefix, loss=None, extra=None):
         """the device half of add_string_metrics, without a host synchronisation: argmax kernel + asynchronous copies into
@@ -350,8 +376,15 @@ class ConvCTCASR(_Base):
             tg_d, ol_d, tl_d = self._device_ints(x.device, targets, out_lens, target_lens)
         else:
             tg_d, ol_d, tl_d = targets, out_lens, target_lens
+        asg = getattr(self.criterion, 'is_asg', False)
+        if asg and getattr(getattr(self, 'grad_reducer', None), 'active', False):
+            # the reducer averages the step engine's gradients only; criterion.transitions would drift apart between the ranks
+            raise NotImplementedError('model.criterion=asg is not supported with data parallelism (more than one rank): the '
+                                      'gradient reducer does not cover criterion.transitions; train on one GPU or use ctc')
         loss = self.criterion(out.transpose(0, 1), tg_d, ol_d, tl_d)
-        if self.async_metrics and x.is_cuda:
+        # (criterion asg: the asynchronous scorer implements the CTC collapse rule, so the synchronous branch -- the Viterbi
+        # decoder -- scores the batch; async_metrics has no effect)
+        if self.async_metrics and x.is_cuda and not asg:
             self.enqueue_string_metrics(out, out_lens, texts, prefix, loss=loss, extra=extra)
             if prefix != 'train':                  # validation: nothing to overlap the scoring with, and the epoch mean
                 self.resolve_metrics(wait_all=True)     # is formed batch by batch

@@ -28,6 +28,19 @@ def to_cfg(o: Any):
     return o
 
 
+CRITERIA = ('ctc', 'asg')
+
+
+def criterion_name(model_cfg) -> str:
+    """``model.criterion`` of a model config: ``ctc`` (the default, also when the key is absent) or ``asg`` (asg.ASGLoss, the
+    criterion of the Wav2Letter paper); anything else is a ValueError naming the two"""
+    name = model_cfg.get('criterion', None) if hasattr(model_cfg, 'get') else None
+    name = 'ctc' if name is None else name
+    if name not in CRITERIA:
+        raise ValueError(f'model.criterion={name!r} is not a criterion: the valid values are ctc and asg')
+    return name
+
+
 _ALIASES = {
     # reference module paths -> this package (config.yaml:14-16 names decoder.GreedyDecoder)
     'decoder': 'wav2letter_pytorch_amd.decoder',
@@ -137,6 +150,8 @@ def load_config(config_dir: str, overrides=()):
         cur[parts[-1]] = _yaml_load(v)
     merged.pop('hydra', None)
     _interpolate(merged, merged)
+    if isinstance(merged.get('model'), dict):
+        criterion_name(merged['model'])          # validated only: an absent key stays absent (and means ctc)
     return to_cfg(merged)
 
 

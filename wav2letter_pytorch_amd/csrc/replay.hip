@@ -215,7 +215,7 @@ const Entry kEntries[] = {
     W2L_E(w2l_bn_act_bwd_reduce), W2L_E(w2l_bn_act_bwd_reduce_slots), W2L_E(w2l_bn_bwd_finalize), W2L_E(w2l_bn_act_bwd_apply),
     W2L_E(w2l_bn_act_bwd_apply_amax), W2L_E(w2l_bn_act_bwd_apply_fin), W2L_E(w2l_bn_act_bwd_apply_slots),
     W2L_E(w2l_quantize_e4m3), W2L_E(w2l_quantize_e4m3_dyn),
-    W2L_E(w2l_log_softmax_fwd), W2L_E(w2l_log_softmax_bwd), W2L_E(w2l_ctc_loss), W2L_E(w2l_argmax),
+    W2L_E(w2l_log_softmax_fwd), W2L_E(w2l_log_softmax_bwd), W2L_E(w2l_ctc_loss), W2L_E(w2l_asg_loss), W2L_E(w2l_argmax),
     W2L_E(w2l_rccl_all_reduce),
 };
 constexpr int kNumEntries = (int)(sizeof(kEntries) / sizeof(kEntries[0]));

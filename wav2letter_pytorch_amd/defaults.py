@@ -23,6 +23,7 @@ SCHEDULER = dict(_target_='torch.optim.lr_scheduler.ExponentialLR', gamma=0.999)
 def _common(labels):
     if isinstance(labels, str):
         labels = list(label_sets.labels_map[labels])
+    # (optional key ``criterion``: ctc, the reference's and the default when absent, or asg, the paper's -- config.criterion_name)
     return dict(input_size=64, labels=labels, audio_conf=dict(AUDIO_CONF),
                 decoder=dict(_target_='decoder.GreedyDecoder', labels=labels), optimizer=dict(OPTIMIZER),
                 scheduler=dict(SCHEDULER))

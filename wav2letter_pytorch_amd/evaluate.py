@@ -34,6 +34,14 @@ def frame_seconds(model) -> float:
 def decode_batch(model, decoder, out, out_lens, word_times: bool = False):
     """posteriors of one batch -> (hypotheses, word timings or Nones).  Word timings: forced alignment of each decoded string
     to the utterance's own frames (``Decoder.align``), then ``get_time_per_word(end_offsets=)``: (word, start s, end s)."""
+    if getattr(getattr(model, 'criterion', None), 'is_asg', False):
+        # a model trained with ASG has no blank: the CTC decoders and the CTC forced alignment do not apply to its output
+        from .asg import ASGDecoder
+        if not isinstance(decoder, ASGDecoder):
+            raise NotImplementedError(f'{type(decoder).__name__} on a model with criterion asg: a transition-aware beam search '
+                                      'is not implemented; use the model\'s own decoder (asg.ASGDecoder, Viterbi)')
+        if word_times:
+            raise NotImplementedError('word_times under criterion asg: forced alignment under ASG is not implemented')
     hyps = decoder.decode(out, out_lens)
     hyps = [h[0] if isinstance(h, (list, tuple)) else h for h in hyps]
     if not word_times:

@@ -51,6 +51,13 @@ def build_config(argv):
     cfg['print_samples'] = int(cfg.get('print_samples') or 0)
     cfg['print_all'] = _truth(cfg.get('print_all', False))
     cfg['word_times'] = _truth(cfg.get('word_times', False))
+    if cfg.model.get('criterion', 'ctc') == 'asg':
+        # the beam searches and the forced alignment implement CTC's blank / collapse rules and know no transitions
+        if cfg.decoder != 'greedy':
+            raise NotImplementedError(f'decoder={cfg.decoder} under model.criterion=asg: a transition-aware beam search is not '
+                                      'implemented; use decoder=greedy (Viterbi decoding with the learned transitions)')
+        if cfg.word_times:
+            raise NotImplementedError('word_times=true under model.criterion=asg: forced alignment under ASG is not implemented')
     cfg.setdefault('output', None)
     return cfg
 
@@ -96,7 +103,10 @@ def main(argv=None):
     ds = SpectrogramDataset(cfg.data.test_manifest, cfg.data.audio_conf, cfg.model.labels, mel_spec=cfg.data.mel_spec,
                             resample=_truth(cfg.data.get('resample', False)))
     loader = BatchAudioDataLoader(ds, batch_size=cfg.data.batch_size)
-    dec = build_decoder(cfg, bool(getattr(model, 'infer_log_probs', True)))
+    if cfg.model.get('criterion', 'ctc') == 'asg':
+        dec = model.ctc_decoder              # decoder=greedy under asg: the model's Viterbi decoder, bound to its transitions
+    else:
+        dec = build_decoder(cfg, bool(getattr(model, 'infer_log_probs', True)))
     metrics, records = evaluate(model, loader, decoder=dec, word_times=cfg.word_times)
     shown = len(records) if cfg.print_all else min(cfg.print_samples, len(records))
     for r in records[:shown]:

@@ -17,7 +17,7 @@ from __future__ import annotations
 import os
 import sys
 
-from .config import _yaml_load, load_config, to_cfg
+from .config import _yaml_load, criterion_name, load_config, to_cfg
 from .launch import spawn_ranks, under_launcher
 
 # Nothing above maps libw2l_hip.so (or imports torch): with trainer.gpus=N this process only starts the ranks, and a launch
@@ -123,6 +123,7 @@ def build_config(argv):
         for p in parts[:-1]:
             cur = cur.setdefault(p, to_cfg({}))
         cur[parts[-1]] = to_cfg(_yaml_load(v))
+    criterion_name(cfg.model)      # model.criterion: ctc | asg (absent: ctc), anything else is an error naming the two
     return cfg
 
 
@@ -145,6 +146,11 @@ def main(argv=None):
         if cfg.data.get(key) in (None, '???'):
             raise SystemExit(f'data.{key} is required (e.g. data.{key}=/path/to/manifest.csv)')
     n_gpus = _requested_gpus(cfg)
+    if criterion_name(cfg.model) == 'asg' and (n_gpus > 1 or int(os.environ.get('WORLD_SIZE', '1')) > 1):
+        # distributed.GradReducer averages the gradients the step engine hands it, i.e. the engine's own weights;
+        # criterion.transitions is not among them
+        raise NotImplementedError('model.criterion=asg is not supported with data parallelism (trainer.gpus > 1 or a launcher '
+                                  'with WORLD_SIZE > 1): the gradient reducer does not cover criterion.transitions')
     if n_gpus > 1 and not under_launcher():
         # Trainer(gpus=N) of the reference = N DDP processes.  This parent has not touched the GPU: it only starts the ranks.
         rc = spawn_ranks(n_gpus, [sys.executable, '-m', 'wav2letter_pytorch_amd.train'] + argv)
