@@ -1022,17 +1022,27 @@ def test_bn_act_fwd_bwd(L, N, T, C, pl, pr, mode, act, f32):
     assert relerr(dyu[:, :T].transpose(1, 2), yr.grad) < 1e-4, relerr(dyu[:, :T].transpose(1, 2), yr.grad)
 
 
-@pytest.mark.parametrize('N,T,C,pl,pr,mode,act,p,lens,h', [
+_CHAIN_AMAX = [
     (3, 150, 128, 12, 12, 1, 1, 0.0, False, 24), (2, 333, 192, 4, 5, 1, 1, 0.3, False, 51), (2, 90, 64, 3, 3, 0, 2, 0.0, True, 38),
     (4, 500, 896, 28, 28, 1, 1, 0.4, False, 56), (1, 40, 64, 7, 7, 1, 0, 0.2, True, 24),
     # 12 000 rows and 8 M elements on: the LOOPED kernels (a wave walks four row groups, the next one's loads in flight) -- utterance
     # boundaries inside a wave's rows (T = 500 and 997 are no multiples of 8 x 4), reflect folds, length masks, ReLU / clamp / none
-    (26, 500, 640, 20, 20, 1, 1, 0.2, False, 40), (13, 997, 640, 6, 6, 0, 2, 0.0, True, 12), (25, 500, 704, 28, 28, 1, 0, 0.3, True, 56)])
-def test_bn_bwd_two_launch_chain_equals_three(L, N, T, C, pl, pr, mode, act, p, lens, h):
+    (26, 500, 640, 20, 20, 1, 1, 0.2, False, 40), (13, 997, 640, 6, 6, 0, 2, 0.0, True, 12), (25, 500, 704, 28, 28, 1, 0, 0.3, True, 56)]
+# without amax the one-shot dy pass takes the row groups per wave that every bf16 training step runs (with amax: always 4):
+# C <= 384: 2 (reflect fold, T no multiple of 16); C > 384: 1 -- 7 slabs, 150 rows in 5 chunks with an utterance boundary inside a
+# wave's rows, asymmetric reflect pads, dropout bits, 39 halo rows dealt over 5 chunks; and 1 with zero pads, ReLU, a length mask
+_CHAIN_NO_AMAX = [(3, 150, 128, 12, 12, 1, 1, 0.0, False, 24), (2, 75, 448, 4, 5, 1, 1, 0.3, False, 13),
+                  (2, 90, 448, 3, 3, 0, 2, 0.0, True, 38)]
+
+
+@pytest.mark.parametrize('N,T,C,pl,pr,mode,act,p,lens,h,with_amax',
+                         [pytest.param(*c, True, id='-'.join(map(str, c))) for c in _CHAIN_AMAX] +
+                         [pytest.param(*c, False, id='-'.join(map(str, c)) + '-noamax') for c in _CHAIN_NO_AMAX])
+def test_bn_bwd_two_launch_chain_equals_three(L, N, T, C, pl, pr, mode, act, p, lens, h, with_amax):
     """the backward chain's fast path (w2l_bn_act_bwd_reduce_slots + w2l_bn_act_bwd_apply_slots: sums added onto 8 slot rows,
     the finalize folded into the dy pass) against reduce + finalize + apply: the same sums (up to the order of the fp32
-    additions), the same dy incl. the zero halo rows of its shared-halo buffer, the same amax; reflect folds, dropout masks
-    and length masks included"""
+    additions), the same dy incl. the zero halo rows of its shared-halo buffer, the same amax (without one: both chains get a
+    null pointer and nothing is written); reflect folds, dropout masks and length masks included"""
     g = torch.Generator().manual_seed(N * 100 + T + C)
     st = L.stream_ptr()
     R = pl + T + pr
@@ -1054,15 +1064,15 @@ def test_bn_bwd_two_launch_chain_equals_three(L, N, T, C, pl, pr, mode, act, p, 
     L.check(L.lib.w2l_bn_act_bwd_reduce(C_.byref(d), C_.byref(gs), None, L.ptr(part), st))
     L.check(L.lib.w2l_bn_bwd_finalize(L.ptr(part), nb, C, 2, L.ptr(sums_a), st))
     L.check(L.lib.w2l_bn_act_bwd_apply_amax(C_.byref(d), C_.byref(gs), None, L.ptr(sums_a), L.ptr(dy_a), None, h, None, None, 0,
-                                            L.ptr(amax_a), st))
+                                            L.ptr(amax_a) if with_amax else None, st))
     # two launches
     slots = torch.zeros(8, 2, C, device='cuda')
     sums_b = torch.zeros(4, C, device='cuda')
     dy_b = torch.full((h + N * (T + h), C), float('nan'), dtype=torch.bfloat16, device='cuda')
     amax_b = torch.zeros(2, 64, device='cuda')
     L.check(L.lib.w2l_bn_act_bwd_reduce_slots(C_.byref(d), C_.byref(gs), L.ptr(slots), 8, st), 'reduce_slots')
-    L.check(L.lib.w2l_bn_act_bwd_apply_slots(C_.byref(d), C_.byref(gs), L.ptr(slots), 8, L.ptr(sums_b), L.ptr(dy_b), h, L.ptr(amax_b),
-                                             st), 'apply_slots')
+    L.check(L.lib.w2l_bn_act_bwd_apply_slots(C_.byref(d), C_.byref(gs), L.ptr(slots), 8, L.ptr(sums_b), L.ptr(dy_b), h,
+                                             L.ptr(amax_b) if with_amax else None, st), 'apply_slots')
     torch.cuda.synchronize()
     assert relerr(slots.sum(0), sums_a[:2]) < 2e-5 and relerr(sums_b[:2], sums_a[:2]) < 2e-5
     a, b = dy_a.float(), dy_b.float()
@@ -1072,6 +1082,7 @@ def test_bn_bwd_two_launch_chain_equals_three(L, N, T, C, pl, pr, mode, act, p, 
     zr[h:].view(N, T + h)[:, :T] = False
     assert not dy_b[zr.cuda()].any()
     assert abs(float(amax_a[0].max()) - float(amax_b[0].max())) <= 1.2e-2 * float(amax_a[0].max())
+    assert with_amax or not (amax_a.any() or amax_b.any())
     # a unit outside the fast path says so
     d2 = _bnact_desc(L, N, T, C, y.float(), scale, shift, mean, invstd, act)
     assert L.lib.w2l_bn_bwd_fast_ok(C_.byref(d2), C_.byref(gs), None) == 0

@@ -9,6 +9,7 @@
 // reflect-padding of the next conv's input (wav2letter.py:28-34,41) incl. its backward fold.
 #include "common.h"
 #include "../../include/w2l_hip.h"
+#include <type_traits>
 
 namespace {
 
@@ -478,6 +479,230 @@ __device__ __forceinline__ void bwd_row(const w2l_bnact_t& d, const Chan& c1, co
     }
 }
 
+// ---- slab helpers: the stages that the slab-form backward kernels (one-shot, looped, apply_fin) are put together from.
+// Where a thread of such a block stands: the block owns a 64-channel slab of one row chunk (neighbours: adjacent slabs of the same
+// rows), a wave is 8 row lanes x 8 channel-group lanes -- one 128-byte line per row
+struct SlabPos {
+    int tid, lane, wave;
+    int G, nslabs;                                     // 8-channel groups / 64-channel slabs of a row
+    int slab, chunk;
+    int cgl, rr;                                       // channel-group lane, row lane (0..7 each)
+    int cg, c;                                         // this lane's channel group, its first channel
+};
+__device__ __forceinline__ SlabPos slab_pos(int C) {
+    SlabPos p;
+    p.tid = threadIdx.x; p.lane = p.tid & 63; p.wave = p.tid >> 6;
+    p.G = C >> 3; p.nslabs = C / BWD_SLAB;
+    p.slab = blockIdx.x % p.nslabs; p.chunk = blockIdx.x / p.nslabs;
+    p.cgl = p.lane & 7; p.rr = p.lane >> 3;
+    p.cg = p.slab * (BWD_SLAB / 8) + p.cgl; p.c = p.cg * 8;
+    return p;
+}
+
+struct FastRow {
+    u16x8 y, g, ga, gb;                                // conv output, gradient of the frame, of its reflected images (left / right halo)
+    unsigned bits;                                     // dropout keep bits
+    bool live, fa, fb, masked;
+    int n, t;
+};
+
+// flags and loads of frame (n, t) from its three addresses: py = y[row][c], pg = the gradient source's row of the frame
+// (dxp[n][pad_l + t][c]), pm = the keep bits of the row's channel group (read under dropout only)
+__device__ __forceinline__ void fast_row_fill(const w2l_bnact_t& d, const w2l_gradsrc_t& s, const bf16_raw* py, const bf16_raw* pg,
+                                              const uint8_t* pm, int n, int t, bool live, FastRow& o) {
+    o.live = live;
+    o.fa = o.fb = o.masked = false;
+    o.bits = 0xFFu;
+    o.n = n; o.t = t;
+    if (!live) return;
+    const int T = d.T;
+    o.y = *reinterpret_cast<const u16x8*>(py);
+    if (d.drop_p > 0.f) o.bits = *pm;
+    o.masked = d.lens && t >= d.lens[n];
+    o.g = *reinterpret_cast<const u16x8*>(pg);
+    if (s.pad_mode == 1) {                             // the reflected halo rows' gradient folds back onto its source frame
+        o.fa = t >= 1 && t <= s.pad_l;
+        o.fb = t <= T - 2 && t >= T - 1 - s.pad_r;
+        if (o.fa) o.ga = *reinterpret_cast<const u16x8*>(pg - 2 * (int64_t)t * d.C);                    // padded row pad_l - t
+        if (o.fb) o.gb = *reinterpret_cast<const u16x8*>(pg + 2 * (int64_t)(T - 1 - t) * d.C);          // pad_l + 2 (T-1) - t
+    }
+}
+__device__ __forceinline__ void fast_row_load(const w2l_bnact_t& d, const w2l_gradsrc_t& s, int64_t row, int64_t rows,
+                                              const SlabPos& p, FastRow& o) {
+    if (row >= rows) {                                 // (the division below stays with the loads, behind this test)
+        fast_row_fill(d, s, nullptr, nullptr, nullptr, 0, 0, false, o);
+        return;
+    }
+    const int n = (int)(row / d.T), t = (int)(row - (int64_t)n * d.T);
+    fast_row_fill(d, s, reinterpret_cast<const bf16_raw*>(d.y) + row * d.C + p.c,
+                  reinterpret_cast<const bf16_raw*>(s.dxp) + ((int64_t)n * s.rows + t + s.pad_l) * d.C + p.c,
+                  d.mask ? d.mask + row * p.G + p.cg : nullptr, n, t, true, o);
+}
+
+// gated gradient and normalised input of one row's 8 channels.  The activation and whether there is dropout are template
+// parameters: these kernels are bound by their instruction count, not by HBM (a plain copy of the same bytes runs at twice
+// their rate: tools/probe/hbm_ceiling.py), and a run-time switch on d.act costs two scalar branches per ELEMENT
+template <int ACT, bool DROP>
+__device__ __forceinline__ void fast_row_eval(const FastRow& r, const Chan& ch, float inv_keep, float g[8], float xh[8]) {
+    float gv[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) gv[j] = bf16_bits_to_f32(r.g[j]);
+    if (r.fa) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) gv[j] += bf16_bits_to_f32(r.ga[j]);
+    }
+    if (r.fb) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) gv[j] += bf16_bits_to_f32(r.gb[j]);
+    }
+    const float gk = DROP ? inv_keep : 1.f;
+    const bool row_ok = !r.masked;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const float y = bf16_bits_to_f32(r.y[j]);
+        float z = y * ch.sc[j] + ch.sh[j];
+        bool pass = row_ok;
+        if (DROP) {
+            pass = pass && ((r.bits >> j) & 1u);
+            z *= inv_keep;                             // (a dropped element's z is never looked at: pass is false)
+        }
+        if (ACT == 1) pass = pass && z >= 0.f && z <= 20.f;      // torch.clamp passes 1 on the CLOSED interval
+        else if (ACT == 2) pass = pass && z > 0.f;
+        g[j] = pass ? gv[j] * gk : 0.f;
+        xh[j] = (y - ch.m[j]) * ch.is[j];
+    }
+}
+
+// row cursor of a lane: the row's index, (utterance, frame) and the three addresses it reads, advanced by 8 rows at a time with
+// additions only (no division, no 64-bit multiply per row; T >= 8: at most one utterance boundary per step -- the launcher checks)
+struct RowCur {
+    int64_t row;
+    int n, t;
+    const bf16_raw* py;                                // y[row][c]
+    const bf16_raw* pg;                                // gradient source row of frame t: dxp[n][pad_l + t][c]
+    const uint8_t* pm;                                 // dropout keep bits of the row's channel group
+};
+__device__ __forceinline__ void rowcur_init(RowCur& q, const w2l_bnact_t& d, const w2l_gradsrc_t& s, int64_t row, const SlabPos& p) {
+    q.row = row;
+    q.n = (int)(row / d.T);
+    q.t = (int)(row - (int64_t)q.n * d.T);
+    q.py = reinterpret_cast<const bf16_raw*>(d.y) + row * d.C + p.c;
+    q.pg = reinterpret_cast<const bf16_raw*>(s.dxp) + ((int64_t)q.n * s.rows + q.t + s.pad_l) * d.C + p.c;
+    q.pm = d.mask ? d.mask + row * p.G + p.cg : nullptr;
+}
+__device__ __forceinline__ void rowcur_step(RowCur& q, const w2l_bnact_t& d, const w2l_gradsrc_t& s, int G) {
+    q.row += 8;
+    q.t += 8;
+    q.py += 8 * (int64_t)d.C;
+    q.pg += 8 * (int64_t)d.C;
+    if (q.pm) q.pm += 8 * G;
+    if (q.t >= d.T) {
+        q.t -= d.T;
+        ++q.n;
+        q.pg += (int64_t)(s.rows - d.T) * d.C;
+    }
+}
+__device__ __forceinline__ void fast_row_load_cur(const w2l_bnact_t& d, const w2l_gradsrc_t& s, const RowCur& q, bool live, FastRow& o) {
+    fast_row_fill(d, s, q.py, q.pg, q.pm, q.n, q.t, live, o);
+}
+
+// closing stage of the reduction kernels: the eight row lanes of a wave combine with lane shuffles, the four waves of the block in
+// LDS, and the block ADDS its 2 x 64 sums onto row (chunk mod slots) of the zero-filled [slots][2][C] buffer
+__device__ __forceinline__ void slab_sums_to_slots(const SlabPos& p, float (&s0)[8], float (&s1)[8], float (&red)[4][2][BWD_SLAB],
+                                                   float* partial, int slots, int C) {
+#pragma unroll
+    for (int m = 8; m < 64; m <<= 1)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            s0[j] += __shfl_xor(s0[j], m, 64);
+            s1[j] += __shfl_xor(s1[j], m, 64);
+        }
+    if (p.rr == 0) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) { red[p.wave][0][p.cgl * 8 + j] = s0[j]; red[p.wave][1][p.cgl * 8 + j] = s1[j]; }
+    }
+    __syncthreads();
+    if (p.tid < 2 * BWD_SLAB) {
+        const int k = p.tid >> 6, cc = p.tid & 63;
+        const float t4 = (red[0][k][cc] + red[1][k][cc]) + (red[2][k][cc] + red[3][k][cc]);
+        atomicAdd(partial + ((int64_t)(p.chunk % slots) * 2 + k) * C + p.slab * BWD_SLAB + cc, t4);
+    }
+}
+
+// opening stage of the dy kernels of the two-launch chain: column sums of partial[nb][2][C] over this slab's channels into
+// ssum[2][64], eight loads in flight, in a fixed order -- every block of a slab arrives at the same bits; the blocks of row
+// chunk 0 publish them (d beta, d gamma).  The caller's barrier follows.
+__device__ __forceinline__ void slot_column_sums(const SlabPos& p, const float* partial, int nb, int C, float (&ssum)[2][BWD_SLAB],
+                                                 float* sums_out) {
+    if (p.tid < 2 * BWD_SLAB) {
+        const int k = p.tid >> 6, cc = p.tid & 63;
+        float a = 0.f;
+        int j = 0;
+        for (; j + 8 <= nb; j += 8) {
+            float v[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) v[u] = partial[((int64_t)(j + u) * 2 + k) * C + p.slab * BWD_SLAB + cc];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) a += v[u];
+        }
+        for (; j < nb; ++j) a += partial[((int64_t)j * 2 + k) * C + p.slab * BWD_SLAB + cc];
+        ssum[k][cc] = a;
+        if (p.chunk == 0) sums_out[(int64_t)k * C + p.slab * BWD_SLAB + cc] = a;
+    }
+}
+
+// (The dy formula, sc * (g - sum(g) / M - xhat * sum(g xhat) / M), is NOT among these helpers: each dy kernel states it in its
+// row loop.  Which of its products fuse with the subtractions depends on the block they land in, and from a helper the
+// compiler lifts sum(g) / M out of the rows' blocks: g - sum(g) / M is then no fused multiply-add -- a low-order bit of dy in the
+// one-shot and the folded kernel.  The looped kernel scales its sums by 1 / M once per wave: its own rounding again.)
+__device__ __forceinline__ float absmax8(float mx, const float (&o)[8]) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) mx = fmaxf(mx, fabsf(o[j]));
+    return mx;
+}
+
+// halo rows of the shared-halo layout of one dy buffer: (N+1) gaps of h > 0 rows each, zero-filled by the same blocks -- a share
+// per row chunk, of which a block stores its slab's 128 bytes per row (lo may be null)
+__device__ __forceinline__ void zero_halo_share(const SlabPos& p, bf16_raw* hi, bf16_raw* lo, int h, int N, int T, int C) {
+    const int nchunks = gridDim.x / p.nslabs;
+    float z[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) z[j] = 0.f;
+    const int total = h * (N + 1);
+    const int per = (total + nchunks - 1) / nchunks;
+    int e = (p.chunk + 1) * per;
+    if (e > total) e = total;
+    for (int hr = p.chunk * per + p.wave * 8 + p.rr; hr < e; hr += 32) {
+        const int gap = hr / h, r = hr - gap * h;
+        store8_split(hi, lo, ((int64_t)gap * (T + h) + r) * C + p.c, z);
+    }
+}
+
+// fp8 mode: max |dy| of the block -> wave -> LDS -> ONE look-then-atomic on the block's amax slot
+__device__ __forceinline__ void block_amax_publish(const SlabPos& p, float mx, float (&smax)[4], float* amax) {
+    if (!amax) return;                                 // (amax is a kernel argument: uniform)
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) mx = fmaxf(mx, __shfl_xor(mx, m, 64));
+    if (p.lane == 0) smax[p.wave] = mx;
+    __syncthreads();
+    if (p.tid == 0) amax_publish(amax, blockIdx.x & (AMAX_SLOTS - 1), fmaxf(fmaxf(smax[0], smax[1]), fmaxf(smax[2], smax[3])));
+}
+// the same per WAVE, without LDS (the general and the apply_fin dy kernels): max |dy| and, with a second dy buffer, max |dy2|.
+// Non-negative floats order like their bit patterns: one integer atomic max per wave
+__device__ __forceinline__ void wave_amax_publish(int lane, float mx1, float mx2, bool two, float* amax) {
+    if (!amax) return;
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) {
+        mx1 = fmaxf(mx1, __shfl_xor(mx1, m, 64));
+        mx2 = fmaxf(mx2, __shfl_xor(mx2, m, 64));
+    }
+    if (lane == 0) {
+        const int slot = blockIdx.x & (AMAX_SLOTS - 1);
+        amax_publish(amax, slot, mx1);
+        if (two) amax_publish(amax, AMAX_SLOTS + slot, mx2);
+    }
+}
+
 // ---- backward reduction: partial[chunk][ncomp][C] = sum over the chunk's rows of g, g*xh1 [, g, g*xh2 with a residual
 // branch].  One WAVE owns a 64-channel slab (8 lanes x 16 bytes = one 128-byte line per row) of one row chunk and walks it
 // 8 rows at a time; the eight row-lanes are combined with lane shuffles and lanes 0..7 store the slab's sums.  No LDS and
@@ -631,10 +856,7 @@ __global__ __launch_bounds__(256) void bn_act_bwd_apply_kernel(w2l_bnact_t d, w2
             for (int j = 0; j < 8; ++j) o1[j] = o.g[j] * c1.sc[j];
         }
         store8_split(dy_hi, dy_lo, ((int64_t)h1 + (int64_t)n * (T + h1) + t) * d.C + c, o1);
-        if (amax) {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) mx1 = fmaxf(mx1, fabsf(o1[j]));
-        }
+        if (amax) mx1 = absmax8(mx1, o1);
         if (HAS2 && dy2_hi) {
             if (d.mean2) {
                 float sg[8], sgx[8];
@@ -647,24 +869,10 @@ __global__ __launch_bounds__(256) void bn_act_bwd_apply_kernel(w2l_bnact_t d, w2
                 for (int j = 0; j < 8; ++j) o2[j] = o.g[j] * c2.sc[j];
             }
             store8_split(dy2_hi, dy2_lo, ((int64_t)h2 + (int64_t)n * (T + h2) + t) * d.C + c, o2);
-            if (amax) {
-#pragma unroll
-                for (int j = 0; j < 8; ++j) mx2 = fmaxf(mx2, fabsf(o2[j]));
-            }
+            if (amax) mx2 = absmax8(mx2, o2);
         }
     }
-    if (amax) {          // non-negative floats order like their bit patterns: one integer atomic max per wave
-#pragma unroll
-        for (int m = 1; m < 64; m <<= 1) {
-            mx1 = fmaxf(mx1, __shfl_xor(mx1, m, 64));
-            mx2 = fmaxf(mx2, __shfl_xor(mx2, m, 64));
-        }
-        if ((threadIdx.x & 63) == 0) {
-            const int slot = blockIdx.x & (AMAX_SLOTS - 1);
-            amax_publish(amax, slot, mx1);
-            if (HAS2 && dy2_hi) amax_publish(amax, AMAX_SLOTS + slot, mx2);
-        }
-    }
+    wave_amax_publish(threadIdx.x & 63, mx1, mx2, HAS2 && dy2_hi, amax);
 }
 
 // ---- backward apply with the finalize folded in ("slab" form).  A block owns a 64-channel slab (one 128-byte line per
@@ -689,10 +897,8 @@ __global__ __launch_bounds__(256) void bn_act_bwd_apply_fin_kernel(w2l_bnact_t d
     constexpr int ncomp = HAS2 ? 4 : 2;
     __shared__ float red[4][ncomp][BWD_SLAB];
     __shared__ float ssum[ncomp][BWD_SLAB];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int G = d.C >> 3;
-    const int nslabs = d.C / BWD_SLAB;
-    const int slab = blockIdx.x % nslabs, chunk = blockIdx.x / nslabs;     // neighbours: adjacent slabs of the same rows
+    const SlabPos p = slab_pos(d.C);
+    const int tid = p.tid, wave = p.wave, slab = p.slab, chunk = p.chunk;
     const int T = d.T, N = d.N;
     // ---- prologue: column sums of partial[nb][ncomp][C] over this slab's channels (thread = channel x quarter of the rows)
     {
@@ -726,8 +932,7 @@ __global__ __launch_bounds__(256) void bn_act_bwd_apply_fin_kernel(w2l_bnact_t d
         }
         __syncthreads();
     }
-    const int cgl = lane & 7, rr = lane >> 3;
-    const int cg = slab * (BWD_SLAB / 8) + cgl, c = cg * 8;
+    const int cgl = p.cgl, rr = p.rr, cg = p.cg, c = p.c, G = p.G;
     Chan c1, c2;
     load_chan(c1, d.scale, d.shift, d.mean, d.invstd, c);
     if (HAS2) load_chan(c2, d.scale2, d.shift2, d.mean2, d.invstd2, c);
@@ -762,10 +967,7 @@ __global__ __launch_bounds__(256) void bn_act_bwd_apply_fin_kernel(w2l_bnact_t d
                 for (int j = 0; j < 8; ++j) o1[j] = o.g[j] * c1.sc[j];
             }
             store8_split(dy_hi, dy_lo, ((int64_t)h1 + (int64_t)n * (T + h1) + t) * d.C + c, o1);
-            if (amax) {
-#pragma unroll
-                for (int j = 0; j < 8; ++j) mx1 = fmaxf(mx1, fabsf(o1[j]));
-            }
+            if (amax) mx1 = absmax8(mx1, o1);
             if (HAS2 && dy2_hi) {
                 if (d.mean2) {
 #pragma unroll
@@ -775,46 +977,13 @@ __global__ __launch_bounds__(256) void bn_act_bwd_apply_fin_kernel(w2l_bnact_t d
                     for (int j = 0; j < 8; ++j) o2[j] = o.g[j] * c2.sc[j];
                 }
                 store8_split(dy2_hi, dy2_lo, ((int64_t)h2 + (int64_t)n * (T + h2) + t) * d.C + c, o2);
-                if (amax) {
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) mx2 = fmaxf(mx2, fabsf(o2[j]));
-                }
+                if (amax) mx2 = absmax8(mx2, o2);
             }
         }
     }
-    // ---- halo rows of the shared-halo layout: (N+1) gaps of h rows each, this block's share (its slab's 128 bytes per row)
-    {
-        const int nchunks = gridDim.x / nslabs;
-        float z[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) z[j] = 0.f;
-        for (int pass = 0; pass < 2; ++pass) {
-            bf16_raw* hi = pass ? dy2_hi : dy_hi;
-            bf16_raw* lo = pass ? dy2_lo : dy_lo;
-            const int h = pass ? h2 : h1;
-            if (hi == nullptr || h == 0) continue;
-            const int total = h * (N + 1);
-            const int per = (total + nchunks - 1) / nchunks;
-            int e = (chunk + 1) * per;
-            if (e > total) e = total;
-            for (int hr = chunk * per + wave * 8 + rr; hr < e; hr += 32) {
-                const int gap = hr / h, r = hr - gap * h;
-                store8_split(hi, lo, ((int64_t)gap * (T + h) + r) * d.C + c, z);
-            }
-        }
-    }
-    if (amax) {
-#pragma unroll
-        for (int m = 1; m < 64; m <<= 1) {
-            mx1 = fmaxf(mx1, __shfl_xor(mx1, m, 64));
-            mx2 = fmaxf(mx2, __shfl_xor(mx2, m, 64));
-        }
-        if (lane == 0) {
-            const int slot = blockIdx.x & (AMAX_SLOTS - 1);
-            amax_publish(amax, slot, mx1);
-            if (HAS2 && dy2_hi) amax_publish(amax, AMAX_SLOTS + slot, mx2);
-        }
-    }
+    if (dy_hi != nullptr && h1 != 0) zero_halo_share(p, dy_hi, dy_lo, h1, N, T, d.C);
+    if (dy2_hi != nullptr && h2 != 0) zero_halo_share(p, dy2_hi, dy2_lo, h2, N, T, d.C);
+    wave_amax_publish(p.lane, mx1, mx2, HAS2 && dy2_hi, amax);
 }
 
 // ---- the backward chain's fast path (round 5): bf16 y, bf16 gradient from ONE source, one branch -- every Wav2Letter unit and
@@ -830,87 +999,18 @@ __global__ __launch_bounds__(256) void bn_act_bwd_apply_fin_kernel(w2l_bnact_t d
 // pass 24.4 / 25.2 / 28.7 / 34.3 us at 1 / 2 / 4 / 8 groups): more rows per wave = more loads in flight per lane but fewer waves per
 // SIMD (their registers), and occupancy wins -- two groups for the reduction, one for the dy pass (two on the narrow layers).
 
-struct FastRow {
-    u16x8 y, g, ga, gb;                                // conv output, gradient of the frame, of its reflected images (left / right halo)
-    unsigned bits;                                     // dropout keep bits
-    bool live, fa, fb, masked;
-    int n, t;
-};
-
-__device__ __forceinline__ void fast_row_load(const w2l_bnact_t& d, const w2l_gradsrc_t& s, int64_t row, int64_t rows, int c,
-                                              int cg, int G, FastRow& o) {
-    o.live = row < rows;
-    o.fa = o.fb = o.masked = false;
-    o.bits = 0xFFu;
-    o.n = 0; o.t = 0;
-    if (!o.live) return;
-    const int T = d.T;
-    const int n = (int)(row / T), t = (int)(row - (int64_t)n * T);
-    o.n = n; o.t = t;
-    o.y = *reinterpret_cast<const u16x8*>(reinterpret_cast<const bf16_raw*>(d.y) + row * d.C + c);
-    if (d.drop_p > 0.f) o.bits = d.mask[row * G + cg];
-    o.masked = d.lens && t >= d.lens[n];
-    const bf16_raw* gp = reinterpret_cast<const bf16_raw*>(s.dxp);
-    const int64_t base = (int64_t)n * s.rows;
-    o.g = *reinterpret_cast<const u16x8*>(gp + (base + t + s.pad_l) * d.C + c);
-    if (s.pad_mode == 1) {                             // the reflected halo rows' gradient folds back onto its source frame
-        o.fa = t >= 1 && t <= s.pad_l;
-        o.fb = t <= T - 2 && t >= T - 1 - s.pad_r;
-        if (o.fa) o.ga = *reinterpret_cast<const u16x8*>(gp + (base + s.pad_l - t) * d.C + c);
-        if (o.fb) o.gb = *reinterpret_cast<const u16x8*>(gp + (base + s.pad_l + 2 * (T - 1) - t) * d.C + c);
-    }
-}
-
-// gated gradient and normalised input of one row's 8 channels.  The activation and whether there is dropout are template
-// parameters: these kernels are bound by their instruction count, not by HBM (a plain copy of the same bytes runs at twice
-// their rate: tools/probe/hbm_ceiling.py), and a run-time switch on d.act costs two scalar branches per ELEMENT
-template <int ACT, bool DROP>
-__device__ __forceinline__ void fast_row_eval(const FastRow& r, const Chan& ch, float inv_keep, float g[8], float xh[8]) {
-    float gv[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) gv[j] = bf16_bits_to_f32(r.g[j]);
-    if (r.fa) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) gv[j] += bf16_bits_to_f32(r.ga[j]);
-    }
-    if (r.fb) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) gv[j] += bf16_bits_to_f32(r.gb[j]);
-    }
-    const float gk = DROP ? inv_keep : 1.f;
-    const bool row_ok = !r.masked;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const float y = bf16_bits_to_f32(r.y[j]);
-        float z = y * ch.sc[j] + ch.sh[j];
-        bool pass = row_ok;
-        if (DROP) {
-            pass = pass && ((r.bits >> j) & 1u);
-            z *= inv_keep;                             // (a dropped element's z is never looked at: pass is false)
-        }
-        if (ACT == 1) pass = pass && z >= 0.f && z <= 20.f;      // torch.clamp passes 1 on the CLOSED interval
-        else if (ACT == 2) pass = pass && z > 0.f;
-        g[j] = pass ? gv[j] * gk : 0.f;
-        xh[j] = (y - ch.m[j]) * ch.is[j];
-    }
-}
-
 template <int U, int ACT, bool DROP>
 __global__ __launch_bounds__(256) void bn_bwd_reduce_fast_kernel(w2l_bnact_t d, w2l_gradsrc_t g1, float* partial, float inv_keep,
                                                                   int slots) {
     __shared__ float red[4][2][BWD_SLAB];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int G = d.C >> 3, nslabs = d.C / BWD_SLAB;
-    const int slab = blockIdx.x % nslabs, chunk = blockIdx.x / nslabs;
-    const int cgl = lane & 7, rr = lane >> 3;
-    const int cg = slab * (BWD_SLAB / 8) + cgl, c = cg * 8;
+    const SlabPos p = slab_pos(d.C);
     const int64_t rows = (int64_t)d.N * d.T;
-    const int64_t q0 = ((int64_t)chunk * 4 + wave) * (U * 8) + rr;
+    const int64_t q0 = ((int64_t)p.chunk * 4 + p.wave) * (U * 8) + p.rr;
     FastRow r[U];
 #pragma unroll
-    for (int u = 0; u < U; ++u) fast_row_load(d, g1, q0 + 8 * u, rows, c, cg, G, r[u]);
+    for (int u = 0; u < U; ++u) fast_row_load(d, g1, q0 + 8 * u, rows, p, r[u]);
     Chan ch;
-    load_chan(ch, d.scale, d.shift, d.mean, d.invstd, c);
+    load_chan(ch, d.scale, d.shift, d.mean, d.invstd, p.c);
     float s0[8], s1[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) { s0[j] = 0.f; s1[j] = 0.f; }
@@ -922,23 +1022,7 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_fast_kernel(w2l_bnact_t d, 
 #pragma unroll
         for (int j = 0; j < 8; ++j) { s0[j] += g[j]; s1[j] += g[j] * xh[j]; }
     }
-#pragma unroll
-    for (int m = 8; m < 64; m <<= 1)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            s0[j] += __shfl_xor(s0[j], m, 64);
-            s1[j] += __shfl_xor(s1[j], m, 64);
-        }
-    if (rr == 0) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) { red[wave][0][cgl * 8 + j] = s0[j]; red[wave][1][cgl * 8 + j] = s1[j]; }
-    }
-    __syncthreads();
-    if (tid < 2 * BWD_SLAB) {
-        const int k = tid >> 6, cc = tid & 63;
-        const float t4 = (red[0][k][cc] + red[1][k][cc]) + (red[2][k][cc] + red[3][k][cc]);
-        atomicAdd(partial + ((int64_t)(chunk % slots) * 2 + k) * d.C + slab * BWD_SLAB + cc, t4);
-    }
+    slab_sums_to_slots(p, s0, s1, red, partial, slots, d.C);
 }
 
 template <int U, int ACT, bool DROP>
@@ -947,38 +1031,20 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_fast_kernel(w2l_bnact_t d, w
                                                                  float* amax) {
     __shared__ float ssum[2][BWD_SLAB];
     __shared__ float smax[4];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int G = d.C >> 3, nslabs = d.C / BWD_SLAB;
-    const int slab = blockIdx.x % nslabs, chunk = blockIdx.x / nslabs;
-    const int cgl = lane & 7, rr = lane >> 3;
-    const int cg = slab * (BWD_SLAB / 8) + cgl, c = cg * 8;
+    const SlabPos p = slab_pos(d.C);
     const int T = d.T, N = d.N;
     const int64_t rows = (int64_t)N * T;
-    const int64_t q0 = ((int64_t)chunk * 4 + wave) * (U * 8) + rr;
+    const int64_t q0 = ((int64_t)p.chunk * 4 + p.wave) * (U * 8) + p.rr;
     FastRow r[U];
 #pragma unroll
-    for (int u = 0; u < U; ++u) fast_row_load(d, g1, q0 + 8 * u, rows, c, cg, G, r[u]);     // before the prologue's round trip
-    if (tid < 2 * BWD_SLAB) {                          // column sums of partial[nb][2][C] over this slab's channels, fixed order
-        const int k = tid >> 6, cc = tid & 63;
-        float a = 0.f;
-        int j = 0;
-        for (; j + 8 <= nb; j += 8) {
-            float v[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) v[u] = partial[((int64_t)(j + u) * 2 + k) * d.C + slab * BWD_SLAB + cc];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) a += v[u];
-        }
-        for (; j < nb; ++j) a += partial[((int64_t)j * 2 + k) * d.C + slab * BWD_SLAB + cc];
-        ssum[k][cc] = a;
-        if (chunk == 0) sums_out[(int64_t)k * d.C + slab * BWD_SLAB + cc] = a;
-    }
+    for (int u = 0; u < U; ++u) fast_row_load(d, g1, q0 + 8 * u, rows, p, r[u]);     // before the prologue's round trip
+    slot_column_sums(p, partial, nb, d.C, ssum, sums_out);
     __syncthreads();
     Chan ch;
-    load_chan(ch, d.scale, d.shift, d.mean, d.invstd, c);
+    load_chan(ch, d.scale, d.shift, d.mean, d.invstd, p.c);
     float sg[8], sgx[8];
 #pragma unroll
-    for (int j = 0; j < 8; ++j) { sg[j] = ssum[0][cgl * 8 + j]; sgx[j] = ssum[1][cgl * 8 + j]; }
+    for (int j = 0; j < 8; ++j) { sg[j] = ssum[0][p.cgl * 8 + j]; sgx[j] = ssum[1][p.cgl * 8 + j]; }
     const float invM = 1.f / ((float)N * (float)T);
     float mx = 0.f;
 #pragma unroll
@@ -993,34 +1059,11 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_fast_kernel(w2l_bnact_t d, w
 #pragma unroll
             for (int j = 0; j < 8; ++j) o[j] = g[j] * ch.sc[j];
         }
-        store8_split(dy_hi, nullptr, ((int64_t)h1 + (int64_t)r[u].n * (T + h1) + r[u].t) * d.C + c, o);
-        if (amax) {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) mx = fmaxf(mx, fabsf(o[j]));
-        }
+        store8_split(dy_hi, nullptr, ((int64_t)h1 + (int64_t)r[u].n * (T + h1) + r[u].t) * d.C + p.c, o);
+        if (amax) mx = absmax8(mx, o);
     }
-    // ---- halo rows of the shared-halo layout: (N+1) gaps of h1 rows each, this block's share (its slab's 128 bytes per row)
-    if (h1 > 0) {
-        const int nchunks = gridDim.x / nslabs;
-        float z[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) z[j] = 0.f;
-        const int total = h1 * (N + 1);
-        const int per = (total + nchunks - 1) / nchunks;
-        int e = (chunk + 1) * per;
-        if (e > total) e = total;
-        for (int hr = chunk * per + wave * 8 + rr; hr < e; hr += 32) {
-            const int gap = hr / h1, rw = hr - gap * h1;
-            store8_split(dy_hi, nullptr, ((int64_t)gap * (T + h1) + rw) * d.C + c, z);
-        }
-    }
-    if (amax) {
-#pragma unroll
-        for (int m = 1; m < 64; m <<= 1) mx = fmaxf(mx, __shfl_xor(mx, m, 64));
-        if (lane == 0) smax[wave] = mx;
-        __syncthreads();                               // (amax is a kernel argument: uniform)
-        if (tid == 0) amax_publish(amax, blockIdx.x & (AMAX_SLOTS - 1), fmaxf(fmaxf(smax[0], smax[1]), fmaxf(smax[2], smax[3])));
-    }
+    if (h1 > 0) zero_halo_share(p, dy_hi, nullptr, h1, N, T, d.C);
+    block_amax_publish(p, mx, smax, amax);
 }
 
 // ---- looped forms (round 5, late): the kernels above give a wave 8-32 rows and then pay, per wave, the channel constants, the
@@ -1028,75 +1071,23 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_fast_kernel(w2l_bnact_t d, w
 // 28 000 such waves take as long to ISSUE on 1 024 SIMDs as the kernels run (17-28 us).  Here a wave walks `iters` row groups of
 // its slab with the next group's loads in flight while it works on the current one, so the per-wave work is paid once per
 // iters x 8 rows.
-// row cursor of a lane: the row's index, (utterance, frame) and the three addresses it reads, advanced by 8 rows at a time with
-// additions only (no division, no 64-bit multiply per row; T >= 8: at most one utterance boundary per step -- the launcher checks)
-struct RowCur {
-    int64_t row;
-    int n, t;
-    const bf16_raw* py;                                // y[row][c]
-    const bf16_raw* pg;                                // gradient source row of frame t: dxp[n][pad_l + t][c]
-    const uint8_t* pm;                                 // dropout keep bits of the row's channel group
-};
-__device__ __forceinline__ void rowcur_init(RowCur& q, const w2l_bnact_t& d, const w2l_gradsrc_t& s, int64_t row, int c, int cg, int G) {
-    q.row = row;
-    q.n = (int)(row / d.T);
-    q.t = (int)(row - (int64_t)q.n * d.T);
-    q.py = reinterpret_cast<const bf16_raw*>(d.y) + row * d.C + c;
-    q.pg = reinterpret_cast<const bf16_raw*>(s.dxp) + ((int64_t)q.n * s.rows + q.t + s.pad_l) * d.C + c;
-    q.pm = d.mask ? d.mask + row * G + cg : nullptr;
-}
-__device__ __forceinline__ void rowcur_step(RowCur& q, const w2l_bnact_t& d, const w2l_gradsrc_t& s, int G) {
-    q.row += 8;
-    q.t += 8;
-    q.py += 8 * (int64_t)d.C;
-    q.pg += 8 * (int64_t)d.C;
-    if (q.pm) q.pm += 8 * G;
-    if (q.t >= d.T) {
-        q.t -= d.T;
-        ++q.n;
-        q.pg += (int64_t)(s.rows - d.T) * d.C;
-    }
-}
-__device__ __forceinline__ void fast_row_load_cur(const w2l_bnact_t& d, const w2l_gradsrc_t& s, const RowCur& q, bool live, FastRow& o) {
-    o.live = live;
-    o.fa = o.fb = o.masked = false;
-    o.bits = 0xFFu;
-    o.n = q.n; o.t = q.t;
-    if (!live) return;
-    const int T = d.T, t = q.t;
-    o.y = *reinterpret_cast<const u16x8*>(q.py);
-    if (d.drop_p > 0.f) o.bits = *q.pm;
-    o.masked = d.lens && t >= d.lens[q.n];
-    o.g = *reinterpret_cast<const u16x8*>(q.pg);
-    if (s.pad_mode == 1) {                             // the reflected halo rows' gradient folds back onto its source frame
-        o.fa = t >= 1 && t <= s.pad_l;
-        o.fb = t <= T - 2 && t >= T - 1 - s.pad_r;
-        if (o.fa) o.ga = *reinterpret_cast<const u16x8*>(q.pg - 2 * (int64_t)t * d.C);                    // padded row pad_l - t
-        if (o.fb) o.gb = *reinterpret_cast<const u16x8*>(q.pg + 2 * (int64_t)(T - 1 - t) * d.C);          // pad_l + 2 (T-1) - t
-    }
-}
-
 template <int ACT, bool DROP>
 __global__ __launch_bounds__(256) void bn_bwd_reduce_loop_kernel(w2l_bnact_t d, w2l_gradsrc_t g1, float* partial, float inv_keep,
                                                                   int slots, int iters) {
     __shared__ float red[4][2][BWD_SLAB];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int G = d.C >> 3, nslabs = d.C / BWD_SLAB;
-    const int slab = blockIdx.x % nslabs, chunk = blockIdx.x / nslabs;
-    const int cgl = lane & 7, rr = lane >> 3;
-    const int cg = slab * (BWD_SLAB / 8) + cgl, c = cg * 8;
+    const SlabPos p = slab_pos(d.C);
     const int64_t rows = (int64_t)d.N * d.T;
     RowCur q;
-    rowcur_init(q, d, g1, ((int64_t)chunk * 4 + wave) * ((int64_t)iters * 8) + rr, c, cg, G);
+    rowcur_init(q, d, g1, ((int64_t)p.chunk * 4 + p.wave) * ((int64_t)iters * 8) + p.rr, p);
     FastRow cur, nxt;
     fast_row_load_cur(d, g1, q, q.row < rows, cur);
     Chan ch;
-    load_chan(ch, d.scale, d.shift, d.mean, d.invstd, c);
+    load_chan(ch, d.scale, d.shift, d.mean, d.invstd, p.c);
     float s0[8], s1[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) { s0[j] = 0.f; s1[j] = 0.f; }
     for (int it = 0; it < iters; ++it) {
-        rowcur_step(q, d, g1, G);
+        rowcur_step(q, d, g1, p.G);
         fast_row_load_cur(d, g1, q, it + 1 < iters && q.row < rows, nxt);
         if (cur.live) {
             float g[8], xh[8];
@@ -1106,23 +1097,7 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_loop_kernel(w2l_bnact_t d, 
         }
         cur = nxt;
     }
-#pragma unroll
-    for (int m = 8; m < 64; m <<= 1)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            s0[j] += __shfl_xor(s0[j], m, 64);
-            s1[j] += __shfl_xor(s1[j], m, 64);
-        }
-    if (rr == 0) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) { red[wave][0][cgl * 8 + j] = s0[j]; red[wave][1][cgl * 8 + j] = s1[j]; }
-    }
-    __syncthreads();
-    if (tid < 2 * BWD_SLAB) {
-        const int k = tid >> 6, cc = tid & 63;
-        const float t4 = (red[0][k][cc] + red[1][k][cc]) + (red[2][k][cc] + red[3][k][cc]);
-        atomicAdd(partial + ((int64_t)(chunk % slots) * 2 + k) * d.C + slab * BWD_SLAB + cc, t4);
-    }
+    slab_sums_to_slots(p, s0, s1, red, partial, slots, d.C);
 }
 
 template <int ACT, bool DROP>
@@ -1131,50 +1106,32 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_loop_kernel(w2l_bnact_t d, w
                                                                  float* amax, int iters) {
     __shared__ float ssum[2][BWD_SLAB];
     __shared__ float smax[4];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int G = d.C >> 3, nslabs = d.C / BWD_SLAB;
-    const int slab = blockIdx.x % nslabs, chunk = blockIdx.x / nslabs;
-    const int cgl = lane & 7, rr = lane >> 3;
-    const int cg = slab * (BWD_SLAB / 8) + cgl, c = cg * 8;
+    const SlabPos p = slab_pos(d.C);
     const int T = d.T, N = d.N;
     const int64_t rows = (int64_t)N * T;
     RowCur q;
-    rowcur_init(q, d, g1, ((int64_t)chunk * 4 + wave) * ((int64_t)iters * 8) + rr, c, cg, G);
-    bf16_raw* pdy = dy_hi + ((int64_t)h1 + (int64_t)q.n * (T + h1) + q.t) * d.C + c;      // dy row of the cursor's frame
+    rowcur_init(q, d, g1, ((int64_t)p.chunk * 4 + p.wave) * ((int64_t)iters * 8) + p.rr, p);
+    bf16_raw* pdy = dy_hi + ((int64_t)h1 + (int64_t)q.n * (T + h1) + q.t) * d.C + p.c;    // dy row of the cursor's frame
     FastRow cur, nxt;
     fast_row_load_cur(d, g1, q, q.row < rows, cur);                                // before the prologue's round trip
-    if (tid < 2 * BWD_SLAB) {                          // column sums of partial[nb][2][C] over this slab's channels, fixed order
-        const int k = tid >> 6, cc = tid & 63;
-        float a = 0.f;
-        int j = 0;
-        for (; j + 8 <= nb; j += 8) {
-            float v[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) v[u] = partial[((int64_t)(j + u) * 2 + k) * d.C + slab * BWD_SLAB + cc];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) a += v[u];
-        }
-        for (; j < nb; ++j) a += partial[((int64_t)j * 2 + k) * d.C + slab * BWD_SLAB + cc];
-        ssum[k][cc] = a;
-        if (chunk == 0) sums_out[(int64_t)k * d.C + slab * BWD_SLAB + cc] = a;
-    }
+    slot_column_sums(p, partial, nb, d.C, ssum, sums_out);
     __syncthreads();
     Chan ch;
-    load_chan(ch, d.scale, d.shift, d.mean, d.invstd, c);
+    load_chan(ch, d.scale, d.shift, d.mean, d.invstd, p.c);
     const float invM = 1.f / ((float)N * (float)T);
     float sg[8], sgx[8];
 #pragma unroll
-    for (int j = 0; j < 8; ++j) { sg[j] = ssum[0][cgl * 8 + j] * invM; sgx[j] = ssum[1][cgl * 8 + j] * invM; }
+    for (int j = 0; j < 8; ++j) { sg[j] = ssum[0][p.cgl * 8 + j] * invM; sgx[j] = ssum[1][p.cgl * 8 + j] * invM; }
     float mx = 0.f;
     for (int it = 0; it < iters; ++it) {
         bf16_raw* const pdy_cur = pdy;
         pdy += (int64_t)(q.t + 8 >= T ? 8 + h1 : 8) * d.C;                           // (an utterance boundary skips its halo rows)
-        rowcur_step(q, d, g1, G);
+        rowcur_step(q, d, g1, p.G);
         fast_row_load_cur(d, g1, q, it + 1 < iters && q.row < rows, nxt);
         if (cur.live) {
             float g[8], xh[8], o[8];
             fast_row_eval<ACT, DROP>(cur, ch, inv_keep, g, xh);
-            if (d.mean) {
+            if (d.mean) {                              // (sg, sgx: scaled by 1 / M above)
 #pragma unroll
                 for (int j = 0; j < 8; ++j) o[j] = ch.sc[j] * (g[j] - sg[j] - xh[j] * sgx[j]);
             } else {
@@ -1182,34 +1139,12 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_loop_kernel(w2l_bnact_t d, w
                 for (int j = 0; j < 8; ++j) o[j] = g[j] * ch.sc[j];
             }
             store8_split(pdy_cur, nullptr, 0, o);
-            if (amax) {
-#pragma unroll
-                for (int j = 0; j < 8; ++j) mx = fmaxf(mx, fabsf(o[j]));
-            }
+            if (amax) mx = absmax8(mx, o);
         }
         cur = nxt;
     }
-    if (h1 > 0) {                                      // halo rows of the shared-halo layout: this block's share
-        const int nchunks = gridDim.x / nslabs;
-        float z[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) z[j] = 0.f;
-        const int total = h1 * (N + 1);
-        const int per = (total + nchunks - 1) / nchunks;
-        int e = (chunk + 1) * per;
-        if (e > total) e = total;
-        for (int hr = chunk * per + wave * 8 + rr; hr < e; hr += 32) {
-            const int gap = hr / h1, rw = hr - gap * h1;
-            store8_split(dy_hi, nullptr, ((int64_t)gap * (T + h1) + rw) * d.C + c, z);
-        }
-    }
-    if (amax) {
-#pragma unroll
-        for (int m = 1; m < 64; m <<= 1) mx = fmaxf(mx, __shfl_xor(mx, m, 64));
-        if (lane == 0) smax[wave] = mx;
-        __syncthreads();
-        if (tid == 0) amax_publish(amax, blockIdx.x & (AMAX_SLOTS - 1), fmaxf(fmaxf(smax[0], smax[1]), fmaxf(smax[2], smax[3])));
-    }
+    if (h1 > 0) zero_halo_share(p, dy_hi, nullptr, h1, N, T, d.C);
+    block_amax_publish(p, mx, smax, amax);
 }
 
 // e4m3 quantisation with the scale taken from a device-resident amax (no host round trip): scale = the power of two that
@@ -1300,6 +1235,47 @@ int check_desc(const w2l_bnact_t* d, const char* who) {
     return 0;
 }
 
+// what every backward entry asks of its gradient source(s) and of the halos of its dy buffer(s); g2 may be null
+int check_gradsrc(const w2l_bnact_t* d, const w2l_gradsrc_t* g1, const w2l_gradsrc_t* g2, int halo, int halo2, const char* who) {
+    W2L_CHECK_ARG(!g2 || g2->f32 == g1->f32, "%s: gradient sources must share a dtype", who);
+    W2L_CHECK_ARG(halo >= 0 && halo2 >= 0, "%s: negative halo", who);
+    W2L_CHECK_ARG(g1->rows >= g1->pad_l + d->T + g1->pad_r && (!g2 || g2->rows >= g2->pad_l + d->T + g2->pad_r),
+                  "%s: gradient source has too few rows per utterance", who);
+    return 0;
+}
+int check_slab(const w2l_bnact_t* d, const char* who) {
+    W2L_CHECK_ARG(d->C % BWD_SLAB == 0, "%s: C=%d must be a multiple of %d", who, d->C, BWD_SLAB);
+    return 0;
+}
+// the shared-halo dy buffer(s): N*T rows + (N+1) gaps of `halos` rows (both buffers' together), indexed with 32 bits
+int check_dy_index(const w2l_bnact_t* d, int halos, const char* who) {
+    W2L_CHECK_ARG(((int64_t)d->N * d->T + (int64_t)halos * (d->N + 1)) * (d->C / 8) < (1LL << 31),
+                  "%s: tensor too large for 32-bit indexing", who);
+    return 0;
+}
+
+// run-time value -> template argument: f(std::integral_constant<int, V>{}) for the V of the list that equals v (the last V
+// when none does); the kernel launch sits in f, a generic lambda, and names its template arguments A() / D() / ...
+template <int V, int... Rest, class F>
+void with_int(int v, F&& f) {
+    if constexpr (sizeof...(Rest) == 0) f(std::integral_constant<int, V>{});
+    else if (v == V) f(std::integral_constant<int, V>{});
+    else with_int<Rest...>(v, f);
+}
+template <class F>
+void with_bool(bool b, F&& f) {
+    if (b) f(std::true_type{});
+    else f(std::false_type{});
+}
+template <class F>
+void with_act(int act, F&& f) { with_int<1, 2, 0>(act, f); }                 // clamp(0, 20), ReLU, none
+template <class F>
+void with_act_drop(const w2l_bnact_t* d, F&& f) {                            // (activation, whether there is dropout)
+    with_act(d->act, [&](auto A) { with_bool(d->drop_p > 0.f, [&](auto D) { f(A, D); }); });
+}
+// row chunks of a slab-form launch whose waves take `groups` row groups (of 8 rows) each, four waves to the block
+inline int slab_chunks(int64_t rows, int groups) { return (int)((rows + 4LL * groups * 8 - 1) / (4LL * groups * 8)); }
+
 }  // namespace
 
 extern "C" int w2l_bn_finalize(const float* partial, int ntiles, int C, int64_t count, const float* gamma,
@@ -1341,15 +1317,10 @@ extern "C" int w2l_bn_act_fwd_q(const w2l_bnact_t* d, void* out_hi, void* out_lo
     W2L_CHECK_ARG(per_utt < (1 << 24) && d->N <= 65535, "bn_act_fwd: more than 2^24 channel groups per utterance or N > 65535");
     const dim3 grid((unsigned)((per_utt + 255) / 256), (unsigned)d->N);
     const float inv_g = 1.f / (float)(d->C / 8);
-#define W2L_FWD_A(F, H, A)                                                                                   \
-    hipLaunchKernelGGL((bn_act_fwd_kernel<F, H, A>), grid, dim3(256), 0, (hipStream_t)stream, *d,               \
-                       (bf16_raw*)out_hi, (bf16_raw*)out_lo, out_rows, pad_l, pad_r, pad_mode, thresh, inv_keep,    \
-                       (uint8_t*)out_q, q_scale, inv_g)
-#define W2L_FWD(F, H) do { if (d->act == 1) W2L_FWD_A(F, H, 1); else if (d->act == 2) W2L_FWD_A(F, H, 2); else W2L_FWD_A(F, H, 0); } while (0)
-    if (d->y_f32) { if (d->y2) W2L_FWD(true, true); else W2L_FWD(true, false); }
-    else { if (d->y2) W2L_FWD(false, true); else W2L_FWD(false, false); }
-#undef W2L_FWD
-#undef W2L_FWD_A
+    with_bool(d->y_f32 != 0, [&](auto F) { with_bool(d->y2 != nullptr, [&](auto H) { with_act(d->act, [&](auto A) {
+        hipLaunchKernelGGL((bn_act_fwd_kernel<F(), H(), A()>), grid, dim3(256), 0, (hipStream_t)stream, *d, (bf16_raw*)out_hi,
+                           (bf16_raw*)out_lo, out_rows, pad_l, pad_r, pad_mode, thresh, inv_keep, (uint8_t*)out_q, q_scale, inv_g);
+    }); }); });
     W2L_CHECK_LAUNCH();
     return 0;
 }
@@ -1358,7 +1329,7 @@ extern "C" int w2l_bn_act_fwd_fin(const w2l_bnact_t* d, const w2l_bnfin_t* f1, c
                                   float q_scale, int out_rows, int pad_l, int pad_r, int pad_mode, void* stream) {
     if (int e = check_desc(d, "bn_act_fwd_fin")) return e;
     W2L_CHECK_ARG(!d->y_f32, "bn_act_fwd_fin: bf16 y only (the fp32 mode takes w2l_bn_finalize + w2l_bn_act_fwd)");
-    W2L_CHECK_ARG(d->C % BWD_SLAB == 0, "bn_act_fwd_fin: C=%d must be a multiple of %d", d->C, BWD_SLAB);
+    if (int e = check_slab(d, "bn_act_fwd_fin")) return e;
     W2L_CHECK_ARG(f1 && (f2 != nullptr) == (d->y2 != nullptr), "bn_act_fwd_fin: one finalize record per branch");
     W2L_CHECK_ARG(!out_q || q_scale > 0.f, "bn_act_fwd_fin: the e4m3 copy needs a positive scale");
     W2L_CHECK_ARG(out_hi && out_rows >= pad_l + d->T + pad_r && pad_l >= 0 && pad_r >= 0, "bn_act_fwd_fin: bad output geometry");
@@ -1382,13 +1353,10 @@ extern "C" int w2l_bn_act_fwd_fin(const w2l_bnact_t* d, const w2l_bnfin_t* f1, c
     const int rpb = fwd_rows_per_block(rows, d->C);
     const int nchunks = (int)((rows + rpb - 1) / rpb);
     const dim3 grid((unsigned)(nchunks * (d->C / BWD_SLAB)));
-#define W2L_FIN_A(H, A)                                                                                                      \
-    hipLaunchKernelGGL((bn_act_fwd_fin_kernel<H, A>), grid, dim3(256), 0, (hipStream_t)stream, *d, b[0], b[1], (bf16_raw*)out_hi, \
-                       out_rows, pad_l, pad_r, pad_mode, thresh, inv_keep, (uint8_t*)out_q, q_scale, rpb)
-#define W2L_FIN(H) do { if (d->act == 1) W2L_FIN_A(H, 1); else if (d->act == 2) W2L_FIN_A(H, 2); else W2L_FIN_A(H, 0); } while (0)
-    if (d->y2) W2L_FIN(true); else W2L_FIN(false);
-#undef W2L_FIN
-#undef W2L_FIN_A
+    with_bool(d->y2 != nullptr, [&](auto H) { with_act(d->act, [&](auto A) {
+        hipLaunchKernelGGL((bn_act_fwd_fin_kernel<H(), A()>), grid, dim3(256), 0, (hipStream_t)stream, *d, b[0], b[1],
+                           (bf16_raw*)out_hi, out_rows, pad_l, pad_r, pad_mode, thresh, inv_keep, (uint8_t*)out_q, q_scale, rpb);
+    }); });
     W2L_CHECK_LAUNCH();
     return 0;
 }
@@ -1417,10 +1385,8 @@ extern "C" int w2l_bn_act_bwd_reduce(const w2l_bnact_t* d, const w2l_gradsrc_t* 
                                      float* partial, void* stream) {
     if (int e = check_desc(d, "bn_act_bwd_reduce")) return e;
     W2L_CHECK_ARG(g1 && g1->dxp && partial, "bn_act_bwd_reduce: null pointer");
-    W2L_CHECK_ARG(!g2 || g2->f32 == g1->f32, "bn_act_bwd_reduce: gradient sources must share a dtype");
-    W2L_CHECK_ARG(g1->rows >= g1->pad_l + d->T + g1->pad_r && (!g2 || g2->rows >= g2->pad_l + d->T + g2->pad_r),
-                  "bn_act_bwd_reduce: gradient source has too few rows per utterance");
-    W2L_CHECK_ARG(d->C % BWD_SLAB == 0, "bn_act_bwd_reduce: C=%d must be a multiple of %d", d->C, BWD_SLAB);
+    if (int e = check_gradsrc(d, g1, g2, 0, 0, "bn_act_bwd_reduce")) return e;
+    if (int e = check_slab(d, "bn_act_bwd_reduce")) return e;
     const int64_t rows = (int64_t)d->N * d->T;
     const int rw = bwd_rows_per_wave(rows, d->C);
     const int nchunks = w2l_bn_bwd_blocks(d->N, d->T, d->C);       // rows of `partial`
@@ -1459,34 +1425,20 @@ extern "C" int w2l_bn_act_bwd_reduce_slots(const w2l_bnact_t* d, const w2l_grads
     if (int e = check_desc(d, "bn_act_bwd_reduce_slots")) return e;
     W2L_CHECK_ARG(g1 && g1->dxp && partial && slots >= 1 && slots <= 64, "bn_act_bwd_reduce_slots: null pointer / slots not in 1..64");
     W2L_CHECK_ARG(bwd_fast_ok(d, g1, nullptr), "bn_act_bwd_reduce_slots: bf16 y and gradient, one branch, one source, C %% 64 == 0 only");
-    W2L_CHECK_ARG(g1->rows >= g1->pad_l + d->T + g1->pad_r, "bn_act_bwd_reduce_slots: gradient source has too few rows per utterance");
+    if (int e = check_gradsrc(d, g1, nullptr, 0, 0, "bn_act_bwd_reduce_slots")) return e;
     const int64_t rows = (int64_t)d->N * d->T;
     const float inv_keep = 1.f / (1.f - d->drop_p);
-    const bool drop = d->drop_p > 0.f;
     const int iters = bn_loop_iters(rows, d->T, d->C);
-    if (iters > 0) {
-        const int nch = (int)((rows + 4LL * iters * 8 - 1) / (4LL * iters * 8));
-        const dim3 lgrid((unsigned)(nch * (d->C / BWD_SLAB)));
-#define W2L_REDL(A, D) hipLaunchKernelGGL((bn_bwd_reduce_loop_kernel<A, D>), lgrid, dim3(256), 0, (hipStream_t)stream, *d, *g1, partial, inv_keep, slots, iters)
-        switch (d->act) {
-            case 1: if (drop) W2L_REDL(1, true); else W2L_REDL(1, false); break;
-            case 2: if (drop) W2L_REDL(2, true); else W2L_REDL(2, false); break;
-            default: if (drop) W2L_REDL(0, true); else W2L_REDL(0, false); break;
-        }
-#undef W2L_REDL
-        W2L_CHECK_LAUNCH();
-        return 0;
-    }
-    constexpr int U = 2;
-    const int nchunks = (int)((rows + 4 * U * 8 - 1) / (4 * U * 8));
-    const dim3 grid((unsigned)(nchunks * (d->C / BWD_SLAB)));
-#define W2L_RED(A, D) hipLaunchKernelGGL((bn_bwd_reduce_fast_kernel<U, A, D>), grid, dim3(256), 0, (hipStream_t)stream, *d, *g1, partial, inv_keep, slots)
-    switch (d->act) {
-        case 1: if (drop) W2L_RED(1, true); else W2L_RED(1, false); break;
-        case 2: if (drop) W2L_RED(2, true); else W2L_RED(2, false); break;
-        default: if (drop) W2L_RED(0, true); else W2L_RED(0, false); break;
-    }
-#undef W2L_RED
+    constexpr int U = 2;                                // row groups per wave of the one-shot form
+    const dim3 grid((unsigned)(slab_chunks(rows, iters > 0 ? iters : U) * (d->C / BWD_SLAB)));
+    with_act_drop(d, [&](auto A, auto D) {
+        if (iters > 0)
+            hipLaunchKernelGGL((bn_bwd_reduce_loop_kernel<A(), D()>), grid, dim3(256), 0, (hipStream_t)stream, *d, *g1, partial,
+                               inv_keep, slots, iters);
+        else
+            hipLaunchKernelGGL((bn_bwd_reduce_fast_kernel<U, A(), D()>), grid, dim3(256), 0, (hipStream_t)stream, *d, *g1, partial,
+                               inv_keep, slots);
+    });
     W2L_CHECK_LAUNCH();
     return 0;
 }
@@ -1496,40 +1448,26 @@ extern "C" int w2l_bn_act_bwd_apply_slots(const w2l_bnact_t* d, const w2l_gradsr
     if (int e = check_desc(d, "bn_act_bwd_apply_slots")) return e;
     W2L_CHECK_ARG(g1 && g1->dxp && dy_hi && partial && sums && nrows > 0 && halo >= 0, "bn_act_bwd_apply_slots: null pointer / no partial rows");
     W2L_CHECK_ARG(bwd_fast_ok(d, g1, nullptr), "bn_act_bwd_apply_slots: bf16 y and gradient, one branch, one source, C %% 64 == 0 only");
-    W2L_CHECK_ARG(g1->rows >= g1->pad_l + d->T + g1->pad_r, "bn_act_bwd_apply_slots: gradient source has too few rows per utterance");
+    if (int e = check_gradsrc(d, g1, nullptr, 0, 0, "bn_act_bwd_apply_slots")) return e;
+    if (int e = check_dy_index(d, halo, "bn_act_bwd_apply_slots")) return e;
     const int64_t rows = (int64_t)d->N * d->T;
-    W2L_CHECK_ARG((rows + (int64_t)halo * (d->N + 1)) * (d->C / 8) < (1LL << 31), "bn_act_bwd_apply_slots: tensor too large for 32-bit indexing");
-    // (fp8 mode, amax: four groups -- a block ends in an atomic on one of W2L_AMAX_SLOTS words, and same-address atomics take
-    // ~0.1 us each one after the other: the fewer blocks the better; measured 9.0 against 10.1 ms per fp8 step)
     const float inv_keep = 1.f / (1.f - d->drop_p);
     const int iters = bn_loop_iters(rows, d->T, d->C);
-    if (iters > 0) {
-        const int nch = (int)((rows + 4LL * iters * 8 - 1) / (4LL * iters * 8));
-        const dim3 lgrid((unsigned)(nch * (d->C / BWD_SLAB)));
-        const bool dropl = d->drop_p > 0.f;
-#define W2L_APPL(A, D) hipLaunchKernelGGL((bn_bwd_apply_loop_kernel<A, D>), lgrid, dim3(256), 0, (hipStream_t)stream, *d, *g1, partial, nrows, sums, (bf16_raw*)dy_hi, halo, inv_keep, amax, iters)
-        switch (d->act) {
-            case 1: if (dropl) W2L_APPL(1, true); else W2L_APPL(1, false); break;
-            case 2: if (dropl) W2L_APPL(2, true); else W2L_APPL(2, false); break;
-            default: if (dropl) W2L_APPL(0, true); else W2L_APPL(0, false); break;
-        }
-#undef W2L_APPL
-        W2L_CHECK_LAUNCH();
-        return 0;
-    }
+    // row groups per wave of the one-shot form (fp8 mode, amax: four groups -- a block ends in an atomic on one of W2L_AMAX_SLOTS
+    // words, and same-address atomics take ~0.1 us each one after the other: the fewer blocks the better; measured 9.0 against
+    // 10.1 ms per fp8 step)
     const int U = amax ? 4 : (d->C <= 384 ? 2 : 1);
-    const int nchunks = (int)((rows + 4 * U * 8 - 1) / (4 * U * 8));
-    const dim3 grid((unsigned)(nchunks * (d->C / BWD_SLAB)));
-#define W2L_APP(UU, A, D) hipLaunchKernelGGL((bn_bwd_apply_fast_kernel<UU, A, D>), grid, dim3(256), 0, (hipStream_t)stream, *d, *g1, partial, nrows, sums, (bf16_raw*)dy_hi, halo, inv_keep, amax)
-#define W2L_APP_U(A, D) do { if (U == 4) W2L_APP(4, A, D); else if (U == 2) W2L_APP(2, A, D); else W2L_APP(1, A, D); } while (0)
-    const bool drop = d->drop_p > 0.f;
-    switch (d->act) {
-        case 1: if (drop) W2L_APP_U(1, true); else W2L_APP_U(1, false); break;
-        case 2: if (drop) W2L_APP_U(2, true); else W2L_APP_U(2, false); break;
-        default: if (drop) W2L_APP_U(0, true); else W2L_APP_U(0, false); break;
-    }
-#undef W2L_APP_U
-#undef W2L_APP
+    const dim3 grid((unsigned)(slab_chunks(rows, iters > 0 ? iters : U) * (d->C / BWD_SLAB)));
+    with_act_drop(d, [&](auto A, auto D) {
+        if (iters > 0)
+            hipLaunchKernelGGL((bn_bwd_apply_loop_kernel<A(), D()>), grid, dim3(256), 0, (hipStream_t)stream, *d, *g1, partial, nrows,
+                               sums, (bf16_raw*)dy_hi, halo, inv_keep, amax, iters);
+        else
+            with_int<4, 2, 1>(U, [&](auto UU) {
+                hipLaunchKernelGGL((bn_bwd_apply_fast_kernel<UU(), A(), D()>), grid, dim3(256), 0, (hipStream_t)stream, *d, *g1,
+                                   partial, nrows, sums, (bf16_raw*)dy_hi, halo, inv_keep, amax);
+            });
+    });
     W2L_CHECK_LAUNCH();
     return 0;
 }
@@ -1553,14 +1491,10 @@ extern "C" int w2l_bn_act_bwd_apply_fin(const w2l_bnact_t* d, const w2l_gradsrc_
                                         void* dy2_hi, void* dy2_lo, int halo2, float* amax, void* stream) {
     if (int e = check_desc(d, "bn_act_bwd_apply_fin")) return e;
     W2L_CHECK_ARG(g1 && g1->dxp && dy_hi && partial && sums && nblocks > 0, "bn_act_bwd_apply_fin: null pointer / no partial rows");
-    W2L_CHECK_ARG(d->C % BWD_SLAB == 0, "bn_act_bwd_apply_fin: C=%d must be a multiple of %d", d->C, BWD_SLAB);
-    W2L_CHECK_ARG(!g2 || g2->f32 == g1->f32, "bn_act_bwd_apply_fin: gradient sources must share a dtype");
-    W2L_CHECK_ARG(halo >= 0 && halo2 >= 0, "bn_act_bwd_apply_fin: negative halo");
-    W2L_CHECK_ARG(g1->rows >= g1->pad_l + d->T + g1->pad_r && (!g2 || g2->rows >= g2->pad_l + d->T + g2->pad_r),
-                  "bn_act_bwd_apply_fin: gradient source has too few rows per utterance");
+    if (int e = check_slab(d, "bn_act_bwd_apply_fin")) return e;
+    if (int e = check_gradsrc(d, g1, g2, halo, halo2, "bn_act_bwd_apply_fin")) return e;
+    if (int e = check_dy_index(d, halo + halo2, "bn_act_bwd_apply_fin")) return e;
     const int64_t rows = (int64_t)d->N * d->T;
-    W2L_CHECK_ARG((rows + (int64_t)(halo + halo2) * (d->N + 1)) * (d->C / 8) < (1LL << 31),
-                  "bn_act_bwd_apply_fin: tensor too large for 32-bit indexing");
     const int rpb = apply_rows_per_block(rows, d->C);
     const int nchunks = (int)((rows + rpb - 1) / rpb);
     const int blocks = nchunks * (d->C / BWD_SLAB);
@@ -1588,15 +1522,10 @@ extern "C" int w2l_bn_act_bwd_apply_amax(const w2l_bnact_t* d, const w2l_gradsrc
     if (int e = check_desc(d, "bn_act_bwd_apply")) return e;
     W2L_CHECK_ARG(g1 && g1->dxp && dy_hi, "bn_act_bwd_apply: null pointer");
     W2L_CHECK_ARG(!d->mean || sums, "bn_act_bwd_apply: BatchNorm backward needs the reduced sums");
-    W2L_CHECK_ARG(!g2 || g2->f32 == g1->f32, "bn_act_bwd_apply: gradient sources must share a dtype");
-    W2L_CHECK_ARG(halo >= 0 && halo2 >= 0, "bn_act_bwd_apply: negative halo");
-    W2L_CHECK_ARG(g1->rows >= g1->pad_l + d->T + g1->pad_r && (!g2 || g2->rows >= g2->pad_l + d->T + g2->pad_r),
-                  "bn_act_bwd_apply: gradient source has too few rows per utterance");
-    const int G = d->C / 8;
-    const int64_t items = (int64_t)d->N * d->T * G + (int64_t)halo * (d->N + 1) * G +
-                          (dy2_hi ? (int64_t)halo2 * (d->N + 1) * G : 0);
-    W2L_CHECK_ARG(items < (1LL << 31), "bn_act_bwd_apply: tensor too large for 32-bit indexing");
-    const int blocks = elementwise_blocks(items);
+    if (int e = check_gradsrc(d, g1, g2, halo, halo2, "bn_act_bwd_apply")) return e;
+    const int halos = halo + (dy2_hi ? halo2 : 0);         // work items: the rows of dy (and of dy2, when there is one)
+    if (int e = check_dy_index(d, halos, "bn_act_bwd_apply")) return e;
+    const int blocks = elementwise_blocks(((int64_t)d->N * d->T + (int64_t)halos * (d->N + 1)) * (d->C / 8));
     const float inv_keep = 1.f / (1.f - d->drop_p);
     w2l_gradsrc_t g2v = g2 ? *g2 : *g1;
     W2L_DISPATCH_BWD(bn_act_bwd_apply_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, *d, *g1, g2v, g2 ? 1 : 0,

@@ -1661,10 +1661,8 @@ class StackEngine:
         acts: List[Act] = ctx['acts']
         N = ctx['out'].shape[0]
         dev = ctx['out'].device
-        st = stream_ptr
         amax_pool = (zeros((len(acts) + 1, 2, AMAX_SLOTS), torch.float32, dev)        # one fill per step
                      if self.fp8 else None)
-        slot_pool = self._slot_pool    # zero rows the two-launch BatchNorm-backward chain adds its sums onto (backward())
         for uc in reversed(ctx['units']):
             u = uc.unit
             oi = uc.out_index
@@ -1679,39 +1677,7 @@ class StackEngine:
             d = self._desc(uc, N, Tout, coutp, p, uc.lens_out)
             g1 = self._gsrc(srcs[0])
             g2 = self._gsrc(srcs[1]) if len(srcs) > 1 else None
-            sums = None
-            fold = fast = False
-            if u.main.has_bn or (u.res is not None and u.res.has_bn):
-                ncomp = 4 if u.res is not None else 2
-                fused = [s_.partial for s_ in srcs if s_.partial is not None]
-                fast = False
-                if len(fused) == len(srcs) and ncomp == 2:
-                    # every gradient source was a data-gradient convolution that formed the sums in its epilogue
-                    fused = list({id(t): t for t in fused}.values())      # (two consumers may have added onto ONE set of slot rows)
-                    partial = fused[0] if len(fused) == 1 else torch.cat(fused, 0)
-                    nb = partial.shape[0]
-                    # (on the step's slot rows: the dy pass with the finalize folded in takes them as they are)
-                    fast = bool(slot_pool is not None and len(fused) == 1 and slot_pool[2].get(id(uc)) is not None and g2 is None
-                                and lib.w2l_bn_bwd_fast_ok(C.byref(d), C.byref(g1), None))
-                elif (FAST_BN_BWD and batch_stats and not precise and g2 is None and ncomp == 2 and slot_pool is not None
-                        and lib.w2l_bn_bwd_fast_ok(C.byref(d), C.byref(g1), None)):
-                    # the two-launch chain: sums added onto STAT_SLOTS zero rows of the step's pool, finalize folded into the dy pass
-                    fast = True
-                    nb = STAT_SLOTS
-                    partial = slot_pool[0][slot_pool[1]: slot_pool[1] + nb * 2 * coutp].view(nb, 2, coutp)
-                    slot_pool[1] += nb * 2 * coutp
-                    check(lib.w2l_bn_act_bwd_reduce_slots(C.byref(d), C.byref(g1), ptr(partial), nb, st()), 'w2l_bn_act_bwd_reduce_slots')
-                else:
-                    nb = lib.w2l_bn_bwd_blocks(N, Tout, coutp)
-                    partial = torch.empty(nb, ncomp, coutp, dtype=torch.float32, device=dev)
-                    check(lib.w2l_bn_act_bwd_reduce(C.byref(d), C.byref(g1), C.byref(g2) if g2 else None, ptr(partial),
-                                                    st()), 'w2l_bn_act_bwd_reduce')
-                sums = small_pool[pool_off: pool_off + 4 * coutp].view(4, coutp)
-                pool_off += 4 * coutp
-                fold = (FOLD_BN_FINALIZE and batch_stats) or fast
-                if not fold:
-                    check(lib.w2l_bn_bwd_finalize(ptr(partial), nb, coutp, ncomp, ptr(sums), st()), 'w2l_bn_bwd_finalize')
-                uc.keep.append((partial, sums))
+            chain, partial, nb, sums, pool_off = self._bn_bwd_reduce(uc, d, g1, g2, srcs, N, coutp, small_pool, pool_off, batch_stats)
             main, res = u.main, u.res
             need_dx_main = self._needs_grad(u.src, ctx)
             # wgrad walks each utterance in 64-row steps (the e4m3 kernel: 128-row steps) over zero rows
@@ -1735,17 +1701,7 @@ class StackEngine:
             amax = amax_pool[oi] if fp8_dgrad or fp8_wgrad else None          # [2][AMAX_SLOTS]: dy, dy2
             amax_w = amax if fp8_wgrad else None
             amax_d = amax if fp8_dgrad else None
-            if fold and fast:
-                check(lib.w2l_bn_act_bwd_apply_slots(C.byref(d), C.byref(g1), ptr(partial), nb, ptr(sums), ptr(dy_hi), h1, ptr(amax),
-                                                     st()), 'w2l_bn_act_bwd_apply_slots')
-            elif fold:
-                check(lib.w2l_bn_act_bwd_apply_fin(C.byref(d), C.byref(g1), C.byref(g2) if g2 else None, ptr(partial), nb,
-                                                   ptr(sums), ptr(dy_hi), ptr(dy_lo), h1, ptr(dy2_hi), ptr(dy2_lo), h2, ptr(amax),
-                                                   st()), 'w2l_bn_act_bwd_apply_fin')
-            else:
-                check(lib.w2l_bn_act_bwd_apply_amax(C.byref(d), C.byref(g1), C.byref(g2) if g2 else None, ptr(sums), ptr(dy_hi),
-                                                    ptr(dy_lo), h1, ptr(dy2_hi), ptr(dy2_lo), h2, ptr(amax), st()),
-                      'w2l_bn_act_bwd_apply')
+            self._bn_bwd_apply(chain, d, g1, g2, partial, nb, sums, dy_hi, dy_lo, h1, dy2_hi, dy2_lo, h2, amax)
             # release the consumed gradient buffers early
             act_grads[oi] = []
             # BN parameter gradients: d beta = sum g, d gamma = sum g * xhat
@@ -1799,6 +1755,49 @@ class StackEngine:
                     act_grads[u.res_src].append(self._dgrad(res, pkr, dy2_hi, dy2_lo, h2, Tout, rsrc,
                                                             self._producer(ctx, u.res_src),
                                                             amax=None if amax_d is None else amax_d[1]))
+
+    def _bn_bwd_reduce(self, uc, d, g1, g2, srcs, N, coutp, small_pool, pool_off, batch_stats):
+        """the reduction launch of a unit's BatchNorm-backward chain, if any, and the finalize launch of 'three' -> (chain, partial, nb,
+        sums, pool_off); chain = the dy launch: 'slots' / 'fold' = finalize folded in, over slot / partial rows; 'three'; 'plain' = no BN"""
+        u, slot_pool = uc.unit, self._slot_pool      # slot_pool: the step's zero rows for 'slots' (backward())
+        if not (u.main.has_bn or (u.res is not None and u.res.has_bn)):
+            return 'plain', None, 0, None, pool_off
+        pd, pg1, pg2, st = C.byref(d), C.byref(g1), None if g2 is None else C.byref(g2), stream_ptr()
+        ncomp = 4 if u.res is not None else 2        # sums per channel: sum g, sum g xhat of each branch
+        def slots_ok():      # the slab-form kernels take the unit: the step has slot rows, one bf16 source, one branch
+            return bool(g2 is None and slot_pool is not None and lib.w2l_bn_bwd_fast_ok(pd, pg1, None))
+        chain = 'fold' if FOLD_BN_FINALIZE and batch_stats else 'three'
+        fused = [s_.partial for s_ in srcs if s_.partial is not None]
+        if len(fused) == len(srcs) and ncomp == 2:      # every gradient source was a data-gradient convolution that formed the sums
+            fused = list({id(t): t for t in fused}.values())      # (two consumers may have added onto ONE set of slot rows)
+            partial = fused[0] if len(fused) == 1 else torch.cat(fused, 0)
+            if slot_pool is not None and len(fused) == 1 and slot_pool[2].get(id(uc)) is not None and slots_ok():
+                chain = 'slots'      # (on the step's slot rows: the dy pass with the finalize folded in takes them as they are)
+        elif FAST_BN_BWD and batch_stats and not self.precise and ncomp == 2 and slots_ok():      # two launches, sums onto zero slot rows
+            chain, partial = 'slots', slot_pool[0][slot_pool[1]: slot_pool[1] + STAT_SLOTS * 2 * coutp].view(STAT_SLOTS, 2, coutp)
+            slot_pool[1] += partial.numel()
+            check(lib.w2l_bn_act_bwd_reduce_slots(pd, pg1, ptr(partial), STAT_SLOTS, st), 'w2l_bn_act_bwd_reduce_slots')
+        else:
+            partial = torch.empty(lib.w2l_bn_bwd_blocks(N, uc.Tout, coutp), ncomp, coutp, dtype=torch.float32, device=small_pool.device)
+            check(lib.w2l_bn_act_bwd_reduce(pd, pg1, pg2, ptr(partial), st), 'w2l_bn_act_bwd_reduce')
+        nb, sums = partial.shape[0], small_pool[pool_off: pool_off + 4 * coutp].view(4, coutp)
+        if chain == 'three':
+            check(lib.w2l_bn_bwd_finalize(ptr(partial), nb, coutp, ncomp, ptr(sums), st), 'w2l_bn_bwd_finalize')
+        uc.keep.append((partial, sums))
+        return chain, partial, nb, sums, pool_off + 4 * coutp
+
+    def _bn_bwd_apply(self, chain, d, g1, g2, partial, nb, sums, dy_hi, dy_lo, h1, dy2_hi, dy2_lo, h2, amax):
+        """the dy launch of the chain that _bn_bwd_reduce named"""
+        pd, pg1, pg2, st = C.byref(d), C.byref(g1), None if g2 is None else C.byref(g2), stream_ptr()
+        if chain == 'slots':
+            check(lib.w2l_bn_act_bwd_apply_slots(pd, pg1, ptr(partial), nb, ptr(sums), ptr(dy_hi), h1, ptr(amax), st), 'w2l_bn_act_bwd_apply_slots')
+        elif chain == 'fold':
+            check(lib.w2l_bn_act_bwd_apply_fin(pd, pg1, pg2, ptr(partial), nb, ptr(sums), ptr(dy_hi), ptr(dy_lo), h1, ptr(dy2_hi),
+                                               ptr(dy2_lo), h2, ptr(amax), st), 'w2l_bn_act_bwd_apply_fin')
+        else:      # 'three', and 'plain' (sums is None: the kernel scales the gated gradient)
+            check(lib.w2l_bn_act_bwd_apply_amax(pd, pg1, pg2, ptr(sums), ptr(dy_hi), ptr(dy_lo), h1, ptr(dy2_hi), ptr(dy2_lo), h2,
+                                                ptr(amax), st), 'w2l_bn_act_bwd_apply')
+
     # ------------------------------------------------------------------ helpers
     def _needs_grad(self, act_index: int, ctx=None) -> bool:
         # the spectrogram needs no gradient in training (base_asr_models.py:78-85); computed only on request
