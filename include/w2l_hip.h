@@ -682,6 +682,38 @@ int w2l_resample(const float* x, int64_t in_stride, float* out, int64_t out_stri
                  const int32_t* rows_dev, const int32_t* banks_host, const int32_t* banks_dev, int n_banks, const float* taps,
                  int64_t n_taps, void* stream);
 
+/* ---- waveform augmentation between w2l_resample and w2l_logmel (data/augment_wave.py; no reference counterpart: the
+ * reference augments spectrograms only, data/augmentations.py) -----------------------------------------------------------
+ * w2l_reverb: x [N][in_stride] -> out [N][out_stride] (a separate buffer), fp32, device, one launch.  rows[n] = {n_in, bank},
+ * banks[b] = {offset, K, d}: the impulse response of bank b is taps[offset ... offset + K), its direct path at tap d;
+ *   out[m] = sum_{j < K} h[j] * x~[m + d - j] for 0 <= m < n_in,  x~ = x inside [0, n_in) and 0 outside, fp32 fmaf chains;
+ *   out[m] = 0 for n_in <= m < out_stride.  A row with bank == -1 is copied bit for bit.
+ * Grid (tile of W2L_REVERB_TILE outputs, row); a block stages W2L_REVERB_CHUNK taps at a time.  No atomics, no cross-block
+ * dependence: two calls give identical bits.  The row and bank tables are passed twice, as for w2l_resample (host copy checked
+ * before anything is launched, device copy read by the kernel).  Rejected: null pointers, out == x, n_in > in_stride or
+ * > out_stride, a bank index outside [-1, n_banks), K < 1 or K > W2L_REVERB_MAX_TAPS, d outside [0, K), a range outside taps.
+ * Call site: data/augment_wave.reverb_device (SpectrogramExtractor.extract_batch(augment=)). */
+#define W2L_REVERB_TILE 1024
+#define W2L_REVERB_CHUNK 512
+#define W2L_REVERB_MAX_TAPS 16384
+int w2l_reverb(const float* x, int64_t in_stride, float* out, int64_t out_stride, int N, const int32_t* rows_host,
+               const int32_t* rows_dev, const int32_t* banks_host, const int32_t* banks_dev, int n_banks, const float* taps,
+               int64_t n_taps, void* stream);
+/* w2l_mix_noise: out[n][m] = fmaf(g_n, z[n][(o + m) mod n_z], x[n][m]) for m < n_in, 0 for n_in <= m < out_stride, with
+ *   g = sqrt(Ps / (Pz * 10^(snr_db / 10))),  Ps = mean_{m < n_in} x[m]^2,  Pz = mean_{m < n_in} z[(o + m) mod n_z]^2,
+ * so that the noise lies snr_db below the utterance over the utterance's own length (a shorter clip wraps).  rows[n] =
+ * {n_in, n_z, o} (host and device copies), snr_db [N] fp32 (device), z [N][z_stride] fp32.  A row with n_z == 0, a row with
+ * Ps == 0 and a row with Pz == 0 are copied bit for bit.  Two launches, grid (tile of W2L_MIX_TILE samples, row): fp64 partial
+ * sums (samples widened before squaring) into slab [N][tiles][2], tiles = ceil(out_stride / W2L_MIX_TILE) -- at least
+ * w2l_mix_noise_slab_doubles(N, out_stride) doubles, owned by the caller -- then every block adds its row's partials in index
+ * order, forms g in double, rounds it once to fp32 and applies it.  No atomics: two calls give identical bits.
+ * Call site: data/augment_wave.mix_noise_device. */
+#define W2L_MIX_TILE 2048
+int64_t w2l_mix_noise_slab_doubles(int N, int64_t out_stride);
+int w2l_mix_noise(const float* x, int64_t x_stride, const float* z, int64_t z_stride, float* out, int64_t out_stride, int N,
+                  const int32_t* rows_host, const int32_t* rows_dev, const float* snr_db, double* slab, int64_t slab_doubles,
+                  void* stream);
+
 /* ---- stream concurrency probe -----------------------------------------------------------------------------------------
  * Launches a chip-filling spin kernel (`rounds` waves of 2 blocks per CU, `spin_us` each) on stream_a, then a one-wave
  * kernel on stream_b that records when it started.  stamps_dev: 3 x int64, zero before the call (caller synchronises

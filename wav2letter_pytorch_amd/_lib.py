@@ -173,6 +173,9 @@ _SIGNATURES = {
     'w2l_feature_normalize': (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_p, c_p, c_p, c_p]),
     'w2l_zero_rects': (c_i, [c_p, c_i, c_i, c_i, c_p, c_i, c_p]),
     'w2l_resample': (c_i, [c_p, c_i64, c_p, c_i64, c_i, c_p, c_p, c_p, c_p, c_i, c_p, c_i64, c_p]),
+    'w2l_reverb': (c_i, [c_p, c_i64, c_p, c_i64, c_i, c_p, c_p, c_p, c_p, c_i, c_p, c_i64, c_p]),
+    'w2l_mix_noise_slab_doubles': (c_i64, [c_i, c_i64]),
+    'w2l_mix_noise': (c_i, [c_p, c_i64, c_p, c_i64, c_p, c_i64, c_i, c_p, c_p, c_p, c_p, c_i64, c_p]),
     'w2l_levenshtein_host': (c_i, [c_p, c_i, c_p, c_i]),
     'w2l_greedy_score_host': (c_i, [c_p, c_i, c_i, c_p, c_i, c_p, c_i, c_p, c_p, c_p, c_p, c_p]),
     'w2l_wgrad_fp8_needs_zero': (c_i, [c_i, c_i, c_i, c_i, c_i]),

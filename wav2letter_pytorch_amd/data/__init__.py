@@ -5,7 +5,7 @@ import importlib
 
 from . import label_sets  # noqa: F401
 
-_LAZY = ('data_loader', 'augmentations', 'mel', 'resample')
+_LAZY = ('data_loader', 'augmentations', 'mel', 'resample', 'augment_wave')
 
 
 def __getattr__(name):

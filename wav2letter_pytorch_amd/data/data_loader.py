@@ -156,7 +156,7 @@ class SpectrogramExtractor(torch.nn.Module):
                              float(self.log_zero_guard_value), ptr(out), tmax, stream_ptr()), 'w2l_logmel')
         return out, tmax
 
-    def _stage(self, signals: Sequence, noise, rates=None, speeds=None):
+    def _stage(self, signals: Sequence, noise, rates=None, speeds=None, augment=None):
         dev = self.fb.device
         if dev.type != 'cuda':
             raise RuntimeError('SpectrogramExtractor runs on MI355X only (HIP kernels, no CPU path)')
@@ -179,6 +179,9 @@ class SpectrogramExtractor(torch.nn.Module):
         audio = host.to(dev, non_blocking=True)
         if rows is not None:
             audio = resample_device(audio, rows, self._banks)         # [N, max n_out], zero past each row's n_out
+        if augment is not None:
+            augmenter, plan = augment                                  # reverberation, then noise: lengths unchanged
+            audio = augmenter.apply(audio, lens, plan)
         lens_d = torch.from_numpy(lens).to(dev, non_blocking=True)
         if noise is None:
             noise_d = torch.randn(audio.shape, dtype=torch.float32, device=dev) if self.dithering > 0 else None
@@ -191,14 +194,16 @@ class SpectrogramExtractor(torch.nn.Module):
                 noise_d[i, :z.shape[0]] = z.to(dev)
         return audio, lens_d, noise_d, lens
 
-    def extract_batch(self, signals: Sequence, noise=None, rates=None, speeds=None):
+    def extract_batch(self, signals: Sequence, noise=None, rates=None, speeds=None, augment=None):
         """signals: N 1-D float arrays (any lengths).  noise: None = draw the dither on the device, False = no dither, or N
         arrays of N(0,1) draws (parity tests inject the reference's).  Returns (inputs fp32 [N, n_mels, T_max] on the
         device, zero beyond each utterance's frames; input_lengths IntTensor [N] on the host) -- _collator's layout.
         rates (the signals' sample rates) / speeds (speed factors), either one given: the staged batch goes through
         w2l_resample (data/resample.py) first; lengths, the dither and the returned input_lengths are those of the resampled
-        rows (noise arrays, if given, are at the resampled lengths).  Both None, or every row at 1/1: the plain path's launches."""
-        audio, lens_d, noise_d, lens = self._stage(signals, noise, rates, speeds)
+        rows (noise arrays, if given, are at the resampled lengths).  Both None, or every row at 1/1: the plain path's launches.
+        augment: (a WaveformAugment, the plan its draw() returned for these N rows) -- reverberation and noise on the staged
+        waveforms, after the resampler and before the dither (data/augment_wave.py); a plan that selects nothing adds no launch."""
+        audio, lens_d, noise_d, lens = self._stage(signals, noise, rates, speeds, augment)
         logmel, tmax = self._launch(audio, lens_d, noise_d, True)
         n = audio.shape[0]
         mean = torch.empty(n, self.n_mels, dtype=torch.float32, device=audio.device)
@@ -227,9 +232,11 @@ class SpectrogramDataset(Dataset):
     ``dataset.raw(i)`` -> the same with the raw samples instead of features (what BatchAudioDataLoader batches).
     ``resample=True`` (not in the reference): files of any rate and channel count; every row is read with ``read_audio`` and
     converted to ``audio_conf['sample_rate']`` on the GPU, instead of the assertion on the first row's rate.
-    ``speed_perturb``: a ``SpeedPerturb`` (or its factors), applied per utterance by BatchAudioDataLoader's batches only."""
+    ``speed_perturb``: a ``SpeedPerturb`` (or its factors), applied per utterance by BatchAudioDataLoader's batches only.
+    ``wave_augment``: a ``WaveformAugment`` (reverberation and noise on the waveform), likewise for the loader's batches only."""
 
-    def __init__(self, manifest_filepath, audio_conf, labels, mel_spec=None, use_cuda=False, resample=False, speed_perturb=None):
+    def __init__(self, manifest_filepath, audio_conf, labels, mel_spec=None, use_cuda=False, resample=False, speed_perturb=None,
+                 wave_augment=None):
         super().__init__()
         rows = self._read_manifest(manifest_filepath)
         self.rows = rows
@@ -244,6 +251,7 @@ class SpectrogramDataset(Dataset):
         if speed_perturb is not None and not isinstance(speed_perturb, SpeedPerturb):
             speed_perturb = SpeedPerturb(speed_perturb)
         self.speed_perturb = speed_perturb
+        self.wave_augment = wave_augment
         self._rates = {}
         if not self.resample:
             self.validate_sample_rate()
@@ -366,6 +374,9 @@ class BatchAudioDataLoader(DataLoader):
         else:
             audio, targets, file_paths, texts = zip(*batch)
         speeds = ds.speed_perturb.draw(len(audio)) if ds.speed_perturb is not None else None
-        inputs, input_lengths = ds.extractor.extract_batch(audio, rates=rates, speeds=speeds)
+        augment = None
+        if ds.wave_augment is not None and ds.wave_augment.active:
+            augment = (ds.wave_augment, ds.wave_augment.draw(len(audio)))
+        inputs, input_lengths = ds.extractor.extract_batch(audio, rates=rates, speeds=speeds, augment=augment)
         tg, target_lengths = _pad_targets(targets)
         return inputs, input_lengths, tg, target_lengths, file_paths, texts

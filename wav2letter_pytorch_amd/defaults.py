@@ -56,7 +56,9 @@ def root_config(model: str = 'wav2letter', **model_kw):
     """The whole tree of configuration/config.yaml: data / model / trainer"""
     m = {'wav2letter': wav2letter_model, 'jasper': jasper_model, 'jasper10x5': jasper10x5_model}[model](**model_kw)
     return to_cfg(dict(data=dict(train_manifest='???', val_manifest='???', batch_size=4, mel_spec=m['input_size'],
-                                 audio_conf=dict(m['audio_conf']), resample=False, speed_perturb=None),
+                                 audio_conf=dict(m['audio_conf']), resample=False, speed_perturb=None,
+                                 noise_manifest=None, noise_prob=0.5, snr_db='5,20', rir_manifest=None, rir_prob=0.5,
+                                 rir_max_seconds=0.5),
                        model=m, trainer=dict(default_root_dir='.', max_epochs=5, max_steps=None, gpus=0)))
 
 

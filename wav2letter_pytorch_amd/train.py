@@ -3,7 +3,9 @@ Hydra / Lightning:
 
     python -m wav2letter_pytorch_amd.train [--config-dir /path/to/configuration] data.train_manifest=train.csv \\
            data.val_manifest=val.csv [model=jasper] [model.mid_layers=20] [trainer.max_epochs=1] \\
-           [data.resample=true] [data.speed_perturb=0.9,1.0,1.1] ...
+           [data.resample=true] [data.speed_perturb=0.9,1.0,1.1] \\
+           [data.rir_manifest=rirs.csv data.rir_prob=0.5 data.rir_max_seconds=0.5] \\
+           [data.noise_manifest=noise.csv data.noise_prob=0.5 data.snr_db=5,20] ...
 
 Same override syntax and config keys as ``python train.py ...``; without ``--config-dir`` the built-in copy of the
 hyper-parameters (defaults.py) is used.  Manifests, labels, feature extraction and batching are data/data_loader.py's;
@@ -11,7 +13,10 @@ the fit loop is trainer.Trainer.  ``trainer.gpus=N`` (the reference's Lightning 
 command line (launch.py), one per GPU; ``python -m torch.distributed.run --nproc-per-node N`` works too.  Every rank trains
 on its own shard of the manifest and gradients are averaged with RCCL (distributed.GradReducer).  ``data.resample=true``:
 manifests may mix sample rates and channel counts (converted on the GPU, data/resample.py); ``data.speed_perturb=`` draws one
-speed factor per training utterance."""
+speed factor per training utterance.  ``data.rir_manifest=`` / ``data.noise_manifest=`` (manifests with an ``audio_filepath``
+column; data/augment_wave.py) augment the training waveforms on the GPU: with probability ``data.rir_prob`` an utterance is
+convolved with one of the room impulse responses (each cut ``data.rir_max_seconds`` after its peak), then with probability
+``data.noise_prob`` a noise clip is added at an SNR drawn from ``data.snr_db=lo,hi``.  Validation is never augmented."""
 from __future__ import annotations
 
 import os
@@ -76,12 +81,15 @@ def get_data_loaders(labels, cfg, rank: int = 0, world: int = 1):
     injects into the reference's loaders."""
     from torch.utils.data.distributed import DistributedSampler
     from .data.data_loader import BatchAudioDataLoader, SpectrogramDataset
+    from .data.augment_wave import from_config
     from .data.resample import parse_speed_factors
     loaders = []
     resample = _truth(cfg.get('resample', False))
     factors = parse_speed_factors(cfg.get('speed_perturb'))         # the train loader only: validation is never perturbed
-    for manifest, perturb in ((cfg.train_manifest, factors), (cfg.val_manifest, None)):
-        ds = SpectrogramDataset(manifest, cfg.audio_conf, labels, mel_spec=cfg.mel_spec, resample=resample, speed_perturb=perturb)
+    wave = from_config(cfg, int(cfg.audio_conf['sample_rate']))     # None unless data.noise_manifest / data.rir_manifest is set
+    for manifest, perturb, augment in ((cfg.train_manifest, factors, wave), (cfg.val_manifest, None, None)):
+        ds = SpectrogramDataset(manifest, cfg.audio_conf, labels, mel_spec=cfg.mel_spec, resample=resample, speed_perturb=perturb,
+                                wave_augment=augment)
         kw = {}
         if world > 1:
             kw['sampler'] = DistributedSampler(range(len(ds)), num_replicas=world, rank=rank, shuffle=False)
@@ -106,7 +114,9 @@ def build_config(argv):
             rest.append(a)
     overrides = [a for a in rest if '=' in a]
     if config_dir is not None:
-        return load_config(config_dir, overrides)
+        cfg = load_config(config_dir, overrides)
+        _check_augment(cfg)
+        return cfg
     from .defaults import root_config
     group = 'wav2letter'
     plain = []
@@ -124,7 +134,15 @@ def build_config(argv):
             cur = cur.setdefault(p, to_cfg({}))
         cur[parts[-1]] = to_cfg(_yaml_load(v))
     criterion_name(cfg.model)      # model.criterion: ctc | asg (absent: ctc), anything else is an error naming the two
+    _check_augment(cfg)
     return cfg
+
+
+def _check_augment(cfg):
+    """data.snr_db is a range lo,hi with lo <= hi, data.noise_prob / data.rir_prob are probabilities: ValueError otherwise"""
+    from .data.augment_wave import check_config
+    if cfg.get('data') is not None:
+        check_config(cfg.data)
 
 
 def _requested_gpus(cfg) -> int:
