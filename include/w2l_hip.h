@@ -301,7 +301,8 @@ typedef struct {
     int32_t act;            /* 0 none, 1 clamp[0,20] (wav2letter.py:46), 2 ReLU (jasper.py:448) */
     float drop_p;           /* nn.Dropout p; 0 => no mask is read or written */
     uint64_t seed, offset;  /* Philox4x32-10 key / stream offset */
-    uint8_t* mask;          /* keep bits, one byte per 8 channels: [N*T*C/8] */
+    uint8_t* mask;          /* keep bits, one byte per 8 channels: [N*T*C/8]; the forward pass does not write the bytes of
+                               frames t >= lens[n] (written as zeros without being evaluated), the backward pass ignores them */
     const int32_t* lens;    /* optional [N]: rows t >= lens[n] produce 0 / receive 0 gradient */
     const uint64_t* offset_dev; /* optional device word ADDED to `offset` when the mask is drawn: a step counter that lives
                                in device memory, so that a captured hipGraph of the step draws fresh masks at every replay */
