@@ -823,6 +823,33 @@ int w2l_sgd_pack_clip(float* p, float* g, float* m, int first_step, float lr, fl
 int w2l_sgd_small_multi_clip(const w2l_sgd_small_t* items_dev, int nitems, int max_n, float lr, float momentum,
                              float weight_decay, int nesterov, const float* clip, void* stream);
 
+/* ---- torch.optim.Adam / AdamW (amsgrad, maximize off), the first optimizer override of model.optimizer._target_ --------------
+ * Called by optim.FusedAdamW.step().  In torch's order (_single_tensor_adam), g read through the clip buffer when clip != NULL:
+ *   decoupled != 0 (AdamW): p *= 1 - lr*wd      else (Adam): g += wd*p
+ *   m = beta1*m + (1-beta1)*g;   v = beta2*v + (1-beta2)*g*g;   p -= dyn[1] * m / (sqrt(v)/dyn[2] + eps)
+ *
+ * What changes from step to step lives in DEVICE memory, so that a recorded optimizer phase (w2l_replay) stays valid under a
+ * per-step learning-rate schedule: state = {step, beta1^step, beta2^step} of one parameter group and the float[4] dyn =
+ * [lr, lr / (1 - beta1^step), sqrt(1 - beta2^step), 0].  w2l_adam_tick (one thread) advances them: step += 1, the powers as
+ * running products in fp64 (a host loop of the same multiplies reproduces them bit for bit; a fresh state is {0, 1.0, 1.0}),
+ * the two quotients formed in fp64 and rounded to fp32 once.  It is the only call of a step whose arguments change, and it
+ * is deliberately NOT a replayable entry point: the caller issues it every step, in front of the recorded list.
+ *
+ * w2l_adam_pack: the update of a tap-major conv weight fused with the operand pack of the next step, exactly as
+ * w2l_sgd_pack (p, g, m, v dense fp32 [Kw][Cout][Cin]; zero_grad, the bf16 hi/lo and e4m3 operands as there).
+ * w2l_adam_small_multi: the same rule for all the small parameters in one launch, no pack; table rows {p, g, m, v, n}.
+ * clip (nullable, both): the float[4] buffer above; coef == 1 and bound == +inf are bit-identical to clip == NULL. */
+typedef struct { int64_t step; double pow1; double pow2; } w2l_adam_state_t;
+typedef struct { float* p; const float* g; float* m; float* v; int32_t n; int32_t pad_; } w2l_adam_small_t;
+int w2l_adam_tick(w2l_adam_state_t* state_dev, float* dyn_dev, double lr, double beta1, double beta2, void* stream);
+int w2l_adam_pack(float* p, float* g, float* m, float* v, const float* dyn, float beta1, float beta2, float eps,
+                  float weight_decay, int decoupled, int zero_grad, int Cout, int Cin, int Kw, void* w_fwd_hi, void* w_fwd_lo,
+                  void* w_dgr_hi, void* w_dgr_lo, void* w_fwd_q, void* w_dgr_q, float q_scale, const float* clip /* nullable */,
+                  void* stream);
+int w2l_adam_small_multi(const w2l_adam_small_t* items_dev, int nitems, int max_n /* the largest items[i].n */, const float* dyn,
+                         float beta1, float beta2, float eps, float weight_decay, int decoupled, const float* clip /* nullable */,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -212,6 +212,10 @@ _SIGNATURES = {
                                 c_p]),
     'w2l_grad_sqnorm_multi': (c_i, [c_p, c_i, c_i64, c_i, c_p, c_f, c_p, c_p, c_p]),
     'w2l_grad_clip_value': (c_i, [c_p, c_f, c_p]),
+    'w2l_adam_tick': (c_i, [c_p, c_p, C.c_double, C.c_double, C.c_double, c_p]),
+    'w2l_adam_pack': (c_i, [c_p, c_p, c_p, c_p, c_p, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_f,
+                            c_p, c_p]),
+    'w2l_adam_small_multi': (c_i, [c_p, c_i, c_i, c_p, c_f, c_f, c_f, c_f, c_i, c_p, c_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
@@ -282,7 +286,7 @@ TRACE_NAMES = {
     'w2l_bn_act_bwd_reduce_slots': 'bn_act_bwd_reduce_kernel', 'w2l_bn_act_bwd_apply_slots': 'bn_act_bwd_apply_kernel', 'w2l_bn_bwd_finalize': 'bn_bwd_finalize_kernel',
     'w2l_bn_act_bwd_apply': 'bn_act_bwd_apply_kernel', 'w2l_bn_act_bwd_apply_amax': 'bn_act_bwd_apply_kernel',
     'w2l_bn_act_bwd_apply_fin': 'bn_act_bwd_apply_kernel', 'w2l_sgd_pack': 'sgd_pack_kernel', 'w2l_pack_weights': 'pack_weights_kernel',
-    'w2l_sgd_pack_clip': 'sgd_pack_kernel', 'w2l_grad_sqnorm_multi': 'grad_norm_kernels',
+    'w2l_sgd_pack_clip': 'sgd_pack_kernel', 'w2l_adam_pack': 'adam_pack_kernel', 'w2l_grad_sqnorm_multi': 'grad_norm_kernels',
     'w2l_asg_loss': 'asg_kernels', 'w2l_asg_viterbi': 'asg_viterbi_kernel',
     'w2l_ctc_loss': 'ctc_kernels', 'w2l_log_softmax_fwd': 'log_softmax_fwd', 'w2l_log_softmax_bwd': 'log_softmax_bwd',
     'w2l_nct_to_ntc': 'nct_to_ntc_kernel', 'w2l_pad_cast': 'pad_cast_kernel', 'w2l_quantize_e4m3': 'quantize_e4m3',

@@ -10,7 +10,7 @@ from typing import Callable, Dict, Sequence
 import torch
 import torch.nn as nn
 
-from .config import criterion_name, instantiate
+from .config import criterion_name, instantiate, scheduler_interval
 from .ctc_loss import CTCLoss
 
 try:  # PyTorch-Lightning is optional: absent in the build image
@@ -286,7 +286,13 @@ class ConvCTCASR(_Base):
         if type(optimizer) is torch.optim.SGD and next(self.parameters()).is_cuda:
             from .optim import FusedSGD            # same update rule and state dict; conv weights update in one fused pass
             optimizer = FusedSGD.from_sgd(optimizer)
+        elif (type(optimizer) in (torch.optim.Adam, torch.optim.AdamW) and next(self.parameters()).is_cuda
+              and not any(g.get(k) for g in optimizer.param_groups for k in ('amsgrad', 'maximize', 'capturable', 'differentiable'))):
+            from .optim import FusedAdamW          # same rule and state dict; step scalars on the device (replayable under a schedule)
+            optimizer = FusedAdamW.from_adam(optimizer)
         scheduler = instantiate(self._cfg.scheduler, optimizer=optimizer)
+        if scheduler_interval(self._cfg) == 'step':          # Lightning's scheduler dict: stepped after every optimizer step
+            return [optimizer], [{'scheduler': scheduler, 'interval': 'step', 'frequency': 1}]
         return [optimizer], [scheduler]
 
     def configure_gradient_clipping(self, optimizer, *args, **kwargs):

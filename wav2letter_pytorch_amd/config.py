@@ -41,6 +41,19 @@ def criterion_name(model_cfg) -> str:
     return name
 
 
+SCHEDULER_INTERVALS = ('epoch', 'step')
+
+
+def scheduler_interval(model_cfg) -> str:
+    """``model.scheduler_interval``: ``epoch`` (the default, also when the key is absent: the scheduler steps once per epoch, as
+    the reference runs it) or ``step`` (once per optimizer step: warm-up schedules, OneCycleLR); anything else is a ValueError"""
+    name = model_cfg.get('scheduler_interval', None) if hasattr(model_cfg, 'get') else None
+    name = 'epoch' if name is None else name
+    if name not in SCHEDULER_INTERVALS:
+        raise ValueError(f'model.scheduler_interval={name!r} is not an interval: the valid values are epoch and step')
+    return name
+
+
 _ALIASES = {
     # reference module paths -> this package (config.yaml:14-16 names decoder.GreedyDecoder)
     'decoder': 'wav2letter_pytorch_amd.decoder',
@@ -152,6 +165,7 @@ def load_config(config_dir: str, overrides=()):
     _interpolate(merged, merged)
     if isinstance(merged.get('model'), dict):
         criterion_name(merged['model'])          # validated only: an absent key stays absent (and means ctc)
+        scheduler_interval(merged['model'])
     return to_cfg(merged)
 
 

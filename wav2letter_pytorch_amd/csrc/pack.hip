@@ -109,6 +109,57 @@ __global__ void sgd_pack_kernel(float* p, float* g, float* m, int first, float l
     }
 }
 
+// ---- Adam / AdamW (torch.optim.Adam / AdamW, _single_tensor_adam; amsgrad, maximize off) ---------------------------------------
+// The element rule is common.h's adam_update (shared with csrc/replay.hip's small-parameter kernel).
+// Fused Adam update of a tap-major conv weight that also emits the GEMM operands of the next step, like sgd_pack_kernel: one
+// pass, read p, g, m, v; write p, m, v, 2 x bf16 (+ 2 x e4m3 in fp8 mode) -- 32 B per parameter where SGD moves 24.
+// CLIP: the gradient is read through clip_grad_read first, as in sgd_pack_kernel.
+template <bool CLIP>
+__global__ void adam_pack_kernel(float* p, float* g, float* m, float* v, const float* dyn, float beta1, float beta2, float eps,
+                                 float wd, int decoupled, int zero_grad, int Cout, int Cin, int Kw, bf16_raw* fwd_hi,
+                                 bf16_raw* fwd_lo, bf16_raw* dgr_hi, bf16_raw* dgr_lo, uint8_t* fwd_q, uint8_t* dgr_q,
+                                 float q_scale, const float* clip) {
+    __shared__ float tile[32][33];
+    const int tx = threadIdx.x, ty = threadIdx.y;
+    const int ci0 = blockIdx.x * 32, co0 = blockIdx.y * 32, kw = blockIdx.z;
+    const adam_scalars s = adam_load_scalars(dyn, beta1, beta2, eps, wd, decoupled);
+    float coef = 1.f, bound = 0.f;
+    if constexpr (CLIP) {
+        coef = clip[W2L_CLIP_COEF];
+        bound = clip[W2L_CLIP_BOUND];
+    }
+    for (int j = ty; j < 32; j += 8) {
+        const int co = co0 + j, ci = ci0 + tx;
+        float out = 0.f;
+        if (co < Cout && ci < Cin) {
+            const int64_t off = ((int64_t)kw * Cout + co) * Cin + ci;
+            float gv = g[off];
+            if constexpr (CLIP) gv = clip_grad_read(gv, coef, bound);
+            if (zero_grad) g[off] = 0.f;
+            float mv = m[off], vv = v[off];
+            const float pv = adam_update(s, p[off], gv, mv, vv);
+            m[off] = mv;
+            v[off] = vv;
+            p[off] = pv;
+            out = pv;
+            if (fwd_hi) put_split(fwd_hi, fwd_lo, off, pv);
+            if (fwd_q) fwd_q[off] = quant1_e4m3(bf16_bits_to_f32(f32_to_bf16_bits(pv)) * q_scale);
+        }
+        tile[j][tx] = out;
+    }
+    __syncthreads();
+    if (dgr_hi) {
+        for (int j = ty; j < 32; j += 8) {
+            const int ci = ci0 + j, co = co0 + tx;
+            if (co < Cout && ci < Cin) {
+                const int64_t o = ((int64_t)(Kw - 1 - kw) * Cin + ci) * Cout + co;
+                put_split(dgr_hi, dgr_lo, o, tile[tx][j]);
+                if (dgr_q) dgr_q[o] = quant1_e4m3(bf16_bits_to_f32(f32_to_bf16_bits(tile[tx][j])) * q_scale);
+            }
+        }
+    }
+}
+
 // ---- Novograd (novograd.py:86-112): per-TENSOR second moment v = EMA of ||g||^2 --------------------------------
 // Three launches per conv weight: deterministic partial sums of g^2, a one-block finalize that updates v (first-step
 // select on the device, optional running max) and leaves denom = sqrt(v) + eps in device memory, and the update fused
@@ -294,6 +345,28 @@ extern "C" int w2l_sgd_pack_clip(float* p, float* g, float* m, int first_step, f
     hipLaunchKernelGGL(sgd_pack_kernel<true>, grid, block, 0, (hipStream_t)stream, p, g, m, first_step, lr, momentum,
                        weight_decay, nesterov, zero_grad, Cout, Cin, Kw, (bf16_raw*)w_fwd_hi, (bf16_raw*)w_fwd_lo,
                        (bf16_raw*)w_dgr_hi, (bf16_raw*)w_dgr_lo, (uint8_t*)w_fwd_q, (uint8_t*)w_dgr_q, q_scale, clip);
+    W2L_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int w2l_adam_pack(float* p, float* g, float* m, float* v, const float* dyn, float beta1, float beta2, float eps,
+                             float weight_decay, int decoupled, int zero_grad, int Cout, int Cin, int Kw, void* w_fwd_hi,
+                             void* w_fwd_lo, void* w_dgr_hi, void* w_dgr_lo, void* w_fwd_q, void* w_dgr_q, float q_scale,
+                             const float* clip, void* stream) {
+    W2L_CHECK_ARG((!w_fwd_q && !w_dgr_q) || (q_scale > 0.f && w_fwd_hi && w_dgr_hi), "adam_pack: e4m3 operands need a scale");
+    W2L_CHECK_ARG(p && g && m && v && dyn, "adam_pack: null pointer");
+    W2L_CHECK_ARG(Cout > 0 && Cin > 0 && Kw > 0, "adam_pack: bad sizes");
+    W2L_CHECK_ARG(!(w_fwd_lo && !w_fwd_hi) && !(w_dgr_lo && !w_dgr_hi), "adam_pack: lo without hi");
+    W2L_CHECK_ARG(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f && eps >= 0.f, "adam_pack: betas in [0, 1), eps >= 0");
+    dim3 grid((Cin + 31) / 32, (Cout + 31) / 32, Kw), block(32, 8);
+    if (clip == nullptr)
+        hipLaunchKernelGGL(adam_pack_kernel<false>, grid, block, 0, (hipStream_t)stream, p, g, m, v, dyn, beta1, beta2, eps,
+                           weight_decay, decoupled, zero_grad, Cout, Cin, Kw, (bf16_raw*)w_fwd_hi, (bf16_raw*)w_fwd_lo,
+                           (bf16_raw*)w_dgr_hi, (bf16_raw*)w_dgr_lo, (uint8_t*)w_fwd_q, (uint8_t*)w_dgr_q, q_scale, nullptr);
+    else
+        hipLaunchKernelGGL(adam_pack_kernel<true>, grid, block, 0, (hipStream_t)stream, p, g, m, v, dyn, beta1, beta2, eps,
+                           weight_decay, decoupled, zero_grad, Cout, Cin, Kw, (bf16_raw*)w_fwd_hi, (bf16_raw*)w_fwd_lo,
+                           (bf16_raw*)w_dgr_hi, (bf16_raw*)w_dgr_lo, (uint8_t*)w_fwd_q, (uint8_t*)w_dgr_q, q_scale, clip);
     W2L_CHECK_LAUNCH();
     return 0;
 }

@@ -119,6 +119,41 @@ __global__ __launch_bounds__(256) void sgd_small_multi_kernel(const w2l_sgd_smal
         it.p[i] = pv - lr * step;
     }
 }
+// torch.optim.Adam / AdamW's update of one small parameter per block row (common.h adam_update); grid and chunking as above
+template <bool CLIP>
+__global__ __launch_bounds__(256) void adam_small_multi_kernel(const w2l_adam_small_t* items, const float* dyn, float beta1, float beta2,
+                                                               float eps, float wd, int decoupled, const float* clip) {
+    const w2l_adam_small_t it = items[blockIdx.x];
+    const int lo = blockIdx.y * SGD_SMALL_CHUNK, hi = min(it.n, lo + SGD_SMALL_CHUNK);
+    const adam_scalars s = adam_load_scalars(dyn, beta1, beta2, eps, wd, decoupled);
+    float coef = 1.f, bound = 0.f;
+    if constexpr (CLIP) {
+        coef = clip[W2L_CLIP_COEF];
+        bound = clip[W2L_CLIP_BOUND];
+    }
+    for (int i = lo + threadIdx.x; i < hi; i += 256) {
+        float gv = it.g[i];
+        if constexpr (CLIP) gv = clip_grad_read(gv, coef, bound);
+        float mv = it.m[i], vv = it.v[i];
+        const float pv = adam_update(s, it.p[i], gv, mv, vv);
+        it.m[i] = mv;
+        it.v[i] = vv;
+        it.p[i] = pv;
+    }
+}
+// the step-dependent scalars of one parameter group, advanced on the device: running products (not pow), so that a host
+// loop of the same double multiplies reproduces pow1 / pow2 bit for bit; the quotients formed in fp64 and rounded once
+__global__ void adam_tick_kernel(w2l_adam_state_t* st, float* dyn, double lr, double beta1, double beta2) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    const double p1 = st->pow1 * beta1, p2 = st->pow2 * beta2;
+    st->step += 1;
+    st->pow1 = p1;
+    st->pow2 = p2;
+    dyn[W2L_ADAM_LR] = (float)lr;
+    dyn[W2L_ADAM_STEP_SIZE] = (float)(lr / (1.0 - p1));
+    dyn[W2L_ADAM_BC2_SQRT] = (float)sqrt(1.0 - p2);
+    dyn[3] = 0.f;
+}
 }  // namespace
 
 extern "C" int w2l_pad_vec_f32(const float* src, int n, float* dst, int cp, float fill, void* stream) {
@@ -166,6 +201,32 @@ extern "C" int w2l_sgd_small_multi_clip(const w2l_sgd_small_t* items_dev, int ni
     return 0;
 }
 
+extern "C" int w2l_adam_small_multi(const w2l_adam_small_t* items_dev, int nitems, int max_n, const float* dyn, float beta1,
+                                    float beta2, float eps, float weight_decay, int decoupled, const float* clip, void* stream) {
+    W2L_CHECK_ARG(items_dev != nullptr || nitems == 0, "adam_small_multi: null table");
+    W2L_CHECK_ARG(dyn != nullptr, "adam_small_multi: null dyn buffer");
+    W2L_CHECK_ARG(max_n >= 0 && max_n <= (1 << 26), "adam_small_multi: max_n (the largest item's element count) out of range");
+    W2L_CHECK_ARG(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f && eps >= 0.f, "adam_small_multi: betas in [0, 1), eps >= 0");
+    if (nitems <= 0 || max_n == 0) return 0;
+    const int chunks = (max_n + SGD_SMALL_CHUNK - 1) / SGD_SMALL_CHUNK;
+    if (clip == nullptr)
+        hipLaunchKernelGGL(adam_small_multi_kernel<false>, dim3(nitems, chunks), dim3(256), 0, (hipStream_t)stream, items_dev, dyn,
+                           beta1, beta2, eps, weight_decay, decoupled, nullptr);
+    else
+        hipLaunchKernelGGL(adam_small_multi_kernel<true>, dim3(nitems, chunks), dim3(256), 0, (hipStream_t)stream, items_dev, dyn,
+                           beta1, beta2, eps, weight_decay, decoupled, clip);
+    W2L_CHECK_LAUNCH();
+    return 0;
+}
+// NOT in the replay table: the one call of an optimizer step whose arguments change from step to step
+extern "C" int w2l_adam_tick(w2l_adam_state_t* state_dev, float* dyn_dev, double lr, double beta1, double beta2, void* stream) {
+    W2L_CHECK_ARG(state_dev != nullptr && dyn_dev != nullptr, "adam_tick: null pointer");
+    W2L_CHECK_ARG(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0, "adam_tick: betas in [0, 1)");
+    hipLaunchKernelGGL(adam_tick_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, state_dev, dyn_dev, lr, beta1, beta2);
+    W2L_CHECK_LAUNCH();
+    return 0;
+}
+
 // ---- the replay loop ------------------------------------------------------------------------------------------------------
 namespace {
 template <class T>
@@ -207,7 +268,7 @@ const Entry kEntries[] = {
     W2L_E(w2l_pad_vec_f32), W2L_E(w2l_counter_add), W2L_E(w2l_add_i64_multi), W2L_E(w2l_sgd_small_multi),
     W2L_E(w2l_sgd_small_multi_clip), W2L_E(w2l_sgd_pack_clip), W2L_E(w2l_grad_sqnorm_multi), W2L_E(w2l_grad_clip_value),
     W2L_E(w2l_conv_stats_mode), W2L_E(w2l_wgrad_deterministic),
-    W2L_E(w2l_pack_weights), W2L_E(w2l_sgd_pack), W2L_E(w2l_novograd_pack), W2L_E(w2l_nct_to_ntc), W2L_E(w2l_pad_cast),
+    W2L_E(w2l_pack_weights), W2L_E(w2l_sgd_pack), W2L_E(w2l_novograd_pack), W2L_E(w2l_adam_pack), W2L_E(w2l_adam_small_multi), W2L_E(w2l_nct_to_ntc), W2L_E(w2l_pad_cast),
     W2L_E(w2l_conv1d_igemm), W2L_E(w2l_conv1d_igemm_ws), W2L_E(w2l_conv1d_igemm_fp8), W2L_E(w2l_conv1d_dgrad_bnreduce_ws),
     W2L_E(w2l_conv1d_wgrad), W2L_E(w2l_conv1d_wgrad_ws), W2L_E(w2l_conv1d_wgrad_group), W2L_E(w2l_conv1d_wgrad_fp8),
     W2L_E(w2l_dwconv_fwd), W2L_E(w2l_dwconv_dgrad), W2L_E(w2l_dwconv_wgrad),

@@ -11,8 +11,8 @@ between the streams -- and from then on replays it:
   phase F   forward pass of the stack (everything engine.forward enqueues)
   phase B   backward pass (engine.backward: BatchNorm / activation backward, data and weight gradients, the join of the
             weight-gradient stream)
-  phase O   optimizer step (optim.FusedSGD.step: the fused conv-weight updates on the optimizer's stream, the small parameters
-            in one launch)
+  phase O   optimizer step (optim.FusedSGD.step / FusedAdamW.step: the fused conv-weight updates on the optimizer's stream,
+            the small parameters in one launch)
   phase X   the weight gradients + fused updates a backward pass held back for the next forward pass (flush_deferred)
 
 each through one w2l_replay call: a C loop over the same extern "C" entry points, every launch on the stream it was recorded
@@ -80,7 +80,8 @@ TRANSIENT = ('fp8 weight scale', 'kernel plans were measured', 'measuring launch
 # the record set whose backward pass ran last on this process (a weak reference to its replayer + the set): how
 # optim.FusedSGD.step finds out that the gradients it is about to consume are a record's static buffers
 _last_backward = [None]
-STATS = {'recorded': 0, 'replayed_F': 0, 'replayed_B': 0, 'replayed_O': 0, 'replayed_X': 0, 'poisoned': []}
+# ('recorded': forward + backward records; 'recorded_O': optimizer phases -- one per record set, clipping mode and signature)
+STATS = {'recorded': 0, 'recorded_O': 0, 'replayed_F': 0, 'replayed_B': 0, 'replayed_O': 0, 'replayed_X': 0, 'poisoned': []}
 
 
 def _say(msg):
@@ -160,6 +161,11 @@ class Group:
 
 
 def opt_signature(opt):
+    """everything a recorded phase O carries BY VALUE (a change re-records it), the clip signature last.  An optimizer may
+    state its own (optim.FusedAdamW: no learning rate -- its kernels read it from device memory)"""
+    own = getattr(opt, '_replay_signature', None)
+    if own is not None:
+        return own()
     clip = opt._clip_signature() if hasattr(opt, '_clip_signature') else None        # armed gradient clipping: its own phase O
     return tuple((g['lr'], g['momentum'], g['weight_decay'], g['nesterov'], g['dampening'], g.get('maximize', False))
                  for g in opt.param_groups) + (opt.__dict__.get('_w2l_state_epoch', 0), clip)      # (epoch: FusedSGD.load_state_dict)
@@ -686,6 +692,7 @@ def optimizer_step(opt, eager_body) -> bool:
         _say('optimizer phase dropped: ' + str(rec.poisoned))
         return True
     rset.O, rset.O_sig = ph, sig
+    STATS['recorded_O'] += 1
     rset.O_ptrs = [p.grad.data_ptr() if p.grad is not None else 0 for p, _ in rset.grads + watched]
     rp.opt_stream = opt._side_state()['stream']
     return True

@@ -16,13 +16,15 @@ manifests may mix sample rates and channel counts (converted on the GPU, data/re
 speed factor per training utterance.  ``data.rir_manifest=`` / ``data.noise_manifest=`` (manifests with an ``audio_filepath``
 column; data/augment_wave.py) augment the training waveforms on the GPU: with probability ``data.rir_prob`` an utterance is
 convolved with one of the room impulse responses (each cut ``data.rir_max_seconds`` after its peak), then with probability
-``data.noise_prob`` a noise clip is added at an SNR drawn from ``data.snr_db=lo,hi``.  Validation is never augmented."""
+``data.noise_prob`` a noise clip is added at an SNR drawn from ``data.snr_db=lo,hi``.  Validation is never augmented.
+``model.scheduler_interval=step`` steps the learning-rate scheduler after every optimizer step instead of once per epoch
+(warm-up schedules; ``model.optimizer._target_=torch.optim.AdamW`` then runs as optim.FusedAdamW without re-recording)."""
 from __future__ import annotations
 
 import os
 import sys
 
-from .config import _yaml_load, criterion_name, load_config, to_cfg
+from .config import _yaml_load, criterion_name, load_config, scheduler_interval, to_cfg
 from .launch import spawn_ranks, under_launcher
 
 # Nothing above maps libw2l_hip.so (or imports torch): with trainer.gpus=N this process only starts the ranks, and a launch
@@ -134,6 +136,7 @@ def build_config(argv):
             cur = cur.setdefault(p, to_cfg({}))
         cur[parts[-1]] = to_cfg(_yaml_load(v))
     criterion_name(cfg.model)      # model.criterion: ctc | asg (absent: ctc), anything else is an error naming the two
+    scheduler_interval(cfg.model)  # model.scheduler_interval: epoch | step (absent: epoch)
     _check_augment(cfg)
     return cfg
 

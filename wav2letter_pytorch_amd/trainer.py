@@ -1,6 +1,7 @@
 """Minimal fit loop standing in for ``pytorch_lightning.Trainer(**cfg.trainer).fit(model, train, val)``
-(reference train.py:34-37) when Lightning is not installed: epochs / max_steps, optimizer + per-epoch
-scheduler from ``configure_optimizers`` (base_asr_models.py:73-76), ``training_step`` /
+(reference train.py:34-37) when Lightning is not installed: epochs / max_steps, optimizer + scheduler from
+``configure_optimizers`` (base_asr_models.py:73-76; a plain scheduler steps once per epoch, Lightning's dict form
+``{'scheduler': s, 'interval': 'step' | 'epoch', 'frequency': k}`` after every k-th optimizer step / epoch), ``training_step`` /
 ``validation_step`` with their ``log_dict`` metrics, one checkpoint per epoch under ``default_root_dir``.
 
 Data parallel (one process per GPU, launch.py / torchrun): every rank runs this loop on its own shard of the
@@ -19,6 +20,29 @@ from typing import Optional
 
 import torch
 import torch.distributed as dist
+
+
+def scheduler_plan(schedulers) -> list:
+    """the second return value of ``configure_optimizers`` as a list of (scheduler, interval, frequency): a plain scheduler
+    is ('epoch', 1); Lightning's dict form names its own (``interval`` 'step' or 'epoch', ``frequency`` a positive int)"""
+    if schedulers is None:
+        return []
+    if not isinstance(schedulers, (list, tuple)):
+        schedulers = [schedulers]
+    plan = []
+    for s in schedulers:
+        if isinstance(s, dict):
+            if 'scheduler' not in s:
+                raise ValueError(f"a scheduler dict needs the key 'scheduler', got {sorted(s)}")
+            interval, every = s.get('interval', 'epoch'), s.get('frequency', 1)
+            if interval not in ('step', 'epoch'):
+                raise ValueError(f"scheduler interval {interval!r} is not supported: use 'step' or 'epoch'")
+            if isinstance(every, bool) or not isinstance(every, int) or every < 1:
+                raise ValueError(f'scheduler frequency must be a positive integer, got {every!r}')
+            plan.append((s['scheduler'], interval, every))
+        else:
+            plan.append((s, 'epoch', 1))
+    return plan
 
 
 class _EpochMean:
@@ -124,6 +148,10 @@ class Trainer:
             raise RuntimeError('wav2letter_pytorch_amd trains on MI355X only (no CPU path); trainer.gpus is implied')
         model = model.cuda()
         optimizers, schedulers = model.configure_optimizers()
+        plan = scheduler_plan(schedulers)
+        schedulers = [sch for sch, _, _ in plan]          # (what checkpoints save and restore: the inner schedulers)
+        per_step = [(sch, every) for sch, interval, every in plan if interval == 'step']
+        per_epoch = [(sch, every) for sch, interval, every in plan if interval == 'epoch']
         opt = optimizers[0]
         model._optimizers = opt
         join = getattr(opt, 'join', lambda: None)
@@ -175,6 +203,9 @@ class Trainer:
                 # backward pass and the update already enqueued -- training_step itself never waits for the GPU
                 model.on_train_batch_end(loss, batch, i)
                 self.global_step += 1
+                for sch, every in per_step:
+                    if self.global_step % every == 0:
+                        sch.step()
                 if self.global_step % self.log_every_n_steps == 0 or self.global_step == 1:
                     if hasattr(model, 'resolve_metrics'):
                         model.resolve_metrics(wait_all=True)         # a logging point reports THIS step (one sync per log line)
@@ -185,8 +216,9 @@ class Trainer:
                     done = True
                     break
             model.on_train_epoch_end()
-            for sch in schedulers:
-                sch.step()
+            for sch, every in per_epoch:
+                if (epoch + 1) % every == 0:
+                    sch.step()
             join()                               # parameters are read below (validation, checkpoint)
             if val_dataloader is not None:
                 model.eval()
