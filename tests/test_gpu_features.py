@@ -1,5 +1,6 @@
 """Feature front-end and augmentation masks on the GPU vs the CPU oracle and the reference-generated
-fixture tests/golden/features.npz (data/data_loader.py:33-88,149-158; data/augmentations.py)."""
+fixture tests/golden/features.npz (data/data_loader.py:33-88,149-158; data/augmentations.py).  w2l_logmel, w2l_feature_normalize
+and w2l_zero_rects are also called directly, per element against float64 references, in tests/test_gpu_frontend_direct.py."""
 import json
 import os
 import random
