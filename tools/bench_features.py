@@ -21,7 +21,7 @@ out = torch.empty(N, 64, T, device='cuda')
 
 
 def run():
-    lm, _ = ext._launch(audio, lens, noise, True)
+    lm = ext._launch(audio, lens, noise, True, T)
     check(lib.w2l_feature_normalize(ptr(lm), ptr(lens), 160, N, T, 64, 1e-5, ptr(mean), ptr(std), ptr(out), stream_ptr()))
 
 

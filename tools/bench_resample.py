@@ -53,7 +53,7 @@ for name, rate, speed in CASES:
     feats = torch.empty(N, 64, T, device='cuda')
 
     def features():
-        lm, _ = ext._launch(out, lens, noise, True)
+        lm = ext._launch(out, lens, noise, True, T)
         check(lib.w2l_feature_normalize(ptr(lm), ptr(lens), ext.hop_length, N, T, 64, 1e-5, ptr(mean), ptr(std), ptr(feats), stream_ptr()))
 
     us = timed(resample)

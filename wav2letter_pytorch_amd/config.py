@@ -54,6 +54,24 @@ def scheduler_interval(model_cfg) -> str:
     return name
 
 
+def _flag(v) -> bool:
+    return v is True or (isinstance(v, str) and v.lower() in ('1', 'true', 'yes'))
+
+
+def bucket_options(data_cfg) -> dict:
+    """The length-bucketing keys of ``data`` (data/bucketing.py) with their defaults, validated: ``bucket_rungs`` (0: off; K > 0:
+    batches are padded to one of K widths), ``bucket_align`` (16: every width is a multiple of it), ``bucket_shuffle`` (true),
+    ``bucket_seed`` (0), ``drop_last`` (false: the one short batch is kept).  A config tree without the keys means off."""
+    get = data_cfg.get if hasattr(data_cfg, 'get') else (lambda k, d=None: d)
+    rungs, align = get('bucket_rungs', 0), get('bucket_align', 16)
+    for name, v, low in (('bucket_rungs', rungs, 0), ('bucket_align', align, 1)):
+        if v is not None and (isinstance(v, bool) or not isinstance(v, int) or v < low):
+            raise ValueError(f'data.{name}={v!r} is not an integer of at least {low}')
+    seed = get('bucket_seed', 0)
+    return dict(rungs=int(rungs or 0), align=int(align or 16), shuffle=_flag(get('bucket_shuffle', True)), seed=int(seed or 0),
+                drop_last=_flag(get('drop_last', False)))
+
+
 _ALIASES = {
     # reference module paths -> this package (config.yaml:14-16 names decoder.GreedyDecoder)
     'decoder': 'wav2letter_pytorch_amd.decoder',

@@ -5,7 +5,7 @@ import importlib
 
 from . import label_sets  # noqa: F401
 
-_LAZY = ('data_loader', 'augmentations', 'mel', 'resample', 'augment_wave')
+_LAZY = ('data_loader', 'augmentations', 'mel', 'resample', 'augment_wave', 'bucketing')
 
 
 def __getattr__(name):

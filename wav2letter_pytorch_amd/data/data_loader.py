@@ -20,6 +20,7 @@ import torch
 from torch.utils.data import DataLoader, Dataset
 
 from .._lib import check, lib, ptr, stream_ptr
+from .bucketing import rung_for
 from .mel import mel_filterbank
 from .resample import BankCache, SpeedPerturb, plan_rows, resample_device
 
@@ -146,15 +147,15 @@ class SpectrogramExtractor(torch.nn.Module):
         return 1 + n_samples // self.hop_length
 
     # ------------------------------------------------------------------ batched device path
-    def _launch(self, audio: torch.Tensor, lens: torch.Tensor, noise: Optional[torch.Tensor], take_log: bool):
+    def _launch(self, audio: torch.Tensor, lens: torch.Tensor, noise: Optional[torch.Tensor], take_log: bool, tmax: int):
+        """``tmax``: the frames per row of the output, at least n_frames(audio row width); frames past a row's own are zeros"""
         n, lmax = audio.shape
-        tmax = self.n_frames(int(lmax))
         out = torch.empty(n, tmax, self.n_mels, dtype=torch.float32, device=audio.device)
         check(lib.w2l_logmel(ptr(audio), ptr(lens), ptr(noise), self.dithering, self.preemph, n, lmax, ptr(self.window),
                              self.win_length, self.n_fft, self.hop_length, ptr(self._fbT), ptr(self._fb_range), self.n_mels,
                              int(take_log),
                              float(self.log_zero_guard_value), ptr(out), tmax, stream_ptr()), 'w2l_logmel')
-        return out, tmax
+        return out
 
     def _stage(self, signals: Sequence, noise, rates=None, speeds=None, augment=None):
         dev = self.fb.device
@@ -194,7 +195,7 @@ class SpectrogramExtractor(torch.nn.Module):
                 noise_d[i, :z.shape[0]] = z.to(dev)
         return audio, lens_d, noise_d, lens
 
-    def extract_batch(self, signals: Sequence, noise=None, rates=None, speeds=None, augment=None):
+    def extract_batch(self, signals: Sequence, noise=None, rates=None, speeds=None, augment=None, pad_frames=None):
         """signals: N 1-D float arrays (any lengths).  noise: None = draw the dither on the device, False = no dither, or N
         arrays of N(0,1) draws (parity tests inject the reference's).  Returns (inputs fp32 [N, n_mels, T_max] on the
         device, zero beyond each utterance's frames; input_lengths IntTensor [N] on the host) -- _collator's layout.
@@ -202,9 +203,18 @@ class SpectrogramExtractor(torch.nn.Module):
         w2l_resample (data/resample.py) first; lengths, the dither and the returned input_lengths are those of the resampled
         rows (noise arrays, if given, are at the resampled lengths).  Both None, or every row at 1/1: the plain path's launches.
         augment: (a WaveformAugment, the plan its draw() returned for these N rows) -- reverberation and noise on the staged
-        waveforms, after the resampler and before the dither (data/augment_wave.py); a plan that selects nothing adds no launch."""
+        waveforms, after the resampler and before the dither (data/augment_wave.py); a plan that selects nothing adds no launch.
+        pad_frames: the output is [N, n_mels, pad_frames] instead: its first T_max columns are what the call without it returns,
+        the rest zeros, input_lengths unchanged (length-bucketed batches, data/bucketing.py).  An int, or a callable T_max -> int
+        (T_max is known only after resampling and speed perturbation); a width below T_max is a ValueError."""
         audio, lens_d, noise_d, lens = self._stage(signals, noise, rates, speeds, augment)
-        logmel, tmax = self._launch(audio, lens_d, noise_d, True)
+        tmax = self.n_frames(int(audio.shape[1]))
+        if pad_frames is not None:
+            width = int(pad_frames(tmax) if callable(pad_frames) else pad_frames)
+            if width < tmax:
+                raise ValueError(f'pad_frames={width} is below the T_max of this batch ({tmax} frames)')
+            tmax = width
+        logmel = self._launch(audio, lens_d, noise_d, True, tmax)
         n = audio.shape[0]
         mean = torch.empty(n, self.n_mels, dtype=torch.float32, device=audio.device)
         std = torch.empty_like(mean)
@@ -217,7 +227,7 @@ class SpectrogramExtractor(torch.nn.Module):
     def _get_spect(self, audio, noise=None):
         """mel power spectrogram [1, n_mels, T] (data_loader.py:64-72)"""
         a, lens_d, noise_d, _ = self._stage([audio], None if noise is None else [noise])
-        out, _ = self._launch(a, lens_d, noise_d, False)
+        out = self._launch(a, lens_d, noise_d, False, self.n_frames(int(a.shape[1])))
         return out.transpose(1, 2).contiguous()
 
     def extract(self, signal, noise=None):
@@ -325,13 +335,17 @@ def _pad_targets(targets):
     return tg, target_lengths
 
 
-def _collator(batch):
+def _collator(batch, ladder=None, align=16):
     """(spect, target, path, text) items -> (inputs [N, F, T_max] right-zero-padded, input_lengths, targets [N, S_max]
-    zero-padded int32, target_lengths, paths, texts) -- data_loader.py:149-158.  Spectrograms may live on the device."""
+    zero-padded int32, target_lengths, paths, texts) -- data_loader.py:149-158.  Spectrograms may live on the device.
+    ``ladder`` (ascending rungs, or a callable T_max -> width): the inputs are zero-padded to the smallest rung at or above
+    T_max instead, above the top rung to the next multiple of ``align`` (data/bucketing.py); input_lengths are unchanged."""
     inputs, targets, file_paths, texts = zip(*batch)
     inputs = [torch.as_tensor(x) for x in inputs]
     input_lengths = torch.IntTensor([x.shape[1] for x in inputs])
     longest = int(input_lengths.max())
+    if ladder is not None:
+        longest = int(ladder(longest)) if callable(ladder) else rung_for(ladder, longest, align)[0]
     out = torch.zeros(len(inputs), inputs[0].shape[0], longest, dtype=torch.float32, device=inputs[0].device)
     for i, x in enumerate(inputs):
         out[i, :, :x.shape[1]] = x
@@ -353,9 +367,16 @@ class _RawItems(Dataset):
 
 class BatchAudioDataLoader(DataLoader):
     """DataLoader yielding the reference's 6-tuple batches (data_loader.py:160-163).  For a SpectrogramDataset the
-    features of the whole batch are computed on the GPU in one pass from the raw audio."""
+    features of the whole batch are computed on the GPU in one pass from the raw audio.
+    ``ladder`` (ascending rungs, data/bucketing.choose_ladder; None = off): every batch is padded to the smallest rung at or
+    above its T_max -- the value after resampling and speed perturbation -- instead of to T_max itself, so that the stream of
+    step shapes is a small repeating set.  A batch above the top rung is padded to the next multiple of ``align``, counted in
+    ``off_ladder``, and still trains.  Usually paired with ``batch_sampler=BucketBatchSampler(...)``."""
 
-    def __init__(self, dataset, *args, **kwargs):
+    def __init__(self, dataset, *args, ladder=None, align=16, **kwargs):
+        self.ladder = None if ladder is None else [int(r) for r in ladder]
+        self.align = int(align)
+        self.off_ladder = 0
         self._spect_ds = dataset if isinstance(dataset, SpectrogramDataset) else None
         if self._spect_ds is not None:
             if kwargs.get('num_workers', 0):
@@ -364,7 +385,16 @@ class BatchAudioDataLoader(DataLoader):
             self.collate_fn = self._device_collate
         else:
             super().__init__(dataset, *args, **kwargs)
-            self.collate_fn = _collator
+            self.collate_fn = _collator if self.ladder is None else self._ladder_collate
+
+    def _pad_width(self, tmax: int) -> int:
+        width, on = rung_for(self.ladder, tmax, self.align)
+        if not on:
+            self.off_ladder += 1
+        return width
+
+    def _ladder_collate(self, batch):
+        return _collator(batch, self._pad_width)
 
     def _device_collate(self, batch):
         ds = self._spect_ds
@@ -377,6 +407,7 @@ class BatchAudioDataLoader(DataLoader):
         augment = None
         if ds.wave_augment is not None and ds.wave_augment.active:
             augment = (ds.wave_augment, ds.wave_augment.draw(len(audio)))
-        inputs, input_lengths = ds.extractor.extract_batch(audio, rates=rates, speeds=speeds, augment=augment)
+        inputs, input_lengths = ds.extractor.extract_batch(audio, rates=rates, speeds=speeds, augment=augment,
+                                                           pad_frames=None if self.ladder is None else self._pad_width)
         tg, target_lengths = _pad_targets(targets)
         return inputs, input_lengths, tg, target_lengths, file_paths, texts

@@ -58,7 +58,8 @@ def root_config(model: str = 'wav2letter', **model_kw):
     return to_cfg(dict(data=dict(train_manifest='???', val_manifest='???', batch_size=4, mel_spec=m['input_size'],
                                  audio_conf=dict(m['audio_conf']), resample=False, speed_perturb=None,
                                  noise_manifest=None, noise_prob=0.5, snr_db='5,20', rir_manifest=None, rir_prob=0.5,
-                                 rir_max_seconds=0.5),
+                                 rir_max_seconds=0.5, bucket_rungs=0, bucket_align=16, bucket_shuffle=True, bucket_seed=0,
+                                 drop_last=False),
                        model=m, trainer=dict(default_root_dir='.', max_epochs=5, max_steps=None, gpus=0)))
 
 

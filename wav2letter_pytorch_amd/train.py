@@ -5,7 +5,8 @@ Hydra / Lightning:
            data.val_manifest=val.csv [model=jasper] [model.mid_layers=20] [trainer.max_epochs=1] \\
            [data.resample=true] [data.speed_perturb=0.9,1.0,1.1] \\
            [data.rir_manifest=rirs.csv data.rir_prob=0.5 data.rir_max_seconds=0.5] \\
-           [data.noise_manifest=noise.csv data.noise_prob=0.5 data.snr_db=5,20] ...
+           [data.noise_manifest=noise.csv data.noise_prob=0.5 data.snr_db=5,20] \\
+           [data.bucket_rungs=6 data.bucket_align=16 data.bucket_shuffle=true data.bucket_seed=0 data.drop_last=false] ...
 
 Same override syntax and config keys as ``python train.py ...``; without ``--config-dir`` the built-in copy of the
 hyper-parameters (defaults.py) is used.  Manifests, labels, feature extraction and batching are data/data_loader.py's;
@@ -18,13 +19,17 @@ column; data/augment_wave.py) augment the training waveforms on the GPU: with pr
 convolved with one of the room impulse responses (each cut ``data.rir_max_seconds`` after its peak), then with probability
 ``data.noise_prob`` a noise clip is added at an SNR drawn from ``data.snr_db=lo,hi``.  Validation is never augmented.
 ``model.scheduler_interval=step`` steps the learning-rate scheduler after every optimizer step instead of once per epoch
-(warm-up schedules; ``model.optimizer._target_=torch.optim.AdamW`` then runs as optim.FusedAdamW without re-recording)."""
+(warm-up schedules; ``model.optimizer._target_=torch.optim.AdamW`` then runs as optim.FusedAdamW without re-recording).
+``data.bucket_rungs=K`` (0, the default: off) batches utterances of similar length together and pads every batch to one of K
+widths chosen from the manifest (data/bucketing.py): the step then meets at most K + 1 shapes, which are tuned once and replayed,
+instead of a new one per batch; ``data.bucket_shuffle`` / ``data.bucket_seed`` shuffle the rows inside each width and the batch
+order per epoch, ``data.drop_last`` drops the one short batch."""
 from __future__ import annotations
 
 import os
 import sys
 
-from .config import _yaml_load, criterion_name, load_config, scheduler_interval, to_cfg
+from .config import _yaml_load, bucket_options, criterion_name, load_config, scheduler_interval, to_cfg
 from .launch import spawn_ranks, under_launcher
 
 # Nothing above maps libw2l_hip.so (or imports torch): with trainer.gpus=N this process only starts the ranks, and a launch
@@ -80,7 +85,9 @@ def get_data_loaders(labels, cfg, rank: int = 0, world: int = 1):
     """train.py:21-26.  With more than one rank each loader walks its own shard of the manifest: a DistributedSampler
     over the raw items (indices rank, rank + world, ...; the tail padded so every rank takes the same number of steps --
     a rank that ran out of batches early would leave the others waiting in a collective), which is what Lightning's DDP
-    injects into the reference's loaders."""
+    injects into the reference's loaders.  ``data.bucket_rungs`` > 0: length-bucketed batches instead (data/bucketing.py) -- each
+    loader gets a ladder chosen from its own manifest and a BucketBatchSampler sharded by rank, which takes the
+    DistributedSampler's place (it too gives every rank the same number of steps); validation is bucketed unshuffled."""
     from torch.utils.data.distributed import DistributedSampler
     from .data.data_loader import BatchAudioDataLoader, SpectrogramDataset
     from .data.augment_wave import from_config
@@ -89,9 +96,19 @@ def get_data_loaders(labels, cfg, rank: int = 0, world: int = 1):
     resample = _truth(cfg.get('resample', False))
     factors = parse_speed_factors(cfg.get('speed_perturb'))         # the train loader only: validation is never perturbed
     wave = from_config(cfg, int(cfg.audio_conf['sample_rate']))     # None unless data.noise_manifest / data.rir_manifest is set
-    for manifest, perturb, augment in ((cfg.train_manifest, factors, wave), (cfg.val_manifest, None, None)):
+    bucket = bucket_options(cfg)
+    for train, (manifest, perturb, augment) in ((True, (cfg.train_manifest, factors, wave)), (False, (cfg.val_manifest, None, None))):
         ds = SpectrogramDataset(manifest, cfg.audio_conf, labels, mel_spec=cfg.mel_spec, resample=resample, speed_perturb=perturb,
                                 wave_augment=augment)
+        if bucket['rungs']:
+            from .data.bucketing import BucketBatchSampler, choose_ladder, nominal_frames
+            frames, align = nominal_frames(ds), bucket['align']
+            # a slowed-down utterance is longer than its manifest row says: the top rung covers the slowest factor
+            ladder = choose_ladder(frames, bucket['rungs'], align, headroom=max(1.0, 1.0 / min(perturb)) if perturb else 1.0)
+            sampler = BucketBatchSampler(frames, cfg.batch_size, ladder, shuffle=train and bucket['shuffle'], seed=bucket['seed'],
+                                         drop_last=train and bucket['drop_last'], num_replicas=world, rank=rank)
+            loaders.append(BatchAudioDataLoader(ds, batch_sampler=sampler, ladder=ladder, align=align))
+            continue
         kw = {}
         if world > 1:
             kw['sampler'] = DistributedSampler(range(len(ds)), num_replicas=world, rank=rank, shuffle=False)
@@ -146,6 +163,7 @@ def _check_augment(cfg):
     from .data.augment_wave import check_config
     if cfg.get('data') is not None:
         check_config(cfg.data)
+        bucket_options(cfg.data)
 
 
 def _requested_gpus(cfg) -> int:

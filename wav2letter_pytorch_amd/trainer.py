@@ -5,7 +5,8 @@
 ``validation_step`` with their ``log_dict`` metrics, one checkpoint per epoch under ``default_root_dir``.
 
 Data parallel (one process per GPU, launch.py / torchrun): every rank runs this loop on its own shard of the
-manifest (train.py attaches a DistributedSampler, as Lightning's DDP does), gradients are averaged by the
+manifest (train.py attaches a DistributedSampler, as Lightning's DDP does, or a rank-sharded BucketBatchSampler with
+``data.bucket_rungs``; ``set_epoch`` is called on either), gradients are averaged by the
 ``distributed.GradReducer`` attached to the model; only rank 0 prints and writes checkpoints.
 
 Checkpoints carry Lightning's keys: ``state_dict`` (reference parameter names), ``epoch``, ``global_step``,
@@ -82,6 +83,7 @@ class Trainer:
         self.current_epoch = 0
         self.logged = []
         self.val_logged = []                 # one dict of epoch-mean validation metrics per epoch
+        self.bucket_logged = []              # one dict per epoch of a length-bucketed train loader (its ``ladder`` is set)
 
     @property
     def global_rank(self) -> int:
@@ -182,17 +184,28 @@ class Trainer:
                      '; eager step (W2L_REPLAY=0)')
                   + ('; string metrics scored behind backward()' if getattr(model, 'async_metrics', False) else '')
                   + (f'; gradient clipping: {self.gradient_clip_algorithm} {self.gradient_clip_val:g}' if self.gradient_clip_val else ''))
+        ladder = getattr(train_dataloader, 'ladder', None)          # length-bucketed batches (data/bucketing.py)
+        if ladder is not None and _replay.ENABLED and len(ladder) + 1 > _replay.MAX_GROUPS:
+            self._say(f'{len(ladder)} rungs and the short last batch are {len(ladder) + 1} step shapes, above the '
+                      f'{_replay.MAX_GROUPS} kept recorded (W2L_REPLAY_MAX_SHAPES): the least recently used shape is re-recorded')
         done = self.max_steps is not None and self.global_step >= self.max_steps
         for epoch in range(first_epoch, self.max_epochs):
             if done:
                 break
             self.current_epoch = epoch
-            sampler = getattr(train_dataloader, 'sampler', None)
-            if hasattr(sampler, 'set_epoch'):
-                sampler.set_epoch(epoch)
+            for sampler in (getattr(train_dataloader, 'sampler', None), getattr(train_dataloader, 'batch_sampler', None)):
+                if hasattr(sampler, 'set_epoch'):
+                    sampler.set_epoch(epoch)
             model.train()
             t0 = time.time()
+            if ladder is not None:
+                shapes, cells, valid, steps0 = set(), 0, 0, self.global_step
+                stats0 = {k: v for k, v in _replay.STATS.items() if isinstance(v, int)}
             for i, batch in enumerate(train_dataloader):
+                if ladder is not None:           # host values only: the shape and the (host) length vector
+                    shapes.add(tuple(batch[0].shape))
+                    cells += batch[0].shape[0] * batch[0].shape[-1]
+                    valid += int(batch[1].sum())
                 opt.zero_grad(set_to_none=True)
                 loss = model.training_step(batch, i)
                 loss.backward()
@@ -216,6 +229,14 @@ class Trainer:
                     done = True
                     break
             model.on_train_epoch_end()
+            if ladder is not None:
+                rec = dict(epoch=epoch, steps=self.global_step - steps0, ladder=list(ladder), shapes=sorted(shapes),
+                           padded_share=(cells - valid) / max(valid, 1), off_ladder=getattr(train_dataloader, 'off_ladder', 0),
+                           tuned_shapes=len(_E._tuned_shapes), **{k: _replay.STATS[k] - v for k, v in stats0.items()})
+                self.bucket_logged.append(rec)
+                self._say(f'epoch {epoch} buckets: ladder {rec["ladder"]}, padding {100 * rec["padded_share"]:.1f} % of the valid '
+                          f'frames, {len(shapes)} step shapes in {rec["steps"]} steps ({rec["off_ladder"]} batches off the ladder so '
+                          'far); replay ' + ' '.join(f'{k}=+{rec[k]}' for k in stats0))
             for sch, every in per_epoch:
                 if (epoch + 1) % every == 0:
                     sch.step()
