@@ -618,6 +618,53 @@ int w2l_ctc_beam_search_lm(const float* probs, const int32_t* sizes, int N, int 
                            int blank, int end_index, int space_index, int k, double alpha, double beta, double prune,
                            int log_probs, const w2l_ngram_lm_t* lm, int order, void* workspace, int64_t workspace_bytes,
                            void* out, void* stream);
+/* ---- ASG prefix beam search and forced alignment (asg_beam.py; host restatements: asg_prefix_beam_search,
+ *      asg_viterbi_align_host): what w2l_ctc_beam_search / _lm / w2l_ctc_align are to a CTC model, for a model trained with
+ *      the ASG criterion (no blank; learned transitions; label repeat_index stands for "the previous letter again") ---- */
+/* workspace bytes for w2l_asg_beam_search (per utterance: a trie of k*T+1 nodes of 12 bytes and its intern table); -1 if out
+ * of range: A outside 1..64, k outside 1..64, T >= 2^24 or k*T >= 2^29 */
+int64_t w2l_asg_beam_search_workspace_bytes(int N, int T, int A, int k);
+/* One workgroup per utterance, one launch for the batch, masses as fp64 natural logs.  x fp32 [N][T][A] contiguous (any real
+ * scores), transitions fp32 [A][A] (g[i][j]: label j at frame t after label i at frame t-1), sizes int32 [N] (NULL: T).  A
+ * hypothesis is an ENCODED label sequence (no two neighbours equal) with one mass, the log-sum over the frame paths that read
+ * it: M_0((c)) = x[0][c]; at frame t a member e with last label l stays (M(e) + g[l][l] + x[t][l]) and is extended by every
+ * c != l (M(e) + g[l][c] + x[t][c]; an extension that is no member but was a candidate of frame t-1 also keeps its own
+ * M_{t-1} + g[c][c] + x[t][c]), log-added in beam order, labels ascending.  Label c takes part in frame t if x[t][c] >
+ * log(prune) or it is the frame's first argmax (prune <= 0: every label).  Rank: M + beta * log(words + 1), the words of the
+ * DECODED text (every repeat label read as the decoded character before it, a leading one dropped) counted as
+ * w2l_ctc_beam_search counts them; ties in first-insertion order; the k best are the next beam.  No end character.
+ * label_info_host[A]: bits 0-7, 9 and 10 as in w2l_ctc_beam_search.  out: that search's layout, double score[N][k] | int32
+ * len[N][k] (-1: empty slot) | int32 status[N] (1: a NaN score or transition) | int32 labels[N][k][T] (ENCODED labels).
+ * Limits: 1 <= k <= 64, 1 <= A <= 64 (k = 64 with A = 64 takes 138 KB of dynamic LDS beside 9 KB static). */
+int w2l_asg_beam_search(const float* x, const float* transitions, const int32_t* sizes, int N, int T, int A,
+                        const int32_t* label_info_host, int repeat_index, int k, double beta, double prune, void* workspace,
+                        int64_t workspace_bytes, void* out, void* stream);
+/* workspace bytes for w2l_asg_beam_search_lm (plus a 64-byte LM state per trie node); -1 if out of range */
+int64_t w2l_asg_beam_search_lm_workspace_bytes(int N, int T, int A, int k, int order);
+/* w2l_asg_beam_search with the tables of w2l_ctc_beam_search_lm (label_info_host bit 11, space_index as there).  A trie node's
+ * LM state spells its DECODED characters (an r after a letter spells the letter again, an r after a space closes nothing, a
+ * leading r spells nothing).  The weight of member i, alpha * ln 10 * (log10 of its text's words with </s>), is added to
+ * exactly one contribution: the extension of member i by the space label, where member i's last decoded character is not the
+ * space and its text has a character other than ' '.  out: w2l_asg_beam_search's layout followed by float lm_log10[N][k]. */
+int w2l_asg_beam_search_lm(const float* x, const float* transitions, const int32_t* sizes, int N, int T, int A,
+                           const int32_t* label_info_host, int repeat_index, int space_index, int k, double alpha, double beta,
+                           double prune, const w2l_ngram_lm_t* lm, int order, void* workspace, int64_t workspace_bytes,
+                           void* out, void* stream);
+/* workspace bytes for w2l_asg_align: 0 while the moves fit in LDS, else N * ceil(T / 16) * (states rounded up to the block's)
+ * * 4; -1 if out of range (T > 32768, Smax > 4095, A outside 1..64) */
+int64_t w2l_asg_align_workspace_bytes(int N, int T, int A, int Smax);
+/* The best frame path of a given target under ASG (the Viterbi form of w2l_asg_loss's Z_tgt), fp32, one workgroup per
+ * utterance.  Arguments, in-place target addressing (row and length strides) and outputs as w2l_ctc_align.  encoded = 0: rows
+ * are RAW transcripts, repeat-encoded on the device as w2l_asg_loss does (a raw label equal to repeat_index: status 2);
+ * encoded = 1: rows are encoded already (rank 0 of w2l_asg_beam_search's out buffer; repeat_index allowed, in front too; two
+ * equal neighbours: status 2).  Over the encoded target y_0 .. y_{S-1}: score[0][0] = x[0][y_0], score[t][s] =
+ * max(score[t-1][s] + g[y_s][y_s], score[t-1][s-1] + g[y_{s-1}][y_s]) + x[t][y_s], a tie goes to staying, the path ends in
+ * state S-1 at the last frame.  status: 0 ok, 1 infeasible (S < 1, S > input_lengths[n], or no finite score), 2 a bad label.
+ * path[N][T]: the ENCODED label of each frame; starts / ends [N][Smax]: first / last frame of each target position. */
+int w2l_asg_align(const float* x, const float* transitions, const int32_t* input_lengths, const int32_t* targets,
+                  int64_t target_stride, const int32_t* target_lengths, int64_t length_stride, int N, int T, int A, int Smax,
+                  int repeat_index, int encoded, void* workspace, int64_t workspace_bytes, float* score, int32_t* status,
+                  int32_t* path, int32_t* starts, int32_t* ends, void* stream);
 /* host-side edit distance over int32 symbol arrays */
 int w2l_levenshtein_host(const int32_t* a_host, int na, const int32_t* b_host, int nb);
 /* ConvCTCASR.add_string_metrics (base_asr_models.py:53-69) for one batch in ONE host call (no device work, no interpreter

@@ -11,7 +11,8 @@ _PUBLIC = {
     'ConvCTCASR': '.base_asr_models', 'CTCLoss': '.ctc_loss', 'Decoder': '.decoder', 'GreedyDecoder': '.decoder',
     'Conv1dBlock': '.wav2letter', 'Wav2Letter': '.wav2letter', 'Jasper': '.jasper', 'JasperBlock': '.jasper',
     'MaskedConv1d': '.jasper', 'ctc_forced_align': '.alignment', 'viterbi_align_host': '.alignment',
-    'ASGLoss': '.asg', 'ASGDecoder': '.asg',
+    'ASGLoss': '.asg', 'ASGDecoder': '.asg', 'ASGBeamSearchDecoder': '.asg_beam', 'ASGBeamSearchLMDecoder': '.asg_beam',
+    'asg_forced_align': '.asg_beam',
 }
 __all__ = sorted(_PUBLIC)
 

@@ -169,6 +169,14 @@ _SIGNATURES = {
     'w2l_ctc_beam_search_lm_workspace_bytes': (c_i64, [c_i, c_i, c_i, c_i]),
     'w2l_ctc_beam_search_lm': (c_i, [c_p, c_p, c_i, c_i, c_i, c_p, c_i, c_i, c_i, c_i, C.c_double, C.c_double, C.c_double, c_i,
                                      C.POINTER(LmTables), c_i, c_p, c_i64, c_p, c_p]),
+    'w2l_asg_beam_search_workspace_bytes': (c_i64, [c_i, c_i, c_i, c_i]),
+    'w2l_asg_beam_search': (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_i, c_i, C.c_double, C.c_double, c_p, c_i64, c_p, c_p]),
+    'w2l_asg_beam_search_lm_workspace_bytes': (c_i64, [c_i, c_i, c_i, c_i, c_i]),
+    'w2l_asg_beam_search_lm': (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_i, c_i, c_i, C.c_double, C.c_double, C.c_double,
+                                     C.POINTER(LmTables), c_i, c_p, c_i64, c_p, c_p]),
+    'w2l_asg_align_workspace_bytes': (c_i64, [c_i, c_i, c_i, c_i]),
+    'w2l_asg_align': (c_i, [c_p, c_p, c_p, c_p, c_i64, c_p, c_i64, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_i64, c_p, c_p, c_p, c_p,
+                            c_p, c_p]),
     'w2l_logmel': (c_i, [c_p, c_p, c_p, c_f, c_f, c_i, c_i64, c_p, c_i, c_i, c_i, c_p, c_p, c_i, c_i, c_f, c_p, c_i, c_p]),
     'w2l_feature_normalize': (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_p, c_p, c_p, c_p]),
     'w2l_zero_rects': (c_i, [c_p, c_i, c_i, c_i, c_p, c_i, c_p]),
@@ -294,6 +302,8 @@ TRACE_NAMES = {
     'w2l_dwconv_wgrad': 'dw_wgrad_kernel', 'w2l_argmax': 'argmax_kernel', 'w2l_novograd_pack': 'novograd_pack_kernel',
     'w2l_ctc_beam_search': 'ctc_beam_search_kernel', 'w2l_ctc_beam_search_lm': 'ctc_beam_search_kernel<LM>',
     'w2l_ngram_lm_build': 'ngram_insert_kernel', 'w2l_ctc_align': 'ctc_align_kernel',
+    'w2l_asg_beam_search': 'asg_beam_search_kernel', 'w2l_asg_beam_search_lm': 'asg_beam_search_kernel<LM>',
+    'w2l_asg_align': 'asg_align_kernel',
 }
 _trace = {'rows': None, 'saved': {}, 'pool': []}
 

@@ -13,7 +13,8 @@ as "the previous letter again": within a run of equal labels the 2nd, 4th, ... m
 ``lll -> l_l``).  The loss kernel encodes raw transcripts on the device; ``encode_repeats`` / ``decode_repeats`` are the host
 reference of that rule and the core of the decoder.
 
-Kernels: csrc/asg.hip (w2l_asg_loss, w2l_asg_viterbi).  There is no CPU path."""
+Kernels: csrc/asg.hip (w2l_asg_loss, w2l_asg_viterbi).  There is no CPU path.  The prefix beam search (with an n-gram model),
+n-best lists and forced alignment of an ASG model live in asg_beam.py (csrc/asg_beam.hip)."""
 from __future__ import annotations
 
 import numpy as np
@@ -219,3 +220,21 @@ class ASGDecoder(Decoder):
         if return_offsets:
             return strings, [[frames] for _, frames in decoded]
         return strings
+
+    def align(self, probs, texts, sizes=None, transitions=None):
+        """forced alignment of ``texts`` (one string per utterance, or one string for a [T, labels] input) to the scores under
+        ASG (asg_beam.asg_forced_align: the texts are repeat-encoded on the device) -> ``(offsets, end_offsets)`` in
+        ``Decoder.align``'s format: ``offsets[n] = [IntTensor]``, the first frame of each character of texts[n], ``end_offsets``
+        its last, so ``get_time_per_word(text, starts, ratio, end_offsets=ends)`` applies.  A text that no frame path spells (empty,
+        or more characters than frames) is a ValueError."""
+        from .asg_beam import asg_forced_align
+        if isinstance(texts, str):
+            texts = [texts]
+        res = asg_forced_align(probs, self.transitions if transitions is None else transitions, list(texts),
+                               input_lengths=sizes, labels=list(self.labels), repeat_index=self.repeat_index)
+        if not res.feasible.all():
+            raise ValueError('ASGDecoder.align: no frame path spells the texts of utterances %s'
+                             % np.nonzero(~res.feasible)[0].tolist())
+        offsets = [[torch.IntTensor(res.starts[n, :len(text)].copy())] for n, text in enumerate(texts)]
+        end_offsets = [[torch.IntTensor(res.ends[n, :len(text)].copy())] for n, text in enumerate(texts)]
+        return offsets, end_offsets

@@ -173,6 +173,9 @@ def __getattr__(name):
     if name in ('GPUPrefixBeamSearchDecoder', 'GPUPrefixBeamSearchLMDecoder', 'prefix_beam_search_gpu'):
         from . import beam_search
         return getattr(beam_search, name)
+    if name in ('ASGBeamSearchDecoder', 'ASGBeamSearchLMDecoder', 'asg_beam_search_gpu', 'asg_forced_align'):
+        from . import asg_beam
+        return getattr(asg_beam, name)
     if name in ('ctc_forced_align', 'viterbi_align_host'):
         from . import alignment
         return getattr(alignment, name)

@@ -239,6 +239,10 @@ class _WgradJob:
     token: Optional[int] = None           # held-back jobs only: the optimizer's token of the backward pass that left it,
     order: int = 0                        # its place in the flush, and the unit in front of which the forward launches it
     at: Optional[int] = None
+    # the dW storage of a job computed into ``param.grad`` (StackEngine._materialize).  A record set's held-back job is computed
+    # again in every replayed step: it writes this buffer again, so the optimizer phase recorded with its address names memory
+    # that stays allocated, at an address that does not depend on what the caching allocator hands out that step
+    grad_buf: Optional[torch.Tensor] = None
 
     # shared-halo layout (include/w2l_hip.h): dy is [halo zero rows][utt 0: Tout rows][halo zero rows][utt 1] ..., so utterance
     # n starts at row halo + n*(Tout+halo); x is [N][src.rows][CP], entered src.pad_l - conv.pad_l rows in (the conv's own padding)
@@ -1961,7 +1965,7 @@ class StackEngine:
         pending = []
         sink = self._reduce_sink(pending)
         for r in recs:
-            self._wgrad_now(r, {}, sink=sink)
+            self._wgrad_now(r, {}, sink=sink, keep=True)
             w, g, _, work = pending.pop()
             if work is not None:
                 work.finish()
@@ -2174,9 +2178,10 @@ class StackEngine:
         _tune_state['dirty'] = True
         return best[1]
 
-    def _wgrad_now(self, job: _WgradJob, grads, fork=None, sink=None):
+    def _wgrad_now(self, job: _WgradJob, grads, fork=None, sink=None, keep=False):
         """dW through w2l_conv1d_wgrad, written in the parameter's own physical layout when possible.
-        fork=(main, side): allocate on main, launch on side after an event recorded on main."""
+        fork=(main, side): allocate on main, launch on side after an event recorded on main.  keep: the job holds on to its dW
+        storage and takes it again the next time it is computed (_WgradJob.grad_buf)."""
         conv, pk, src, f8, Tout = job.conv, job.pk, job.src, job.f8, job.Tout
         w, dev = conv.weight, conv.weight.device
         N, kw = job.N, conv.kernel
@@ -2211,10 +2216,21 @@ class StackEngine:
         if (dw is not None and need_zero and w.grad is None and dw.device == dev and dw.is_contiguous()
                 and tuple(dw.shape) == job.dw_shape):
             need_zero = False
+        elif (keep and job.grad_buf is not None and w.grad is None and job.grad_buf.device == dev
+                and tuple(job.grad_buf.shape) == job.dw_shape):
+            # Only a record set's job comes here twice (an eager backward pass makes new jobs), so this is the static-gradient
+            # rule of every replayed step.  ``w.grad is None``: autograd is not about to add into that tensor (zero_grad with
+            # set_to_none=False, or a second backward pass, take a fresh buffer as before).  Its last reader was the previous
+            # step's update of this weight, possibly on the optimizer's stream: this step's forward convolution of the layer
+            # waited for that update (weight_event), so the caller's stream is already ordered after it; a data-parallel
+            # all-reduce of it was finished inside _materialize.
+            dw = job.grad_buf
         else:
             # allocated on the main stream (the caching allocator then owns it there), zero-filled on the side stream:
             # the fill of a split-K gradient is as far off the critical path as the kernel that accumulates into it
             dw = torch.empty(job.dw_shape, dtype=torch.float32, device=dev)
+        if keep:
+            job.grad_buf = dw
         with self._on_side(fork, (dw,) + job.held()):
             if need_zero:
                 zero_(dw)

@@ -38,10 +38,12 @@ def decode_batch(model, decoder, out, out_lens, word_times: bool = False):
         # a model trained with ASG has no blank: the CTC decoders and the CTC forced alignment do not apply to its output
         from .asg import ASGDecoder
         if not isinstance(decoder, ASGDecoder):
-            raise NotImplementedError(f'{type(decoder).__name__} on a model with criterion asg: a transition-aware beam search '
-                                      'is not implemented; use the model\'s own decoder (asg.ASGDecoder, Viterbi)')
+            raise NotImplementedError(f'{type(decoder).__name__} on a model with criterion asg: the CTC decoders and the CTC beam '
+                                      'search know no transitions; use an asg.ASGDecoder (the model\'s own Viterbi decoder, or '
+                                      'asg_beam.ASGBeamSearchDecoder / ASGBeamSearchLMDecoder)')
         if word_times:
-            raise NotImplementedError('word_times under criterion asg: forced alignment under ASG is not implemented')
+            raise NotImplementedError('word_times under criterion asg is not wired in here: forced alignment under ASG is '
+                                      'ASGDecoder.align (asg_beam.asg_forced_align)')
     hyps = decoder.decode(out, out_lens)
     hyps = [h[0] if isinstance(h, (list, tuple)) else h for h in hyps]
     if not word_times:

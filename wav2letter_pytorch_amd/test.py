@@ -2,14 +2,15 @@
 shipped:
 
     python -m wav2letter_pytorch_amd.test [--config-dir /path/to/configuration] model_path=run/epoch=4-step=900.ckpt \\
-           data.test_manifest=test.csv [model=jasper] [model.mid_layers=20] [decoder=greedy|beam|beam_lm] [lm_path=lm.arpa] \\
+           data.test_manifest=test.csv [model=jasper] [model.mid_layers=20] [decoder=greedy|beam|beam_lm|asg_beam|asg_beam_lm] [lm_path=lm.arpa] \\
            [beam.k=5] [beam.alpha=0.3] [beam.beta=5] [beam.prune=1e-3] [print_samples=K | print_all=true] \\
            [output=hyps.jsonl] [word_times=true] [data.resample=true]
 
 ``train.py``'s override syntax and config tree.  The forward pass is ``model.infer`` (one fused launch per convolution);
 ``test_loss``, corpus-level ``test_cer`` / ``test_wer`` and ``test_len_ratio`` are printed and returned.  ``output=`` writes one
 JSON line per utterance: path, text, hypothesis, character and word errors (and each word's start / end seconds with
-``word_times=true``, by forced alignment of the hypothesis)."""
+``word_times=true``, by forced alignment of the hypothesis).  ``decoder=asg_beam|asg_beam_lm`` are the beam searches of a model
+trained with ``model.criterion=asg`` (asg_beam.py), bound to the checkpoint's learned transitions."""
 from __future__ import annotations
 
 import json
@@ -17,7 +18,9 @@ import sys
 
 from .train import build_config as _train_config
 
-DECODERS = ('greedy', 'beam', 'beam_lm')
+DECODERS = ('greedy', 'beam', 'beam_lm', 'asg_beam', 'asg_beam_lm')
+LM_DECODERS = ('beam_lm', 'asg_beam_lm')
+ASG_DECODERS = ('asg_beam', 'asg_beam_lm')
 BEAM_DEFAULTS = dict(k=5, alpha=0.3, beta=5, prune=1e-3)
 
 
@@ -27,8 +30,9 @@ def _truth(v) -> bool:
 
 def build_config(argv):
     """the config tree of ``train.build_config`` plus the evaluation keys, checked: ``model_path`` and
-    ``data.test_manifest`` are required (SystemExit naming the key), ``decoder`` is one of greedy / beam / beam_lm,
-    ``lm_path`` belongs to ``decoder=beam_lm`` only (and that decoder needs it)."""
+    ``data.test_manifest`` are required (SystemExit naming the key), ``decoder`` is one of greedy / beam / beam_lm /
+    asg_beam / asg_beam_lm (the last two only with ``model.criterion=asg``), ``lm_path`` belongs to ``decoder=beam_lm`` and
+    ``decoder=asg_beam_lm`` only (and those decoders need it)."""
     cfg = _train_config(argv)
     if cfg.get('model_path') in (None, '???', ''):
         raise SystemExit('model_path is required (e.g. model_path=/path/to/epoch=0-step=100.ckpt)')
@@ -38,10 +42,13 @@ def build_config(argv):
     if cfg.decoder not in DECODERS:
         raise SystemExit(f'decoder={cfg.decoder!r} is not one of {", ".join(DECODERS)}')
     lm = cfg.get('lm_path')
-    if lm and cfg.decoder != 'beam_lm':
-        raise SystemExit(f'lm_path is given but decoder={cfg.decoder}: a language model needs decoder=beam_lm')
-    if cfg.decoder == 'beam_lm' and not lm:
-        raise SystemExit('decoder=beam_lm needs lm_path=/path/to/model.arpa')
+    if lm and cfg.decoder not in LM_DECODERS:
+        raise SystemExit(f'lm_path is given but decoder={cfg.decoder}: a language model needs decoder=beam_lm '
+                         '(or asg_beam_lm under model.criterion=asg)')
+    if cfg.decoder in LM_DECODERS and not lm:
+        raise SystemExit(f'decoder={cfg.decoder} needs lm_path=/path/to/model.arpa')
+    if cfg.decoder in ASG_DECODERS and cfg.model.get('criterion', 'ctc') != 'asg':
+        raise SystemExit(f'decoder={cfg.decoder} decodes with learned transitions: it needs model.criterion=asg')
     beam = dict(BEAM_DEFAULTS)
     beam.update(cfg.get('beam') or {})
     unknown = sorted(set(beam) - set(BEAM_DEFAULTS))
@@ -52,12 +59,13 @@ def build_config(argv):
     cfg['print_all'] = _truth(cfg.get('print_all', False))
     cfg['word_times'] = _truth(cfg.get('word_times', False))
     if cfg.model.get('criterion', 'ctc') == 'asg':
-        # the beam searches and the forced alignment implement CTC's blank / collapse rules and know no transitions
-        if cfg.decoder != 'greedy':
-            raise NotImplementedError(f'decoder={cfg.decoder} under model.criterion=asg: a transition-aware beam search is not '
-                                      'implemented; use decoder=greedy (Viterbi decoding with the learned transitions)')
+        # decoder=beam|beam_lm and the CLI's word times implement CTC's blank / collapse rules and know no transitions
+        if cfg.decoder in ('beam', 'beam_lm'):
+            raise NotImplementedError(f'decoder={cfg.decoder} under model.criterion=asg: the CTC beam search knows no '
+                                      f'transitions; use decoder=asg_{cfg.decoder} (or decoder=greedy: Viterbi decoding)')
         if cfg.word_times:
-            raise NotImplementedError('word_times=true under model.criterion=asg: forced alignment under ASG is not implemented')
+            raise NotImplementedError('word_times=true under model.criterion=asg is not wired into the command line: forced '
+                                      'alignment under ASG is ASGDecoder.align (asg_beam.asg_forced_align)')
     cfg.setdefault('output', None)
     return cfg
 
@@ -67,6 +75,11 @@ def decoder_spec(cfg, log_probs: bool):
     labels = cfg.model.labels
     if cfg.decoder == 'greedy':
         return 'GreedyDecoder', dict(labels=labels)
+    if cfg.decoder in ASG_DECODERS:            # (``transitions`` is bound by main(), to the model's criterion)
+        kw = dict(labels=labels, k=int(cfg.beam.k), beta=float(cfg.beam.beta), prune=float(cfg.beam.prune))
+        if cfg.decoder == 'asg_beam':
+            return 'ASGBeamSearchDecoder', kw
+        return 'ASGBeamSearchLMDecoder', dict(lm_path=cfg.lm_path, alpha=float(cfg.beam.alpha), **kw)
     kw = dict(labels=labels, k=int(cfg.beam.k), alpha=float(cfg.beam.alpha), beta=float(cfg.beam.beta),
               prune=float(cfg.beam.prune), log_probs=log_probs)
     if cfg.decoder == 'beam':
@@ -74,9 +87,13 @@ def decoder_spec(cfg, log_probs: bool):
     return 'GPUPrefixBeamSearchLMDecoder', dict(lm_path=cfg.lm_path, **kw)
 
 
-def build_decoder(cfg, log_probs: bool):
+def build_decoder(cfg, log_probs: bool, transitions=None):
+    """``transitions``: the criterion of an ASG model (decoder=asg_beam|asg_beam_lm read its transitions at every call)"""
     from . import beam_search, decoder
     name, kw = decoder_spec(cfg, log_probs)
+    if name.startswith('ASG'):
+        from . import asg_beam
+        return getattr(asg_beam, name)(transitions=transitions, **kw)
     return getattr(decoder if name == 'GreedyDecoder' else beam_search, name)(**kw)
 
 
@@ -103,7 +120,9 @@ def main(argv=None):
     ds = SpectrogramDataset(cfg.data.test_manifest, cfg.data.audio_conf, cfg.model.labels, mel_spec=cfg.data.mel_spec,
                             resample=_truth(cfg.data.get('resample', False)))
     loader = BatchAudioDataLoader(ds, batch_size=cfg.data.batch_size)
-    if cfg.model.get('criterion', 'ctc') == 'asg':
+    if cfg.decoder in ASG_DECODERS:
+        dec = build_decoder(cfg, True, transitions=model.criterion)
+    elif cfg.model.get('criterion', 'ctc') == 'asg':
         dec = model.ctc_decoder              # decoder=greedy under asg: the model's Viterbi decoder, bound to its transitions
     else:
         dec = build_decoder(cfg, bool(getattr(model, 'infer_log_probs', True)))
