@@ -411,7 +411,9 @@ int w2l_quantize_e4m3_dyn(const void* src_bf16, int64_t n, const float* amax, vo
 /* The data gradient of a stride-1 nn.Conv1d FUSED with w2l_bn_act_bwd_reduce of the layer that produced the conv's input
  * (d describes that layer: bf16 y, one branch).  dxp [flat_rows][d->C] bf16 is the gradient wrt the padded activation,
  * computed over the shared-halo dy buffer as one sequence exactly like w2l_conv1d_igemm_ws(N = 1, Tout = flat_rows, w =
- * the flipped-tap operand); row v of it is padded row v % per of utterance v / per (per >= pad_l + d->T + pad_r).  The
+ * the flipped-tap operand); row v of it is padded row v % per of utterance v / per (per >= pad_l + d->T + pad_r, and
+ * flat_rows == d->N * per EXACTLY: a row beyond would be counted with the y, mask and lens of an utterance that does not
+ * exist, so any other flat_rows is rejected).  The
  * epilogue, which holds that gradient in registers, also writes partial[tile][2][d->C] -- per 128-row tile
  * (w2l_conv_stat_tiles(1, flat_rows) rows) the sums of g*gate and g*gate*xhat, every padded row counted with the gate
  * and xhat of its source frame (itself, or its mirror under reflect padding) -- so the separate reduction pass over dxp

@@ -1,6 +1,8 @@
 """Float64 references of the BatchNorm / dropout / activation family (csrc/bn_act.hip), restated from the formulas in
 include/w2l_hip.h and the kernels -- plain NumPy, nothing of the engine's Python.  Pinned by tests/test_cpu_bn_refs.py (torch
-float64 autograd, the published Philox known answers, planted defects), used by tests/test_gpu_bn_direct.py.
+float64 autograd, the published Philox known answers, planted defects), used by tests/test_gpu_bn_direct.py.  At the end: the
+data gradient fused with the backward reduce (conv_igemm.hip, EPI = 1), pinned by tests/test_cpu_dgrad_bnreduce_refs.py and
+used by tests/test_gpu_dgrad_bnreduce_direct.py.
 
 Bounds are carried as ``Tr`` (value, magnitude sum, rounding depth) exactly as kernel_refs.py derives them.  What is particular
 to this family:
@@ -289,22 +291,24 @@ def bn_act_fwd_ref(N, T, C, y, scale, shift, y2=None, scale2=None, shift2=None, 
 
 def fold_grad(dxp, N, T, C, pad_l, pad_r, pad_mode, defect=None):
     """gradient of every frame from a padded source [N][rows][C]: its own row plus, under reflect padding, the halo rows that
-    mirror it (t in [1, pad_l] on the left, t in [T-1-pad_r, T-2] on the right).  Returns (sum, sum of |.|, terms)"""
-    dxp = np.asarray(dxp, dtype=np.float64)
+    mirror it (t in [1, pad_l] on the left, t in [T-1-pad_r, T-2] on the right).  Returns (sum, sum of |.|, terms).
+    A tracked source (Tr: a gradient that is itself a computed value, dgrad_bnreduce_ref) folds its own magnitude sum; its
+    depth is the caller's to add (bn_act_bwd_ref)."""
+    mag = dxp.a if isinstance(dxp, Tr) else None
+    dxp = np.asarray(dxp.v if isinstance(dxp, Tr) else dxp, dtype=np.float64)
+    mag = np.abs(dxp) if mag is None else mag
     g = dxp[:, pad_l:pad_l + T].copy()
-    a = np.abs(g)
+    a = mag[:, pad_l:pad_l + T].copy()
     terms = np.ones(T, dtype=np.int64)
     if pad_mode == 1:
         for t in range(1, min(pad_l, T - 1) + 1):
-            v = dxp[:, pad_l - t]
-            g[:, t] += v
-            a[:, t] += np.abs(v)
+            g[:, t] += dxp[:, pad_l - t]
+            a[:, t] += mag[:, pad_l - t]
             terms[t] += 1
         hi = T - 3 if defect == 'fold_right_T2' else T - 2
         for t in range(max(T - 1 - pad_r, 0), hi + 1):
-            v = dxp[:, pad_l + 2 * (T - 1) - t]
-            g[:, t] += v
-            a[:, t] += np.abs(v)
+            g[:, t] += dxp[:, pad_l + 2 * (T - 1) - t]
+            a[:, t] += mag[:, pad_l + 2 * (T - 1) - t]
             terms[t] += 1
     return g, a, terms
 
@@ -321,18 +325,19 @@ def bn_act_bwd_ref(N, T, C, y, scale, shift, mean, invstd, srcs, y2=None, scale2
     if has2:
         y2 = np.asarray(y2, dtype=np.float64).reshape(N, T, C)
     z = preact(y, scale, shift, y2, scale2, shift2)
-    gv, ga, terms = None, None, 0
+    gv, ga, terms, src_d = None, None, 0, 0
     for dxp, pl, pr_, pm in srcs:
         v, a, t = fold_grad(dxp, N, T, C, pl, pr_, pm, defect)
         gv, ga = (v, a) if gv is None else (gv + v, ga + a)
         terms = terms + t
+        src_d = max(src_d, dxp.d if isinstance(dxp, Tr) else 0)        # a tracked source brings its own depth
     gate = np.ones((N, T, C), dtype=bool)
     for n, lim in enumerate(lens_limits(N, T, lens)):
         gate[n, lim:] = False
     masked = ~gate[:, :, :1]
     zv = z.v
     gk = Tr(1.0)
-    gd = int(terms.max()) - 1
+    gd = int(terms.max()) - 1 + src_d
     if p > 0:
         ik = inv_keep_f32(p)
         zv = zv * ik
@@ -655,3 +660,182 @@ def make_partial(rows, C, per_row, seed, const_channel=None):
         x[:, :, const_channel] = 1.5
     pr = np.stack([x.sum(1), (x * x).sum(1)], axis=1).astype(np.float32)
     return pr, rows * per_row
+
+
+# ---- the data gradient fused with the BatchNorm-backward reduce (conv_igemm_kernel EPI = 1, w2l_conv1d_dgrad_bnreduce_ws) ----
+
+DG_DEFECTS = ('dead_rows_counted', 'mirror_own_gate', 'lens_on_halo_row', 'mask_nibble', 'no_gk_grad')
+
+
+def dgrad_ref(dy, w, Kw, dil, halo, flat_rows):
+    """the flat data gradient of a stride-1 convolution over the WHOLE shared-halo buffer dy [halo + flat_rows][Cout] as one
+    sequence (w2l_conv1d_igemm_ws(N = 1, Tout = flat_rows) on the flipped-tap operand): row v reads dy rows v + (halo - hb) + k dil,
+    hb = (Kw - 1) dil, with w[:, :, Kw - 1 - k] (w [Cout][Cin][Kw]).  Returns Tr [flat_rows][Cin]: A = sum |dy| |w|, depth Kw Cout."""
+    dy, w = np.asarray(dy, dtype=np.float64), np.asarray(w, dtype=np.float64)
+    Cout, Cin, _ = w.shape
+    hb = (Kw - 1) * dil
+    assert halo >= hb and dy.shape == (halo + flat_rows, Cout)
+    v, a = np.zeros((flat_rows, Cin)), np.zeros((flat_rows, Cin))
+    for k in range(Kw):
+        r0 = halo - hb + k * dil
+        v += dy[r0:r0 + flat_rows] @ w[:, :, Kw - 1 - k]
+        a += np.abs(dy[r0:r0 + flat_rows]) @ np.abs(w[:, :, Kw - 1 - k])
+    return Tr(v, a, Kw * Cout)
+
+
+def _swap_nibbles(mask):
+    m = np.asarray(mask, dtype=np.uint8)
+    return ((m << 4) | (m >> 4)).astype(np.uint8)
+
+
+def _rowwise_sums(dx, per, N, T, C, y, scale, shift, mean, invstd, act, p, mask, lens, pad_l, pad_r, pad_mode, defect):
+    """a WRONG epilogue, for the planted defects only: every padded row (n, u) counted by itself with the gate and xhat of a
+    frame ts(u) -- the formulation in which the defects are mistakes of one line.  (defect = None is the right answer computed
+    the other way round; test_cpu_dgrad_bnreduce_refs.py holds it against the fold-first reference.)"""
+    Tp = pad_l + T + pad_r
+    u = np.arange(per)
+    raw = u - pad_l
+    live = np.broadcast_to(u < Tp if defect != 'dead_rows_counted' else np.ones(per, dtype=bool), (N, per)).copy()
+    out = (raw < 0) | (raw >= T)
+    if pad_mode == 1:
+        ts = np.where(raw < 0, -raw, np.where(raw >= T, 2 * (T - 1) - raw, raw))
+    else:
+        ts = raw
+        live &= ~out
+    ts = np.clip(ts, 0, T - 1)
+    if defect == 'mirror_own_gate':
+        ts = np.clip(raw, 0, T - 1)
+    lims = np.asarray(lens_limits(N, T, lens))
+    if lens is not None:
+        live &= (raw[None, :] if defect == 'lens_on_halo_row' else ts[None, :]) < lims[:, None]
+    z = preact(np.asarray(y, dtype=np.float64).reshape(N, T, C), scale, shift).v
+    gate = np.ones((N, T, C), dtype=bool)
+    gk = 1.0
+    if p > 0:
+        ik = inv_keep_f32(p)
+        z = z * ik
+        gate &= unpack_keep(_swap_nibbles(mask) if defect == 'mask_nibble' else mask, N, T, C)
+        gk = 1.0 if defect == 'no_gk_grad' else ik
+    if act == 1:
+        gate &= (z >= 0) & (z <= 20)
+    elif act == 2:
+        gate &= z > 0
+    w8 = (gate[:, ts] & live[:, :, None]) * gk                                     # [N][per][C]
+    xh = np.zeros((N, T, C)) if mean is None else (np.asarray(y, dtype=np.float64).reshape(N, T, C) - mean) * invstd
+    gv, ga = dx.v.reshape(N, per, C) * w8, dx.a.reshape(N, per, C) * w8
+    d = dx.d + (1 if p > 0 else 0) + N * Tp
+    return Tr(np.stack([gv.sum((0, 1)), (gv * xh[:, ts]).sum((0, 1))]),
+              np.stack([ga.sum((0, 1)), (ga * np.abs(xh[:, ts])).sum((0, 1))]), d + 3)
+
+
+def bnreduce_sums_ref(dx, per, N, T, C, y, scale, shift, mean, invstd, act, p, mask, lens, pad_l, pad_r, pad_mode, defect=None):
+    """sums [2][C] (Tr) of g gate gk and g gate gk xhat from the flat gradient dx (Tr [N * per][C]; a plain array counts as
+    exact): bn_act_bwd_ref fed with the first pad_l + T + pad_r rows of every utterance as its single gradient source -- folded
+    onto the frames first, gated second.  The row sum has depth N (pad_l + T + pad_r): what the device adds up, row by row."""
+    dx = dx if isinstance(dx, Tr) else Tr(dx)
+    assert dx.v.shape == (N * per, C) and per >= pad_l + T + pad_r
+    if defect is not None:
+        assert defect in DG_DEFECTS
+        return _rowwise_sums(dx, per, N, T, C, y, scale, shift, mean, invstd, act, p, mask, lens, pad_l, pad_r, pad_mode, defect)
+    Tp = pad_l + T + pad_r
+    src = Tr(dx.v.reshape(N, per, C)[:, :Tp], dx.a.reshape(N, per, C)[:, :Tp], dx.d)
+    res = bn_act_bwd_ref(N, T, C, y, scale, shift, mean, invstd, [(src, pad_l, pad_r, pad_mode)], act=act, p=p, mask=mask,
+                         lens=lens, sum_depth=N * Tp)
+    return res['sums']
+
+
+def dgrad_bnreduce_ref(dy, w, Kw, dil, halo, per, flat_rows, N, T, C, y, scale, shift, mean, invstd, act, p, mask, lens, pad_l,
+                       pad_r, pad_mode, defect=None):
+    """w2l_conv1d_dgrad_bnreduce_ws: dict(dx = the flat gradient (Tr [flat_rows][C], dead rows included), sums = Tr [2][C])"""
+    assert flat_rows == N * per and np.asarray(w).shape[1] == C
+    dx = dgrad_ref(dy, w, Kw, dil, halo, flat_rows)
+    return dict(dx=dx, sums=bnreduce_sums_ref(dx, per, N, T, C, y, scale, shift, mean, invstd, act, p, mask, lens, pad_l, pad_r,
+                                              pad_mode, defect))
+
+
+@dataclasses.dataclass(frozen=True)
+class DgCase:
+    """a stride-1 convolution (Cout, Kw, dil) whose input is the padded activation of the producer unit ``u`` (a Case: N, T, C,
+    act, p, lens, pads), and the shared-halo geometry of its dy: Tout = pad_l + T + pad_r - hb frames per utterance, ``halo``
+    rows between them, per = Tout + halo rows of dx per utterance of which the first pad_l + T + pad_r are the padded rows"""
+    u: Case
+    Cout: int
+    Kw: int
+    dil: int
+    halo: int
+
+    @property
+    def name(self):
+        return self.u.name
+
+    @property
+    def hb(self):
+        return (self.Kw - 1) * self.dil
+
+    @property
+    def Tp(self):
+        return self.u.pad_l + self.u.T + self.u.pad_r
+
+    @property
+    def Tout(self):
+        return self.Tp - self.hb
+
+    @property
+    def per(self):
+        return self.Tout + self.halo
+
+    @property
+    def flat_rows(self):
+        return self.u.N * self.per
+
+
+def engine_halo(Tout, hb):
+    """the engine's: the utterances of the flat sequence start on 64-row boundaries"""
+    return max(hb, (Tout + 63) // 64 * 64 - Tout)
+
+
+@functools.lru_cache(maxsize=16)
+def make_dg_case(g, variant=0, zero_halo=False):
+    """make_case of the producer plus dy (the WHOLE shared-halo buffer random bf16 values, halo rows too, unless zero_halo: the
+    kernel is the plain convolution over the buffer whatever it holds, and only so are the dead rows of dx non-zero) and the
+    conv weight [Cout][C][Kw] (bf16 values).  variant: other dy and w for the same producer (a second consumer)."""
+    D = dict(make_case(g.u))
+    rng = np.random.default_rng(7000 + 10 * g.u.seed + variant)
+    c = g.u
+    dy = _bf16_round(rng.standard_normal((g.halo + g.flat_rows, g.Cout)).astype(np.float32))
+    if zero_halo:
+        fr = (np.arange(g.halo + g.flat_rows) - g.halo) % g.per
+        dy[(np.arange(g.halo + g.flat_rows) < g.halo) | (fr >= g.Tout)] = 0.0
+    D['dy'] = dy
+    D['w'] = _bf16_round((rng.standard_normal((g.Cout, c.C, g.Kw)) / np.sqrt(g.Cout * g.Kw)).astype(np.float32))
+    return D
+
+
+def dg_ref_of(g, D, defect=None, dx=None):
+    """dgrad_bnreduce_ref of a case; dx given (exact accumulators): the sums alone"""
+    c = g.u
+    tail = (c.N, c.T, c.C, D['y'], D['scale'], D['shift'], D['mean'], D['invstd'], c.act, c.p, D['mask'], D['lens'], c.pad_l, c.pad_r,
+            c.pad_mode, defect)
+    if dx is not None:
+        return bnreduce_sums_ref(dx, g.per, *tail)
+    return dgrad_bnreduce_ref(D['dy'], D['w'], g.Kw, g.dil, g.halo, g.per, g.flat_rows, *tail)
+
+
+def dg_defect_applies(g, defect):
+    """whether a defect can show on a case at all, from its geometry alone"""
+    c = g.u
+    reflect = c.pad_mode == 1 and (c.pad_l or c.pad_r)
+    return {'dead_rows_counted': reflect and g.per > g.Tp, 'mirror_own_gate': bool(reflect),
+            'lens_on_halo_row': bool(reflect) and c.lens != 'none', 'mask_nibble': c.p > 0, 'no_gk_grad': c.p > 0}[defect]
+
+
+# the cases of tests/test_gpu_dgrad_bnreduce_direct.py (C % 64 == 0; N per = 459 .. 576 flat rows)
+DG_A = DgCase(Case('A_per153', 3, 141, 192, act=1, p=0.25, lens='ragged', pad_l=6, pad_r=6, pad_mode=1, seed=71), 128, 7, 2, 12)
+DG_B = DgCase(Case('B_engine_per', 3, 141, 192, act=1, p=0.25, lens='ragged', pad_l=6, pad_r=6, pad_mode=1, seed=72), 128, 7, 2,
+              engine_halo(141, 12))
+DG_C = DgCase(Case('C_zero_relu', 5, 97, 320, act=2, pad_l=3, pad_r=3, pad_mode=0, seed=73), 128, 7, 1, 9)
+DG_D = DgCase(Case('D_longest_mirror', 12, 19, 128, act=1, p=0.25, lens='ragged', pad_l=6, pad_r=18, pad_mode=1, seed=74), 192, 7, 4,
+              27)
+DG_E = DgCase(Case('E_no_batchnorm', 3, 141, 192, bn1=0, act=2, p=0.25, lens='ragged', pad_l=6, pad_r=6, pad_mode=1, seed=75), 128,
+              7, 2, 15)
+DG_CASES = [DG_A, DG_B, DG_C, DG_D, DG_E]

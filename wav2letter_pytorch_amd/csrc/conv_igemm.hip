@@ -1180,7 +1180,9 @@ static int plan(const ConvProblem& pr, const Epilogue* ep, int forced, ConvPlan&
         W2L_CHECK_ARG(d && d->y && !d->y_f32 && !d->y2 && pr.stats && !pr.y_f32 && !pr.accumulate && !pr.bias && pr.N == 1 &&
                       pr.stride == 1,
                       "conv1d_dgrad_bnreduce: needs a bf16 single-branch layer, a statistics buffer and a flat bf16 output");
-        W2L_CHECK_ARG(d->C == pr.Cout && per > 0 && pad_l >= 0 && pad_r >= 0 && (int64_t)d->N * per <= pr.Tout &&
+        // flat_rows == N * per exactly: the epilogue derives the utterance of a row as row / per with no upper limit, so a row
+        // beyond N * per would be counted with the y, mask and lens of an utterance that does not exist
+        W2L_CHECK_ARG(d->C == pr.Cout && per > 0 && pad_l >= 0 && pad_r >= 0 && d->N > 0 && (int64_t)d->N * per == pr.Tout &&
                       per >= pad_l + d->T + pad_r,
                       "conv1d_dgrad_bnreduce: geometry mismatch (C=%d vs %d, per=%d, N=%d, rows=%d)", d->C, pr.Cout, per, d->N,
                       pr.Tout);
