@@ -137,8 +137,14 @@ int w2l_conv1d_igemm_fp8_tune(const void* xq, int64_t x_bstride, int64_t x_rows_
 
 /* tuning hook: force configuration idx (>= 0) for every later w2l_conv1d_igemm call MADE BY THE CALLING THREAD (the
  * setting is thread-local: launches from other threads are never affected); -1 = automatic.
- * idx = block shape (0..20) + 21 * K-loop structure (0: barrier at the top of a step, 1: barrier mid-step);
- * a call whose problem the forced configuration cannot run returns an error. */
+ * idx = block shape (0..25) + 26 * K-loop structure (0: barrier at the top of a step, 1: barrier mid-step)
+ *       + 52 * split option (0..6: 1, 2, 3, 4, 5, 6, 8 blocks per tile through the split-K workspace; 7: stream-K).
+ * A call whose problem the forced configuration cannot run returns an error and launches nothing: block shape 20 (it
+ * spills; kept for index stability), a shape whose tiles do not fit LDS, stride 2 on any shape but 128x128 (index 2),
+ * statistics on tile rows (w2l_conv_stats_mode(0)) with a shape that is not 128 or 256 columns wide.  A split option the
+ * problem or the workspace cannot carry (fewer than two K steps per block, no workspace) silently runs one block per tile,
+ * and so does stream-K under a fused epilogue or where its ranges would be shorter than eight steps: w2l_conv_plan(forced
+ * idx) tells what a launch really gets (out[2] blocks per tile, out[3] stream-K blocks). */
 void w2l_conv_force_tile_config(int idx);
 /* likewise for the e4m3 kernel: idx = index into its list of 13 block shapes; an infeasible one (statistics need 128-row
  * tiles, LDS) makes w2l_conv1d_igemm_fp8 fail with a message */

@@ -230,10 +230,13 @@ def bn_finalize_ref(partial, C, count, gamma, beta, eps, momentum, running_mean,
 # ---- forward -------------------------------------------------------------------------------------------------------------------
 
 def preact(y, scale, shift, y2=None, scale2=None, shift2=None):
-    """z = y*scale + shift [+ y2*scale2 + shift2] as Tr; a NULL scale is the identity (y * 1 + 0: exact)"""
-    z = Tr(y) if scale is None else Tr(y) * Tr(scale) + Tr(shift)
+    """z = y*scale + shift [+ y2*scale2 + shift2] as Tr; a NULL scale is the identity (y * 1 + 0: exact).  y and y2 may be
+    tracked values themselves (the accumulators of a convolution: conv_refs.infer_ref) and then bring their magnitude and depth;
+    a plain array is an exact input, as before"""
+    tr = lambda a: a if isinstance(a, Tr) else Tr(a)
+    z = tr(y) if scale is None else tr(y) * Tr(scale) + Tr(shift)
     if y2 is not None:
-        z = z + (Tr(y2) if scale2 is None else Tr(y2) * Tr(scale2) + Tr(shift2))
+        z = z + (tr(y2) if scale2 is None else tr(y2) * Tr(scale2) + Tr(shift2))
     return z
 
 

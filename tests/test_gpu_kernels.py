@@ -1,7 +1,8 @@
 """Kernel-level parity on a real MI355X: C-ABI entry points against the CPU oracle
 (oracle/w2l_oracle.py, torch-CPU fp32 / numpy) on the same seeded inputs.  The depthwise-convolution, fused-optimizer and
 pad-cast entry points are called directly in tests/test_gpu_kernels_direct.py, against float64 references; the softmax, CTC
-and argmax entry points in tests/test_gpu_frontend_direct.py, every CTC kernel variant included.
+and argmax entry points in tests/test_gpu_frontend_direct.py, every CTC kernel variant included; the implicit GEMM forward, its
+BatchNorm partial sums and its fused inference epilogue per element and per forced configuration in tests/test_gpu_conv_direct.py.
 Tolerances: bf16-operand kernels are compared on bf16-rounded inputs (fp32 accumulate) at
 2e-3 relative to the output scale; fp32 elementwise kernels at 1e-5."""
 import ctypes as C
