@@ -626,6 +626,37 @@ int w2l_ctc_beam_search_lm(const float* probs, const int32_t* sizes, int N, int 
                            int blank, int end_index, int space_index, int k, double alpha, double beta, double prune,
                            int log_probs, const w2l_ngram_lm_t* lm, int order, void* workspace, int64_t workspace_bytes,
                            void* out, void* stream);
+/* ---- the two searches constrained to a word list (lexicon.Lexicon) ---- */
+/* The spelling trie of a lexicon, in the form and with the limits of w2l_ngram_lm_t's (built by w2l_ngram_lm_build):
+ * trie_keys[slot] == node << 8 | canonical label -> child node trie_vals[slot], root 0; trie_word[node] >= 0 where the node
+ * spells a whole word.  The trie of an n-gram model may be passed as it is. */
+typedef struct {
+    const uint64_t* trie_keys;
+    const int32_t* trie_vals;
+    int64_t trie_cap;
+    const int32_t* trie_word;
+    int32_t n_trie_nodes;   /* trie_word length */
+} w2l_lexicon_t;
+/* workspace bytes of the lexicon searches: those of their parents (a beam slot's trie node lives in LDS, and the node of a new
+ * member is found from its parent slot's, so nothing is kept per interned prefix); -1 if out of range */
+int64_t w2l_ctc_beam_search_lex_workspace_bytes(int N, int T, int k);
+int64_t w2l_ctc_beam_search_lm_lex_workspace_bytes(int N, int T, int k, int order);
+/* w2l_ctc_beam_search / w2l_ctc_beam_search_lm where no mass is given to a string that leaves the lexicon.  A separator is
+ * the space (space_index, -1: none) or end_char; the partial word of a string is what follows its last separator.  The
+ * extension of beam member i by label c that is not itself a beam member takes part in the frame only if it is legal: c a
+ * separator and member i's partial word empty or a whole word, or c another label and (partial word + c) a prefix of a word
+ * (one probe of the trie); otherwise it gets no mass, like a pruned label.  complete_only != 0: out holds only the members of
+ * the final beam whose partial word is empty or a whole word, in rank order, the other slots empty (all members if there is
+ * none).  label_info_host bit 11 and the other arguments as in w2l_ctc_beam_search_lm; out as in the parent; 512 bytes of
+ * static LDS more than the parent. */
+int w2l_ctc_beam_search_lex(const float* probs, const int32_t* sizes, int N, int T, int A, const int32_t* label_info_host,
+                            int blank, int end_index, int space_index, int k, double beta, double prune, int log_probs,
+                            const w2l_lexicon_t* lexicon, int complete_only, void* workspace, int64_t workspace_bytes,
+                            void* out, void* stream);
+int w2l_ctc_beam_search_lm_lex(const float* probs, const int32_t* sizes, int N, int T, int A, const int32_t* label_info_host,
+                               int blank, int end_index, int space_index, int k, double alpha, double beta, double prune,
+                               int log_probs, const w2l_ngram_lm_t* lm, int order, const w2l_lexicon_t* lexicon,
+                               int complete_only, void* workspace, int64_t workspace_bytes, void* out, void* stream);
 /* ---- ASG prefix beam search and forced alignment (asg_beam.py; host restatements: asg_prefix_beam_search,
  *      asg_viterbi_align_host): what w2l_ctc_beam_search / _lm / w2l_ctc_align are to a CTC model, for a model trained with
  *      the ASG criterion (no blank; learned transitions; label repeat_index stands for "the previous letter again") ---- */

@@ -1,0 +1,357 @@
+"""The lexicon-constrained device beam searches (w2l_ctc_beam_search_lex / w2l_ctc_beam_search_lm_lex) against the host recursion
+``prefix_beam_search(..., lexicon=...)`` on float64 posteriors: strings equal, log weights within 1e-9 relative, ``lm_log10``
+bit-equal to ``np.float32(lm.score(...))`` -- the comparison of tests/test_gpu_beam_search_lm.py.
+
+Posteriors are generated in float32 and widened exactly.  Three of the four utterances are bursts of a few letters of the
+lexicon's words with a rival label boosted almost as much; the fourth spells only X, Y, Z (no lexicon word has one): nothing but
+the empty string is legal there."""
+import ctypes as C
+import functools
+import itertools
+
+import numpy as np
+import pytest
+import torch
+
+from wav2letter_pytorch_amd._lib import LexTables, lib, ptr, stream_ptr
+from wav2letter_pytorch_amd.alignment import ctc_forced_align
+from wav2letter_pytorch_amd.beam_search import (GPUPrefixBeamSearchDecoder, GPUPrefixBeamSearchLMDecoder, _beam_search_device,
+                                                _label_info, prefix_beam_search, prefix_beam_search_gpu)
+from wav2letter_pytorch_amd.data.label_sets import english_labels
+from wav2letter_pytorch_amd.lexicon import Lexicon
+from wav2letter_pytorch_amd.ngram_lm import ArpaLM
+
+pytestmark = pytest.mark.gpu
+
+LABELS = list(english_labels) + ['>', 'B']                      # 29 labels, an end_char, a duplicate of 'B' (index 30 -> 3)
+WORDS = ['A', 'AB', 'ABBA', 'ALL', 'BE', 'BED', 'CAB', "D'C", 'DEB', 'EB', 'C', 'LEAD', 'DÉJÀ']
+LM_WORDS = ['A', 'AB', 'ABBA', 'ALL', 'BE', 'BED', 'CAD', 'DEB', 'ELL', 'C', "E'D"]     # not the lexicon: some in, some out
+N = 4
+SIZES = {24: [24, 17, 24, 24], 40: [40, 40, 29, 40]}
+
+
+@functools.lru_cache(maxsize=None)
+def _lexicon():
+    return Lexicon(WORDS)
+
+
+@functools.lru_cache(maxsize=None)
+def _posteriors(t, seed=0):
+    """float32 [4, t, 31]; shared by the tests, never written"""
+    rng = np.random.default_rng(1000 * t + seed)
+    a = len(LABELS)
+    cand = [LABELS.index(c) for c in "ABCDEL'"] + [30, 30, 3, 2, 2]      # the duplicate label takes part; A, B often
+    space, end = LABELS.index(' '), LABELS.index('>')
+    logits = rng.standard_normal((N, t, a))
+    for u in range(N - 1):
+        f = 0
+        while f < t:
+            if rng.random() < 0.4:
+                logits[u, f, 0] += rng.uniform(3.0, 6.0)
+                f += 1
+                continue
+            c = space if rng.random() < 0.3 else cand[rng.integers(len(cand))]
+            burst = int(rng.integers(1, 3))
+            b = rng.uniform(3.0, 6.0)
+            logits[u, f:f + burst, c] += b
+            logits[u, f:f + burst, cand[rng.integers(len(cand))]] += b - rng.uniform(0, 1.5)
+            f += burst
+    # a closed hypothesis keeps its mass while the open ones decay: end_char only where an utterance ends
+    for u in range(N - 1):
+        logits[u, :SIZES[t][u] - 2, end] -= 25.0
+        logits[u, SIZES[t][u] - 1, end] += (5.0, 3.0, 0.0)[u]
+    # the last utterance: X, Y, Z against the blank, every other label 20 nats down.  The duplicated label and end_char 60:
+    # the mass of an extension that fell off the beam is added once per label of its character (it doubles every frame for
+    # 'B'), and a closed '>' does not decay
+    junk = [LABELS.index(c) for c in 'XYZ']
+    logits[N - 1] -= 20.0
+    logits[N - 1, :, [0] + junk] += 20.0
+    logits[N - 1, :, [3, 30, end]] -= 40.0
+    logits[N - 1, :, 0] += 2.0
+    for f in range(0, t, 3):
+        logits[N - 1, f, junk[(f // 3) % 3]] += rng.uniform(3.0, 5.0)
+    e = np.exp(logits - logits.max(-1, keepdims=True))
+    return (e / e.sum(-1, keepdims=True)).astype(np.float32)
+
+
+def _write_arpa(path, words, order, seed):
+    """a random order-``order`` model over ``words``: every higher n-gram extends a lower one by an older word"""
+    rng = np.random.default_rng(seed)
+    lines = {1: ['-2.0\t<unk>', '-99\t<s>\t%.5f' % -rng.uniform(0, 0.5), '%.5f\t</s>' % -rng.uniform(0.3, 1.5)]}
+    lines[1] += ['%.5f\t%s\t%.5f' % (-rng.uniform(0.3, 2.5), w, -rng.uniform(0, 0.6)) for w in words]
+    grams = [(w,) for w in words + ['</s>']]
+    for n in range(2, order + 1):
+        cur = set()
+        while len(cur) < 60:
+            base = grams[rng.integers(len(grams))]
+            if base[0] != '<s>':
+                cur.add(((['<s>'] + words)[rng.integers(len(words) + 1)],) + base)
+        grams = sorted(cur)
+        lines[n] = ['%.5f\t%s' % (-rng.uniform(0.05, 1.5), ' '.join(g)) + ('' if n == order else '\t%.5f' % -rng.uniform(0, 0.6))
+                    for g in grams]
+    text = '\\data\\\n' + ''.join('ngram %d=%d\n' % (n, len(lines[n])) for n in lines)
+    for n in lines:
+        text += '\n\\%d-grams:\n' % n + '\n'.join(lines[n]) + '\n'
+    path.write_text(text + '\n\\end\\\n')
+    return ArpaLM(str(path))
+
+
+@pytest.fixture(scope='module')
+def models(tmp_path_factory):
+    d = tmp_path_factory.mktemp('lex_lm')
+    return dict(bigram=_write_arpa(d / 'b.arpa', LM_WORDS, 2, 1), trigram=_write_arpa(d / 't.arpa', WORDS[:-1], 3, 2),
+                dir=d)
+
+
+_HOST = {}
+
+
+def _host(t, u, k, beta, prune, lm, alpha, lexicon, complete_only):
+    """prefix_beam_search on the float64 posteriors of utterance u, computed once per argument set"""
+    key = (t, u, k, beta, prune, id(lm), alpha, id(lexicon), complete_only)
+    if key not in _HOST:
+        weigh = None
+        if lm is not None:
+            if not hasattr(lm, '_weigh'):
+                lm._weigh = functools.lru_cache(maxsize=None)(lambda s: 10 ** lm.score(s))
+            weigh = lm._weigh
+        p = _posteriors(t)[u, :SIZES[t][u]].astype(np.float64)
+        _HOST[key] = prefix_beam_search(p, LABELS, lm=weigh, k=k, alpha=alpha, beta=beta, prune=prune, return_weights=True,
+                                        lexicon=lexicon, complete_only=complete_only)
+    return _HOST[key]
+
+
+def _strip_score(lm, s):
+    return np.float32(lm.score(s.strip(' >'))) if s.replace(' ', '') else np.float32(0)
+
+
+def _words_of(s):
+    return s.replace('>', ' ').split()
+
+
+def _compare(t, k, beta, prune, lm, lexicon, complete_only, alpha=1.0):
+    """device vs host on the four utterances: best string, log weight, lm_log10 of every returned prefix, lexicon membership"""
+    if isinstance(lexicon, str):                                 # 'lm': the host's lexicon is the model's vocabulary
+        if not hasattr(lm, '_host_lex'):
+            lm._host_lex = Lexicon.from_lm(lm)
+        host_lex = lm._host_lex
+    else:
+        host_lex = lexicon
+    x = torch.from_numpy(_posteriors(t)).cuda()
+    got = _beam_search_device(x, LABELS, 0, k, beta, prune, '>', torch.tensor(SIZES[t]), False, lm=lm, alpha=alpha,
+                              lexicon=lexicon, complete_only=complete_only)
+    scores, lengths, idx = got[:3]
+    bests = []
+    for u in range(N):
+        best, w = _host(t, u, k, beta, prune, lm, alpha, host_lex, complete_only)
+        found = [''.join(LABELS[j] for j in idx[u, r, :lengths[u, r]]) for r in range(k) if lengths[u, r] >= 0]
+        if w == 0:                                               # the beam emptied (every label that passed the prune was
+            assert best == '' and not found                      # illegal, the blank did not pass): '' on both sides
+            bests.append(best)
+            continue
+        assert found[0] == best, (u, found[0], best)
+        assert w > 1e-250
+        assert abs(scores[u, 0] - np.log(w)) <= 1e-9 * max(1.0, abs(np.log(w))), (u, scores[u, 0], np.log(w))
+        assert all(a >= b for a, b in zip(scores[u, :len(found)], scores[u, 1:len(found)]))
+        for r, s in enumerate(found):
+            assert host_lex.allows(s), (u, r, s)
+            if lm is not None:
+                assert got[3][u, r].tobytes() == _strip_score(lm, s).tobytes(), (u, r, s, got[3][u, r])
+        if complete_only and any(host_lex.complete(s) for s in found):
+            assert all(host_lex.complete(s) and all(wd in host_lex for wd in _words_of(s)) for s in found), (u, found)
+        bests.append(best)
+    assert bests[N - 1] == ''                                    # X, Y, Z spell nothing: only the empty string is legal
+    return bests
+
+
+CASES = list(itertools.product((24, 40), (1, 3, 8, 32), (0, 5), (1e-3, 0)))
+
+
+def test_the_unconstrained_decode_leaves_the_lexicon():
+    """the premise of every comparison below: without the constraint, at least 3 of the 4 decodes hold a non-lexicon word"""
+    lex = _lexicon()
+    for t in (24, 40):
+        plain = prefix_beam_search_gpu(_posteriors(t), LABELS, k=8, sizes=SIZES[t])
+        outside = [any(w not in lex for w in _words_of(s)) for s in plain]
+        assert sum(outside) >= 3, plain
+        assert outside[N - 1] and set(plain[N - 1]) <= set('XYZ')
+
+
+@pytest.mark.parametrize('t,k,beta,prune', CASES)
+def test_lexicon_only(t, k, beta, prune):
+    lex = _lexicon()
+    on = _compare(t, k, beta, prune, None, lex, True)
+    off = _compare(t, k, beta, prune, None, lex, False)
+    assert lex.stats['unspellable'] == 1
+    for a, b in zip(on, off):                                    # the filter drops members, it does not change them
+        assert lex.complete(a) or a == b
+
+
+@pytest.mark.parametrize('t,k,beta,prune', CASES)
+def test_lexicon_with_bigram(models, t, k, beta, prune):
+    """the lexicon is a separate list: some of its words are <unk> to the model, some of the model's words are banned"""
+    for complete_only in (True, False):
+        _compare(t, k, beta, prune, models['bigram'], _lexicon(), complete_only)
+
+
+@pytest.mark.parametrize('t,k,beta,prune', CASES)
+def test_lexicon_from_lm(models, t, k, beta, prune):
+    """lexicon='lm': the model's own trie (order 3), shared on the device"""
+    lm = models['trigram']
+    for complete_only in (True, False):
+        _compare(t, k, beta, prune, lm, 'lm', complete_only, alpha=0.7)
+    assert lm._lexicon.to_device(LABELS, 0, 'cuda').shared
+
+
+def test_nbest(models):
+    lex, lm = _lexicon(), models['bigram']
+    for t, k, kw in ((24, 8, dict()), (40, 32, dict(lm=lm, alpha=1.0))):
+        p = _posteriors(t)
+        full = prefix_beam_search_gpu(p, LABELS, k=k, beta=0, nbest=k, sizes=SIZES[t], lexicon=lex, complete_only=False, **kw)
+        done = prefix_beam_search_gpu(p, LABELS, k=k, beta=0, nbest=k, sizes=SIZES[t], lexicon=lex, **kw)
+        for u in range(N):
+            assert all(lex.allows(s) for s, _ in full[u])
+            want = [(s, w) for s, w in full[u] if lex.complete(s)] or full[u]
+            assert done[u] == want                               # the complete members, in rank order, their own weights
+            best, w = _host(t, u, k, 0, 1e-3, kw.get('lm'), 1.0, lex, True)
+            assert done[u][0][0] == best and abs(done[u][0][1] - np.log(w)) <= 1e-9 * max(1.0, abs(np.log(w)))
+        assert any(len(d) < len(f) for d, f in zip(done, full))  # ... and the filter did drop something
+
+
+def test_return_offsets(models):
+    lex = _lexicon()
+    for t, kw in ((24, dict()), (40, dict(lm=models['trigram'], alpha=0.7))):
+        p = _posteriors(t)
+        lexicon = 'lm' if kw else lex
+        plain = prefix_beam_search_gpu(p, LABELS, k=8, sizes=SIZES[t], lexicon=lexicon, **kw)
+        strings, offsets = prefix_beam_search_gpu(p, LABELS, k=8, sizes=SIZES[t], lexicon=lexicon, return_offsets=True, **kw)
+        assert strings == plain
+        res = ctc_forced_align(p, strings, input_lengths=SIZES[t], log_probs=False, labels=LABELS)
+        for u, s in enumerate(strings):
+            assert offsets[u].dtype == torch.int32 and offsets[u].tolist() == res.starts[u, :len(s)].tolist(), (u, s)
+        assert any(len(s) > 2 for s in strings)
+    # log-probability input and the decoder classes: the same strings
+    t = 24
+    x = torch.from_numpy(_posteriors(t)).cuda()
+    want = prefix_beam_search_gpu(x, LABELS, k=8, sizes=SIZES[t], lexicon=lex)
+    assert prefix_beam_search_gpu(x.double().log().float(), LABELS, k=8, sizes=SIZES[t], lexicon=lex, log_probs=True,
+                                  prune=-1) == prefix_beam_search_gpu(x, LABELS, k=8, sizes=SIZES[t], lexicon=lex, prune=0)
+    dec = GPUPrefixBeamSearchDecoder(None, LABELS, k=8, lexicon=lex)
+    assert dec.decode(x, torch.tensor(SIZES[t])) == want
+    words = models['dir'] / 'words.txt'
+    words.write_text(''.join('%s %s\n' % (w, ' '.join(w)) for w in WORDS))
+    dec = GPUPrefixBeamSearchLMDecoder(None, LABELS, k=8, lexicon=str(words))
+    assert dec.decode(x, torch.tensor(SIZES[t])) == want
+    one, off = dec.decode(x[0], return_offsets=True)
+    assert one == prefix_beam_search_gpu(x[0], LABELS, k=8, lexicon=lex) and len(off[0]) == len(one)
+
+
+def test_existing_searches_unchanged_around_a_lexicon_call(models):
+    """the LM-free and LM searches without a lexicon, before and after lexicon launches in the same process: bit-equal"""
+    lm = models['bigram']
+    x = torch.from_numpy(_posteriors(40)).cuda()
+
+    def both():
+        return [_beam_search_device(x, LABELS, 0, k, 5, 1e-3, '>', None, False, **kw)
+                for k in (3, 32) for kw in (dict(), dict(lm=lm, alpha=1.0))]
+    before = both()
+    for kw in (dict(), dict(lm=lm), dict(lm=models['trigram'], lexicon='lm')):
+        kw.setdefault('lexicon', _lexicon())
+        changed = prefix_beam_search_gpu(x, LABELS, k=32, **kw)
+        assert changed != prefix_beam_search_gpu(x, LABELS, k=32, lm=kw.get('lm'))
+    for a, b in zip(before, both()):
+        assert a[0].tobytes() == b[0].tobytes() and a[1].tobytes() == b[1].tobytes()     # scores, lengths
+        for u, r in zip(*np.nonzero(a[1] >= 0)):
+            assert a[2][u, r, :a[1][u, r]].tobytes() == b[2][u, r, :a[1][u, r]].tobytes()
+        if len(a) > 3:
+            assert a[3].tobytes() == b[3].tobytes()
+
+
+def test_entry_point_errors(models):
+    t, k = 24, 4
+    x = torch.from_numpy(_posteriors(t)).cuda()
+    dev_lex = _lexicon().to_device(LABELS, 0, 'cuda')
+    lm = models['bigram']
+    dev_lm = lm.to_device(LABELS, 0, 'cuda')
+    info, end = _label_info(LABELS, 0, '>')
+    info = info | np.array([ch.isspace() << 11 for ch in LABELS], dtype=np.int32)
+    space = LABELS.index(' ')
+    tabbed = LABELS[:-3] + ['\t'] + LABELS[-2:]
+    info_tab = _label_info(tabbed, 0, '>')[0] | np.array([ch.isspace() << 11 for ch in tabbed], dtype=np.int32)
+    ws_bytes = int(lib.w2l_ctc_beam_search_lm_lex_workspace_bytes(N, t, k, lm.order))
+    assert ws_bytes == int(lib.w2l_ctc_beam_search_lm_workspace_bytes(N, t, k, lm.order)) > 0
+    assert int(lib.w2l_ctc_beam_search_lex_workspace_bytes(N, t, k)) == int(lib.w2l_ctc_beam_search_workspace_bytes(N, t, k))
+    assert int(lib.w2l_ctc_beam_search_lex_workspace_bytes(N, t, 0)) == -1
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device='cuda')
+    out = torch.full((12 * N * k + 4 * N + 4 * N * k * t + 4 * N * k,), 0x5a, dtype=torch.uint8, device='cuda')
+
+    def call(desc, inf, sp, with_lm):
+        vp = inf.ctypes.data_as(C.c_void_p)
+        if with_lm:
+            return lib.w2l_ctc_beam_search_lm_lex(ptr(x), None, N, t, len(LABELS), vp, 0, end, sp, k, 1.0, 5.0, 1e-3, 0,
+                                                  dev_lm.desc_ref, lm.order, desc, 1, ptr(ws), ws_bytes, ptr(out), stream_ptr())
+        return lib.w2l_ctc_beam_search_lex(ptr(x), None, N, t, len(LABELS), vp, 0, end, sp, k, 5.0, 1e-3, 0, desc, 1,
+                                           ptr(ws), ws_bytes, ptr(out), stream_ptr())
+    good = dev_lex.desc
+    nodes = good.n_trie_nodes
+    full = LexTables(good.trie_keys, good.trie_vals, good.trie_cap, good.trie_word, int(good.trie_cap // 2 + 2))
+    odd_cap = LexTables(good.trie_keys, good.trie_vals, good.trie_cap - 1, good.trie_word, nodes)
+    no_keys = LexTables(None, good.trie_vals, good.trie_cap, good.trie_word, nodes)
+    no_word = LexTables(good.trie_keys, good.trie_vals, good.trie_cap, None, nodes)
+    for with_lm in (False, True):
+        for desc in (full, odd_cap, no_keys, no_word):
+            assert call(C.byref(desc), info, space, with_lm) != 0
+        assert call(None, info, space, with_lm) != 0
+        assert call(C.byref(good), info_tab, -1, with_lm) != 0                   # whitespace other than ' '
+        assert call(C.byref(good), info, space - 1, with_lm) != 0                # not the first index of a label... of ' '
+    torch.cuda.synchronize()
+    assert bool((out == 0x5a).all())                             # nothing was launched
+    assert call(C.byref(good), info, space, False) == 0 and call(C.byref(good), info, space, True) == 0
+    torch.cuda.synchronize()
+    with pytest.raises(ValueError, match='whitespace'):
+        prefix_beam_search_gpu(_posteriors(t), tabbed, lexicon=_lexicon())
+    with pytest.raises(TypeError):
+        prefix_beam_search_gpu(_posteriors(t), LABELS, lexicon=WORDS)
+    with pytest.raises(ValueError, match="'lm'"):
+        prefix_beam_search_gpu(_posteriors(t), LABELS, lexicon='lm')
+
+
+def test_cli_lexicon_from_lm_with_word_times(tmp_path, monkeypatch, capsys):
+    """``test`` with decoder=beam_lm lexicon_from_lm=true word_times=true on a checkpoint of a few steps"""
+    import json
+    import os
+    import wave
+    from wav2letter_pytorch_amd import test as T, train
+    monkeypatch.setattr('wav2letter_pytorch_amd.data.data_loader.SpectrogramExtractor.dithering', 0.0)
+    rng = np.random.default_rng(0)
+    texts = ['ab cab', 'a ab', 'cab a', 'ab ab']
+    man = str(tmp_path / 'manifest.json')
+    with open(man, 'w') as f:
+        for i, text in enumerate(texts):
+            sig = (0.1 * rng.standard_normal(int(16000 * (0.6 + 0.1 * (i % 3))))).astype(np.float32)
+            path = str(tmp_path / f'u{i}.wav')
+            with wave.open(path, 'wb') as w:
+                w.setnchannels(1); w.setsampwidth(2); w.setframerate(16000)
+                w.writeframes((sig * 32767).astype(np.int16).tobytes())
+            f.write(json.dumps({'audio_filepath': path, 'text': text}) + '\n')
+    root = str(tmp_path / 'run')
+    common = ['model.mid_layers=2', 'data.batch_size=2']
+    _, model = train.main(common + [f'data.train_manifest={man}', f'data.val_manifest={man}', 'trainer.max_epochs=1',
+                                    f'trainer.default_root_dir={root}', 'model.optimizer.lr=1e-3'])
+    ckpt = [os.path.join(root, f) for f in os.listdir(root) if f.endswith('.ckpt')][0]
+    vocab = ['ab', 'cab', 'a', 'the', "it's", 'A1']
+    arpa = str(tmp_path / 'lm.arpa')
+    with open(arpa, 'w') as f:
+        f.write('\\data\\\nngram 1=%d\n\n\\1-grams:\n-1.0\t<unk>\n-99\t<s>\n-1.0\t</s>\n' % (3 + len(vocab))
+                + ''.join('-0.9\t%s\n' % w for w in vocab) + '\n\\end\\\n')
+    capsys.readouterr()
+    metrics, records = T.main(common + [f'model_path={ckpt}', f'data.test_manifest={man}', 'decoder=beam_lm', f'lm_path={arpa}',
+                                        'lexicon_from_lm=true', 'word_times=true', 'beam.k=4', 'beam.alpha=0.5'])
+    assert 'test_wer=' in capsys.readouterr().out
+    assert len(records) == len(texts) and np.isfinite(metrics['test_wer'])
+    labels = set(model.labels)
+    spellable = {w for w in vocab if set(w) <= labels}
+    assert spellable
+    for r in records:
+        assert all(w in spellable for w in r['hypothesis'].split()), r['hypothesis']
+        assert [w['word'] for w in r['words']] == r['hypothesis'].split()

@@ -60,6 +60,12 @@ class LmTables(C.Structure):
                 ('n_words', C.c_int32), ('n_trie_nodes', C.c_int32)]
 
 
+class LexTables(C.Structure):
+    """w2l_lexicon_t (include/w2l_hip.h): the device spelling trie of a word list (lexicon.DeviceLexicon)."""
+    _fields_ = [('trie_keys', c_p), ('trie_vals', c_p), ('trie_cap', C.c_int64), ('trie_word', c_p),
+                ('n_trie_nodes', C.c_int32)]
+
+
 class BnActEpi(C.Structure):
     """w2l_bnact_epi_t (include/w2l_hip.h): the fused inference epilogue of w2l_conv1d_igemm_bnact."""
     _fields_ = [('scale', c_p), ('shift', c_p), ('res', c_p), ('res_lo', c_p), ('act', C.c_int32), ('lens', c_p),
@@ -169,6 +175,12 @@ _SIGNATURES = {
     'w2l_ctc_beam_search_lm_workspace_bytes': (c_i64, [c_i, c_i, c_i, c_i]),
     'w2l_ctc_beam_search_lm': (c_i, [c_p, c_p, c_i, c_i, c_i, c_p, c_i, c_i, c_i, c_i, C.c_double, C.c_double, C.c_double, c_i,
                                      C.POINTER(LmTables), c_i, c_p, c_i64, c_p, c_p]),
+    'w2l_ctc_beam_search_lex_workspace_bytes': (c_i64, [c_i, c_i, c_i]),
+    'w2l_ctc_beam_search_lm_lex_workspace_bytes': (c_i64, [c_i, c_i, c_i, c_i]),
+    'w2l_ctc_beam_search_lex': (c_i, [c_p, c_p, c_i, c_i, c_i, c_p, c_i, c_i, c_i, c_i, C.c_double, C.c_double, c_i,
+                                      C.POINTER(LexTables), c_i, c_p, c_i64, c_p, c_p]),
+    'w2l_ctc_beam_search_lm_lex': (c_i, [c_p, c_p, c_i, c_i, c_i, c_p, c_i, c_i, c_i, c_i, C.c_double, C.c_double, C.c_double,
+                                         c_i, C.POINTER(LmTables), c_i, C.POINTER(LexTables), c_i, c_p, c_i64, c_p, c_p]),
     'w2l_asg_beam_search_workspace_bytes': (c_i64, [c_i, c_i, c_i, c_i]),
     'w2l_asg_beam_search': (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_i, c_i, C.c_double, C.c_double, c_p, c_i64, c_p, c_p]),
     'w2l_asg_beam_search_lm_workspace_bytes': (c_i64, [c_i, c_i, c_i, c_i, c_i]),
@@ -301,6 +313,7 @@ TRACE_NAMES = {
     'w2l_quantize_e4m3_dyn': 'quantize_e4m3_dyn', 'w2l_dwconv_fwd': 'dw_fwd_kernel', 'w2l_dwconv_dgrad': 'dw_dgrad_kernel',
     'w2l_dwconv_wgrad': 'dw_wgrad_kernel', 'w2l_argmax': 'argmax_kernel', 'w2l_novograd_pack': 'novograd_pack_kernel',
     'w2l_ctc_beam_search': 'ctc_beam_search_kernel', 'w2l_ctc_beam_search_lm': 'ctc_beam_search_kernel<LM>',
+    'w2l_ctc_beam_search_lex': 'ctc_beam_search_kernel<LEX>', 'w2l_ctc_beam_search_lm_lex': 'ctc_beam_search_kernel<LM,LEX>',
     'w2l_ngram_lm_build': 'ngram_insert_kernel', 'w2l_ctc_align': 'ctc_align_kernel',
     'w2l_asg_beam_search': 'asg_beam_search_kernel', 'w2l_asg_beam_search_lm': 'asg_beam_search_kernel<LM>',
     'w2l_asg_align': 'asg_align_kernel',

@@ -16,6 +16,7 @@ character offsets come back in the same copy."""
 from __future__ import annotations
 
 import ctypes as C
+import os
 import re
 from typing import Callable, Dict, List, Optional, Sequence
 
@@ -61,8 +62,17 @@ class _Step:
 
 def prefix_beam_search(ctc, labels: Sequence[str], blank_index: int = 0, lm: Optional[Callable[[str], float]] = None,
                        k: int = 5, alpha: float = 0.3, beta: float = 5, prune: float = 0.001, end_char: str = '>',
-                       return_weights: bool = False):
-    """ctc: [timesteps, alphabet] probabilities.  Returns the best prefix (and its ranking weight)."""
+                       return_weights: bool = False, lexicon=None, complete_only: bool = True,
+                       stats: Optional[dict] = None):
+    """ctc: [timesteps, alphabet] probabilities.  Returns the best prefix (and its ranking weight).
+
+    ``lexicon`` (a lexicon.Lexicon; None: no constraint): an extension ``pre + ch`` that is not legal (Lexicon.allows) gets no
+    mass -- not the ``p * (pb + pnb)`` term, not the two terms of an extension that fell off the beam; the repeat branch's
+    contribution to ``pre`` itself stays.  With ``complete_only`` the result is the best beam member whose trailing partial word
+    is empty or a whole word (Lexicon.complete); if the final beam holds none, the best member as it is.  Weights are the
+    members' own, not renormalised.
+
+    ``stats`` (a dict): ``frames`` and ``live`` (the candidates with a positive mass, summed over the frames) are added to it."""
     ctc = np.asarray(ctc)
     assert ctc.shape[1] == len(labels), "ctc size:%d, labels: %d" % (ctc.shape[1], len(labels))
     assert ctc.shape[0] > 1, "ctc length: %d was too short" % ctc.shape[0]
@@ -73,6 +83,12 @@ def prefix_beam_search(ctc, labels: Sequence[str], blank_index: int = 0, lm: Opt
     for i, ch in enumerate(labels):
         first_index.setdefault(ch, i)
     blank = labels[blank_index]
+    legal: Dict[str, bool] = {}
+
+    def allowed(ext):
+        if ext not in legal:
+            legal[ext] = lexicon.allows(ext, end_char)
+        return legal[ext]
 
     prev = _Step()
     prev.pb[''] = 1.0
@@ -96,6 +112,10 @@ def prefix_beam_search(ctc, labels: Sequence[str], blank_index: int = 0, lm: Opt
                     cur.add_b(pre, frame[blank_index] * (pb_prev + pnb_prev))
                     continue
                 ext = pre + ch
+                if lexicon is not None and not allowed(ext):     # the extension leaves the word list: no mass for it
+                    if pre and ch == pre[-1]:
+                        cur.add_nb(pre, p * pnb_prev)
+                    continue
                 if pre and ch == pre[-1]:                # repeated character: only a blank separates two copies
                     cur.add_nb(ext, p * pb_prev)
                     cur.add_nb(pre, p * pnb_prev)
@@ -108,11 +128,16 @@ def prefix_beam_search(ctc, labels: Sequence[str], blank_index: int = 0, lm: Opt
                     cur.add_b(ext, frame[blank_index] * (prev.pb.get(ext, 0.0) + prev.pnb.get(ext, 0.0)))
                     cur.add_nb(ext, p * prev.pnb.get(ext, 0.0))
         ranked = cur.total()
+        if stats is not None:
+            stats['frames'] = stats.get('frames', 0) + 1
+            stats['live'] = stats.get('live', 0) + len(ranked)
         order = sorted(ranked, key=lambda s: ranked[s] * (_n_words(s) + 1) ** beta, reverse=True)   # stable
         beam = order[:k]
         prev = cur
     if not beam:
         beam = ['']
+    if lexicon is not None and complete_only:
+        beam = [s for s in beam if lexicon.complete(s, end_char)] or beam
     best = beam[0]
     if return_weights:
         return best, ranked.get(best, 0) * (_n_words(best) + 1) ** beta
@@ -183,11 +208,12 @@ def _align_starts(host, n, t, beam_bytes):
 
 
 def _beam_search_device(probs, labels, blank_index, k, beta, prune, end_char, sizes, log_probs, lm=None, alpha=0.3,
-                        offsets=False):
+                        offsets=False, lexicon=None, complete_only=True):
     """one launch of w2l_ctc_beam_search for probs [N, T, A] on the current stream; returns the host arrays
     (scores [N, k], lengths [N, k], labels [N, k, T]).  With ``lm`` (an ngram_lm.ArpaLM) one launch of
     w2l_ctc_beam_search_lm, and a fourth array: lm_log10 [N, k] float32, the LM total of each result.  With ``offsets`` a
-    launch of w2l_ctc_align follows and one more array: starts int32 [N, T], the first frame of each label of rank 0."""
+    launch of w2l_ctc_align follows and one more array: starts int32 [N, T], the first frame of each label of rank 0.  With
+    ``lexicon`` (a lexicon.Lexicon, or 'lm': the vocabulary of ``lm``) the launch is w2l_ctc_beam_search_lex / _lm_lex."""
     if probs.dim() != 3:
         raise ValueError('expected [N, T, labels] or [T, labels] posteriors, got shape %s' % (tuple(probs.shape),))
     n, t, a = probs.shape
@@ -214,9 +240,9 @@ def _beam_search_device(probs, labels, blank_index, k, beta, prune, end_char, si
         if bool((host < 2).any()) or bool((host > t).any()):
             raise ValueError('sizes must lie in [2, %d], got %s' % (t, host.tolist()))
         sz = host.to(torch.int32).to(dev, non_blocking=True)
-    if lm is not None:
+    if lm is not None or lexicon is not None:
         return _beam_search_device_lm(x, sz, labels, info, blank_index, end_index, k, alpha, beta, prune, log_probs, lm,
-                                      offsets)
+                                      offsets, lexicon, complete_only)
     ws_bytes = int(lib.w2l_ctc_beam_search_workspace_bytes(n, t, k))
     if ws_bytes < 0:
         raise ValueError('prefix_beam_search_gpu: k=%d with T=%d is out of range' % (k, t))
@@ -241,29 +267,65 @@ def _beam_search_device(probs, labels, blank_index, k, beta, prune, end_char, si
     return scores, lengths, idx
 
 
-def _beam_search_device_lm(x, sz, labels, info, blank_index, end_index, k, alpha, beta, prune, log_probs, lm, offsets=False):
-    """_beam_search_device's launch of w2l_ctc_beam_search_lm (x, sz already on the device)"""
+def _resolve_lexicon(lexicon, lm):
+    """a Lexicon from ``lexicon``: a Lexicon, a path, or 'lm' (the vocabulary of the ArpaLM ``lm``, cached on it)"""
+    from .lexicon import Lexicon
+    if isinstance(lexicon, Lexicon):
+        return lexicon
+    if isinstance(lexicon, str) and lexicon == 'lm':
+        if lm is None:
+            raise ValueError("lexicon='lm' needs a language model (lm=)")
+        if getattr(lm, '_lexicon', None) is None:
+            lm._lexicon = Lexicon.from_lm(lm)
+        return lm._lexicon
+    if isinstance(lexicon, (str, os.PathLike)):
+        return Lexicon(lexicon)
+    raise TypeError("lexicon must be a lexicon.Lexicon, a path or 'lm', got %s" % type(lexicon).__name__)
+
+
+def _beam_search_device_lm(x, sz, labels, info, blank_index, end_index, k, alpha, beta, prune, log_probs, lm, offsets=False,
+                           lexicon=None, complete_only=True):
+    """_beam_search_device's launch of w2l_ctc_beam_search_lm, or with ``lexicon`` of w2l_ctc_beam_search_lm_lex /
+    w2l_ctc_beam_search_lex (``lm`` None) (x, sz already on the device)"""
     from .ngram_lm import ArpaLM
-    if not isinstance(lm, ArpaLM):
+    if lm is not None and not isinstance(lm, ArpaLM):
         raise TypeError('lm must be an ngram_lm.ArpaLM, got %s' % type(lm).__name__)
     odd = [ch for ch in labels if ch.isspace() and ch != ' ']
     if odd:
-        raise ValueError('prefix_beam_search_gpu: whitespace labels other than a space (%r) cannot be scored by a word LM' % odd)
+        raise ValueError('prefix_beam_search_gpu: whitespace labels other than a space (%r) cannot be scored by a word LM'
+                         % odd if lm is not None else
+                         'prefix_beam_search_gpu: whitespace labels other than a space (%r) cannot separate the words of a '
+                         'lexicon' % odd)
     n, t, a = x.shape
     dev = x.device
     info = info | np.array([ch.isspace() << 11 for ch in labels], dtype=np.int32)
     space_index = labels.index(' ') if ' ' in labels else -1
-    tables = lm.to_device(labels, blank_index, dev)
-    ws_bytes = int(lib.w2l_ctc_beam_search_lm_workspace_bytes(n, t, k, lm.order))
+    tables = lm.to_device(labels, blank_index, dev) if lm is not None else None
+    lex = _resolve_lexicon(lexicon, lm).to_device(labels, blank_index, dev) if lexicon is not None else None
+    if lm is None:
+        ws_bytes = int(lib.w2l_ctc_beam_search_lex_workspace_bytes(n, t, k))
+    elif lex is None:
+        ws_bytes = int(lib.w2l_ctc_beam_search_lm_workspace_bytes(n, t, k, lm.order))
+    else:
+        ws_bytes = int(lib.w2l_ctc_beam_search_lm_lex_workspace_bytes(n, t, k, lm.order))
     if ws_bytes < 0:
-        raise ValueError('prefix_beam_search_gpu: k=%d with T=%d (LM order %d) is out of range' % (k, t, lm.order))
+        raise ValueError('prefix_beam_search_gpu: k=%d with T=%d%s is out of range'
+                         % (k, t, '' if lm is None else ' (LM order %d)' % lm.order))
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-    beam_bytes = 12 * n * k + 4 * n + 4 * n * k * t + 4 * n * k
+    beam_bytes = 12 * n * k + 4 * n + 4 * n * k * t + (4 * n * k if lm is not None else 0)
     out = torch.empty(beam_bytes + (align_sections(n, t, t)[5] if offsets else 0), dtype=torch.uint8, device=dev)
-    check(lib.w2l_ctc_beam_search_lm(ptr(x), ptr(sz), n, t, a, info.ctypes.data_as(C.c_void_p), int(blank_index),
-                                     int(end_index), space_index, int(k), float(alpha), float(beta), float(prune),
-                                     int(bool(log_probs)), tables.desc_ref, lm.order, ptr(ws), ws_bytes, ptr(out), stream_ptr()),
-          'w2l_ctc_beam_search_lm')
+    head = (ptr(x), ptr(sz), n, t, a, info.ctypes.data_as(C.c_void_p), int(blank_index), int(end_index), space_index, int(k))
+    tail = (ptr(ws), ws_bytes, ptr(out), stream_ptr())
+    if lm is None:
+        check(lib.w2l_ctc_beam_search_lex(*head, float(beta), float(prune), int(bool(log_probs)), lex.desc_ref,
+                                          int(bool(complete_only)), *tail), 'w2l_ctc_beam_search_lex')
+    elif lex is None:
+        check(lib.w2l_ctc_beam_search_lm(*head, float(alpha), float(beta), float(prune), int(bool(log_probs)), tables.desc_ref,
+                                         lm.order, *tail), 'w2l_ctc_beam_search_lm')
+    else:
+        check(lib.w2l_ctc_beam_search_lm_lex(*head, float(alpha), float(beta), float(prune), int(bool(log_probs)),
+                                             tables.desc_ref, lm.order, lex.desc_ref, int(bool(complete_only)), *tail),
+              'w2l_ctc_beam_search_lm_lex')
     align_ws = _align_best(x, sz, out, n, t, k, blank_index, log_probs, beam_bytes) if offsets else None
     host = out.cpu().numpy()                           # the one copy to the host
     del align_ws
@@ -272,17 +334,20 @@ def _beam_search_device_lm(x, sz, labels, info, blank_index, end_index, k, alpha
     lengths = rest[:n * k].reshape(n, k)
     status = rest[n * k:n * k + n]
     idx = rest[n * k + n:n * k + n + n * k * t].reshape(n, k, t)
-    lm_log10 = rest[n * k + n + n * k * t:n * k + n + n * k * t + n * k].view(np.float32).reshape(n, k)
     if status.any():
         raise ValueError('ctc output contains negative numbers (utterances %s)' % np.nonzero(status)[0].tolist())
+    got = (scores, lengths, idx)
+    if lm is not None:
+        got += (rest[n * k + n + n * k * t:n * k + n + n * k * t + n * k].view(np.float32).reshape(n, k),)
     if offsets:
-        return scores, lengths, idx, lm_log10, _align_starts(host, n, t, beam_bytes)
-    return scores, lengths, idx, lm_log10
+        got += (_align_starts(host, n, t, beam_bytes),)
+    return got
 
 
 def prefix_beam_search_gpu(probs, labels: Sequence[str], blank_index: int = 0, k: int = 5, beta: float = 5,
                            prune: float = 0.001, end_char: str = '>', sizes=None, log_probs: bool = False, nbest: int = 1,
-                           return_weights: bool = False, lm=None, alpha: float = 0.3, return_offsets: bool = False):
+                           return_weights: bool = False, lm=None, alpha: float = 0.3, return_offsets: bool = False,
+                           lexicon=None, complete_only: bool = True):
     """prefix_beam_search on the MI355X: one launch for a whole batch, masses as fp64 logs (no underflow on long
     utterances; the host function's float32 products do underflow), the host's candidate order and ties.  ``lm``: an
     ngram_lm.ArpaLM scored as the host's ``lm=lambda s: 10 ** lm.score(s)`` with weight ``alpha`` (None: no LM).
@@ -293,7 +358,13 @@ def prefix_beam_search_gpu(probs, labels: Sequence[str], blank_index: int = 0, k
     pairs, best first (log weight = log(mass * (words + 1) ** beta), the host's ranking weight).  A [T, labels] input gives one
     result, a batch a list of N.  ``return_offsets`` (only with ``nbest == 1``): ``(results, offsets)``, offsets an IntTensor
     per utterance holding the first frame of each character of its best prefix on that prefix's best frame path (one more
-    launch, w2l_ctc_align, on the same stream; still one copy to the host)."""
+    launch, w2l_ctc_align, on the same stream; still one copy to the host).
+
+    ``lexicon`` (a lexicon.Lexicon, a path to a word list, or 'lm': the vocabulary of ``lm``; None: no constraint): no mass
+    goes to a string with a word outside the lexicon, as in prefix_beam_search(lexicon=...), with or without ``lm``.  With
+    ``complete_only`` the results (best, n-best, offsets) are drawn from the members of the final beam whose trailing partial
+    word is empty or a whole word, in rank order with their own weights; if there is none, from the whole beam.  Labels that
+    are whitespace other than a space are an error with a lexicon, as with an LM."""
     labels = list(labels)
     if not 1 <= nbest <= k:
         raise ValueError('nbest=%d must lie in [1, k=%d]' % (nbest, k))
@@ -306,7 +377,7 @@ def prefix_beam_search_gpu(probs, labels: Sequence[str], blank_index: int = 0, k
         if sizes is not None:
             sizes = [int(np.asarray(sizes).reshape(-1)[0])]
     got = _beam_search_device(x, labels, blank_index, k, beta, prune, end_char, sizes, log_probs, lm=lm, alpha=alpha,
-                              offsets=return_offsets)
+                              offsets=return_offsets, lexicon=lexicon, complete_only=complete_only)
     scores, lengths, idx = got[:3]
     results = []
     for u in range(scores.shape[0]):
@@ -334,10 +405,14 @@ def _nest_offsets(got, single):
 
 class GPUPrefixBeamSearchDecoder(Decoder):
     """PrefixBeamSearchLMDecoder on the MI355X (prefix_beam_search_gpu): the same constructor (plus ``log_probs``), no
-    language model -- a scoring callable cannot run on the device."""
+    language model -- a scoring callable cannot run on the device.  ``lexicon``: a lexicon.Lexicon or a path to a word list
+    that constrains the search (prefix_beam_search_gpu)."""
 
-    def __init__(self, lm_path, labels, blank_index=0, k=5, alpha=0.3, beta=5, prune=1e-3, log_probs=False):
+    def __init__(self, lm_path, labels, blank_index=0, k=5, alpha=0.3, beta=5, prune=1e-3, log_probs=False, lexicon=None):
         super(GPUPrefixBeamSearchDecoder, self).__init__(labels, blank_index)
+        if isinstance(lexicon, str) and lexicon == 'lm':
+            raise ValueError("GPUPrefixBeamSearchDecoder has no language model: lexicon='lm' needs GPUPrefixBeamSearchLMDecoder")
+        self.lexicon = _resolve_lexicon(lexicon, None) if lexicon is not None else None
         if lm_path:
             raise ValueError('GPUPrefixBeamSearchDecoder has no language model (lm_path=%r, alpha=%r): use '
                              'PrefixBeamSearchLMDecoder, the host decoder, for LM scoring' % (lm_path, alpha))
@@ -351,18 +426,20 @@ class GPUPrefixBeamSearchDecoder(Decoder):
             raise RuntimeError('Decoding with wrong shape: %s, expected either [Batch X Frames X Labels] or '
                                '[Frames X Labels]' % str(tuple(probs.shape)))
         got = prefix_beam_search_gpu(probs, self.labels, self.blank_index, self.k, self.beta, self.prune, sizes=sizes,
-                                     log_probs=self.log_probs, return_offsets=return_offsets)
+                                     log_probs=self.log_probs, return_offsets=return_offsets, lexicon=self.lexicon)
         return _nest_offsets(got, len(probs.shape) == 2) if return_offsets else got
 
 
 class GPUPrefixBeamSearchLMDecoder(Decoder):
     """PrefixBeamSearchLMDecoder on the MI355X with an ARPA n-gram model read without kenlm (ngram_lm.ArpaLM, plain or
-    .gz): the reference decoder's constructor (plus ``log_probs``); a falsy ``lm_path`` decodes without an LM."""
+    .gz): the reference decoder's constructor (plus ``log_probs``); a falsy ``lm_path`` decodes without an LM.  ``lexicon``: a
+    lexicon.Lexicon, a path to a word list, or 'lm' (the model's vocabulary) that constrains the search."""
 
-    def __init__(self, lm_path, labels, blank_index=0, k=5, alpha=0.3, beta=5, prune=1e-3, log_probs=False):
+    def __init__(self, lm_path, labels, blank_index=0, k=5, alpha=0.3, beta=5, prune=1e-3, log_probs=False, lexicon=None):
         super(GPUPrefixBeamSearchLMDecoder, self).__init__(labels, blank_index)
         from .ngram_lm import ArpaLM
         self.lm = ArpaLM(lm_path) if lm_path else None
+        self.lexicon = _resolve_lexicon(lexicon, self.lm) if lexicon is not None else None
         self.k, self.alpha, self.beta, self.prune, self.log_probs = k, alpha, beta, prune, log_probs
 
     def decode(self, probs, sizes=None, return_offsets=False):
@@ -373,7 +450,8 @@ class GPUPrefixBeamSearchLMDecoder(Decoder):
             raise RuntimeError('Decoding with wrong shape: %s, expected either [Batch X Frames X Labels] or '
                                '[Frames X Labels]' % str(tuple(probs.shape)))
         got = prefix_beam_search_gpu(probs, self.labels, self.blank_index, self.k, self.beta, self.prune, sizes=sizes,
-                                     log_probs=self.log_probs, lm=self.lm, alpha=self.alpha, return_offsets=return_offsets)
+                                     log_probs=self.log_probs, lm=self.lm, alpha=self.alpha, return_offsets=return_offsets,
+                                     lexicon=self.lexicon)
         return _nest_offsets(got, len(probs.shape) == 2) if return_offsets else got
 
 

@@ -50,6 +50,24 @@ __device__ __forceinline__ int tab_find(const uint64_t* keys, const int32_t* val
     }
 }
 
+// ------------------------------------------------------------------------------------------------------------- lexicon
+struct LexArgs {                              // w2l_lexicon_t on the device (lexicon.Lexicon), plus the search's parameters
+    const uint64_t* tkeys;
+    const int32_t* tvals;
+    const int32_t* tword;
+    uint32_t tmask;
+    int space, complete_only;
+};
+
+// the lexicon's trie node of (partial word at node `trie`) + canonical label c; < 0: the extension leaves the word list.
+// A separator (the space, end_char) closes an empty partial word or a whole word, and the partial word is empty again.
+__device__ __forceinline__ int lex_step(const LexArgs& X, int trie, int c, int endc) {
+    if (c == X.space || c == endc) return trie == 0 || X.tword[trie] >= 0 ? 0 : -1;
+    return tab_find(X.tkeys, X.tvals, X.tmask, ((uint64_t)trie << 8) | (uint64_t)c);
+}
+
+__device__ __forceinline__ bool lex_complete(const LexArgs& X, int trie) { return trie == 0 || X.tword[trie] >= 0; }
+
 // log10 q(w | s) (ngram_lm.ArpaLM.q) by the reverse-suffix walk w, h_1 w, h_2 h_1 w, ...; with nx, also the state after w
 __device__ float lm_word(const LmArgs& L, const NodeLM& s, int w, NodeLM* nx) {
     int e = w;

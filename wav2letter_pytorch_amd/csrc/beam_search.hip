@@ -23,6 +23,12 @@
 // With a language model (LM = true, w2l_ctc_beam_search_lm): every trie node also carries an LM state (NodeLM, after the
 // intern table in the workspace), computed once by the P3 thread that interns the node from its parent's state and its
 // character.  P2 adds a member's LM weight to the one contribution the host weights (parent_part, a word-closing label).
+//
+// With a lexicon (LEX = true, w2l_ctc_beam_search_lex / _lm_lex): every beam slot carries the lexicon's spelling-trie node of
+// its partial word (lex_trie, LDS).  The P2 thread of an extension entry that is not a beam member probes the trie once
+// (lex_step); an extension that leaves the word list gets no mass, exactly like a pruned label.  The node of a new member is a
+// function of its parent slot's node and its character, so P3 finds it with the same probe and nothing is kept per interned
+// prefix.  The output stage keeps the members whose partial word is empty or a whole word (complete_only).
 #include "common.h"
 #include "beam_lm.h"
 #include "../../include/w2l_hip.h"
@@ -63,15 +69,16 @@ struct Beam {                         // one frame's beam, slot-indexed
     double pb[BS_KMAX], pnb[BS_KMAX], score[BS_KMAX];
 };
 
-template <bool LM>
+template <bool LM, bool LEX>
 __global__ __launch_bounds__(BS_THREADS) void ctc_beam_search_kernel(
     const float* __restrict__ probs, const int32_t* __restrict__ sizes, int T, int A, LabelInfo info, int blank, int endc,
     int k, double beta, double prune, int log_probs, char* __restrict__ ws, int64_t ws_per_utt, int hash_cap,
     double* __restrict__ out_score, int32_t* __restrict__ out_len, int32_t* __restrict__ out_status,
-    int32_t* __restrict__ out_labels, LmArgs lmargs, float* __restrict__ out_lm) {
+    int32_t* __restrict__ out_labels, LmArgs lmargs, float* __restrict__ out_lm, LexArgs lex) {
     __shared__ Beam beams[2];
     __shared__ double lm_w[2][LM ? BS_KMAX : 1];          // LM weight (natural log) of each beam slot
     __shared__ int lm_on[2][LM ? BS_KMAX : 1];             // ... and whether it applies (a non-space character)
+    __shared__ int lex_trie[2][LEX ? BS_KMAX : 1];        // lexicon trie node of each beam slot's partial word
     __shared__ double lpd[BS_AMAX];
     __shared__ int alph[BS_AMAX], act[BS_AMAX], lab[BS_AMAX];
     __shared__ int s_m[2], s_nalph, s_count, s_bad;
@@ -112,6 +119,7 @@ __global__ __launch_bounds__(BS_THREADS) void ctc_beam_search_kernel(
             lm_w[0][0] = 0.0;
             lm_on[0][0] = 0;
         }
+        if constexpr (LEX) lex_trie[0][0] = 0;
         s_m[0] = 1;
         s_m[1] = 0;
         s_bad = 0;
@@ -192,7 +200,10 @@ __global__ __launch_bounds__(BS_THREADS) void ctc_beam_search_kernel(
                 const int i = e / A, c = e - i * A;
                 const int mv = mem[ent];
                 const int s = (mv >> 7) == t + 1 ? (mv & 127) : -1;
-                const bool ext = act[c] == t + 1 && !closed(B, i);   // labels of c passed the prune; slot i is open
+                bool ext = act[c] == t + 1 && !closed(B, i);         // labels of c passed the prune; slot i is open
+                if constexpr (LEX) {                                 // ... and the extension stays in the lexicon
+                    if (ext && s < 0) ext = lex_step(lex, lex_trie[cur][i], c, endc) >= 0;
+                }
                 if (ext || s >= 0) {
                     live = true;
                     // contributions of slot i extended by c (beam_search.py: the non-blank branches of pre = slot i)
@@ -312,8 +323,10 @@ __global__ __launch_bounds__(BS_THREADS) void ctc_beam_search_kernel(
                 NB.node[r] = B.node[s]; NB.parent[r] = B.parent[s]; NB.chr[r] = B.chr[s];
                 NB.words[r] = B.words[s]; NB.len[r] = B.len[s]; NB.prevslot[r] = s;
                 if constexpr (LM) { lm_w[cur ^ 1][r] = lm_w[cur][s]; lm_on[cur ^ 1][r] = lm_on[cur][s]; }
+                if constexpr (LEX) lex_trie[cur ^ 1][r] = lex_trie[cur][s];
             } else {
                 const int par = B.node[i];
+                if constexpr (LEX) lex_trie[cur ^ 1][r] = lex_step(lex, lex_trie[cur][i], c, endc);   // >= 0: P2 let it live
                 const uint64_t key = ((uint64_t)par << 8) | (uint64_t)c;
                 uint32_t h = key_hash(key) & (hash_cap - 1);
                 int node = -1;
@@ -358,15 +371,28 @@ __global__ __launch_bounds__(BS_THREADS) void ctc_beam_search_kernel(
     // ---------------------------------------------------------------- output: backtrack the final beam
     const int m = s_m[cur];
     const Beam& B = beams[cur];
+    int src = tid, mout = m;                               // slot tid of the output holds beam member src (if tid < mout)
+    if constexpr (LEX) {
+        // complete_only: the members whose partial word is empty or a whole word, in rank order (all of them if there is none)
+        if (wave == 0 && lex.complete_only) {
+            const uint64_t done = __ballot(tid < m && lex_complete(lex, lex_trie[cur][tid]));
+            if (done) {
+                mout = __popcll(done);
+                uint64_t rest = done;                      // the tid-th set bit
+                for (int j = 0; j < tid && rest; ++j) rest &= rest - 1;
+                src = rest ? __ffsll((unsigned long long)rest) - 1 : 0;
+            }
+        }
+    }
     if (tid < k) {
         const int64_t o = (int64_t)n * k + tid;
-        if (tid < m) {
-            const int len = B.len[tid];
-            out_score[o] = B.score[tid];
+        if (tid < mout) {
+            const int len = B.len[src];
+            out_score[o] = B.score[src];
             out_len[o] = len;
-            if constexpr (LM) out_lm[o] = nd_lm[B.node[tid]].total;
+            if constexpr (LM) out_lm[o] = nd_lm[B.node[src]].total;
             int32_t* lab_out = out_labels + o * T;
-            int node = B.node[tid];
+            int node = B.node[src];
             for (int p = len - 1; p >= 0; --p) {
                 lab_out[p] = nd_chr[node];
                 node = nd_parent[node];
@@ -406,11 +432,12 @@ extern "C" int64_t w2l_ctc_beam_search_workspace_bytes(int N, int T, int k) {
 
 namespace {
 
-// the checks and the launch shared by both entry points (ws_per_utt: the workspace stride of one utterance)
-template <bool LM>
+// the checks and the launch shared by the entry points (ws_per_utt: the workspace stride of one utterance)
+template <bool LM, bool LEX = false>
 int launch_search(const char* name, const float* probs, const int32_t* sizes, int N, int T, int A, const int32_t* label_info_host,
                   int blank, int end_index, int k, double beta, double prune, int log_probs, void* workspace,
-                  int64_t workspace_bytes, int64_t need, int64_t ws_per_utt, void* out, const LmArgs& lm, void* stream) {
+                  int64_t workspace_bytes, int64_t need, int64_t ws_per_utt, void* out, const LmArgs& lm, void* stream,
+                  const LexArgs& lex = LexArgs{}) {
     W2L_CHECK_ARG(probs && label_info_host && workspace && out && N > 0 && T > 0, "%s: bad arguments", name);
     W2L_CHECK_ARG(A >= 1 && A <= BS_AMAX, "%s: %d labels, supported 1..%d", name, A, BS_AMAX);
     W2L_CHECK_ARG(k >= 1 && k <= BS_KMAX, "%s: beam width k=%d, supported 1..%d", name, k, BS_KMAX);
@@ -419,7 +446,7 @@ int launch_search(const char* name, const float* probs, const int32_t* sizes, in
     W2L_CHECK_ARG((int64_t)k * T < (1 << 29) && T < (1 << 24), "%s: k*T = %lld too large", name, (long long)k * T);
     W2L_CHECK_ARG(need > 0 && workspace_bytes >= need, "%s: workspace of %lld bytes, %lld needed", name,
                   (long long)workspace_bytes, (long long)need);
-    const void* kern = (const void*)ctc_beam_search_kernel<LM>;
+    const void* kern = (const void*)ctc_beam_search_kernel<LM, LEX>;
     hipFuncAttributes fa;
     W2L_CHECK_HIP(hipFuncGetAttributes(&fa, kern));
     const int64_t lds = lds_bytes(k, A);
@@ -441,9 +468,9 @@ int launch_search(const char* name, const float* probs, const int32_t* sizes, in
     int32_t* out_status = out_len + (int64_t)N * k;
     int32_t* out_labels = out_status + N;
     float* out_lm = LM ? (float*)(out_labels + (int64_t)N * k * T) : nullptr;
-    hipLaunchKernelGGL(ctc_beam_search_kernel<LM>, dim3(N), dim3(BS_THREADS), (size_t)lds, (hipStream_t)stream, probs, sizes, T,
-                       A, info, blank, end_index, k, beta, prune, log_probs, (char*)workspace, ws_per_utt, hash_capacity(T, k),
-                       out_score, out_len, out_status, out_labels, lm, out_lm);
+    hipLaunchKernelGGL((ctc_beam_search_kernel<LM, LEX>), dim3(N), dim3(BS_THREADS), (size_t)lds, (hipStream_t)stream, probs,
+                       sizes, T, A, info, blank, end_index, k, beta, prune, log_probs, (char*)workspace, ws_per_utt,
+                       hash_capacity(T, k), out_score, out_len, out_status, out_labels, lm, out_lm, lex);
     W2L_CHECK_LAUNCH();
     return 0;
 }
@@ -503,41 +530,110 @@ extern "C" int64_t w2l_ctc_beam_search_lm_workspace_bytes(int N, int T, int k, i
     return (int64_t)N * lm_ws_stride(T, k);
 }
 
+namespace {
+
+// the argument checks of the LM entry points, and the device form of the tables
+int lm_args(const char* name, const int32_t* label_info_host, int A, int space_index, double alpha, const w2l_ngram_lm_t* lm,
+            int order, int T, int k, LmArgs* a) {
+    W2L_CHECK_ARG(lm && label_info_host && A >= 1 && A <= BS_AMAX, "%s: bad arguments", name);
+    W2L_CHECK_ARG(order >= 1 && order <= LM_MAXORDER, "%s: order %d, supported 1..%d", name, order, LM_MAXORDER);
+    W2L_CHECK_ARG(space_index >= -1 && space_index < A && (space_index < 0 || (label_info_host[space_index] & 0xff) == space_index),
+                  "%s: space index %d is not the first index of a label", name, space_index);
+    for (int i = 0; i < A; ++i)
+        W2L_CHECK_ARG(!(label_info_host[i] & 0x800) || (label_info_host[i] & 0xff) == space_index,
+                      "%s: label %d is whitespace other than ' '", name, i);
+    W2L_CHECK_ARG(lm->prob && lm->bo && lm->ngram_keys && lm->ngram_vals && lm->trie_keys && lm->trie_vals && lm->trie_word,
+                  "%s: a table pointer is NULL", name);
+    W2L_CHECK_ARG(lm->n_words >= 3 && lm->n_entries >= lm->n_words && lm->n_entries < (1 << 30) && lm->n_trie_nodes >= 1,
+                  "%s: %d entries, %d words, %d trie nodes (3 <= words <= entries < 2^30)", name, lm->n_entries,
+                  lm->n_words, lm->n_trie_nodes);
+    W2L_CHECK_ARG(pow2_cap(lm->ngram_cap) && lm->ngram_cap >= 2 * (int64_t)(lm->n_entries - lm->n_words) && pow2_cap(lm->trie_cap)
+                      && lm->trie_cap >= 2 * (int64_t)(lm->n_trie_nodes - 1),
+                  "%s: table capacities %lld / %lld (powers of two in [16, 2^31], at most half full)", name,
+                  (long long)lm->ngram_cap, (long long)lm->trie_cap);
+    a->prob = lm->prob;
+    a->bo = lm->bo;
+    a->nkeys = lm->ngram_keys;
+    a->nvals = lm->ngram_vals;
+    a->tkeys = lm->trie_keys;
+    a->tvals = lm->trie_vals;
+    a->tword = lm->trie_word;
+    a->nmask = (uint32_t)(lm->ngram_cap - 1);
+    a->tmask = (uint32_t)(lm->trie_cap - 1);
+    a->order = order;
+    a->space = space_index;
+    a->alpha_ln10 = alpha * 2.302585092994045684;
+    a->state_off = lm_state_offset(T, k);
+    return 0;
+}
+
+// ... and of the lexicon entry points
+int lex_args(const char* name, const int32_t* label_info_host, int A, int space_index, const w2l_lexicon_t* lexicon,
+             int complete_only, LexArgs* x) {
+    W2L_CHECK_ARG(lexicon && label_info_host && A >= 1 && A <= BS_AMAX, "%s: bad arguments", name);
+    W2L_CHECK_ARG(space_index >= -1 && space_index < A && (space_index < 0 || (label_info_host[space_index] & 0xff) == space_index),
+                  "%s: space index %d is not the first index of a label", name, space_index);
+    for (int i = 0; i < A; ++i)
+        W2L_CHECK_ARG(!(label_info_host[i] & 0x800) || (label_info_host[i] & 0xff) == space_index,
+                      "%s: label %d is whitespace other than ' '", name, i);
+    W2L_CHECK_ARG(lexicon->trie_keys && lexicon->trie_vals && lexicon->trie_word, "%s: a lexicon table pointer is NULL", name);
+    W2L_CHECK_ARG(lexicon->n_trie_nodes >= 1 && pow2_cap(lexicon->trie_cap)
+                      && lexicon->trie_cap >= 2 * (int64_t)(lexicon->n_trie_nodes - 1),
+                  "%s: lexicon of %d trie nodes in a table of capacity %lld (a power of two in [16, 2^31], at most half full)",
+                  name, lexicon->n_trie_nodes, (long long)lexicon->trie_cap);
+    x->tkeys = lexicon->trie_keys;
+    x->tvals = lexicon->trie_vals;
+    x->tword = lexicon->trie_word;
+    x->tmask = (uint32_t)(lexicon->trie_cap - 1);
+    x->space = space_index;
+    x->complete_only = complete_only != 0;
+    return 0;
+}
+
+}  // namespace
+
 extern "C" int w2l_ctc_beam_search_lm(const float* probs, const int32_t* sizes, int N, int T, int A,
                                       const int32_t* label_info_host, int blank, int end_index, int space_index, int k,
                                       double alpha, double beta, double prune, int log_probs, const w2l_ngram_lm_t* lm,
                                       int order, void* workspace, int64_t workspace_bytes, void* out, void* stream) {
-    W2L_CHECK_ARG(lm && label_info_host && A >= 1 && A <= BS_AMAX, "ctc_beam_search_lm: bad arguments");
-    W2L_CHECK_ARG(order >= 1 && order <= LM_MAXORDER, "ctc_beam_search_lm: order %d, supported 1..%d", order, LM_MAXORDER);
-    W2L_CHECK_ARG(space_index >= -1 && space_index < A && (space_index < 0 || (label_info_host[space_index] & 0xff) == space_index),
-                  "ctc_beam_search_lm: space index %d is not the first index of a label", space_index);
-    for (int i = 0; i < A; ++i)
-        W2L_CHECK_ARG(!(label_info_host[i] & 0x800) || (label_info_host[i] & 0xff) == space_index,
-                      "ctc_beam_search_lm: label %d is whitespace other than ' '", i);
-    W2L_CHECK_ARG(lm->prob && lm->bo && lm->ngram_keys && lm->ngram_vals && lm->trie_keys && lm->trie_vals && lm->trie_word,
-                  "ctc_beam_search_lm: a table pointer is NULL");
-    W2L_CHECK_ARG(lm->n_words >= 3 && lm->n_entries >= lm->n_words && lm->n_entries < (1 << 30) && lm->n_trie_nodes >= 1,
-                  "ctc_beam_search_lm: %d entries, %d words, %d trie nodes (3 <= words <= entries < 2^30)", lm->n_entries,
-                  lm->n_words, lm->n_trie_nodes);
-    W2L_CHECK_ARG(pow2_cap(lm->ngram_cap) && lm->ngram_cap >= 2 * (int64_t)(lm->n_entries - lm->n_words) && pow2_cap(lm->trie_cap)
-                      && lm->trie_cap >= 2 * (int64_t)(lm->n_trie_nodes - 1),
-                  "ctc_beam_search_lm: table capacities %lld / %lld (powers of two in [16, 2^31], at most half full)",
-                  (long long)lm->ngram_cap, (long long)lm->trie_cap);
     LmArgs a;
-    a.prob = lm->prob;
-    a.bo = lm->bo;
-    a.nkeys = lm->ngram_keys;
-    a.nvals = lm->ngram_vals;
-    a.tkeys = lm->trie_keys;
-    a.tvals = lm->trie_vals;
-    a.tword = lm->trie_word;
-    a.nmask = (uint32_t)(lm->ngram_cap - 1);
-    a.tmask = (uint32_t)(lm->trie_cap - 1);
-    a.order = order;
-    a.space = space_index;
-    a.alpha_ln10 = alpha * 2.302585092994045684;
-    a.state_off = lm_state_offset(T, k);
+    if (int rc = lm_args("ctc_beam_search_lm", label_info_host, A, space_index, alpha, lm, order, T, k, &a)) return rc;
     return launch_search<true>("ctc_beam_search_lm", probs, sizes, N, T, A, label_info_host, blank, end_index, k, beta, prune,
                                log_probs, workspace, workspace_bytes, w2l_ctc_beam_search_lm_workspace_bytes(N, T, k, order),
                                lm_ws_stride(T, k), out, a, stream);
+}
+
+// The lexicon searches keep no state per interned prefix (see the head of this file): their workspaces are their parents'.
+extern "C" int64_t w2l_ctc_beam_search_lex_workspace_bytes(int N, int T, int k) {
+    return w2l_ctc_beam_search_workspace_bytes(N, T, k);
+}
+
+extern "C" int64_t w2l_ctc_beam_search_lm_lex_workspace_bytes(int N, int T, int k, int order) {
+    return w2l_ctc_beam_search_lm_workspace_bytes(N, T, k, order);
+}
+
+extern "C" int w2l_ctc_beam_search_lex(const float* probs, const int32_t* sizes, int N, int T, int A,
+                                       const int32_t* label_info_host, int blank, int end_index, int space_index, int k,
+                                       double beta, double prune, int log_probs, const w2l_lexicon_t* lexicon,
+                                       int complete_only, void* workspace, int64_t workspace_bytes, void* out, void* stream) {
+    LexArgs x;
+    if (int rc = lex_args("ctc_beam_search_lex", label_info_host, A, space_index, lexicon, complete_only, &x)) return rc;
+    return launch_search<false, true>("ctc_beam_search_lex", probs, sizes, N, T, A, label_info_host, blank, end_index, k, beta,
+                                      prune, log_probs, workspace, workspace_bytes,
+                                      w2l_ctc_beam_search_lex_workspace_bytes(N, T, k), ws_stride(T, k), out, LmArgs{}, stream, x);
+}
+
+extern "C" int w2l_ctc_beam_search_lm_lex(const float* probs, const int32_t* sizes, int N, int T, int A,
+                                          const int32_t* label_info_host, int blank, int end_index, int space_index, int k,
+                                          double alpha, double beta, double prune, int log_probs, const w2l_ngram_lm_t* lm,
+                                          int order, const w2l_lexicon_t* lexicon, int complete_only, void* workspace,
+                                          int64_t workspace_bytes, void* out, void* stream) {
+    LmArgs a;
+    LexArgs x;
+    if (int rc = lm_args("ctc_beam_search_lm_lex", label_info_host, A, space_index, alpha, lm, order, T, k, &a)) return rc;
+    if (int rc = lex_args("ctc_beam_search_lm_lex", label_info_host, A, space_index, lexicon, complete_only, &x)) return rc;
+    return launch_search<true, true>("ctc_beam_search_lm_lex", probs, sizes, N, T, A, label_info_host, blank, end_index, k, beta,
+                                     prune, log_probs, workspace, workspace_bytes,
+                                     w2l_ctc_beam_search_lm_lex_workspace_bytes(N, T, k, order), lm_ws_stride(T, k), out, a,
+                                     stream, x);
 }

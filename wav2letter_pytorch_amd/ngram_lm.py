@@ -57,6 +57,37 @@ def table_capacity(n: int) -> int:
     return cap
 
 
+def build_spelling_trie(words, labels: Sequence[str], blank_index: int = 0):
+    """the flat spelling trie of ``words`` (pairs (id, word), in insertion order) over ``labels``: (keys uint64 (node << 8 |
+    canonical label), vals int32 (child node), word int32 [nodes] (the id a node spells, -1), the number of words dropped).  A
+    word is dropped when one of its characters is not a label, is the blank's character or is whitespace; a duplicate
+    label spells with its first index.  Shared by ArpaLM.spelling_trie and lexicon.Lexicon.spelling_trie."""
+    labels = list(labels)
+    first: Dict[str, int] = {}
+    for i, ch in enumerate(labels):
+        first.setdefault(ch, i)
+    first.pop(labels[blank_index], None)
+    children: Dict[Tuple[int, int], int] = {}
+    word = [-1]
+    dropped = 0
+    for wid, w in words:
+        if not all(ch in first and not ch.isspace() for ch in w):
+            dropped += 1
+            continue
+        node = 0
+        for ch in w:
+            key = (node, first[ch])
+            child = children.get(key)
+            if child is None:
+                child = children[key] = len(word)
+                word.append(-1)
+            node = child
+        word[node] = wid
+    keys = np.array([(nd << 8) | c for nd, c in children], dtype=np.uint64)
+    vals = np.array(list(children.values()), dtype=np.int32)
+    return keys, vals, np.array(word, dtype=np.int32), dropped
+
+
 class ArpaLM:
     """An ARPA n-gram model (order <= 6).  Word ids: <unk> = 0, <s> = 1, </s> = 2, then the file's unigram order."""
 
@@ -248,27 +279,7 @@ class ArpaLM:
         ck = (tuple(labels), blank_index)
         if ck in self._tries:
             return self._tries[ck]
-        first: Dict[str, int] = {}
-        for i, ch in enumerate(labels):
-            first.setdefault(ch, i)
-        first.pop(labels[blank_index], None)
-        children: Dict[Tuple[int, int], int] = {}
-        word = [-1]
-        for wid, w in enumerate(self.words):
-            if not all(ch in first and not ch.isspace() for ch in w):
-                continue
-            node = 0
-            for ch in w:
-                key = (node, first[ch])
-                child = children.get(key)
-                if child is None:
-                    child = children[key] = len(word)
-                    word.append(-1)
-                node = child
-            word[node] = wid
-        keys = np.array([(nd << 8) | c for nd, c in children], dtype=np.uint64)
-        vals = np.array(list(children.values()), dtype=np.int32)
-        out = (keys, vals, np.array(word, dtype=np.int32))
+        out = build_spelling_trie(enumerate(self.words), labels, blank_index)[:3]
         self._tries[ck] = out
         return out
 

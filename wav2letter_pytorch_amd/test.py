@@ -4,13 +4,15 @@ shipped:
     python -m wav2letter_pytorch_amd.test [--config-dir /path/to/configuration] model_path=run/epoch=4-step=900.ckpt \\
            data.test_manifest=test.csv [model=jasper] [model.mid_layers=20] [decoder=greedy|beam|beam_lm|asg_beam|asg_beam_lm] [lm_path=lm.arpa] \\
            [beam.k=5] [beam.alpha=0.3] [beam.beta=5] [beam.prune=1e-3] [print_samples=K | print_all=true] \\
-           [output=hyps.jsonl] [word_times=true] [data.resample=true]
+           [lexicon_path=words.txt | lexicon_from_lm=true] [output=hyps.jsonl] [word_times=true] [data.resample=true]
 
 ``train.py``'s override syntax and config tree.  The forward pass is ``model.infer`` (one fused launch per convolution);
 ``test_loss``, corpus-level ``test_cer`` / ``test_wer`` and ``test_len_ratio`` are printed and returned.  ``output=`` writes one
 JSON line per utterance: path, text, hypothesis, character and word errors (and each word's start / end seconds with
 ``word_times=true``, by forced alignment of the hypothesis).  ``decoder=asg_beam|asg_beam_lm`` are the beam searches of a model
-trained with ``model.criterion=asg`` (asg_beam.py), bound to the checkpoint's learned transitions."""
+trained with ``model.criterion=asg`` (asg_beam.py), bound to the checkpoint's learned transitions.  ``lexicon_path=`` (a word
+list, one word per line; ``decoder=beam|beam_lm``) or ``lexicon_from_lm=true`` (the model's vocabulary; ``decoder=beam_lm``)
+constrains the beam search to strings of lexicon words (lexicon.py).  It is not built for the ASG beam searches."""
 from __future__ import annotations
 
 import json
@@ -21,6 +23,7 @@ from .train import build_config as _train_config
 DECODERS = ('greedy', 'beam', 'beam_lm', 'asg_beam', 'asg_beam_lm')
 LM_DECODERS = ('beam_lm', 'asg_beam_lm')
 ASG_DECODERS = ('asg_beam', 'asg_beam_lm')
+LEXICON_DECODERS = ('beam', 'beam_lm')
 BEAM_DEFAULTS = dict(k=5, alpha=0.3, beta=5, prune=1e-3)
 
 
@@ -32,7 +35,8 @@ def build_config(argv):
     """the config tree of ``train.build_config`` plus the evaluation keys, checked: ``model_path`` and
     ``data.test_manifest`` are required (SystemExit naming the key), ``decoder`` is one of greedy / beam / beam_lm /
     asg_beam / asg_beam_lm (the last two only with ``model.criterion=asg``), ``lm_path`` belongs to ``decoder=beam_lm`` and
-    ``decoder=asg_beam_lm`` only (and those decoders need it)."""
+    ``decoder=asg_beam_lm`` only (and those decoders need it), ``lexicon_path`` to ``decoder=beam|beam_lm`` and
+    ``lexicon_from_lm`` to ``decoder=beam_lm`` (one of the two at most)."""
     cfg = _train_config(argv)
     if cfg.get('model_path') in (None, '???', ''):
         raise SystemExit('model_path is required (e.g. model_path=/path/to/epoch=0-step=100.ckpt)')
@@ -47,6 +51,22 @@ def build_config(argv):
                          '(or asg_beam_lm under model.criterion=asg)')
     if cfg.decoder in LM_DECODERS and not lm:
         raise SystemExit(f'decoder={cfg.decoder} needs lm_path=/path/to/model.arpa')
+    cfg['lexicon_from_lm'] = _truth(cfg.get('lexicon_from_lm', False))
+    cfg.setdefault('lexicon_path', None)
+    for key in ('lexicon_path', 'lexicon_from_lm'):
+        if not cfg[key]:
+            continue
+        if cfg.decoder in ASG_DECODERS:
+            raise SystemExit(f'{key} is given but decoder={cfg.decoder}: the lexicon constraint is not built for ASG beam '
+                             'search (decoder=beam|beam_lm have it)')
+        if cfg.decoder not in LEXICON_DECODERS:
+            raise SystemExit(f'{key} is given but decoder={cfg.decoder}: a lexicon constrains a beam search '
+                             '(decoder=beam or decoder=beam_lm)')
+    if cfg.lexicon_path and cfg.lexicon_from_lm:
+        raise SystemExit('lexicon_path and lexicon_from_lm are both given: the search takes one lexicon')
+    if cfg.lexicon_from_lm and cfg.decoder != 'beam_lm':
+        raise SystemExit(f'lexicon_from_lm is given but decoder={cfg.decoder}: the vocabulary of a language model needs '
+                         'decoder=beam_lm')
     if cfg.decoder in ASG_DECODERS and cfg.model.get('criterion', 'ctc') != 'asg':
         raise SystemExit(f'decoder={cfg.decoder} decodes with learned transitions: it needs model.criterion=asg')
     beam = dict(BEAM_DEFAULTS)
@@ -82,6 +102,9 @@ def decoder_spec(cfg, log_probs: bool):
         return 'ASGBeamSearchLMDecoder', dict(lm_path=cfg.lm_path, alpha=float(cfg.beam.alpha), **kw)
     kw = dict(labels=labels, k=int(cfg.beam.k), alpha=float(cfg.beam.alpha), beta=float(cfg.beam.beta),
               prune=float(cfg.beam.prune), log_probs=log_probs)
+    lexicon = 'lm' if cfg.get('lexicon_from_lm') else cfg.get('lexicon_path')
+    if lexicon:                                # (the key is absent without a lexicon: the decoders' defaults)
+        kw['lexicon'] = lexicon
     if cfg.decoder == 'beam':
         return 'GPUPrefixBeamSearchDecoder', dict(lm_path=None, **kw)
     return 'GPUPrefixBeamSearchLMDecoder', dict(lm_path=cfg.lm_path, **kw)
