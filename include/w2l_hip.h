@@ -657,6 +657,26 @@ int w2l_ctc_beam_search_lm_lex(const float* probs, const int32_t* sizes, int N, 
                                int blank, int end_index, int space_index, int k, double alpha, double beta, double prune,
                                int log_probs, const w2l_ngram_lm_t* lm, int order, const w2l_lexicon_t* lexicon,
                                int complete_only, void* workspace, int64_t workspace_bytes, void* out, void* stream);
+/* ---- hotword boosting in the four searches above (lexicon.Lexicon.boost_chars) ---- */
+/* workspace bytes of w2l_ctc_beam_search_hot: those of the search without hotwords (order 0: no LM, w2l_ctc_beam_search's;
+ * otherwise w2l_ctc_beam_search_lm's); -1 if out of range */
+int64_t w2l_ctc_beam_search_hot_workspace_bytes(int N, int T, int k, int order);
+/* w2l_ctc_beam_search (lm and lexicon NULL), _lm (lexicon NULL), _lex (lm NULL) or _lm_lex with a list of hotwords, given as
+ * the spelling trie of a word list of its own (a w2l_lexicon_t; separate from lexicon's and from lm's).  h(s) = the characters
+ * of the closed words of s (those followed by the space or end_char) that are hotwords, plus the characters of its partial
+ * word while that is a non-empty prefix of a hotword (a provisional credit: it goes when the word leaves the trie or is
+ * closed as something else).  The ranking weight becomes mass * (words + 1)^beta * exp(hotword_weight * h): the score
+ * written to out includes hotword_weight * h; masses, the LM term, the prune, ties and the lexicon rule are untouched.
+ * hotword_weight: natural-log units per character, any finite real; 0 gives the output of the search without hotwords.  The
+ * arguments a NULL lm / lexicon leaves unused (alpha, order / complete_only) are ignored; out has lm_log10 only with lm.  One
+ * more trie probe per new candidate; 1.5 KB of static LDS more than the same search without hotwords; nothing per interned
+ * prefix.  A NULL or over-full hotword table, a capacity that is no power of two, a non-finite weight and a whitespace label
+ * other than ' ' are argument errors. */
+int w2l_ctc_beam_search_hot(const float* probs, const int32_t* sizes, int N, int T, int A, const int32_t* label_info_host,
+                            int blank, int end_index, int space_index, int k, double alpha, double beta, double prune,
+                            int log_probs, const w2l_ngram_lm_t* lm, int order, const w2l_lexicon_t* lexicon,
+                            int complete_only, const w2l_lexicon_t* hotwords, double hotword_weight, void* workspace,
+                            int64_t workspace_bytes, void* out, void* stream);
 /* ---- ASG prefix beam search and forced alignment (asg_beam.py; host restatements: asg_prefix_beam_search,
  *      asg_viterbi_align_host): what w2l_ctc_beam_search / _lm / w2l_ctc_align are to a CTC model, for a model trained with
  *      the ASG criterion (no blank; learned transitions; label repeat_index stands for "the previous letter again") ---- */

@@ -1,0 +1,424 @@
+"""Hotword boosting in the device beam searches (w2l_ctc_beam_search_hot, all four LM / lexicon combinations) against the host
+recursion ``prefix_beam_search(..., hotwords=, hotword_weight=)`` on float64 posteriors: strings equal, log weights within 1e-9
+relative, ``lm_log10`` bit-equal to ``np.float32(lm.score(...))`` -- the comparison of tests/test_gpu_lexicon.py.
+
+Posteriors are generated in float32 and widened exactly.  Three of the four utterances are bursts of a few letters with a rival
+label boosted almost as much, around scripted passages that set the hotwords ABBA and BED against their prefixes closed as words
+(``AB ``, ``BE ``); the fourth spells only X, Y, Z: no hotword, and under a lexicon nothing but the empty string.  What the
+fixture must provoke (a decode the boost changes, a credit withdrawn, a credit still live in the final beam) is asserted on
+the host's results alone, for every case with k >= 3 and a positive weight, so no comparison passes vacuously."""
+import ctypes as C
+import functools
+import itertools
+
+import numpy as np
+import pytest
+import torch
+
+from wav2letter_pytorch_amd._lib import LexTables, lib, ptr, stream_ptr
+from wav2letter_pytorch_amd.alignment import ctc_forced_align
+from wav2letter_pytorch_amd.beam_search import (GPUPrefixBeamSearchDecoder, GPUPrefixBeamSearchLMDecoder, _beam_search_device,
+                                                _label_info, prefix_beam_search, prefix_beam_search_gpu)
+from wav2letter_pytorch_amd.data.label_sets import english_labels
+from wav2letter_pytorch_amd.lexicon import Lexicon
+from wav2letter_pytorch_amd.ngram_lm import ArpaLM
+
+pytestmark = pytest.mark.gpu
+
+LABELS = list(english_labels) + ['>', 'B']                      # 29 labels, an end_char, a duplicate of 'B' (index 30 -> 3)
+HOTWORDS = ['ABBA', 'BED', 'DÉJÀ']                              # (the last cannot be spelled)
+WORDS = ['A', 'AB', 'ABBA', 'ALL', 'BE', 'BED', 'CAB', "D'C", 'DEB', 'EB', 'C', 'LEAD', 'B', 'D', 'E', 'ABB']    # the lexicon
+LM_WORDS = ['A', 'AB', 'ABBA', 'ALL', 'BE', 'BED', 'CAD', 'DEB', 'ELL', 'C', "E'D"]     # another list: some in, some out
+N = 4
+SIZES = {24: [24, 17, 24, 24], 40: [40, 40, 29, 40]}
+GAMMAS = (0.7, -0.5)
+BIGRAM_ALPHA = 0.3      # the decoders' default; at 1.0 this random model forbids every space and no word is ever closed
+# scripted passages: (utterance, first frame counted from the start (>= 0) or from the utterance's end (< 0), letters ('_' is
+# the blank), position of the frame with a close rival, the rival).  A prefix of a hotword closed as a word with the hotword's
+# next letter as the rival ('AB ' against 'ABB', 'BE ' against 'BED', 'ABB>' against 'ABBA>', 'BE>' against 'BED>'), and an
+# open 'AB' at the end of the utterance that no end_char closes
+SCRIPT = ((0, 0, 'AB_ ', 3, 'B'), (0, -7, ' AB_B_>', 5, 'A'), (1, 0, 'BE_ ', 3, 'D'), (1, -5, ' BE_>', 3, 'D'),
+          (2, 0, 'AB_ ', -1, ''), (2, -4, ' _AB', -1, ''))
+
+
+@functools.lru_cache(maxsize=None)
+def _hotwords():
+    return Lexicon(HOTWORDS)
+
+
+@functools.lru_cache(maxsize=None)
+def _lexicon():
+    return Lexicon(WORDS)
+
+
+@functools.lru_cache(maxsize=None)
+def _posteriors(t, seed=0):
+    """float32 [4, t, 31]; shared by the tests, never written"""
+    rng = np.random.default_rng(1000 * t + seed)
+    a = len(LABELS)
+    cand = [LABELS.index(c) for c in "ABCDEL'"] + [30, 30, 3, 2, 2]      # the duplicate label takes part; A, B often
+    space, end = LABELS.index(' '), LABELS.index('>')
+    logits = rng.standard_normal((N, t, a))
+    for u in range(N - 1):
+        f = 0
+        while f < t:
+            if rng.random() < 0.4:
+                logits[u, f, 0] += rng.uniform(3.0, 6.0)
+                f += 1
+                continue
+            c = space if rng.random() < 0.3 else cand[rng.integers(len(cand))]
+            burst = int(rng.integers(1, 3))
+            b = rng.uniform(3.0, 6.0)
+            logits[u, f:f + burst, c] += b
+            logits[u, f:f + burst, cand[rng.integers(len(cand))]] += b - rng.uniform(0, 1.5)
+            f += burst
+    for u, f0, text, at, rival in SCRIPT:                        # one frame per letter, 7 nats over the noise
+        f0 = f0 if f0 >= 0 else SIZES[t][u] + f0
+        logits[u, f0:f0 + len(text)] = rng.standard_normal((len(text), a))
+        for j, ch in enumerate(text):
+            logits[u, f0 + j, 0 if ch == '_' else LABELS.index(ch)] += 7.0
+        if at >= 0:                                              # the rival: a factor e^0.5 down
+            main = 0 if text[at] == '_' else LABELS.index(text[at])
+            logits[u, f0 + at, LABELS.index(rival)] = logits[u, f0 + at, main] - 0.5
+    # a closed hypothesis keeps its mass while the open ones decay: end_char only where an utterance ends (not in the third)
+    for u in range(N - 1):
+        logits[u, :SIZES[t][u] - 2, end] -= 25.0
+        logits[u, SIZES[t][u] - 1, end] += (5.0, 3.0, -25.0)[u]
+    logits[2, SIZES[t][2] - 2, end] -= 25.0
+    # the last utterance: X, Y, Z against the blank, every other label 20 nats down (the duplicated label and end_char 60)
+    junk = [LABELS.index(c) for c in 'XYZ']
+    logits[N - 1] -= 20.0
+    logits[N - 1, :, [0] + junk] += 20.0
+    logits[N - 1, :, [3, 30, end]] -= 40.0
+    logits[N - 1, :, 0] += 2.0
+    for f in range(0, t, 3):
+        logits[N - 1, f, junk[(f // 3) % 3]] += rng.uniform(3.0, 5.0)
+    e = np.exp(logits - logits.max(-1, keepdims=True))
+    return (e / e.sum(-1, keepdims=True)).astype(np.float32)
+
+
+def _write_arpa(path, words, order, seed):
+    """a random order-``order`` model over ``words``: every higher n-gram extends a lower one by an older word"""
+    rng = np.random.default_rng(seed)
+    lines = {1: ['-2.0\t<unk>', '-99\t<s>\t%.5f' % -rng.uniform(0, 0.5), '%.5f\t</s>' % -rng.uniform(0.3, 1.5)]}
+    lines[1] += ['%.5f\t%s\t%.5f' % (-rng.uniform(0.3, 2.5), w, -rng.uniform(0, 0.6)) for w in words]
+    grams = [(w,) for w in words + ['</s>']]
+    for n in range(2, order + 1):
+        cur = set()
+        while len(cur) < 60:
+            base = grams[rng.integers(len(grams))]
+            if base[0] != '<s>':
+                cur.add(((['<s>'] + words)[rng.integers(len(words) + 1)],) + base)
+        grams = sorted(cur)
+        lines[n] = ['%.5f\t%s' % (-rng.uniform(0.05, 1.5), ' '.join(g)) + ('' if n == order else '\t%.5f' % -rng.uniform(0, 0.6))
+                    for g in grams]
+    text = '\\data\\\n' + ''.join('ngram %d=%d\n' % (n, len(lines[n])) for n in lines)
+    for n in lines:
+        text += '\n\\%d-grams:\n' % n + '\n'.join(lines[n]) + '\n'
+    path.write_text(text + '\n\\end\\\n')
+    return ArpaLM(str(path))
+
+
+@pytest.fixture(scope='module')
+def models(tmp_path_factory):
+    d = tmp_path_factory.mktemp('hot_lm')
+    return dict(bigram=_write_arpa(d / 'b.arpa', LM_WORDS, 2, 3), trigram=_write_arpa(d / 't.arpa', WORDS, 3, 2), dir=d)
+
+
+_HOST = {}
+
+
+def _host(t, u, k, beta, prune, lm, alpha, lexicon, gamma):
+    """prefix_beam_search on the float64 posteriors of utterance u, computed once per argument set: (best, weight, final beam).
+    ``gamma`` None: no hotwords"""
+    key = (t, u, k, beta, prune, id(lm), alpha, id(lexicon), gamma)
+    if key not in _HOST:
+        weigh = None
+        if lm is not None:
+            if not hasattr(lm, '_weigh'):
+                lm._weigh = functools.lru_cache(maxsize=None)(lambda s: 10 ** lm.score(s))
+            weigh = lm._weigh
+        p = _posteriors(t)[u, :SIZES[t][u]].astype(np.float64)
+        stats = {}
+        hot = dict(hotwords=_hotwords(), hotword_weight=gamma) if gamma is not None else {}
+        best, w = prefix_beam_search(p, LABELS, lm=weigh, k=k, alpha=alpha, beta=beta, prune=prune, return_weights=True,
+                                     lexicon=lexicon, stats=stats, **hot)
+        _HOST[key] = (best, w, stats['beam'])
+    return _HOST[key]
+
+
+def _strip_score(lm, s):
+    return np.float32(lm.score(s.strip(' >'))) if s.replace(' ', '') else np.float32(0)
+
+
+def _host_lexicon(lm, lexicon):
+    if isinstance(lexicon, str):                                 # 'lm': the host's lexicon is the model's vocabulary
+        if not hasattr(lm, '_host_lex'):
+            lm._host_lex = Lexicon.from_lm(lm)
+        return lm._host_lex
+    return lexicon
+
+
+def _fixture_conditions(t, k, beta, prune, lm, alpha, host_lex, gamma):
+    """on the host's results alone: (a decode that the boost changed, a final beam with a string that closed a proper prefix
+    of a hotword, a final beam with a string whose partial word holds a credit)"""
+    hot = _hotwords().spellable(LABELS, 0)
+    prefixes = {w[:i] for w in hot.words for i in range(1, len(w))} - set(hot.words)
+    changed = withdrawn = live = False
+    for u in range(N):
+        best, _, beam = _host(t, u, k, beta, prune, lm, alpha, host_lex, gamma)
+        changed |= best != _host(t, u, k, beta, prune, lm, alpha, host_lex, 0.0)[0]
+        for s in beam:
+            parts = s.replace('>', ' ').split(' ')
+            withdrawn |= any(p in prefixes for p in parts[:-1])
+            live |= parts[-1] != '' and hot.boost_chars(parts[-1]) == len(parts[-1])
+    return changed, withdrawn, live
+
+
+def _compare(t, k, beta, prune, lm, lexicon, gamma, alpha=1.0):
+    """device vs host on the four utterances: best string, log weight, lm_log10 of every returned prefix"""
+    host_lex = _host_lexicon(lm, lexicon)
+    x = torch.from_numpy(_posteriors(t)).cuda()
+    got = _beam_search_device(x, LABELS, 0, k, beta, prune, '>', torch.tensor(SIZES[t]), False, lm=lm, alpha=alpha,
+                              lexicon=lexicon, hotwords=_hotwords(), hotword_weight=gamma)
+    scores, lengths, idx = got[:3]
+    for u in range(N):
+        best, w, _ = _host(t, u, k, beta, prune, lm, alpha, host_lex, gamma)
+        found = [''.join(LABELS[j] for j in idx[u, r, :lengths[u, r]]) for r in range(k) if lengths[u, r] >= 0]
+        if w == 0:                                               # the beam emptied (a lexicon with every label illegal)
+            assert best == '' and not found
+            continue
+        assert found[0] == best, (u, found[0], best)
+        assert w > 1e-250
+        assert abs(scores[u, 0] - np.log(w)) <= 1e-9 * max(1.0, abs(np.log(w))), (u, scores[u, 0], np.log(w))
+        assert all(a >= b for a, b in zip(scores[u, :len(found)], scores[u, 1:len(found)]))
+        for r, s in enumerate(found):
+            assert host_lex is None or host_lex.allows(s), (u, r, s)
+            if lm is not None:
+                assert got[3][u, r].tobytes() == _strip_score(lm, s).tobytes(), (u, r, s, got[3][u, r])
+    if k >= 3 and gamma > 0:
+        assert _fixture_conditions(t, k, beta, prune, lm, alpha, host_lex, gamma) == (True, True, True)
+
+
+CASES = list(itertools.product((24, 40), (1, 3, 8, 32), (0, 5), (1e-3, 0)))
+
+
+def test_hotwords_are_dropped_and_counted():
+    hot = _hotwords()
+    hot.spelling_trie(LABELS, 0)
+    assert hot.stats['unspellable'] == 1 and hot.spellable(LABELS, 0).words == ['ABBA', 'BED']
+
+
+@pytest.mark.parametrize('t,k,beta,prune', CASES)
+def test_hotwords_only(t, k, beta, prune):
+    for gamma in GAMMAS:
+        _compare(t, k, beta, prune, None, None, gamma)
+
+
+@pytest.mark.parametrize('t,k,beta,prune', CASES)
+def test_hotwords_with_bigram(models, t, k, beta, prune):
+    for gamma in GAMMAS:
+        _compare(t, k, beta, prune, models['bigram'], None, gamma, alpha=BIGRAM_ALPHA)
+
+
+@pytest.mark.parametrize('t,k,beta,prune', CASES)
+def test_hotwords_with_lexicon(t, k, beta, prune):
+    for gamma in GAMMAS:
+        _compare(t, k, beta, prune, None, _lexicon(), gamma)
+
+
+@pytest.mark.parametrize('t,k,beta,prune', CASES)
+def test_hotwords_with_lexicon_from_lm(models, t, k, beta, prune):
+    """lexicon='lm' at order 3: three tries in one launch (the model's, shared with the lexicon, and the hotwords' own)"""
+    for gamma in GAMMAS:
+        _compare(t, k, beta, prune, models['trigram'], 'lm', gamma, alpha=0.7)
+
+
+def _combos(models):
+    """the four (LM, LEX) combinations as keywords of the device search"""
+    return (dict(), dict(lm=models['bigram'], alpha=BIGRAM_ALPHA), dict(lexicon=_lexicon()),
+            dict(lm=models['trigram'], alpha=0.7, lexicon='lm'))
+
+
+def test_nbest(models):
+    hot = _hotwords()
+    for (t, k), kw in zip(((24, 8), (40, 32), (40, 8), (24, 32)), _combos(models)):
+        p = _posteriors(t)
+        full = prefix_beam_search_gpu(p, LABELS, k=k, beta=0, nbest=k, sizes=SIZES[t], hotwords=hot, hotword_weight=0.7, **kw)
+        one = prefix_beam_search_gpu(p, LABELS, k=k, beta=0, sizes=SIZES[t], hotwords=hot, hotword_weight=0.7,
+                                     return_weights=True, **kw)
+        host_lex = _host_lexicon(kw.get('lm'), kw.get('lexicon'))
+        for u in range(N):
+            best, w, beam = _host(t, u, k, 0, 1e-3, kw.get('lm'), kw.get('alpha', 1.0), host_lex, 0.7)
+            if w == 0:
+                assert full[u] == [('', float('-inf'))]
+                continue
+            assert full[u][0] == one[u] and full[u][0][0] == best
+            assert abs(full[u][0][1] - np.log(w)) <= 1e-9 * max(1.0, abs(np.log(w)))
+            assert all(a[1] >= b[1] for a, b in zip(full[u], full[u][1:]))
+            if host_lex is None:                                 # (no complete_only filter: the list is the final beam)
+                assert [s for s, _ in full[u]] == beam
+        assert any(len(f) > 1 for f in full)
+
+
+def test_return_offsets(models):
+    hot = _hotwords()
+    for t, kw in zip((24, 40, 24, 40), _combos(models)):
+        p = _posteriors(t)
+        plain = prefix_beam_search_gpu(p, LABELS, k=8, sizes=SIZES[t], hotwords=hot, hotword_weight=0.7, **kw)
+        strings, offsets = prefix_beam_search_gpu(p, LABELS, k=8, sizes=SIZES[t], hotwords=hot, hotword_weight=0.7,
+                                                  return_offsets=True, **kw)
+        assert strings == plain
+        res = ctc_forced_align(p, strings, input_lengths=SIZES[t], log_probs=False, labels=LABELS)
+        for u, s in enumerate(strings):
+            assert offsets[u].dtype == torch.int32 and offsets[u].tolist() == res.starts[u, :len(s)].tolist(), (u, s)
+        assert any(len(s) > 2 for s in strings)
+    # log-probability input, an iterable and a path, and the decoder classes: the same strings
+    t = 24
+    x = torch.from_numpy(_posteriors(t)).cuda()
+    want = prefix_beam_search_gpu(x, LABELS, k=8, sizes=SIZES[t], hotwords=hot)                  # the default weight: 1.0
+    assert want == prefix_beam_search_gpu(x, LABELS, k=8, sizes=SIZES[t], hotwords=iter(HOTWORDS), hotword_weight=1.0)
+    assert want != prefix_beam_search_gpu(x, LABELS, k=8, sizes=SIZES[t])
+    assert prefix_beam_search_gpu(x.double().log().float(), LABELS, k=8, sizes=SIZES[t], hotwords=hot, log_probs=True,
+                                  prune=-1) == prefix_beam_search_gpu(x, LABELS, k=8, sizes=SIZES[t], hotwords=hot, prune=0)
+    dec = GPUPrefixBeamSearchDecoder(None, LABELS, k=8, hotwords=hot)
+    assert dec.decode(x, torch.tensor(SIZES[t])) == want
+    words = models['dir'] / 'hot.txt'
+    words.write_text(''.join('%s\n' % w for w in HOTWORDS))
+    dec = GPUPrefixBeamSearchLMDecoder(None, LABELS, k=8, hotwords=str(words))
+    assert dec.decode(x, torch.tensor(SIZES[t])) == want
+    one, off = dec.decode(x[0], return_offsets=True)
+    assert one == prefix_beam_search_gpu(x[0], LABELS, k=8, hotwords=hot) and len(off[0]) == len(one)
+
+
+def _same_buffers(a, b):
+    assert len(a) == len(b)
+    assert a[0].tobytes() == b[0].tobytes() and a[1].tobytes() == b[1].tobytes()     # scores, lengths
+    for u, r in zip(*np.nonzero(a[1] >= 0)):
+        assert a[2][u, r, :a[1][u, r]].tobytes() == b[2][u, r, :a[1][u, r]].tobytes()
+    if len(a) > 3:
+        assert a[3].tobytes() == b[3].tobytes()                                      # lm_log10
+
+
+def test_weight_zero_is_the_search_without_hotwords(models):
+    """the HOT instantiations at hotword_weight=0 against the four existing entry points: the output buffers bit for bit"""
+    for t, sizes in ((40, torch.tensor(SIZES[40])), (24, None)):
+        x = torch.from_numpy(_posteriors(t)).cuda()
+        for kw in _combos(models):
+            for k in (3, 32):
+                plain = _beam_search_device(x, LABELS, 0, k, 5, 1e-3, '>', sizes, False, **kw)
+                for zero in (0.0, -0.0):
+                    hot = _beam_search_device(x, LABELS, 0, k, 5, 1e-3, '>', sizes, False, hotwords=_hotwords(),
+                                              hotword_weight=zero, **kw)
+                    _same_buffers(plain, hot)
+
+
+def test_existing_searches_unchanged_around_hotword_calls(models):
+    """the four searches without hotwords, before and after hotword launches in the same process: bit-equal"""
+    x = torch.from_numpy(_posteriors(40)).cuda()
+
+    def four():
+        return [_beam_search_device(x, LABELS, 0, k, 5, 1e-3, '>', None, False, **kw) for k in (3, 32) for kw in _combos(models)]
+    before = four()
+    changed = 0
+    for kw in _combos(models):
+        boosted = prefix_beam_search_gpu(x, LABELS, k=32, sizes=SIZES[40], hotwords=_hotwords(), hotword_weight=0.7, **kw)
+        changed += boosted != prefix_beam_search_gpu(x, LABELS, k=32, sizes=SIZES[40], **kw)
+    assert changed == 4                                          # the hotword launches did something else
+    for a, b in zip(before, four()):
+        _same_buffers(a, b)
+
+
+def test_entry_point_errors(models):
+    t, k = 24, 4
+    x = torch.from_numpy(_posteriors(t)).cuda()
+    dev_hot = _hotwords().to_device(LABELS, 0, 'cuda')
+    dev_lex = _lexicon().to_device(LABELS, 0, 'cuda')
+    lm = models['bigram']
+    dev_lm = lm.to_device(LABELS, 0, 'cuda')
+    info, end = _label_info(LABELS, 0, '>')
+    info = info | np.array([ch.isspace() << 11 for ch in LABELS], dtype=np.int32)
+    space = LABELS.index(' ')
+    tabbed = LABELS[:-3] + ['\t'] + LABELS[-2:]
+    info_tab = _label_info(tabbed, 0, '>')[0] | np.array([ch.isspace() << 11 for ch in tabbed], dtype=np.int32)
+    ws_bytes = int(lib.w2l_ctc_beam_search_hot_workspace_bytes(N, t, k, lm.order))
+    assert ws_bytes == int(lib.w2l_ctc_beam_search_lm_workspace_bytes(N, t, k, lm.order)) > 0
+    assert int(lib.w2l_ctc_beam_search_hot_workspace_bytes(N, t, k, 0)) == int(lib.w2l_ctc_beam_search_workspace_bytes(N, t, k))
+    assert int(lib.w2l_ctc_beam_search_hot_workspace_bytes(N, t, 0, 0)) == -1
+    assert int(lib.w2l_ctc_beam_search_hot_workspace_bytes(N, t, k, 7)) == -1
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device='cuda')
+    out = torch.full((12 * N * k + 4 * N + 4 * N * k * t + 4 * N * k,), 0x5a, dtype=torch.uint8, device='cuda')
+
+    def call(desc, inf, sp, with_lm, with_lex, weight=0.7, lex_desc=None):
+        vp = inf.ctypes.data_as(C.c_void_p)
+        if lex_desc is None:
+            lex_desc = dev_lex.desc_ref if with_lex else None
+        return lib.w2l_ctc_beam_search_hot(ptr(x), None, N, t, len(LABELS), vp, 0, end, sp, k, 1.0, 5.0, 1e-3, 0,
+                                           dev_lm.desc_ref if with_lm else None, lm.order if with_lm else 0, lex_desc, 1, desc,
+                                           weight, ptr(ws), ws_bytes, ptr(out), stream_ptr())
+    good = dev_hot.desc
+    nodes = good.n_trie_nodes
+    full = LexTables(good.trie_keys, good.trie_vals, good.trie_cap, good.trie_word, int(good.trie_cap // 2 + 2))
+    odd_cap = LexTables(good.trie_keys, good.trie_vals, good.trie_cap - 1, good.trie_word, nodes)
+    no_keys = LexTables(None, good.trie_vals, good.trie_cap, good.trie_word, nodes)
+    no_word = LexTables(good.trie_keys, good.trie_vals, good.trie_cap, None, nodes)
+    for with_lm, with_lex in itertools.product((False, True), repeat=2):
+        for desc in (full, odd_cap, no_keys, no_word):
+            assert call(C.byref(desc), info, space, with_lm, with_lex) != 0
+        assert call(None, info, space, with_lm, with_lex) != 0
+        for weight in (float('inf'), float('-inf'), float('nan')):
+            assert call(C.byref(good), info, space, with_lm, with_lex, weight) != 0
+        assert call(C.byref(good), info_tab, -1, with_lm, with_lex) != 0                 # whitespace other than ' '
+        assert call(C.byref(good), info, space - 1, with_lm, with_lex) != 0              # not the first index of ' '
+        assert call(C.byref(good), info, space, with_lm, with_lex, lex_desc=C.byref(odd_cap)) != 0      # a bad lexicon
+    torch.cuda.synchronize()
+    assert bool((out == 0x5a).all())                             # nothing was launched
+    for with_lm, with_lex in itertools.product((False, True), repeat=2):
+        assert call(C.byref(good), info, space, with_lm, with_lex) == 0
+    torch.cuda.synchronize()
+    with pytest.raises(ValueError, match='whitespace'):
+        prefix_beam_search_gpu(_posteriors(t), tabbed, hotwords=_hotwords())
+    with pytest.raises(ValueError, match='finite'):
+        prefix_beam_search_gpu(_posteriors(t), LABELS, hotwords=_hotwords(), hotword_weight=float('nan'))
+    with pytest.raises(ValueError, match='not a word'):
+        prefix_beam_search_gpu(_posteriors(t), LABELS, hotwords=['NEW YORK'])
+    with pytest.raises(ValueError, match='spelled'):
+        prefix_beam_search_gpu(_posteriors(t), LABELS, hotwords=['DÉJÀ'])
+
+
+def test_cli_hotwords_with_word_times(tmp_path, monkeypatch, capsys):
+    """``test`` with decoder=beam hotwords_path= word_times=true on a checkpoint of a few steps"""
+    import json
+    import os
+    import wave
+    from wav2letter_pytorch_amd import test as T, train
+    monkeypatch.setattr('wav2letter_pytorch_amd.data.data_loader.SpectrogramExtractor.dithering', 0.0)
+    rng = np.random.default_rng(0)
+    texts = ['ab cab', 'a ab', 'cab a', 'ab ab']
+    man = str(tmp_path / 'manifest.json')
+    with open(man, 'w') as f:
+        for i, text in enumerate(texts):
+            sig = (0.1 * rng.standard_normal(int(16000 * (0.6 + 0.1 * (i % 3))))).astype(np.float32)
+            path = str(tmp_path / f'u{i}.wav')
+            with wave.open(path, 'wb') as w:
+                w.setnchannels(1); w.setsampwidth(2); w.setframerate(16000)
+                w.writeframes((sig * 32767).astype(np.int16).tobytes())
+            f.write(json.dumps({'audio_filepath': path, 'text': text}) + '\n')
+    root = str(tmp_path / 'run')
+    common = ['model.mid_layers=2', 'data.batch_size=2']
+    train.main(common + [f'data.train_manifest={man}', f'data.val_manifest={man}', 'trainer.max_epochs=1',
+                         f'trainer.default_root_dir={root}', 'model.optimizer.lr=1e-3'])
+    ckpt = [os.path.join(root, f) for f in os.listdir(root) if f.endswith('.ckpt')][0]
+    hot = str(tmp_path / 'hot.txt')
+    with open(hot, 'w') as f:
+        f.write('# names\ncab\nab\nA1\n')
+    args = common + [f'model_path={ckpt}', f'data.test_manifest={man}', 'decoder=beam', 'beam.k=4']
+    _, plain = T.main(args)
+    _, zero = T.main(args + [f'hotwords_path={hot}', 'hotword_weight=0'])
+    assert [r['hypothesis'] for r in zero] == [r['hypothesis'] for r in plain]
+    capsys.readouterr()
+    metrics, records = T.main(args + [f'hotwords_path={hot}', 'hotword_weight=2.5', 'word_times=true'])
+    assert 'test_wer=' in capsys.readouterr().out
+    assert len(records) == len(texts) and np.isfinite(metrics['test_wer'])
+    for r in records:
+        assert [w['word'] for w in r['words']] == r['hypothesis'].split()

@@ -12,10 +12,13 @@ batch (w2l_ctc_beam_search, csrc/beam_search.hip), in fp64 logs; with an ARPA n-
 prefix_beam_search_gpu, GPUPrefixBeamSearchLMDecoder) the same launch scores words on the device (w2l_ctc_beam_search_lm)
 as the host does with ``lm=lambda s: 10 ** arpa.score(s)``.  With ``return_offsets`` a second launch on the same stream
 (w2l_ctc_align, alignment.py) aligns each best prefix to the posteriors where it lies in the search's device buffer, and the
-character offsets come back in the same copy."""
+character offsets come back in the same copy.  ``lexicon=`` confines the searches to a word list (lexicon.py); ``hotwords=`` /
+``hotword_weight=`` make them prefer a list of words without forbidding anything else: the ranking weight of a string gains
+``exp(hotword_weight * h)``, ``h`` = Lexicon.boost_chars (w2l_ctc_beam_search_hot; host and device state the same rule)."""
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 import re
 from typing import Callable, Dict, List, Optional, Sequence
@@ -63,7 +66,7 @@ class _Step:
 def prefix_beam_search(ctc, labels: Sequence[str], blank_index: int = 0, lm: Optional[Callable[[str], float]] = None,
                        k: int = 5, alpha: float = 0.3, beta: float = 5, prune: float = 0.001, end_char: str = '>',
                        return_weights: bool = False, lexicon=None, complete_only: bool = True,
-                       stats: Optional[dict] = None):
+                       stats: Optional[dict] = None, hotwords=None, hotword_weight: float = 0.0):
     """ctc: [timesteps, alphabet] probabilities.  Returns the best prefix (and its ranking weight).
 
     ``lexicon`` (a lexicon.Lexicon; None: no constraint): an extension ``pre + ch`` that is not legal (Lexicon.allows) gets no
@@ -72,7 +75,12 @@ def prefix_beam_search(ctc, labels: Sequence[str], blank_index: int = 0, lm: Opt
     is empty or a whole word (Lexicon.complete); if the final beam holds none, the best member as it is.  Weights are the
     members' own, not renormalised.
 
-    ``stats`` (a dict): ``frames`` and ``live`` (the candidates with a positive mass, summed over the frames) are added to it."""
+    ``hotwords`` (a lexicon.Lexicon, a path to a word list or an iterable of single words; None: no boosting): the ranking
+    weight of a string ``s``, in every frame and as returned, gets the factor ``exp(hotword_weight * h(s))``, ``h`` =
+    Lexicon.boost_chars of the words the labels can spell.  Masses, the LM weight, the prune and ties are untouched.
+
+    ``stats`` (a dict): ``frames`` and ``live`` (the candidates with a positive mass, summed over the frames) are added to it,
+    and ``beam`` is set to the final beam, best first."""
     ctc = np.asarray(ctc)
     assert ctc.shape[1] == len(labels), "ctc size:%d, labels: %d" % (ctc.shape[1], len(labels))
     assert ctc.shape[0] > 1, "ctc length: %d was too short" % ctc.shape[0]
@@ -84,6 +92,17 @@ def prefix_beam_search(ctc, labels: Sequence[str], blank_index: int = 0, lm: Opt
         first_index.setdefault(ch, i)
     blank = labels[blank_index]
     legal: Dict[str, bool] = {}
+    if hotwords is None:
+        def weight(s):
+            return ranked.get(s, 0) * (_n_words(s) + 1) ** beta
+    else:
+        hot = _resolve_hotwords(hotwords).spellable(labels, blank_index)
+        gamma = float(hotword_weight)
+        if not math.isfinite(gamma):
+            raise ValueError('hotword_weight must be finite, got %r' % (hotword_weight,))
+
+        def weight(s):
+            return ranked.get(s, 0) * (_n_words(s) + 1) ** beta * math.exp(gamma * hot.boost_chars(s, end_char))
 
     def allowed(ext):
         if ext not in legal:
@@ -131,16 +150,18 @@ def prefix_beam_search(ctc, labels: Sequence[str], blank_index: int = 0, lm: Opt
         if stats is not None:
             stats['frames'] = stats.get('frames', 0) + 1
             stats['live'] = stats.get('live', 0) + len(ranked)
-        order = sorted(ranked, key=lambda s: ranked[s] * (_n_words(s) + 1) ** beta, reverse=True)   # stable
+        order = sorted(ranked, key=weight, reverse=True)   # stable
         beam = order[:k]
         prev = cur
     if not beam:
         beam = ['']
+    if stats is not None:
+        stats['beam'] = list(beam)                       # the final beam in rank order (before complete_only)
     if lexicon is not None and complete_only:
         beam = [s for s in beam if lexicon.complete(s, end_char)] or beam
     best = beam[0]
     if return_weights:
-        return best, ranked.get(best, 0) * (_n_words(best) + 1) ** beta
+        return best, weight(best)
     return best
 
 
@@ -208,12 +229,13 @@ def _align_starts(host, n, t, beam_bytes):
 
 
 def _beam_search_device(probs, labels, blank_index, k, beta, prune, end_char, sizes, log_probs, lm=None, alpha=0.3,
-                        offsets=False, lexicon=None, complete_only=True):
+                        offsets=False, lexicon=None, complete_only=True, hotwords=None, hotword_weight=0.0):
     """one launch of w2l_ctc_beam_search for probs [N, T, A] on the current stream; returns the host arrays
     (scores [N, k], lengths [N, k], labels [N, k, T]).  With ``lm`` (an ngram_lm.ArpaLM) one launch of
     w2l_ctc_beam_search_lm, and a fourth array: lm_log10 [N, k] float32, the LM total of each result.  With ``offsets`` a
     launch of w2l_ctc_align follows and one more array: starts int32 [N, T], the first frame of each label of rank 0.  With
-    ``lexicon`` (a lexicon.Lexicon, or 'lm': the vocabulary of ``lm``) the launch is w2l_ctc_beam_search_lex / _lm_lex."""
+    ``lexicon`` (a lexicon.Lexicon, or 'lm': the vocabulary of ``lm``) the launch is w2l_ctc_beam_search_lex / _lm_lex.  With
+    ``hotwords`` (see _resolve_hotwords) it is w2l_ctc_beam_search_hot, whatever ``lm`` and ``lexicon`` are."""
     if probs.dim() != 3:
         raise ValueError('expected [N, T, labels] or [T, labels] posteriors, got shape %s' % (tuple(probs.shape),))
     n, t, a = probs.shape
@@ -240,9 +262,9 @@ def _beam_search_device(probs, labels, blank_index, k, beta, prune, end_char, si
         if bool((host < 2).any()) or bool((host > t).any()):
             raise ValueError('sizes must lie in [2, %d], got %s' % (t, host.tolist()))
         sz = host.to(torch.int32).to(dev, non_blocking=True)
-    if lm is not None or lexicon is not None:
+    if lm is not None or lexicon is not None or hotwords is not None:
         return _beam_search_device_lm(x, sz, labels, info, blank_index, end_index, k, alpha, beta, prune, log_probs, lm,
-                                      offsets, lexicon, complete_only)
+                                      offsets, lexicon, complete_only, hotwords, hotword_weight)
     ws_bytes = int(lib.w2l_ctc_beam_search_workspace_bytes(n, t, k))
     if ws_bytes < 0:
         raise ValueError('prefix_beam_search_gpu: k=%d with T=%d is out of range' % (k, t))
@@ -283,10 +305,17 @@ def _resolve_lexicon(lexicon, lm):
     raise TypeError("lexicon must be a lexicon.Lexicon, a path or 'lm', got %s" % type(lexicon).__name__)
 
 
+def _resolve_hotwords(hotwords):
+    """a Lexicon holding the hotword list ``hotwords``: a Lexicon, a path to a word list, or an iterable of single words (an
+    entry with whitespace is a ValueError)"""
+    from .lexicon import Lexicon
+    return hotwords if isinstance(hotwords, Lexicon) else Lexicon(hotwords)
+
+
 def _beam_search_device_lm(x, sz, labels, info, blank_index, end_index, k, alpha, beta, prune, log_probs, lm, offsets=False,
-                           lexicon=None, complete_only=True):
+                           lexicon=None, complete_only=True, hotwords=None, hotword_weight=0.0):
     """_beam_search_device's launch of w2l_ctc_beam_search_lm, or with ``lexicon`` of w2l_ctc_beam_search_lm_lex /
-    w2l_ctc_beam_search_lex (``lm`` None) (x, sz already on the device)"""
+    w2l_ctc_beam_search_lex (``lm`` None), or with ``hotwords`` of w2l_ctc_beam_search_hot (x, sz already on the device)"""
     from .ngram_lm import ArpaLM
     if lm is not None and not isinstance(lm, ArpaLM):
         raise TypeError('lm must be an ngram_lm.ArpaLM, got %s' % type(lm).__name__)
@@ -295,14 +324,19 @@ def _beam_search_device_lm(x, sz, labels, info, blank_index, end_index, k, alpha
         raise ValueError('prefix_beam_search_gpu: whitespace labels other than a space (%r) cannot be scored by a word LM'
                          % odd if lm is not None else
                          'prefix_beam_search_gpu: whitespace labels other than a space (%r) cannot separate the words of a '
-                         'lexicon' % odd)
+                         'lexicon or of a hotword list' % odd)
+    if hotwords is not None and not math.isfinite(float(hotword_weight)):
+        raise ValueError('prefix_beam_search_gpu: hotword_weight must be finite, got %r' % (hotword_weight,))
     n, t, a = x.shape
     dev = x.device
     info = info | np.array([ch.isspace() << 11 for ch in labels], dtype=np.int32)
     space_index = labels.index(' ') if ' ' in labels else -1
     tables = lm.to_device(labels, blank_index, dev) if lm is not None else None
     lex = _resolve_lexicon(lexicon, lm).to_device(labels, blank_index, dev) if lexicon is not None else None
-    if lm is None:
+    hot = _resolve_hotwords(hotwords).to_device(labels, blank_index, dev) if hotwords is not None else None
+    if hot is not None:
+        ws_bytes = int(lib.w2l_ctc_beam_search_hot_workspace_bytes(n, t, k, lm.order if lm is not None else 0))
+    elif lm is None:
         ws_bytes = int(lib.w2l_ctc_beam_search_lex_workspace_bytes(n, t, k))
     elif lex is None:
         ws_bytes = int(lib.w2l_ctc_beam_search_lm_workspace_bytes(n, t, k, lm.order))
@@ -316,7 +350,12 @@ def _beam_search_device_lm(x, sz, labels, info, blank_index, end_index, k, alpha
     out = torch.empty(beam_bytes + (align_sections(n, t, t)[5] if offsets else 0), dtype=torch.uint8, device=dev)
     head = (ptr(x), ptr(sz), n, t, a, info.ctypes.data_as(C.c_void_p), int(blank_index), int(end_index), space_index, int(k))
     tail = (ptr(ws), ws_bytes, ptr(out), stream_ptr())
-    if lm is None:
+    if hot is not None:
+        check(lib.w2l_ctc_beam_search_hot(*head, float(alpha), float(beta), float(prune), int(bool(log_probs)),
+                                          tables.desc_ref if tables is not None else None, lm.order if lm is not None else 0,
+                                          lex.desc_ref if lex is not None else None, int(bool(complete_only)), hot.desc_ref,
+                                          float(hotword_weight), *tail), 'w2l_ctc_beam_search_hot')
+    elif lm is None:
         check(lib.w2l_ctc_beam_search_lex(*head, float(beta), float(prune), int(bool(log_probs)), lex.desc_ref,
                                           int(bool(complete_only)), *tail), 'w2l_ctc_beam_search_lex')
     elif lex is None:
@@ -347,7 +386,7 @@ def _beam_search_device_lm(x, sz, labels, info, blank_index, end_index, k, alpha
 def prefix_beam_search_gpu(probs, labels: Sequence[str], blank_index: int = 0, k: int = 5, beta: float = 5,
                            prune: float = 0.001, end_char: str = '>', sizes=None, log_probs: bool = False, nbest: int = 1,
                            return_weights: bool = False, lm=None, alpha: float = 0.3, return_offsets: bool = False,
-                           lexicon=None, complete_only: bool = True):
+                           lexicon=None, complete_only: bool = True, hotwords=None, hotword_weight: float = 1.0):
     """prefix_beam_search on the MI355X: one launch for a whole batch, masses as fp64 logs (no underflow on long
     utterances; the host function's float32 products do underflow), the host's candidate order and ties.  ``lm``: an
     ngram_lm.ArpaLM scored as the host's ``lm=lambda s: 10 ** lm.score(s)`` with weight ``alpha`` (None: no LM).
@@ -364,7 +403,14 @@ def prefix_beam_search_gpu(probs, labels: Sequence[str], blank_index: int = 0, k
     goes to a string with a word outside the lexicon, as in prefix_beam_search(lexicon=...), with or without ``lm``.  With
     ``complete_only`` the results (best, n-best, offsets) are drawn from the members of the final beam whose trailing partial
     word is empty or a whole word, in rank order with their own weights; if there is none, from the whole beam.  Labels that
-    are whitespace other than a space are an error with a lexicon, as with an LM."""
+    are whitespace other than a space are an error with a lexicon, as with an LM.
+
+    ``hotwords`` (a lexicon.Lexicon, a path to a word list, or an iterable of single words; None: no boosting) with
+    ``hotword_weight`` (natural-log units per matched character, any finite real; the default of 1.0 is a convention, not a
+    tuned value): the ranking weight gets the factor ``exp(hotword_weight * h)``, ``h`` = Lexicon.boost_chars of the string
+    -- the characters of its closed words that are hotwords plus, provisionally, those of a partial word that is a prefix of a
+    hotword -- as in prefix_beam_search(hotwords=...).  It goes with every other argument; the returned log weights include it.
+    Weight 0 gives the results of no hotwords.  Single words only; one weight for the whole list."""
     labels = list(labels)
     if not 1 <= nbest <= k:
         raise ValueError('nbest=%d must lie in [1, k=%d]' % (nbest, k))
@@ -377,7 +423,8 @@ def prefix_beam_search_gpu(probs, labels: Sequence[str], blank_index: int = 0, k
         if sizes is not None:
             sizes = [int(np.asarray(sizes).reshape(-1)[0])]
     got = _beam_search_device(x, labels, blank_index, k, beta, prune, end_char, sizes, log_probs, lm=lm, alpha=alpha,
-                              offsets=return_offsets, lexicon=lexicon, complete_only=complete_only)
+                              offsets=return_offsets, lexicon=lexicon, complete_only=complete_only, hotwords=hotwords,
+                              hotword_weight=hotword_weight)
     scores, lengths, idx = got[:3]
     results = []
     for u in range(scores.shape[0]):
@@ -403,13 +450,28 @@ def _nest_offsets(got, single):
     return (results, [offs]) if single else (results, [[o] for o in offs])
 
 
+def _decoder_hotwords(hotwords, hotword_weight, labels, blank_index):
+    """the constructors' check of ``hotwords`` / ``hotword_weight``: (Lexicon or None, weight); ValueError for an entry with
+    whitespace, for a list of which the labels can spell nothing, and for a weight that is not finite"""
+    if hotwords is None:
+        return None, float(hotword_weight)
+    hot = _resolve_hotwords(hotwords)
+    hot.spelling_trie(labels, blank_index)
+    if not math.isfinite(float(hotword_weight)):
+        raise ValueError('hotword_weight must be finite, got %r' % (hotword_weight,))
+    return hot, float(hotword_weight)
+
+
 class GPUPrefixBeamSearchDecoder(Decoder):
     """PrefixBeamSearchLMDecoder on the MI355X (prefix_beam_search_gpu): the same constructor (plus ``log_probs``), no
     language model -- a scoring callable cannot run on the device.  ``lexicon``: a lexicon.Lexicon or a path to a word list
-    that constrains the search (prefix_beam_search_gpu)."""
+    that constrains the search (prefix_beam_search_gpu).  ``hotwords``: a lexicon.Lexicon, a path or an iterable of single
+    words that the search prefers by ``hotword_weight`` per matched character (1.0 is a convention, not a tuned value)."""
 
-    def __init__(self, lm_path, labels, blank_index=0, k=5, alpha=0.3, beta=5, prune=1e-3, log_probs=False, lexicon=None):
+    def __init__(self, lm_path, labels, blank_index=0, k=5, alpha=0.3, beta=5, prune=1e-3, log_probs=False, lexicon=None,
+                 hotwords=None, hotword_weight=1.0):
         super(GPUPrefixBeamSearchDecoder, self).__init__(labels, blank_index)
+        self.hotwords, self.hotword_weight = _decoder_hotwords(hotwords, hotword_weight, self.labels, blank_index)
         if isinstance(lexicon, str) and lexicon == 'lm':
             raise ValueError("GPUPrefixBeamSearchDecoder has no language model: lexicon='lm' needs GPUPrefixBeamSearchLMDecoder")
         self.lexicon = _resolve_lexicon(lexicon, None) if lexicon is not None else None
@@ -426,17 +488,21 @@ class GPUPrefixBeamSearchDecoder(Decoder):
             raise RuntimeError('Decoding with wrong shape: %s, expected either [Batch X Frames X Labels] or '
                                '[Frames X Labels]' % str(tuple(probs.shape)))
         got = prefix_beam_search_gpu(probs, self.labels, self.blank_index, self.k, self.beta, self.prune, sizes=sizes,
-                                     log_probs=self.log_probs, return_offsets=return_offsets, lexicon=self.lexicon)
+                                     log_probs=self.log_probs, return_offsets=return_offsets, lexicon=self.lexicon,
+                                     hotwords=self.hotwords, hotword_weight=self.hotword_weight)
         return _nest_offsets(got, len(probs.shape) == 2) if return_offsets else got
 
 
 class GPUPrefixBeamSearchLMDecoder(Decoder):
     """PrefixBeamSearchLMDecoder on the MI355X with an ARPA n-gram model read without kenlm (ngram_lm.ArpaLM, plain or
     .gz): the reference decoder's constructor (plus ``log_probs``); a falsy ``lm_path`` decodes without an LM.  ``lexicon``: a
-    lexicon.Lexicon, a path to a word list, or 'lm' (the model's vocabulary) that constrains the search."""
+    lexicon.Lexicon, a path to a word list, or 'lm' (the model's vocabulary) that constrains the search.  ``hotwords`` /
+    ``hotword_weight``: as in GPUPrefixBeamSearchDecoder."""
 
-    def __init__(self, lm_path, labels, blank_index=0, k=5, alpha=0.3, beta=5, prune=1e-3, log_probs=False, lexicon=None):
+    def __init__(self, lm_path, labels, blank_index=0, k=5, alpha=0.3, beta=5, prune=1e-3, log_probs=False, lexicon=None,
+                 hotwords=None, hotword_weight=1.0):
         super(GPUPrefixBeamSearchLMDecoder, self).__init__(labels, blank_index)
+        self.hotwords, self.hotword_weight = _decoder_hotwords(hotwords, hotword_weight, self.labels, blank_index)
         from .ngram_lm import ArpaLM
         self.lm = ArpaLM(lm_path) if lm_path else None
         self.lexicon = _resolve_lexicon(lexicon, self.lm) if lexicon is not None else None
@@ -451,7 +517,7 @@ class GPUPrefixBeamSearchLMDecoder(Decoder):
                                '[Frames X Labels]' % str(tuple(probs.shape)))
         got = prefix_beam_search_gpu(probs, self.labels, self.blank_index, self.k, self.beta, self.prune, sizes=sizes,
                                      log_probs=self.log_probs, lm=self.lm, alpha=self.alpha, return_offsets=return_offsets,
-                                     lexicon=self.lexicon)
+                                     lexicon=self.lexicon, hotwords=self.hotwords, hotword_weight=self.hotword_weight)
         return _nest_offsets(got, len(probs.shape) == 2) if return_offsets else got
 
 

@@ -68,6 +68,38 @@ __device__ __forceinline__ int lex_step(const LexArgs& X, int trie, int c, int e
 
 __device__ __forceinline__ bool lex_complete(const LexArgs& X, int trie) { return trie == 0 || X.tword[trie] >= 0; }
 
+// ------------------------------------------------------------------------------------------------------------ hotwords
+struct HotArgs {                              // the hotword list's spelling trie (a w2l_lexicon_t) and the bonus per character
+    const uint64_t* tkeys;
+    const int32_t* tvals;
+    const int32_t* tword;
+    uint32_t tmask;
+    int space;
+    double gamma;
+};
+
+struct HotState {                             // of a string: h = credit + (node > 0 ? depth : 0), Lexicon.boost_chars
+    int node;                                 // hotword-trie node of the partial word: 0 empty, -1 it has left the trie
+    int depth;                                // characters of the partial word (kept while the node is alive)
+    int credit;                               // characters of the closed words that are hotwords
+};
+
+// the state of (string of state s) + canonical label c.  A separator credits the partial word if it is a whole hotword and
+// empties it; another label walks the trie (one probe) while the partial word is still on it.
+__device__ __forceinline__ HotState hot_step(const HotArgs& H, HotState s, int c, int endc) {
+    if (c == H.space || c == endc) {
+        if (s.node > 0 && H.tword[s.node] >= 0) s.credit += s.depth;
+        s.node = 0;
+        s.depth = 0;
+    } else if (s.node >= 0) {
+        s.node = tab_find(H.tkeys, H.tvals, H.tmask, ((uint64_t)s.node << 8) | (uint64_t)c);
+        s.depth += 1;
+    }
+    return s;
+}
+
+__device__ __forceinline__ int hot_chars(const HotState& s) { return s.credit + (s.node > 0 ? s.depth : 0); }
+
 // log10 q(w | s) (ngram_lm.ArpaLM.q) by the reverse-suffix walk w, h_1 w, h_2 h_1 w, ...; with nx, also the state after w
 __device__ float lm_word(const LmArgs& L, const NodeLM& s, int w, NodeLM* nx) {
     int e = w;

@@ -29,6 +29,12 @@
 // (lex_step); an extension that leaves the word list gets no mass, exactly like a pruned label.  The node of a new member is a
 // function of its parent slot's node and its character, so P3 finds it with the same probe and nothing is kept per interned
 // prefix.  The output stage keeps the members whose partial word is empty or a whole word (complete_only).
+//
+// With hotwords (HOT = true, w2l_ctc_beam_search_hot; any LM / LEX combination): every beam slot carries the hotword-trie walk
+// of its string (hot_st, LDS: node of the partial word, its depth, the characters credited by closed hotwords).  The rank key
+// gains gamma * h, h = hot_chars(state); masses are untouched.  The state of an extension is a function of its parent slot's
+// state and its character (hot_step: one probe), computed by the P2 thread of a non-member extension for the key and again by
+// the P3 thread that places a new member, as lex_trie is.
 #include "common.h"
 #include "beam_lm.h"
 #include "../../include/w2l_hip.h"
@@ -69,16 +75,17 @@ struct Beam {                         // one frame's beam, slot-indexed
     double pb[BS_KMAX], pnb[BS_KMAX], score[BS_KMAX];
 };
 
-template <bool LM, bool LEX>
+template <bool LM, bool LEX, bool HOT>
 __global__ __launch_bounds__(BS_THREADS) void ctc_beam_search_kernel(
     const float* __restrict__ probs, const int32_t* __restrict__ sizes, int T, int A, LabelInfo info, int blank, int endc,
     int k, double beta, double prune, int log_probs, char* __restrict__ ws, int64_t ws_per_utt, int hash_cap,
     double* __restrict__ out_score, int32_t* __restrict__ out_len, int32_t* __restrict__ out_status,
-    int32_t* __restrict__ out_labels, LmArgs lmargs, float* __restrict__ out_lm, LexArgs lex) {
+    int32_t* __restrict__ out_labels, LmArgs lmargs, float* __restrict__ out_lm, LexArgs lex, HotArgs hot) {
     __shared__ Beam beams[2];
     __shared__ double lm_w[2][LM ? BS_KMAX : 1];          // LM weight (natural log) of each beam slot
     __shared__ int lm_on[2][LM ? BS_KMAX : 1];             // ... and whether it applies (a non-space character)
     __shared__ int lex_trie[2][LEX ? BS_KMAX : 1];        // lexicon trie node of each beam slot's partial word
+    __shared__ HotState hot_st[2][HOT ? BS_KMAX : 1];     // hotword walk of each beam slot's string
     __shared__ double lpd[BS_AMAX];
     __shared__ int alph[BS_AMAX], act[BS_AMAX], lab[BS_AMAX];
     __shared__ int s_m[2], s_nalph, s_count, s_bad;
@@ -120,6 +127,7 @@ __global__ __launch_bounds__(BS_THREADS) void ctc_beam_search_kernel(
             lm_on[0][0] = 0;
         }
         if constexpr (LEX) lex_trie[0][0] = 0;
+        if constexpr (HOT) hot_st[0][0] = HotState{0, 0, 0};
         s_m[0] = 1;
         s_m[1] = 0;
         s_bad = 0;
@@ -196,6 +204,7 @@ __global__ __launch_bounds__(BS_THREADS) void ctc_beam_search_kernel(
             Acc acc;
             bool live = false;
             int words = 0;
+            [[maybe_unused]] int hchars = 0;                         // HOT: h of the entry's string
             if (e < m * A) {
                 const int i = e / A, c = e - i * A;
                 const int mv = mem[ent];
@@ -245,8 +254,10 @@ __global__ __launch_bounds__(BS_THREADS) void ctc_beam_search_kernel(
                     if (s < 0) {
                         parent_part();
                         words = B.words[i] + ((lab[c] & 0x400) && B.chr[i] >= 0 && (lab[B.chr[i]] & 0x200));
+                        if constexpr (HOT) hchars = hot_chars(hot_step(hot, hot_st[cur][i], c, endc));
                     } else {
                         words = B.words[s];
+                        if constexpr (HOT) hchars = hot_chars(hot_st[cur][s]);
                         if (i < s) parent_part();
                         // own contributions of member s (blank, repeated character, or the closed-hypothesis assignment)
                         if (closed(B, s)) {
@@ -270,6 +281,7 @@ __global__ __launch_bounds__(BS_THREADS) void ctc_beam_search_kernel(
                 if (B.ps[s] < 0) {                         // a member whose parent is not in the beam (the root included)
                     live = true;
                     words = B.words[s];
+                    if constexpr (HOT) hchars = hot_chars(hot_st[cur][s]);
                     if (closed(B, s)) {
                         acc.b = B.pb[s];
                         acc.nb = B.pnb[s];
@@ -291,7 +303,8 @@ __global__ __launch_bounds__(BS_THREADS) void ctc_beam_search_kernel(
             const double total = lae(acc.b, acc.nb);
             if (live && total > -INFINITY) {               // Counter addition keeps strictly positive masses only
                 const int slot = atomicAdd(&s_count, 1);
-                lsc[slot] = total + beta * log((double)(words + 1));
+                if constexpr (HOT) lsc[slot] = total + beta * log((double)(words + 1)) + hot.gamma * (double)hchars;
+                else lsc[slot] = total + beta * log((double)(words + 1));
                 lkey[slot] = acc.bseq != 0x7fffffff ? acc.bseq : BS_NOT_PB + acc.nbseq;
                 lent[slot] = ent;
             }
@@ -324,9 +337,11 @@ __global__ __launch_bounds__(BS_THREADS) void ctc_beam_search_kernel(
                 NB.words[r] = B.words[s]; NB.len[r] = B.len[s]; NB.prevslot[r] = s;
                 if constexpr (LM) { lm_w[cur ^ 1][r] = lm_w[cur][s]; lm_on[cur ^ 1][r] = lm_on[cur][s]; }
                 if constexpr (LEX) lex_trie[cur ^ 1][r] = lex_trie[cur][s];
+                if constexpr (HOT) hot_st[cur ^ 1][r] = hot_st[cur][s];
             } else {
                 const int par = B.node[i];
                 if constexpr (LEX) lex_trie[cur ^ 1][r] = lex_step(lex, lex_trie[cur][i], c, endc);   // >= 0: P2 let it live
+                if constexpr (HOT) hot_st[cur ^ 1][r] = hot_step(hot, hot_st[cur][i], c, endc);
                 const uint64_t key = ((uint64_t)par << 8) | (uint64_t)c;
                 uint32_t h = key_hash(key) & (hash_cap - 1);
                 int node = -1;
@@ -433,11 +448,11 @@ extern "C" int64_t w2l_ctc_beam_search_workspace_bytes(int N, int T, int k) {
 namespace {
 
 // the checks and the launch shared by the entry points (ws_per_utt: the workspace stride of one utterance)
-template <bool LM, bool LEX = false>
+template <bool LM, bool LEX = false, bool HOT = false>
 int launch_search(const char* name, const float* probs, const int32_t* sizes, int N, int T, int A, const int32_t* label_info_host,
                   int blank, int end_index, int k, double beta, double prune, int log_probs, void* workspace,
                   int64_t workspace_bytes, int64_t need, int64_t ws_per_utt, void* out, const LmArgs& lm, void* stream,
-                  const LexArgs& lex = LexArgs{}) {
+                  const LexArgs& lex = LexArgs{}, const HotArgs& hot = HotArgs{}) {
     W2L_CHECK_ARG(probs && label_info_host && workspace && out && N > 0 && T > 0, "%s: bad arguments", name);
     W2L_CHECK_ARG(A >= 1 && A <= BS_AMAX, "%s: %d labels, supported 1..%d", name, A, BS_AMAX);
     W2L_CHECK_ARG(k >= 1 && k <= BS_KMAX, "%s: beam width k=%d, supported 1..%d", name, k, BS_KMAX);
@@ -446,7 +461,7 @@ int launch_search(const char* name, const float* probs, const int32_t* sizes, in
     W2L_CHECK_ARG((int64_t)k * T < (1 << 29) && T < (1 << 24), "%s: k*T = %lld too large", name, (long long)k * T);
     W2L_CHECK_ARG(need > 0 && workspace_bytes >= need, "%s: workspace of %lld bytes, %lld needed", name,
                   (long long)workspace_bytes, (long long)need);
-    const void* kern = (const void*)ctc_beam_search_kernel<LM, LEX>;
+    const void* kern = (const void*)ctc_beam_search_kernel<LM, LEX, HOT>;
     hipFuncAttributes fa;
     W2L_CHECK_HIP(hipFuncGetAttributes(&fa, kern));
     const int64_t lds = lds_bytes(k, A);
@@ -468,9 +483,9 @@ int launch_search(const char* name, const float* probs, const int32_t* sizes, in
     int32_t* out_status = out_len + (int64_t)N * k;
     int32_t* out_labels = out_status + N;
     float* out_lm = LM ? (float*)(out_labels + (int64_t)N * k * T) : nullptr;
-    hipLaunchKernelGGL((ctc_beam_search_kernel<LM, LEX>), dim3(N), dim3(BS_THREADS), (size_t)lds, (hipStream_t)stream, probs,
+    hipLaunchKernelGGL((ctc_beam_search_kernel<LM, LEX, HOT>), dim3(N), dim3(BS_THREADS), (size_t)lds, (hipStream_t)stream, probs,
                        sizes, T, A, info, blank, end_index, k, beta, prune, log_probs, (char*)workspace, ws_per_utt,
-                       hash_capacity(T, k), out_score, out_len, out_status, out_labels, lm, out_lm, lex);
+                       hash_capacity(T, k), out_score, out_len, out_status, out_labels, lm, out_lm, lex, hot);
     W2L_CHECK_LAUNCH();
     return 0;
 }
@@ -636,4 +651,60 @@ extern "C" int w2l_ctc_beam_search_lm_lex(const float* probs, const int32_t* siz
                                      prune, log_probs, workspace, workspace_bytes,
                                      w2l_ctc_beam_search_lm_lex_workspace_bytes(N, T, k, order), lm_ws_stride(T, k), out, a,
                                      stream, x);
+}
+
+// ---- hotword boosting: the four searches above with gamma * h in the rank key (HOT = true) ----
+namespace {
+
+int hot_args(const char* name, const int32_t* label_info_host, int A, int space_index, const w2l_lexicon_t* hotwords,
+             double hotword_weight, HotArgs* h) {
+    W2L_CHECK_ARG(hotwords && label_info_host && A >= 1 && A <= BS_AMAX, "%s: bad arguments", name);
+    W2L_CHECK_ARG(std::isfinite(hotword_weight), "%s: the hotword weight is not finite", name);
+    W2L_CHECK_ARG(space_index >= -1 && space_index < A && (space_index < 0 || (label_info_host[space_index] & 0xff) == space_index),
+                  "%s: space index %d is not the first index of a label", name, space_index);
+    for (int i = 0; i < A; ++i)
+        W2L_CHECK_ARG(!(label_info_host[i] & 0x800) || (label_info_host[i] & 0xff) == space_index,
+                      "%s: label %d is whitespace other than ' '", name, i);
+    W2L_CHECK_ARG(hotwords->trie_keys && hotwords->trie_vals && hotwords->trie_word, "%s: a hotword table pointer is NULL", name);
+    W2L_CHECK_ARG(hotwords->n_trie_nodes >= 1 && pow2_cap(hotwords->trie_cap)
+                      && hotwords->trie_cap >= 2 * (int64_t)(hotwords->n_trie_nodes - 1),
+                  "%s: hotwords of %d trie nodes in a table of capacity %lld (a power of two in [16, 2^31], at most half full)",
+                  name, hotwords->n_trie_nodes, (long long)hotwords->trie_cap);
+    h->tkeys = hotwords->trie_keys;
+    h->tvals = hotwords->trie_vals;
+    h->tword = hotwords->trie_word;
+    h->tmask = (uint32_t)(hotwords->trie_cap - 1);
+    h->space = space_index;
+    h->gamma = hotword_weight;
+    return 0;
+}
+
+}  // namespace
+
+// Nothing is kept per interned prefix here either: the workspace is that of the search without hotwords (order 0: no LM).
+extern "C" int64_t w2l_ctc_beam_search_hot_workspace_bytes(int N, int T, int k, int order) {
+    return order == 0 ? w2l_ctc_beam_search_workspace_bytes(N, T, k) : w2l_ctc_beam_search_lm_workspace_bytes(N, T, k, order);
+}
+
+extern "C" int w2l_ctc_beam_search_hot(const float* probs, const int32_t* sizes, int N, int T, int A,
+                                       const int32_t* label_info_host, int blank, int end_index, int space_index, int k,
+                                       double alpha, double beta, double prune, int log_probs, const w2l_ngram_lm_t* lm,
+                                       int order, const w2l_lexicon_t* lexicon, int complete_only,
+                                       const w2l_lexicon_t* hotwords, double hotword_weight, void* workspace,
+                                       int64_t workspace_bytes, void* out, void* stream) {
+    const char* name = "ctc_beam_search_hot";
+    LmArgs a{};
+    LexArgs x{};
+    HotArgs h{};
+    if (int rc = hot_args(name, label_info_host, A, space_index, hotwords, hotword_weight, &h)) return rc;
+    if (lm) if (int rc = lm_args(name, label_info_host, A, space_index, alpha, lm, order, T, k, &a)) return rc;
+    if (lexicon) if (int rc = lex_args(name, label_info_host, A, space_index, lexicon, complete_only, &x)) return rc;
+    const int64_t need = w2l_ctc_beam_search_hot_workspace_bytes(N, T, k, lm ? order : 0);
+    const int64_t stride = lm ? lm_ws_stride(T, k) : ws_stride(T, k);
+#define W2L_HOT_LAUNCH(LM_, LEX_)                                                                                              \
+    launch_search<LM_, LEX_, true>(name, probs, sizes, N, T, A, label_info_host, blank, end_index, k, beta, prune, log_probs,   \
+                                   workspace, workspace_bytes, need, stride, out, a, stream, x, h)
+    if (lm) return lexicon ? W2L_HOT_LAUNCH(true, true) : W2L_HOT_LAUNCH(true, false);
+    return lexicon ? W2L_HOT_LAUNCH(false, true) : W2L_HOT_LAUNCH(false, false);
+#undef W2L_HOT_LAUNCH
 }

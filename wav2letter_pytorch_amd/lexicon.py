@@ -12,7 +12,10 @@ Legal strings are prefix-closed.  A legal string is **complete** when its traili
 
 Device layout (``spelling_trie`` / ``to_device``): the flat trie of ngram_lm.ArpaLM.spelling_trie -- an open-addressing table
 keyed by the exact pair (trie node << 8 | canonical label) -> child node, root 0, and ``word[node] >= 0`` where a node spells a
-whole word -- so the trie of an n-gram model is a lexicon as it is (``Lexicon.from_lm`` shares it, see ``to_device``)."""
+whole word -- so the trie of an n-gram model is a lexicon as it is (``Lexicon.from_lm`` shares it, see ``to_device``).
+
+The same container holds a list of **hotwords** (``hotwords=`` of the searches): there the walk over the trie removes nothing,
+it counts the characters ``h`` that the search rewards (``Lexicon.boost_chars``, the oracle of that feature)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -65,6 +68,7 @@ class Lexicon:
         self.stats = dict(words=len(self.words), duplicates=dups, unspellable=0)
         self.lm = None                                 # from_lm: the model whose vocabulary this is
         self._tries: Dict[tuple, tuple] = {}
+        self._spellable: Dict[tuple, 'Lexicon'] = {}
         self._device: Dict[tuple, 'DeviceLexicon'] = {}
 
     @classmethod
@@ -97,6 +101,32 @@ class Lexicon:
         """the trailing partial word of ``string`` is empty or a whole lexicon word"""
         last = self._parts(string, end_char)[-1]
         return last == '' or last in self._words
+
+    def boost_chars(self, string: str, end_char: str = '>') -> int:
+        """``h(string)`` of hotword boosting, this list being the hotwords: the characters of the closed words (those followed
+        by a separator) that are in the list, plus the characters of the trailing partial word if it is non-empty and a prefix
+        of a word of the list (a whole word counts).  The partial word's credit is provisional: it is gone when the word
+        leaves the list's prefixes or is closed as something that is not in the list."""
+        parts = self._parts(string, end_char)
+        h = sum(len(p) for p in parts[:-1] if p in self._words)
+        if parts[-1] and parts[-1] in self._prefixes:
+            h += len(parts[-1])
+        return h
+
+    def spellable(self, labels: Sequence[str], blank_index: int = 0) -> 'Lexicon':
+        """the Lexicon of the words that ``labels`` can spell (spelling_trie's rule; this one if it drops none), so that the
+        ``str`` oracle speaks of the words the flat trie holds.  ValueError if none is left."""
+        labels = list(labels)
+        ck = (tuple(labels), blank_index)
+        if ck not in self._spellable:
+            ok = set(labels) - {labels[blank_index]}
+            kept = [w for w in self.words if all(ch in ok for ch in w)]
+            self.stats['unspellable'] = len(self.words) - len(kept)
+            if not kept:
+                raise ValueError('Lexicon: none of the %d words can be spelled with the labels %r' % (len(self.words),
+                                                                                                   ''.join(labels)))
+            self._spellable[ck] = self if len(kept) == len(self.words) else Lexicon(kept)
+        return self._spellable[ck]
 
     # ---------------------------------------------------------------------------------------------------------- flat trie
     def spelling_trie(self, labels: Sequence[str], blank_index: int = 0):

@@ -4,7 +4,8 @@ shipped:
     python -m wav2letter_pytorch_amd.test [--config-dir /path/to/configuration] model_path=run/epoch=4-step=900.ckpt \\
            data.test_manifest=test.csv [model=jasper] [model.mid_layers=20] [decoder=greedy|beam|beam_lm|asg_beam|asg_beam_lm] [lm_path=lm.arpa] \\
            [beam.k=5] [beam.alpha=0.3] [beam.beta=5] [beam.prune=1e-3] [print_samples=K | print_all=true] \\
-           [lexicon_path=words.txt | lexicon_from_lm=true] [output=hyps.jsonl] [word_times=true] [data.resample=true]
+           [lexicon_path=words.txt | lexicon_from_lm=true] [hotwords_path=words.txt [hotword_weight=1.0]] \\
+           [output=hyps.jsonl] [word_times=true] [data.resample=true]
 
 ``train.py``'s override syntax and config tree.  The forward pass is ``model.infer`` (one fused launch per convolution);
 ``test_loss``, corpus-level ``test_cer`` / ``test_wer`` and ``test_len_ratio`` are printed and returned.  ``output=`` writes one
@@ -12,10 +13,14 @@ JSON line per utterance: path, text, hypothesis, character and word errors (and 
 ``word_times=true``, by forced alignment of the hypothesis).  ``decoder=asg_beam|asg_beam_lm`` are the beam searches of a model
 trained with ``model.criterion=asg`` (asg_beam.py), bound to the checkpoint's learned transitions.  ``lexicon_path=`` (a word
 list, one word per line; ``decoder=beam|beam_lm``) or ``lexicon_from_lm=true`` (the model's vocabulary; ``decoder=beam_lm``)
-constrains the beam search to strings of lexicon words (lexicon.py).  It is not built for the ASG beam searches."""
+constrains the beam search to strings of lexicon words (lexicon.py).  ``hotwords_path=`` (a word list, one single word per
+line; ``decoder=beam|beam_lm``) makes the beam search prefer those words by ``hotword_weight=`` natural-log units per matched
+character (default 1.0: a convention, not a tuned value) without forbidding anything else.  Neither is built for the ASG
+beam searches."""
 from __future__ import annotations
 
 import json
+import math
 import sys
 
 from .train import build_config as _train_config
@@ -36,7 +41,8 @@ def build_config(argv):
     ``data.test_manifest`` are required (SystemExit naming the key), ``decoder`` is one of greedy / beam / beam_lm /
     asg_beam / asg_beam_lm (the last two only with ``model.criterion=asg``), ``lm_path`` belongs to ``decoder=beam_lm`` and
     ``decoder=asg_beam_lm`` only (and those decoders need it), ``lexicon_path`` to ``decoder=beam|beam_lm`` and
-    ``lexicon_from_lm`` to ``decoder=beam_lm`` (one of the two at most)."""
+    ``lexicon_from_lm`` to ``decoder=beam_lm`` (one of the two at most), ``hotwords_path`` to ``decoder=beam|beam_lm`` and
+    ``hotword_weight`` (a finite number) to ``hotwords_path``."""
     cfg = _train_config(argv)
     if cfg.get('model_path') in (None, '???', ''):
         raise SystemExit('model_path is required (e.g. model_path=/path/to/epoch=0-step=100.ckpt)')
@@ -67,6 +73,26 @@ def build_config(argv):
     if cfg.lexicon_from_lm and cfg.decoder != 'beam_lm':
         raise SystemExit(f'lexicon_from_lm is given but decoder={cfg.decoder}: the vocabulary of a language model needs '
                          'decoder=beam_lm')
+    cfg.setdefault('hotwords_path', None)
+    cfg.setdefault('hotword_weight', None)
+    for key in ('hotwords_path', 'hotword_weight'):
+        if cfg[key] in (None, ''):
+            continue
+        if cfg.decoder in ASG_DECODERS:
+            raise SystemExit(f'{key} is given but decoder={cfg.decoder}: hotword boosting is not built for ASG beam search '
+                             '(decoder=beam|beam_lm have it)')
+        if cfg.decoder not in LEXICON_DECODERS:
+            raise SystemExit(f'{key} is given but decoder={cfg.decoder}: hotwords bias a beam search '
+                             '(decoder=beam or decoder=beam_lm)')
+    if cfg.hotword_weight not in (None, ''):
+        if not cfg.hotwords_path:
+            raise SystemExit('hotword_weight is given without hotwords_path=/path/to/words.txt')
+        try:
+            cfg['hotword_weight'] = float(cfg.hotword_weight)
+        except (TypeError, ValueError):
+            raise SystemExit(f'hotword_weight={cfg.hotword_weight!r} is not a number')
+        if not math.isfinite(cfg.hotword_weight):
+            raise SystemExit(f'hotword_weight={cfg.hotword_weight!r} is not finite')
     if cfg.decoder in ASG_DECODERS and cfg.model.get('criterion', 'ctc') != 'asg':
         raise SystemExit(f'decoder={cfg.decoder} decodes with learned transitions: it needs model.criterion=asg')
     beam = dict(BEAM_DEFAULTS)
@@ -105,6 +131,9 @@ def decoder_spec(cfg, log_probs: bool):
     lexicon = 'lm' if cfg.get('lexicon_from_lm') else cfg.get('lexicon_path')
     if lexicon:                                # (the key is absent without a lexicon: the decoders' defaults)
         kw['lexicon'] = lexicon
+    if cfg.get('hotwords_path'):               # (likewise absent without hotwords)
+        kw['hotwords'] = cfg.hotwords_path
+        kw['hotword_weight'] = 1.0 if cfg.get('hotword_weight') in (None, '') else float(cfg.hotword_weight)
     if cfg.decoder == 'beam':
         return 'GPUPrefixBeamSearchDecoder', dict(lm_path=None, **kw)
     return 'GPUPrefixBeamSearchLMDecoder', dict(lm_path=cfg.lm_path, **kw)
