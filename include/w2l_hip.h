@@ -26,7 +26,8 @@ extern "C" {
 #endif
 
 const char* w2l_last_error(void);
-int w2l_abi_version(void);            /* 2 (1 -> 2: w2l_bnact_t gained the trailing field q_clipped) */
+int w2l_abi_version(void);            /* 2 (1 -> 2: w2l_bnact_t gained the trailing field q_clipped).  It counts struct
+                                       * layouts, not symbols: adding or removing an entry point does not change it */
 
 /* ---- layout / packing ---------------------------------------------------- */
 
@@ -568,24 +569,7 @@ int w2l_asg_viterbi(const float* x, const float* transitions, const int32_t* inp
 /* ---- greedy decode (decoder.py:136) + Levenshtein (decoder.py:49,60) ---- */
 /* argmax over the last dim, ties -> lowest index (torch.max): probs fp32 [rows][C] -> idx int32 [rows] */
 int w2l_argmax(const float* probs, int64_t rows, int C, int32_t* idx, void* stream);
-/* ---- CTC prefix beam search (decoder.py:147-267 without a language model; beam_search.prefix_beam_search) ---- */
-/* workspace bytes for w2l_ctc_beam_search (per utterance: a trie of k*T+1 nodes and its intern table); -1 if out of range */
-int64_t w2l_ctc_beam_search_workspace_bytes(int N, int T, int k);
-/* One workgroup per utterance, one launch for the batch, masses as fp64 logs.  probs fp32 [N][T][A] contiguous: probabilities,
- * or log-probabilities if log_probs; sizes int32 [N] (NULL: T) = the frames decoded of each utterance.  label_info_host[A]:
- * bits 0-7 the first index of the label's character (duplicate labels: the first index wins), bit 8 the label's character
- * is the blank's, bit 9 it is a word character (\w), bit 10 a word separator ([\s|>]).  end_index: first index of end_char,
- * -1 if absent (a prefix ending in it is carried unchanged).  A frame extends with the labels whose probability is > prune
- * (lp > log(prune) for log input); ranking = mass * (words + 1)^beta, ties in the host's first-insertion order.
- * out (one buffer, one copy to the host): double score[N][k] (log of the ranking weight, -inf for an empty slot) |
- * int32 len[N][k] (-1: empty slot) | int32 status[N] (1: a probability was negative or NaN) | int32 labels[N][k][T]
- * (first label indices, the first len of each row valid); slot 0 is the best prefix.  Limits: 1 <= k <= 64, 1 <= A <= 128,
- * and the candidate tables (48 * k * (A + 1) + 8 * k * A bytes) fit in LDS beside 9 KB of fixed state: k=32 with A=64 is
- * 114 KB; an error otherwise. */
-int w2l_ctc_beam_search(const float* probs, const int32_t* sizes, int N, int T, int A, const int32_t* label_info_host,
-                        int blank, int end_index, int k, double beta, double prune, int log_probs, void* workspace,
-                        int64_t workspace_bytes, void* out, void* stream);
-/* ---- the same search with a word n-gram language model (ngram_lm.ArpaLM; decoder.py:210-212 with lm_weigh) ---- */
+/* ---- the word tables of the beam searches: an n-gram language model, a lexicon, a list of hotwords ---- */
 /* Device tables of an ARPA model in reverse-suffix form (see ngram_lm.py).  Entry e of an n-gram: prob[e] (log10, NaN for a
  * context-only entry that suffix closure inserted), bo[e] (log10 backoff, 0 if none); a unigram's entry is its word id
  * (<unk> = 0, <s> = 1, </s> = 2).  The entry of h_2 h_1 w is ngram_vals[slot] where ngram_keys[slot] == (entry of h_1 w) << 32
@@ -610,23 +594,6 @@ typedef struct {
  * one CAS per probe; the table is cleared first.  *dups (device int32, not cleared) counts keys found already present. */
 int w2l_ngram_lm_build(const uint64_t* keys, const int32_t* vals, int64_t n, uint64_t* table_keys, int32_t* table_vals,
                        int64_t cap, int32_t* dups, void* stream);
-/* workspace bytes for w2l_ctc_beam_search_lm (w2l_ctc_beam_search's plus a 64-byte LM state per trie node); -1 if out of
- * range (order outside 1..6 included) */
-int64_t w2l_ctc_beam_search_lm_workspace_bytes(int N, int T, int k, int order);
-/* w2l_ctc_beam_search with the LM of lm (an order-`order` model, 1 <= order <= 6).  label_info_host as there, plus bit 11:
- * the label's character is whitespace (only ' ' may be, an error otherwise); space_index: first index of ' ' (-1: none).
- * Each trie node carries an LM state (the last order-1 word ids and their context backoffs, the float32 sum of the words
- * closed so far, the spelling-trie node of the partial word: 0 empty, -1 left the trie (scored as <unk>)), computed once when
- * the node is interned.  The weight of member i, alpha * ln 10 * (log10 of its words with </s>, float32 in ArpaLM.score's
- * order), multiplies exactly one contribution: E(i, c)'s p * (pb + pnb) where c is the space or end_char, c is not member i's
- * last character and member i has a character other than ' '.  out: w2l_ctc_beam_search's layout followed by float
- * lm_log10[N][k], the LM total of each result (0 for an empty slot or a string of spaces).  LDS: 1.5 KB of static state more
- * than w2l_ctc_beam_search; the same dynamic tables and limits. */
-int w2l_ctc_beam_search_lm(const float* probs, const int32_t* sizes, int N, int T, int A, const int32_t* label_info_host,
-                           int blank, int end_index, int space_index, int k, double alpha, double beta, double prune,
-                           int log_probs, const w2l_ngram_lm_t* lm, int order, void* workspace, int64_t workspace_bytes,
-                           void* out, void* stream);
-/* ---- the two searches constrained to a word list (lexicon.Lexicon) ---- */
 /* The spelling trie of a lexicon, in the form and with the limits of w2l_ngram_lm_t's (built by w2l_ngram_lm_build):
  * trie_keys[slot] == node << 8 | canonical label -> child node trie_vals[slot], root 0; trie_word[node] >= 0 where the node
  * spells a whole word.  The trie of an n-gram model may be passed as it is. */
@@ -637,52 +604,70 @@ typedef struct {
     const int32_t* trie_word;
     int32_t n_trie_nodes;   /* trie_word length */
 } w2l_lexicon_t;
-/* workspace bytes of the lexicon searches: those of their parents (a beam slot's trie node lives in LDS, and the node of a new
- * member is found from its parent slot's, so nothing is kept per interned prefix); -1 if out of range */
-int64_t w2l_ctc_beam_search_lex_workspace_bytes(int N, int T, int k);
-int64_t w2l_ctc_beam_search_lm_lex_workspace_bytes(int N, int T, int k, int order);
-/* w2l_ctc_beam_search / w2l_ctc_beam_search_lm where no mass is given to a string that leaves the lexicon.  A separator is
- * the space (space_index, -1: none) or end_char; the partial word of a string is what follows its last separator.  The
- * extension of beam member i by label c that is not itself a beam member takes part in the frame only if it is legal: c a
- * separator and member i's partial word empty or a whole word, or c another label and (partial word + c) a prefix of a word
- * (one probe of the trie); otherwise it gets no mass, like a pruned label.  complete_only != 0: out holds only the members of
- * the final beam whose partial word is empty or a whole word, in rank order, the other slots empty (all members if there is
- * none).  label_info_host bit 11 and the other arguments as in w2l_ctc_beam_search_lm; out as in the parent; 512 bytes of
- * static LDS more than the parent. */
-int w2l_ctc_beam_search_lex(const float* probs, const int32_t* sizes, int N, int T, int A, const int32_t* label_info_host,
-                            int blank, int end_index, int space_index, int k, double beta, double prune, int log_probs,
-                            const w2l_lexicon_t* lexicon, int complete_only, void* workspace, int64_t workspace_bytes,
-                            void* out, void* stream);
-int w2l_ctc_beam_search_lm_lex(const float* probs, const int32_t* sizes, int N, int T, int A, const int32_t* label_info_host,
-                               int blank, int end_index, int space_index, int k, double alpha, double beta, double prune,
-                               int log_probs, const w2l_ngram_lm_t* lm, int order, const w2l_lexicon_t* lexicon,
-                               int complete_only, void* workspace, int64_t workspace_bytes, void* out, void* stream);
-/* ---- hotword boosting in the four searches above (lexicon.Lexicon.boost_chars) ---- */
-/* workspace bytes of w2l_ctc_beam_search_hot: those of the search without hotwords (order 0: no LM, w2l_ctc_beam_search's;
- * otherwise w2l_ctc_beam_search_lm's); -1 if out of range */
-int64_t w2l_ctc_beam_search_hot_workspace_bytes(int N, int T, int k, int order);
-/* w2l_ctc_beam_search (lm and lexicon NULL), _lm (lexicon NULL), _lex (lm NULL) or _lm_lex with a list of hotwords, given as
- * the spelling trie of a word list of its own (a w2l_lexicon_t; separate from lexicon's and from lm's).  h(s) = the characters
- * of the closed words of s (those followed by the space or end_char) that are hotwords, plus the characters of its partial
- * word while that is a non-empty prefix of a hotword (a provisional credit: it goes when the word leaves the trie or is
- * closed as something else).  The ranking weight becomes mass * (words + 1)^beta * exp(hotword_weight * h): the score
- * written to out includes hotword_weight * h; masses, the LM term, the prune, ties and the lexicon rule are untouched.
- * hotword_weight: natural-log units per character, any finite real; 0 gives the output of the search without hotwords.  The
- * arguments a NULL lm / lexicon leaves unused (alpha, order / complete_only) are ignored; out has lm_log10 only with lm.  One
- * more trie probe per new candidate; 1.5 KB of static LDS more than the same search without hotwords; nothing per interned
- * prefix.  A NULL or over-full hotword table, a capacity that is no power of two, a non-finite weight and a whitespace label
- * other than ' ' are argument errors. */
-int w2l_ctc_beam_search_hot(const float* probs, const int32_t* sizes, int N, int T, int A, const int32_t* label_info_host,
-                            int blank, int end_index, int space_index, int k, double alpha, double beta, double prune,
-                            int log_probs, const w2l_ngram_lm_t* lm, int order, const w2l_lexicon_t* lexicon,
-                            int complete_only, const w2l_lexicon_t* hotwords, double hotword_weight, void* workspace,
-                            int64_t workspace_bytes, void* out, void* stream);
+/* ---- CTC prefix beam search (decoder.py:147-267; beam_search.prefix_beam_search), optionally with a word n-gram language
+ *      model (ngram_lm.ArpaLM; decoder.py:210-212 with lm_weigh), constrained to a lexicon (lexicon.Lexicon) and
+ *      preferring hotwords (Lexicon.boost_chars).  One entry point: each of lm, lexicon and hotwords may be NULL,
+ *      independently, and the call launches ctc_beam_search_kernel<lm != NULL, lexicon != NULL, hotwords != NULL> -- a NULL
+ *      table is a search compiled without it, not the search with it at weight 0 ---- */
+/* workspace bytes for w2l_ctc_beam_search: per utterance a trie of k*T+1 nodes and its intern table, plus with an LM of order
+ * `order` (1..6; 0: no LM) a 64-byte LM state per trie node.  A lexicon and hotwords keep nothing per interned prefix (a beam
+ * slot's trie node lives in LDS, and the node of a new member is found from its parent slot's).  -1 if out of range: N, T or
+ * k < 1, k*T >= 2^29, order outside 0..6. */
+int64_t w2l_ctc_beam_search_workspace_bytes(int N, int T, int k, int order);
+/* One workgroup per utterance, one launch for the batch, masses as fp64 logs.  probs fp32 [N][T][A] contiguous: probabilities,
+ * or log-probabilities if log_probs; sizes int32 [N] (NULL: T) = the frames decoded of each utterance.  label_info_host[A]:
+ * bits 0-7 the first index of the label's character (duplicate labels: the first index wins), bit 8 the label's character
+ * is the blank's, bit 9 it is a word character (\w), bit 10 a word separator ([\s|>]).  end_index: first index of end_char,
+ * -1 if absent (a prefix ending in it is carried unchanged).  A frame extends with the labels whose probability is > prune
+ * (lp > log(prune) for log input); ranking = mass * (words + 1)^beta, ties in the host's first-insertion order.
+ * out (one buffer, one copy to the host): double score[N][k] (log of the ranking weight, -inf for an empty slot) |
+ * int32 len[N][k] (-1: empty slot) | int32 status[N] (1: a probability was negative or NaN) | int32 labels[N][k][T]
+ * (first label indices, the first len of each row valid); slot 0 is the best prefix.  Limits: 1 <= k <= 64, 1 <= A <= 128,
+ * and the candidate tables (48 * k * (A + 1) + 8 * k * A bytes) fit in LDS beside 9 KB of fixed state: k=32 with A=64 is
+ * 114 KB; an error otherwise.
+ *
+ * With at least one of the three tables: label_info_host bit 11 = the label's character is whitespace (only ' ' may be, an
+ * error otherwise) and space_index = the first index of ' ' (-1: none) are read and checked; without any, neither is.
+ *
+ * lm (an order-`order` model, 1 <= order <= 6): each trie node carries an LM state (the last order-1 word ids and their
+ * context backoffs, the float32 sum of the words closed so far, the spelling-trie node of the partial word: 0 empty, -1 left
+ * the trie (scored as <unk>)), computed once when the node is interned.  The weight of member i, alpha * ln 10 * (log10 of
+ * its words with </s>, float32 in ArpaLM.score's order), multiplies exactly one contribution: E(i, c)'s p * (pb + pnb) where
+ * c is the space or end_char, c is not member i's last character and member i has a character other than ' '.  out is
+ * followed by float lm_log10[N][k], the LM total of each result (0 for an empty slot or a string of spaces); 1.5 KB more of
+ * static LDS.  lm NULL: alpha and order are ignored, out has no lm_log10 section, the workspace is that of order 0.
+ *
+ * lexicon: no mass is given to a string that leaves the word list.  A separator is the space or end_char; the partial word
+ * of a string is what follows its last separator.  The extension of beam member i by label c that is not itself a beam
+ * member takes part in the frame only if it is legal: c a separator and member i's partial word empty or a whole word, or c
+ * another label and (partial word + c) a prefix of a word (one probe of the trie); otherwise it gets no mass, like a pruned
+ * label.  complete_only != 0: out holds only the members of the final beam whose partial word is empty or a whole word, in
+ * rank order, the other slots empty (all members if there is none).  512 bytes more of static LDS.  lexicon NULL:
+ * complete_only is not read.
+ *
+ * hotwords: the spelling trie of a word list of its own (separate from lexicon's and from lm's).  h(s) = the characters of
+ * the closed words of s (those followed by the space or end_char) that are hotwords, plus the characters of its partial word
+ * while that is a non-empty prefix of a hotword (a provisional credit: it goes when the word leaves the trie or is closed as
+ * something else).  The ranking weight becomes mass * (words + 1)^beta * exp(hotword_weight * h): the score written to out
+ * includes hotword_weight * h; masses, the LM term, the prune, ties and the lexicon rule are untouched.  hotword_weight:
+ * natural-log units per character, any finite real (an error otherwise); 0 gives the output of the search without hotwords.
+ * One more trie probe per new candidate; 1.5 KB more of static LDS.  hotwords NULL: hotword_weight is not read.
+ *
+ * Argument errors (nothing is launched; w2l_last_error names ctc_beam_search): a table given with a NULL pointer in it, an
+ * over-full table or a capacity that is no power of two, an order outside 1..6 with lm, a space_index that is not the first
+ * index of a label, a whitespace label other than ' ', a non-finite weight, a workspace smaller than the query's answer. */
+int w2l_ctc_beam_search(const float* probs, const int32_t* sizes, int N, int T, int A, const int32_t* label_info_host,
+                        int blank, int end_index, int space_index, int k, double alpha, double beta, double prune,
+                        int log_probs, const w2l_ngram_lm_t* lm, int order, const w2l_lexicon_t* lexicon,
+                        int complete_only, const w2l_lexicon_t* hotwords, double hotword_weight, void* workspace,
+                        int64_t workspace_bytes, void* out, void* stream);
 /* ---- ASG prefix beam search and forced alignment (asg_beam.py; host restatements: asg_prefix_beam_search,
- *      asg_viterbi_align_host): what w2l_ctc_beam_search / _lm / w2l_ctc_align are to a CTC model, for a model trained with
+ *      asg_viterbi_align_host): what w2l_ctc_beam_search / w2l_ctc_align are to a CTC model, for a model trained with
  *      the ASG criterion (no blank; learned transitions; label repeat_index stands for "the previous letter again") ---- */
-/* workspace bytes for w2l_asg_beam_search (per utterance: a trie of k*T+1 nodes of 12 bytes and its intern table); -1 if out
- * of range: A outside 1..64, k outside 1..64, T >= 2^24 or k*T >= 2^29 */
-int64_t w2l_asg_beam_search_workspace_bytes(int N, int T, int A, int k);
+/* workspace bytes for w2l_asg_beam_search (per utterance: a trie of k*T+1 nodes of 12 bytes and its intern table, plus with an
+ * LM of order `order` (1..6; 0: no LM) a 64-byte LM state per trie node); -1 if out of range: A outside 1..64, k outside
+ * 1..64, T >= 2^24, k*T >= 2^29 or order outside 0..6 */
+int64_t w2l_asg_beam_search_workspace_bytes(int N, int T, int A, int k, int order);
 /* One workgroup per utterance, one launch for the batch, masses as fp64 natural logs.  x fp32 [N][T][A] contiguous (any real
  * scores), transitions fp32 [A][A] (g[i][j]: label j at frame t after label i at frame t-1), sizes int32 [N] (NULL: T).  A
  * hypothesis is an ENCODED label sequence (no two neighbours equal) with one mass, the log-sum over the frame paths that read
@@ -694,21 +679,19 @@ int64_t w2l_asg_beam_search_workspace_bytes(int N, int T, int A, int k);
  * w2l_ctc_beam_search counts them; ties in first-insertion order; the k best are the next beam.  No end character.
  * label_info_host[A]: bits 0-7, 9 and 10 as in w2l_ctc_beam_search.  out: that search's layout, double score[N][k] | int32
  * len[N][k] (-1: empty slot) | int32 status[N] (1: a NaN score or transition) | int32 labels[N][k][T] (ENCODED labels).
- * Limits: 1 <= k <= 64, 1 <= A <= 64 (k = 64 with A = 64 takes 138 KB of dynamic LDS beside 9 KB static). */
+ * Limits: 1 <= k <= 64, 1 <= A <= 64 (k = 64 with A = 64 takes 138 KB of dynamic LDS beside 9 KB static).
+ *
+ * lm may be NULL; the call launches asg_beam_search_kernel<lm != NULL>.  With lm (tables, order, label_info_host bit 11 and
+ * space_index as in w2l_ctc_beam_search, checked only here): a trie node's LM state spells its DECODED characters (an r after
+ * a letter spells the letter again, an r after a space closes nothing, a leading r spells nothing).  The weight of member i,
+ * alpha * ln 10 * (log10 of its text's words with </s>), is added to exactly one contribution: the extension of member i by
+ * the space label, where member i's last decoded character is not the space and its text has a character other than ' '.
+ * out is followed by float lm_log10[N][k].  lm NULL: space_index, alpha and order are ignored, out has no lm_log10 section,
+ * the workspace is that of order 0.  Argument errors as in w2l_ctc_beam_search; w2l_last_error names asg_beam_search. */
 int w2l_asg_beam_search(const float* x, const float* transitions, const int32_t* sizes, int N, int T, int A,
-                        const int32_t* label_info_host, int repeat_index, int k, double beta, double prune, void* workspace,
-                        int64_t workspace_bytes, void* out, void* stream);
-/* workspace bytes for w2l_asg_beam_search_lm (plus a 64-byte LM state per trie node); -1 if out of range */
-int64_t w2l_asg_beam_search_lm_workspace_bytes(int N, int T, int A, int k, int order);
-/* w2l_asg_beam_search with the tables of w2l_ctc_beam_search_lm (label_info_host bit 11, space_index as there).  A trie node's
- * LM state spells its DECODED characters (an r after a letter spells the letter again, an r after a space closes nothing, a
- * leading r spells nothing).  The weight of member i, alpha * ln 10 * (log10 of its text's words with </s>), is added to
- * exactly one contribution: the extension of member i by the space label, where member i's last decoded character is not the
- * space and its text has a character other than ' '.  out: w2l_asg_beam_search's layout followed by float lm_log10[N][k]. */
-int w2l_asg_beam_search_lm(const float* x, const float* transitions, const int32_t* sizes, int N, int T, int A,
-                           const int32_t* label_info_host, int repeat_index, int space_index, int k, double alpha, double beta,
-                           double prune, const w2l_ngram_lm_t* lm, int order, void* workspace, int64_t workspace_bytes,
-                           void* out, void* stream);
+                        const int32_t* label_info_host, int repeat_index, int space_index, int k, double alpha, double beta,
+                        double prune, const w2l_ngram_lm_t* lm, int order, void* workspace, int64_t workspace_bytes, void* out,
+                        void* stream);
 /* workspace bytes for w2l_asg_align: 0 while the moves fit in LDS, else N * ceil(T / 16) * (states rounded up to the block's)
  * * 4; -1 if out of range (T > 32768, Smax > 4095, A outside 1..64) */
 int64_t w2l_asg_align_workspace_bytes(int N, int T, int A, int Smax);

@@ -175,13 +175,13 @@ def test_cli_values():
 def test_abi_answers_on_the_host():
     from wav2letter_pytorch_amd._lib import lib
     assert lib.w2l_abi_version() == 2
-    assert lib.w2l_asg_beam_search_workspace_bytes(2, 50, 65, 5) == -1
-    assert lib.w2l_asg_beam_search_workspace_bytes(2, 50, 29, 65) == -1
-    assert lib.w2l_asg_beam_search_workspace_bytes(2, 50, 29, 0) == -1
-    assert lib.w2l_asg_beam_search_workspace_bytes(2, 50, 29, 5) > 0
-    assert lib.w2l_asg_beam_search_workspace_bytes(1, 8, 64, 64) > 0
-    assert lib.w2l_asg_beam_search_lm_workspace_bytes(2, 50, 29, 5, 7) == -1
-    assert lib.w2l_asg_beam_search_lm_workspace_bytes(2, 50, 29, 5, 3) > lib.w2l_asg_beam_search_workspace_bytes(2, 50, 29, 5)
+    assert lib.w2l_asg_beam_search_workspace_bytes(2, 50, 65, 5, 0) == -1
+    assert lib.w2l_asg_beam_search_workspace_bytes(2, 50, 29, 65, 0) == -1
+    assert lib.w2l_asg_beam_search_workspace_bytes(2, 50, 29, 0, 0) == -1
+    assert lib.w2l_asg_beam_search_workspace_bytes(2, 50, 29, 5, 0) > 0
+    assert lib.w2l_asg_beam_search_workspace_bytes(1, 8, 64, 64, 0) > 0
+    assert lib.w2l_asg_beam_search_workspace_bytes(2, 50, 29, 5, 7) == -1
+    assert lib.w2l_asg_beam_search_workspace_bytes(2, 50, 29, 5, 3) > lib.w2l_asg_beam_search_workspace_bytes(2, 50, 29, 5, 0)
     assert lib.w2l_asg_align_workspace_bytes(2, 100, 29, 40) == 0
     assert lib.w2l_asg_align_workspace_bytes(2, 100, 65, 40) == -1 and lib.w2l_asg_align_workspace_bytes(2, 100, 29, 4096) == -1
     assert lib.w2l_asg_align_workspace_bytes(2, 32768, 29, 4095) > 0

@@ -196,7 +196,7 @@ def random_arpa(seed, order=5, vocab=40, per_order=300, extra=20):
 
 
 def walk_scores(lm, sentences):
-    """ArpaLM.score(s) for every s, as w2l_ctc_beam_search_lm computes it: float32 state per sentence (last order-1 word
+    """ArpaLM.score(s) for every s, as w2l_ctc_beam_search computes it with lm: float32 state per sentence (last order-1 word
     ids, their context backoffs), q by the reverse-suffix walk over flat_tables() (keys looked up exactly), vectorised"""
     flat = lm.flat_tables()
     P, BO = flat['prob'], flat['bo']

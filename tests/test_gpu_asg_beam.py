@@ -1,4 +1,4 @@
-"""w2l_asg_beam_search / w2l_asg_beam_search_lm against the host restatement (asg_beam.asg_prefix_beam_search): strings and
+"""w2l_asg_beam_search, without and with lm, against the host restatement (asg_beam.asg_prefix_beam_search): strings and
 n-best order identical, scores within 1e-9 * max(1, |ref|) -- the margin the CTC beam tests use for the same fp64 log
 arithmetic.  Inputs are generated in float32 and widened exactly for the host."""
 import functools

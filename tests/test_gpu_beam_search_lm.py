@@ -1,4 +1,4 @@
-"""The device beam search with an ARPA n-gram model (w2l_ctc_beam_search_lm) against the host recursion with
+"""The device beam search with an ARPA n-gram model (w2l_ctc_beam_search with lm) against the host recursion with
 ``lm=lambda s: 10 ** arpa.score(s)``.
 
 The models are generated at run time over short words of a few letters, so that the decoded strings are mostly

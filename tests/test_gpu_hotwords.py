@@ -1,4 +1,4 @@
-"""Hotword boosting in the device beam searches (w2l_ctc_beam_search_hot, all four LM / lexicon combinations) against the host
+"""Hotword boosting in the device beam searches (w2l_ctc_beam_search with hotwords, all four LM / lexicon combinations) against the host
 recursion ``prefix_beam_search(..., hotwords=, hotword_weight=)`` on float64 posteriors: strings equal, log weights within 1e-9
 relative, ``lm_log10`` bit-equal to ``np.float32(lm.score(...))`` -- the comparison of tests/test_gpu_lexicon.py.
 
@@ -341,11 +341,11 @@ def test_entry_point_errors(models):
     space = LABELS.index(' ')
     tabbed = LABELS[:-3] + ['\t'] + LABELS[-2:]
     info_tab = _label_info(tabbed, 0, '>')[0] | np.array([ch.isspace() << 11 for ch in tabbed], dtype=np.int32)
-    ws_bytes = int(lib.w2l_ctc_beam_search_hot_workspace_bytes(N, t, k, lm.order))
-    assert ws_bytes == int(lib.w2l_ctc_beam_search_lm_workspace_bytes(N, t, k, lm.order)) > 0
-    assert int(lib.w2l_ctc_beam_search_hot_workspace_bytes(N, t, k, 0)) == int(lib.w2l_ctc_beam_search_workspace_bytes(N, t, k))
-    assert int(lib.w2l_ctc_beam_search_hot_workspace_bytes(N, t, 0, 0)) == -1
-    assert int(lib.w2l_ctc_beam_search_hot_workspace_bytes(N, t, k, 7)) == -1
+    # hotwords add nothing to the workspace: the query knows the LM order alone (0: none)
+    ws_bytes = int(lib.w2l_ctc_beam_search_workspace_bytes(N, t, k, lm.order))
+    assert ws_bytes > int(lib.w2l_ctc_beam_search_workspace_bytes(N, t, k, 0)) > 0
+    assert int(lib.w2l_ctc_beam_search_workspace_bytes(N, t, 0, 0)) == -1
+    assert int(lib.w2l_ctc_beam_search_workspace_bytes(N, t, k, 7)) == -1
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device='cuda')
     out = torch.full((12 * N * k + 4 * N + 4 * N * k * t + 4 * N * k,), 0x5a, dtype=torch.uint8, device='cuda')
 
@@ -353,9 +353,9 @@ def test_entry_point_errors(models):
         vp = inf.ctypes.data_as(C.c_void_p)
         if lex_desc is None:
             lex_desc = dev_lex.desc_ref if with_lex else None
-        return lib.w2l_ctc_beam_search_hot(ptr(x), None, N, t, len(LABELS), vp, 0, end, sp, k, 1.0, 5.0, 1e-3, 0,
-                                           dev_lm.desc_ref if with_lm else None, lm.order if with_lm else 0, lex_desc, 1, desc,
-                                           weight, ptr(ws), ws_bytes, ptr(out), stream_ptr())
+        return lib.w2l_ctc_beam_search(ptr(x), None, N, t, len(LABELS), vp, 0, end, sp, k, 1.0, 5.0, 1e-3, 0,
+                                       dev_lm.desc_ref if with_lm else None, lm.order if with_lm else 0, lex_desc, 1, desc,
+                                       weight, ptr(ws), ws_bytes, ptr(out), stream_ptr())
     good = dev_hot.desc
     nodes = good.n_trie_nodes
     full = LexTables(good.trie_keys, good.trie_vals, good.trie_cap, good.trie_word, int(good.trie_cap // 2 + 2))
@@ -365,7 +365,6 @@ def test_entry_point_errors(models):
     for with_lm, with_lex in itertools.product((False, True), repeat=2):
         for desc in (full, odd_cap, no_keys, no_word):
             assert call(C.byref(desc), info, space, with_lm, with_lex) != 0
-        assert call(None, info, space, with_lm, with_lex) != 0
         for weight in (float('inf'), float('-inf'), float('nan')):
             assert call(C.byref(good), info, space, with_lm, with_lex, weight) != 0
         assert call(C.byref(good), info_tab, -1, with_lm, with_lex) != 0                 # whitespace other than ' '
@@ -375,6 +374,8 @@ def test_entry_point_errors(models):
     assert bool((out == 0x5a).all())                             # nothing was launched
     for with_lm, with_lex in itertools.product((False, True), repeat=2):
         assert call(C.byref(good), info, space, with_lm, with_lex) == 0
+        # a NULL descriptor is no error at the one entry point: it is the search without hotwords, whose weight is not read
+        assert call(None, info, space, with_lm, with_lex, float('nan')) == 0
     torch.cuda.synchronize()
     with pytest.raises(ValueError, match='whitespace'):
         prefix_beam_search_gpu(_posteriors(t), tabbed, hotwords=_hotwords())

@@ -1,4 +1,4 @@
-"""The lexicon-constrained device beam searches (w2l_ctc_beam_search_lex / w2l_ctc_beam_search_lm_lex) against the host recursion
+"""The lexicon-constrained device beam searches (w2l_ctc_beam_search with a lexicon, with and without lm) against the host recursion
 ``prefix_beam_search(..., lexicon=...)`` on float64 posteriors: strings equal, log weights within 1e-9 relative, ``lm_log10``
 bit-equal to ``np.float32(lm.score(...))`` -- the comparison of tests/test_gpu_beam_search_lm.py.
 
@@ -278,20 +278,20 @@ def test_entry_point_errors(models):
     space = LABELS.index(' ')
     tabbed = LABELS[:-3] + ['\t'] + LABELS[-2:]
     info_tab = _label_info(tabbed, 0, '>')[0] | np.array([ch.isspace() << 11 for ch in tabbed], dtype=np.int32)
-    ws_bytes = int(lib.w2l_ctc_beam_search_lm_lex_workspace_bytes(N, t, k, lm.order))
-    assert ws_bytes == int(lib.w2l_ctc_beam_search_lm_workspace_bytes(N, t, k, lm.order)) > 0
-    assert int(lib.w2l_ctc_beam_search_lex_workspace_bytes(N, t, k)) == int(lib.w2l_ctc_beam_search_workspace_bytes(N, t, k))
-    assert int(lib.w2l_ctc_beam_search_lex_workspace_bytes(N, t, 0)) == -1
+    # the lexicon adds nothing to the workspace: the query knows the LM order alone (0: none)
+    ws_bytes = int(lib.w2l_ctc_beam_search_workspace_bytes(N, t, k, lm.order))
+    assert ws_bytes > int(lib.w2l_ctc_beam_search_workspace_bytes(N, t, k, 0)) > 0
+    assert int(lib.w2l_ctc_beam_search_workspace_bytes(N, t, 0, 0)) == -1
+    assert int(lib.w2l_ctc_beam_search_workspace_bytes(N, t, 0, lm.order)) == -1
+    assert int(lib.w2l_ctc_beam_search_workspace_bytes(N, t, k, 7)) == -1
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device='cuda')
     out = torch.full((12 * N * k + 4 * N + 4 * N * k * t + 4 * N * k,), 0x5a, dtype=torch.uint8, device='cuda')
 
     def call(desc, inf, sp, with_lm):
         vp = inf.ctypes.data_as(C.c_void_p)
-        if with_lm:
-            return lib.w2l_ctc_beam_search_lm_lex(ptr(x), None, N, t, len(LABELS), vp, 0, end, sp, k, 1.0, 5.0, 1e-3, 0,
-                                                  dev_lm.desc_ref, lm.order, desc, 1, ptr(ws), ws_bytes, ptr(out), stream_ptr())
-        return lib.w2l_ctc_beam_search_lex(ptr(x), None, N, t, len(LABELS), vp, 0, end, sp, k, 5.0, 1e-3, 0, desc, 1,
-                                           ptr(ws), ws_bytes, ptr(out), stream_ptr())
+        return lib.w2l_ctc_beam_search(ptr(x), None, N, t, len(LABELS), vp, 0, end, sp, k, 1.0, 5.0, 1e-3, 0,
+                                       dev_lm.desc_ref if with_lm else None, lm.order if with_lm else 0, desc, 1, None, 0.0,
+                                       ptr(ws), ws_bytes, ptr(out), stream_ptr())
     good = dev_lex.desc
     nodes = good.n_trie_nodes
     full = LexTables(good.trie_keys, good.trie_vals, good.trie_cap, good.trie_word, int(good.trie_cap // 2 + 2))
@@ -301,12 +301,13 @@ def test_entry_point_errors(models):
     for with_lm in (False, True):
         for desc in (full, odd_cap, no_keys, no_word):
             assert call(C.byref(desc), info, space, with_lm) != 0
-        assert call(None, info, space, with_lm) != 0
         assert call(C.byref(good), info_tab, -1, with_lm) != 0                   # whitespace other than ' '
         assert call(C.byref(good), info, space - 1, with_lm) != 0                # not the first index of a label... of ' '
     torch.cuda.synchronize()
     assert bool((out == 0x5a).all())                             # nothing was launched
     assert call(C.byref(good), info, space, False) == 0 and call(C.byref(good), info, space, True) == 0
+    # a NULL descriptor is no error at the one entry point: it is the search without a lexicon (plain, and with the LM)
+    assert call(None, info, space, False) == 0 and call(None, info, space, True) == 0
     torch.cuda.synchronize()
     with pytest.raises(ValueError, match='whitespace'):
         prefix_beam_search_gpu(_posteriors(t), tabbed, lexicon=_lexicon())

@@ -3,7 +3,7 @@
 output frames, 29 labels, k in {5, 32}.
 
     w2l_asg_beam_search      against  w2l_ctc_beam_search
-    w2l_asg_beam_search_lm   against  w2l_ctc_beam_search_lm   (a generated trigram model over short words)
+    the same two with lm     (a generated trigram model over short words)
     w2l_asg_align            against  w2l_ctc_align            (targets of 80 labels)
 
 Both searches read the SAME log-probabilities: labels held for a few frames each, a rival almost as likely, a trained ASG
@@ -112,34 +112,25 @@ def search_pair(x, g, k, lm, beta=5.0, prune=1e-3, alpha=0.5):
     extra = 4 * n * k if lm is not None else 0
     out_a = torch.empty(12 * n * k + 4 * n + 4 * n * k * t + extra, dtype=torch.uint8, device=dev)
     out_c = torch.empty_like(out_a)
-    if lm is None:
-        wa = int(lib.w2l_asg_beam_search_workspace_bytes(n, t, a, k))
-        wc = int(lib.w2l_ctc_beam_search_workspace_bytes(n, t, k))
-    else:
+    tables, lm_ref, order = None, None, 0
+    if lm is not None:
         ctc_info = ctc_info | np.array([ch.isspace() << 11 for ch in labels], dtype=np.int32)
         tables = lm.to_device(labels, 0, dev)
-        wa = int(lib.w2l_asg_beam_search_lm_workspace_bytes(n, t, a, k, lm.order))
-        wc = int(lib.w2l_ctc_beam_search_lm_workspace_bytes(n, t, k, lm.order))
+        lm_ref, order = tables.desc_ref, lm.order
+    wa = int(lib.w2l_asg_beam_search_workspace_bytes(n, t, a, k, order))
+    wc = int(lib.w2l_ctc_beam_search_workspace_bytes(n, t, k, order))
     ws_a = torch.empty(wa, dtype=torch.uint8, device=dev)
     ws_c = torch.empty(wc, dtype=torch.uint8, device=dev)
 
     def asg():
-        if lm is None:
-            check(lib.w2l_asg_beam_search(ptr(x), ptr(g), None, n, t, a, asg_info.ctypes.data_as(VP), 0, k, beta, prune, ptr(ws_a),
-                                          wa, ptr(out_a), stream_ptr()), 'w2l_asg_beam_search')
-        else:
-            check(lib.w2l_asg_beam_search_lm(ptr(x), ptr(g), None, n, t, a, asg_info.ctypes.data_as(VP), 0, space, k, alpha, beta,
-                                             prune, tables.desc_ref, lm.order, ptr(ws_a), wa, ptr(out_a), stream_ptr()),
-                  'w2l_asg_beam_search_lm')
+        _keep = tables                                 # (lm_ref points at its device tables)
+        check(lib.w2l_asg_beam_search(ptr(x), ptr(g), None, n, t, a, asg_info.ctypes.data_as(VP), 0, space, k, alpha, beta, prune,
+                                      lm_ref, order, ptr(ws_a), wa, ptr(out_a), stream_ptr()), 'w2l_asg_beam_search')
 
     def ctc():
-        if lm is None:
-            check(lib.w2l_ctc_beam_search(ptr(x), None, n, t, a, ctc_info.ctypes.data_as(VP), 0, end, k, beta, prune, 1, ptr(ws_c),
-                                          wc, ptr(out_c), stream_ptr()), 'w2l_ctc_beam_search')
-        else:
-            check(lib.w2l_ctc_beam_search_lm(ptr(x), None, n, t, a, ctc_info.ctypes.data_as(VP), 0, end, space, k, alpha, beta,
-                                             prune, 1, tables.desc_ref, lm.order, ptr(ws_c), wc, ptr(out_c), stream_ptr()),
-                  'w2l_ctc_beam_search_lm')
+        check(lib.w2l_ctc_beam_search(ptr(x), None, n, t, a, ctc_info.ctypes.data_as(VP), 0, end, space, k, alpha, beta, prune, 1,
+                                      lm_ref, order, None, 0, None, 0.0, ptr(ws_c), wc, ptr(out_c), stream_ptr()),
+              'w2l_ctc_beam_search')
     return asg, ctc
 
 

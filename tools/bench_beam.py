@@ -43,13 +43,14 @@ def peaky(seed, n, t, a, blank=0, boost=(6.0, 12.0), p_blank=0.6, max_burst=3):
 def time_launches(x, k, reps, beta=5.0, prune=1e-3):
     n, t, a = x.shape
     info, end = _label_info(english_labels, 0, '>')
-    ws_bytes = int(lib.w2l_ctc_beam_search_workspace_bytes(n, t, k))
+    ws_bytes = int(lib.w2l_ctc_beam_search_workspace_bytes(n, t, k, 0))
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
     out = torch.empty(12 * n * k + 4 * n + 4 * n * k * t, dtype=torch.uint8, device=x.device)
 
     def launch():
-        check(lib.w2l_ctc_beam_search(ptr(x), None, n, t, a, info.ctypes.data_as(C.c_void_p), 0, end, k, beta, prune, 0,
-                                      ptr(ws), ws_bytes, ptr(out), stream_ptr()), 'w2l_ctc_beam_search')
+        check(lib.w2l_ctc_beam_search(ptr(x), None, n, t, a, info.ctypes.data_as(C.c_void_p), 0, end, -1, k, 0.0, beta, prune, 0,
+                                      None, 0, None, 0, None, 0.0, ptr(ws), ws_bytes, ptr(out), stream_ptr()),
+              'w2l_ctc_beam_search')
     for _ in range(3):
         launch()
     s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """What hotword boosting costs the device CTC prefix beam searches: each of the four kernels {no LM, LM} x {no lexicon, lexicon}
-(w2l_ctc_beam_search, _lex, _lm, _lm_lex) against its HOT instantiation (w2l_ctc_beam_search_hot) from the same build, in one
-process, on the ``spelled`` posteriors of tools/bench_beam_lex.py (bursts that spell random words of the vocabulary): N=32
+(w2l_ctc_beam_search with hotwords NULL) against its HOT instantiation (the same call with a hotword list) from the same build,
+in one process, on the ``spelled`` posteriors of tools/bench_beam_lex.py (bursts that spell random words of the vocabulary): N=32
 utterances, T in {500, 1000}, 29 labels, k in {5, 16, 32}.  The model, the lexicon and their shared trie are that tool's; the
 hotwords are ``--hotwords`` words drawn from the vocabulary (so the posteriors do spell them), in a trie of their own.
 
@@ -40,18 +40,15 @@ COMBOS = ('plain', 'lex', 'lm', 'lm_lex')
 
 
 def launcher(x, k, combo, lm, tables, dev_lex, dev_hot, weight, alpha, beta=5.0, prune=1e-3):
-    """a callable that launches one search of ``combo`` on x: the existing entry point (``dev_hot`` None) or
-    w2l_ctc_beam_search_hot with ``weight``.  Each launcher owns its workspace and output buffer."""
+    """a callable that launches one search of ``combo`` on x: w2l_ctc_beam_search without hotwords (``dev_hot`` None) or with
+    them at ``weight``.  Each launcher owns its workspace and output buffer."""
     n, t, a = x.shape
     info, end = _label_info(english_labels, 0, '>')
     info = info | np.array([ch.isspace() << 11 for ch in english_labels], dtype=np.int32)
     vp = info.ctypes.data_as(C.c_void_p)
     space = english_labels.index(' ')
     with_lm, with_lex = combo in ('lm', 'lm_lex'), combo in ('lex', 'lm_lex')
-    if with_lm:
-        ws_bytes = int(lib.w2l_ctc_beam_search_lm_workspace_bytes(n, t, k, lm.order))
-    else:
-        ws_bytes = int(lib.w2l_ctc_beam_search_workspace_bytes(n, t, k))
+    ws_bytes = int(lib.w2l_ctc_beam_search_workspace_bytes(n, t, k, lm.order if with_lm else 0))
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
     out = torch.empty(12 * n * k + 4 * n + 4 * n * k * t + 4 * n * k, dtype=torch.uint8, device=x.device)
     head = (ptr(x), None, n, t, a, vp, 0, end)
@@ -61,19 +58,8 @@ def launcher(x, k, combo, lm, tables, dev_lex, dev_hot, weight, alpha, beta=5.0,
 
     def launch():
         _keep = info                                   # (vp points into it)
-        if dev_hot is not None:
-            check(lib.w2l_ctc_beam_search_hot(*head, space, k, alpha, beta, prune, 0, lm_ref, order, lex_ref, 1,
-                                              dev_hot.desc_ref, weight, *tail), 'w2l_ctc_beam_search_hot')
-        elif combo == 'plain':
-            check(lib.w2l_ctc_beam_search(*head, k, beta, prune, 0, *tail), 'w2l_ctc_beam_search')
-        elif combo == 'lex':
-            check(lib.w2l_ctc_beam_search_lex(*head, space, k, beta, prune, 0, lex_ref, 1, *tail), 'w2l_ctc_beam_search_lex')
-        elif combo == 'lm':
-            check(lib.w2l_ctc_beam_search_lm(*head, space, k, alpha, beta, prune, 0, lm_ref, order, *tail),
-                  'w2l_ctc_beam_search_lm')
-        else:
-            check(lib.w2l_ctc_beam_search_lm_lex(*head, space, k, alpha, beta, prune, 0, lm_ref, order, lex_ref, 1, *tail),
-                  'w2l_ctc_beam_search_lm_lex')
+        check(lib.w2l_ctc_beam_search(*head, space, k, alpha, beta, prune, 0, lm_ref, order, lex_ref, 1,
+                                      dev_hot.desc_ref if dev_hot is not None else None, weight, *tail), 'w2l_ctc_beam_search')
     return launch
 
 

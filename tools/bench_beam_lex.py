@@ -38,27 +38,28 @@ from wav2letter_pytorch_amd.ngram_lm import ArpaLM  # noqa: E402
 
 
 def time_lex_launches(x, k, reps, dev_lex, lm=None, tables=None, alpha=0.5, beta=5.0, prune=1e-3):
-    """ms per launch of w2l_ctc_beam_search_lex, or with ``lm`` of w2l_ctc_beam_search_lm_lex"""
+    """ms per launch of w2l_ctc_beam_search with the lexicon, and with ``lm`` if given"""
     n, t, a = x.shape
     info, end = _label_info(english_labels, 0, '>')
     info = info | np.array([ch.isspace() << 11 for ch in english_labels], dtype=np.int32)
     vp = info.ctypes.data_as(C.c_void_p)
     space = english_labels.index(' ')
     if lm is None:
-        ws_bytes = int(lib.w2l_ctc_beam_search_lex_workspace_bytes(n, t, k))
+        ws_bytes = int(lib.w2l_ctc_beam_search_workspace_bytes(n, t, k, 0))
     else:
-        ws_bytes = int(lib.w2l_ctc_beam_search_lm_lex_workspace_bytes(n, t, k, lm.order))
+        ws_bytes = int(lib.w2l_ctc_beam_search_workspace_bytes(n, t, k, lm.order))
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
     out = torch.empty(12 * n * k + 4 * n + 4 * n * k * t + 4 * n * k, dtype=torch.uint8, device=x.device)
 
     def launch():
         if lm is None:
-            check(lib.w2l_ctc_beam_search_lex(ptr(x), None, n, t, a, vp, 0, end, space, k, beta, prune, 0, dev_lex.desc_ref, 1,
-                                              ptr(ws), ws_bytes, ptr(out), stream_ptr()), 'w2l_ctc_beam_search_lex')
+            check(lib.w2l_ctc_beam_search(ptr(x), None, n, t, a, vp, 0, end, space, k, 0.0, beta, prune, 0, None, 0,
+                                          dev_lex.desc_ref, 1, None, 0.0, ptr(ws), ws_bytes, ptr(out), stream_ptr()),
+                  'w2l_ctc_beam_search')
         else:
-            check(lib.w2l_ctc_beam_search_lm_lex(ptr(x), None, n, t, a, vp, 0, end, space, k, alpha, beta, prune, 0,
-                                                 tables.desc_ref, lm.order, dev_lex.desc_ref, 1, ptr(ws), ws_bytes, ptr(out),
-                                                 stream_ptr()), 'w2l_ctc_beam_search_lm_lex')
+            check(lib.w2l_ctc_beam_search(ptr(x), None, n, t, a, vp, 0, end, space, k, alpha, beta, prune, 0, tables.desc_ref,
+                                          lm.order, dev_lex.desc_ref, 1, None, 0.0, ptr(ws), ws_bytes, ptr(out), stream_ptr()),
+                  'w2l_ctc_beam_search')
     for _ in range(2):
         launch()
     s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Device CTC prefix beam search with an ARPA n-gram model (w2l_ctc_beam_search_lm) against the same search without one
-(w2l_ctc_beam_search): N=32 utterances, T in {500, 1000}, 29 labels, k in {5, 16, 32}, the posteriors of
+"""Device CTC prefix beam search with an ARPA n-gram model (w2l_ctc_beam_search with lm) against the same search without one
+(lm NULL): N=32 utterances, T in {500, 1000}, 29 labels, k in {5, 16, 32}, the posteriors of
 tools/bench_beam.py.  The model is a synthetic suffix-closed 3-gram generated at run time (a vocabulary of random letter
 strings; nothing is committed), loaded by ngram_lm.ArpaLM.  Also reported: the device table build (w2l_ngram_lm_build,
 host-to-device copies included) and the host prefix_beam_search with the ArpaLM on one float64 utterance.
@@ -70,14 +70,14 @@ def time_lm_launches(x, k, reps, lm, tables, alpha=0.5, beta=5.0, prune=1e-3):
     info, end = _label_info(english_labels, 0, '>')
     info = info | np.array([ch.isspace() << 11 for ch in english_labels], dtype=np.int32)
     space = english_labels.index(' ')
-    ws_bytes = int(lib.w2l_ctc_beam_search_lm_workspace_bytes(n, t, k, lm.order))
+    ws_bytes = int(lib.w2l_ctc_beam_search_workspace_bytes(n, t, k, lm.order))
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
     out = torch.empty(12 * n * k + 4 * n + 4 * n * k * t + 4 * n * k, dtype=torch.uint8, device=x.device)
 
     def launch():
-        check(lib.w2l_ctc_beam_search_lm(ptr(x), None, n, t, a, info.ctypes.data_as(C.c_void_p), 0, end, space, k, alpha, beta,
-                                         prune, 0, tables.desc_ref, lm.order, ptr(ws), ws_bytes, ptr(out), stream_ptr()),
-              'w2l_ctc_beam_search_lm')
+        check(lib.w2l_ctc_beam_search(ptr(x), None, n, t, a, info.ctypes.data_as(C.c_void_p), 0, end, space, k, alpha, beta,
+                                      prune, 0, tables.desc_ref, lm.order, None, 0, None, 0.0, ptr(ws), ws_bytes, ptr(out),
+                                      stream_ptr()), 'w2l_ctc_beam_search')
     for _ in range(2):
         launch()
     s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)

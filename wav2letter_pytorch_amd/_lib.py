@@ -168,28 +168,14 @@ _SIGNATURES = {
     'w2l_ctc_align_workspace_bytes': (c_i64, [c_i, c_i, c_i]),
     'w2l_ctc_align': (c_i, [c_p, c_p, c_p, c_i64, c_p, c_i64, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_i64, c_p, c_p, c_p, c_p, c_p,
                             c_p]),
-    'w2l_ctc_beam_search_workspace_bytes': (c_i64, [c_i, c_i, c_i]),
-    'w2l_ctc_beam_search': (c_i, [c_p, c_p, c_i, c_i, c_i, c_p, c_i, c_i, c_i, C.c_double, C.c_double, c_i, c_p, c_i64, c_p,
-                                  c_p]),
+    'w2l_ctc_beam_search_workspace_bytes': (c_i64, [c_i, c_i, c_i, c_i]),
+    'w2l_ctc_beam_search': (c_i, [c_p, c_p, c_i, c_i, c_i, c_p, c_i, c_i, c_i, c_i, C.c_double, C.c_double, C.c_double, c_i,
+                                  C.POINTER(LmTables), c_i, C.POINTER(LexTables), c_i, C.POINTER(LexTables), C.c_double,
+                                  c_p, c_i64, c_p, c_p]),
     'w2l_ngram_lm_build': (c_i, [c_p, c_p, c_i64, c_p, c_p, c_i64, c_p, c_p]),
-    'w2l_ctc_beam_search_lm_workspace_bytes': (c_i64, [c_i, c_i, c_i, c_i]),
-    'w2l_ctc_beam_search_lm': (c_i, [c_p, c_p, c_i, c_i, c_i, c_p, c_i, c_i, c_i, c_i, C.c_double, C.c_double, C.c_double, c_i,
-                                     C.POINTER(LmTables), c_i, c_p, c_i64, c_p, c_p]),
-    'w2l_ctc_beam_search_lex_workspace_bytes': (c_i64, [c_i, c_i, c_i]),
-    'w2l_ctc_beam_search_lm_lex_workspace_bytes': (c_i64, [c_i, c_i, c_i, c_i]),
-    'w2l_ctc_beam_search_lex': (c_i, [c_p, c_p, c_i, c_i, c_i, c_p, c_i, c_i, c_i, c_i, C.c_double, C.c_double, c_i,
-                                      C.POINTER(LexTables), c_i, c_p, c_i64, c_p, c_p]),
-    'w2l_ctc_beam_search_lm_lex': (c_i, [c_p, c_p, c_i, c_i, c_i, c_p, c_i, c_i, c_i, c_i, C.c_double, C.c_double, C.c_double,
-                                         c_i, C.POINTER(LmTables), c_i, C.POINTER(LexTables), c_i, c_p, c_i64, c_p, c_p]),
-    'w2l_ctc_beam_search_hot_workspace_bytes': (c_i64, [c_i, c_i, c_i, c_i]),
-    'w2l_ctc_beam_search_hot': (c_i, [c_p, c_p, c_i, c_i, c_i, c_p, c_i, c_i, c_i, c_i, C.c_double, C.c_double, C.c_double, c_i,
-                                      C.POINTER(LmTables), c_i, C.POINTER(LexTables), c_i, C.POINTER(LexTables), C.c_double,
-                                      c_p, c_i64, c_p, c_p]),
-    'w2l_asg_beam_search_workspace_bytes': (c_i64, [c_i, c_i, c_i, c_i]),
-    'w2l_asg_beam_search': (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_i, c_i, C.c_double, C.c_double, c_p, c_i64, c_p, c_p]),
-    'w2l_asg_beam_search_lm_workspace_bytes': (c_i64, [c_i, c_i, c_i, c_i, c_i]),
-    'w2l_asg_beam_search_lm': (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_i, c_i, c_i, C.c_double, C.c_double, C.c_double,
-                                     C.POINTER(LmTables), c_i, c_p, c_i64, c_p, c_p]),
+    'w2l_asg_beam_search_workspace_bytes': (c_i64, [c_i, c_i, c_i, c_i, c_i]),
+    'w2l_asg_beam_search': (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_i, c_i, c_i, C.c_double, C.c_double, C.c_double,
+                                  C.POINTER(LmTables), c_i, c_p, c_i64, c_p, c_p]),
     'w2l_asg_align_workspace_bytes': (c_i64, [c_i, c_i, c_i, c_i]),
     'w2l_asg_align': (c_i, [c_p, c_p, c_p, c_p, c_i64, c_p, c_i64, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_i64, c_p, c_p, c_p, c_p,
                             c_p, c_p]),
@@ -316,10 +302,8 @@ TRACE_NAMES = {
     'w2l_nct_to_ntc': 'nct_to_ntc_kernel', 'w2l_pad_cast': 'pad_cast_kernel', 'w2l_quantize_e4m3': 'quantize_e4m3',
     'w2l_quantize_e4m3_dyn': 'quantize_e4m3_dyn', 'w2l_dwconv_fwd': 'dw_fwd_kernel', 'w2l_dwconv_dgrad': 'dw_dgrad_kernel',
     'w2l_dwconv_wgrad': 'dw_wgrad_kernel', 'w2l_argmax': 'argmax_kernel', 'w2l_novograd_pack': 'novograd_pack_kernel',
-    'w2l_ctc_beam_search': 'ctc_beam_search_kernel', 'w2l_ctc_beam_search_lm': 'ctc_beam_search_kernel<LM>',
-    'w2l_ctc_beam_search_lex': 'ctc_beam_search_kernel<LEX>', 'w2l_ctc_beam_search_lm_lex': 'ctc_beam_search_kernel<LM,LEX>',
-    'w2l_ctc_beam_search_hot': 'ctc_beam_search_kernel<HOT>', 'w2l_ngram_lm_build': 'ngram_insert_kernel', 'w2l_ctc_align': 'ctc_align_kernel',
-    'w2l_asg_beam_search': 'asg_beam_search_kernel', 'w2l_asg_beam_search_lm': 'asg_beam_search_kernel<LM>',
+    'w2l_ctc_beam_search': 'ctc_beam_search_kernel', 'w2l_ngram_lm_build': 'ngram_insert_kernel', 'w2l_ctc_align': 'ctc_align_kernel',
+    'w2l_asg_beam_search': 'asg_beam_search_kernel',
     'w2l_asg_align': 'asg_align_kernel',
 }
 _trace = {'rows': None, 'saved': {}, 'pool': []}

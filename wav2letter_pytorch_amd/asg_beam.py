@@ -21,7 +21,7 @@ extend contribution gets ``alpha * ln(lm(text of e))`` when c is the space, the 
 its text has a non-space character (the rule of the CTC search, on decoded characters).
 
 asg_prefix_beam_search / asg_viterbi_align_host restate the recursions on the host (the oracles of the device tests);
-asg_beam_search_gpu / asg_forced_align launch csrc/asg_beam.hip (w2l_asg_beam_search, w2l_asg_beam_search_lm, w2l_asg_align)."""
+asg_beam_search_gpu / asg_forced_align launch csrc/asg_beam.hip (w2l_asg_beam_search, w2l_asg_align)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -36,7 +36,7 @@ from . import _lib
 from ._lib import check, lib, ptr, stream_ptr
 from .alignment import Alignment, HostAlignment, _targets_to_array, align_sections, split_align
 from .asg import MAX_LABELS, ASGDecoder, _check_labels, decode_repeats, encode_repeats
-from .beam_search import _SEP_RE, _WORDCH_RE, _n_words
+from .beam_search import _SEP_RE, _WORDCH_RE, _n_words, split_search_out
 
 _NINF = float('-inf')
 
@@ -274,7 +274,7 @@ def launch_asg_align(x, g, sz, tg_ptr: int, tg_stride: int, len_ptr: int, len_st
 
 
 def _search_device(x, g, sz, labels, repeat_index, k, beta, prune, lm, alpha, offsets):
-    """one launch of w2l_asg_beam_search (with ``lm``: w2l_asg_beam_search_lm) for x [N, T, A] on the current stream, with
+    """one launch of w2l_asg_beam_search (``lm`` None: passed as NULL) for x [N, T, A] on the current stream, with
     ``offsets`` followed by w2l_asg_align on rank 0 where the search wrote it; one copy to the host.  -> (scores [N, k],
     lengths [N, k], encoded labels [N, k, T], lm_log10 [N, k] or None, starts [N, T] or None)"""
     n, t, a = x.shape
@@ -282,9 +282,8 @@ def _search_device(x, g, sz, labels, repeat_index, k, beta, prune, lm, alpha, of
     info = _label_info(labels, lm is not None)
     if offsets and t > 4095:
         raise ValueError('return_offsets: %d frames, w2l_asg_align takes targets of at most 4095 labels' % t)
-    if lm is None:
-        ws_bytes = int(lib.w2l_asg_beam_search_workspace_bytes(n, t, a, k))
-    else:
+    tables, space_index = None, -1
+    if lm is not None:
         from .ngram_lm import ArpaLM
         if not isinstance(lm, ArpaLM):
             raise TypeError('lm must be an ngram_lm.ArpaLM, got %s' % type(lm).__name__)
@@ -292,22 +291,18 @@ def _search_device(x, g, sz, labels, repeat_index, k, beta, prune, lm, alpha, of
         if odd:
             raise ValueError('asg_beam_search_gpu: whitespace labels other than a space (%r) cannot be scored by a word LM' % odd)
         tables = lm.to_device(labels, repeat_index, dev)
-        ws_bytes = int(lib.w2l_asg_beam_search_lm_workspace_bytes(n, t, a, k, lm.order))
+        space_index = labels.index(' ') if ' ' in labels else -1
+    order = lm.order if lm is not None else 0
+    ws_bytes = int(lib.w2l_asg_beam_search_workspace_bytes(n, t, a, k, order))
     if ws_bytes < 0:
         raise ValueError('asg_beam_search_gpu: k=%d (1..64), %d labels (1..%d) or T=%d is out of range' % (k, a, MAX_LABELS, t))
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
     beam_bytes = 12 * n * k + 4 * n + 4 * n * k * t + (4 * n * k if lm is not None else 0)
     out = torch.empty(beam_bytes + (align_sections(n, t, t)[5] if offsets else 0), dtype=torch.uint8, device=dev)
-    vp = C.c_void_p
-    if lm is None:
-        check(lib.w2l_asg_beam_search(ptr(x), ptr(g), ptr(sz), n, t, a, info.ctypes.data_as(vp), int(repeat_index), int(k),
-                                      float(beta), float(prune), ptr(ws), ws_bytes, ptr(out), stream_ptr()),
-              'w2l_asg_beam_search')
-    else:
-        space_index = labels.index(' ') if ' ' in labels else -1
-        check(lib.w2l_asg_beam_search_lm(ptr(x), ptr(g), ptr(sz), n, t, a, info.ctypes.data_as(vp), int(repeat_index),
-                                         space_index, int(k), float(alpha), float(beta), float(prune), tables.desc_ref,
-                                         lm.order, ptr(ws), ws_bytes, ptr(out), stream_ptr()), 'w2l_asg_beam_search_lm')
+    check(lib.w2l_asg_beam_search(ptr(x), ptr(g), ptr(sz), n, t, a, info.ctypes.data_as(C.c_void_p), int(repeat_index),
+                                  space_index, int(k), float(alpha), float(beta), float(prune),
+                                  tables.desc_ref if tables is not None else None, order, ptr(ws), ws_bytes, ptr(out),
+                                  stream_ptr()), 'w2l_asg_beam_search')
     align_ws = None
     if offsets:
         # rank 0 of every utterance, aligned where it lies: labels int32 [N, k, T] from byte 12 N k + 4 N (row stride k T),
@@ -316,12 +311,7 @@ def _search_device(x, g, sz, labels, repeat_index, k, beta, prune, lm, alpha, of
                                     repeat_index, True, out, beam_bytes)
     host = out.cpu().numpy()                           # the one copy to the host (ordered after the launches on this stream)
     del align_ws
-    scores = host[:8 * n * k].view(np.float64).reshape(n, k)
-    rest = host[8 * n * k:beam_bytes].view(np.int32)
-    lengths = rest[:n * k].reshape(n, k)
-    status = rest[n * k:n * k + n]
-    idx = rest[n * k + n:n * k + n + n * k * t].reshape(n, k, t)
-    lm_log10 = rest[n * k + n + n * k * t:].view(np.float32).reshape(n, k) if lm is not None else None
+    scores, lengths, status, idx, lm_log10 = split_search_out(host, n, k, t, lm is not None)
     if status.any():
         raise ValueError('the scores or transitions contain NaN (utterances %s)' % np.nonzero(status)[0].tolist())
     starts = None

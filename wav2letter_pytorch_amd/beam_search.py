@@ -9,12 +9,12 @@ strictly positive masses survive a step, ties keep first-seen order.
 
 prefix_beam_search_gpu / GPUPrefixBeamSearchDecoder run the same recursion without a language model as one HIP launch per
 batch (w2l_ctc_beam_search, csrc/beam_search.hip), in fp64 logs; with an ARPA n-gram model (ngram_lm.ArpaLM: ``lm=`` of
-prefix_beam_search_gpu, GPUPrefixBeamSearchLMDecoder) the same launch scores words on the device (w2l_ctc_beam_search_lm)
+prefix_beam_search_gpu, GPUPrefixBeamSearchLMDecoder) the same launch scores words on the device (w2l_ctc_beam_search with lm)
 as the host does with ``lm=lambda s: 10 ** arpa.score(s)``.  With ``return_offsets`` a second launch on the same stream
 (w2l_ctc_align, alignment.py) aligns each best prefix to the posteriors where it lies in the search's device buffer, and the
 character offsets come back in the same copy.  ``lexicon=`` confines the searches to a word list (lexicon.py); ``hotwords=`` /
 ``hotword_weight=`` make them prefer a list of words without forbidding anything else: the ranking weight of a string gains
-``exp(hotword_weight * h)``, ``h`` = Lexicon.boost_chars (w2l_ctc_beam_search_hot; host and device state the same rule)."""
+``exp(hotword_weight * h)``, ``h`` = Lexicon.boost_chars (w2l_ctc_beam_search with hotwords; host and device state the same rule)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -228,14 +228,49 @@ def _align_starts(host, n, t, beam_bytes):
     return starts
 
 
+def _resolve_lexicon(lexicon, lm):
+    """a Lexicon from ``lexicon``: a Lexicon, a path, or 'lm' (the vocabulary of the ArpaLM ``lm``, cached on it)"""
+    from .lexicon import Lexicon
+    if isinstance(lexicon, Lexicon):
+        return lexicon
+    if isinstance(lexicon, str) and lexicon == 'lm':
+        if lm is None:
+            raise ValueError("lexicon='lm' needs a language model (lm=)")
+        if getattr(lm, '_lexicon', None) is None:
+            lm._lexicon = Lexicon.from_lm(lm)
+        return lm._lexicon
+    if isinstance(lexicon, (str, os.PathLike)):
+        return Lexicon(lexicon)
+    raise TypeError("lexicon must be a lexicon.Lexicon, a path or 'lm', got %s" % type(lexicon).__name__)
+
+
+def _resolve_hotwords(hotwords):
+    """a Lexicon holding the hotword list ``hotwords``: a Lexicon, a path to a word list, or an iterable of single words (an
+    entry with whitespace is a ValueError)"""
+    from .lexicon import Lexicon
+    return hotwords if isinstance(hotwords, Lexicon) else Lexicon(hotwords)
+
+
+def split_search_out(host, n, k, t, with_lm):
+    """the sections of a beam search's ``out`` buffer (include/w2l_hip.h; ``host``: its bytes on the host, anything after them
+    ignored) -> scores float64 [n, k], lengths int32 [n, k], status int32 [n], labels int32 [n, k, t], lm_log10 float32 [n, k]
+    (None unless ``with_lm``)"""
+    scores = host[:8 * n * k].view(np.float64).reshape(n, k)
+    rest = host[8 * n * k:12 * n * k + 4 * n + 4 * n * k * t + (4 * n * k if with_lm else 0)].view(np.int32)
+    lengths = rest[:n * k].reshape(n, k)
+    status = rest[n * k:n * k + n]
+    idx = rest[n * k + n:n * k + n + n * k * t].reshape(n, k, t)
+    lm_log10 = rest[n * k + n + n * k * t:].view(np.float32).reshape(n, k) if with_lm else None
+    return scores, lengths, status, idx, lm_log10
+
+
 def _beam_search_device(probs, labels, blank_index, k, beta, prune, end_char, sizes, log_probs, lm=None, alpha=0.3,
                         offsets=False, lexicon=None, complete_only=True, hotwords=None, hotword_weight=0.0):
     """one launch of w2l_ctc_beam_search for probs [N, T, A] on the current stream; returns the host arrays
-    (scores [N, k], lengths [N, k], labels [N, k, T]).  With ``lm`` (an ngram_lm.ArpaLM) one launch of
-    w2l_ctc_beam_search_lm, and a fourth array: lm_log10 [N, k] float32, the LM total of each result.  With ``offsets`` a
-    launch of w2l_ctc_align follows and one more array: starts int32 [N, T], the first frame of each label of rank 0.  With
-    ``lexicon`` (a lexicon.Lexicon, or 'lm': the vocabulary of ``lm``) the launch is w2l_ctc_beam_search_lex / _lm_lex.  With
-    ``hotwords`` (see _resolve_hotwords) it is w2l_ctc_beam_search_hot, whatever ``lm`` and ``lexicon`` are."""
+    (scores [N, k], lengths [N, k], labels [N, k, T]).  With ``lm`` (an ngram_lm.ArpaLM) a fourth array: lm_log10 [N, k]
+    float32, the LM total of each result.  With ``offsets`` a launch of w2l_ctc_align follows and one more array: starts
+    int32 [N, T], the first frame of each label of rank 0.  ``lexicon`` (a lexicon.Lexicon, or 'lm': the vocabulary of ``lm``)
+    and ``hotwords`` (see _resolve_hotwords) are the entry point's other two tables; a table that is None is passed as NULL."""
     if probs.dim() != 3:
         raise ValueError('expected [N, T, labels] or [T, labels] posteriors, got shape %s' % (tuple(probs.shape),))
     n, t, a = probs.shape
@@ -262,122 +297,47 @@ def _beam_search_device(probs, labels, blank_index, k, beta, prune, end_char, si
         if bool((host < 2).any()) or bool((host > t).any()):
             raise ValueError('sizes must lie in [2, %d], got %s' % (t, host.tolist()))
         sz = host.to(torch.int32).to(dev, non_blocking=True)
+    space_index = -1
     if lm is not None or lexicon is not None or hotwords is not None:
-        return _beam_search_device_lm(x, sz, labels, info, blank_index, end_index, k, alpha, beta, prune, log_probs, lm,
-                                      offsets, lexicon, complete_only, hotwords, hotword_weight)
-    ws_bytes = int(lib.w2l_ctc_beam_search_workspace_bytes(n, t, k))
-    if ws_bytes < 0:
-        raise ValueError('prefix_beam_search_gpu: k=%d with T=%d is out of range' % (k, t))
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-    beam_bytes = 12 * n * k + 4 * n + 4 * n * k * t
-    out = torch.empty(beam_bytes + (align_sections(n, t, t)[5] if offsets else 0), dtype=torch.uint8, device=dev)
-    check(lib.w2l_ctc_beam_search(ptr(x), ptr(sz), n, t, a, info.ctypes.data_as(C.c_void_p), int(blank_index), int(end_index),
-                                  int(k), float(beta), float(prune), int(bool(log_probs)), ptr(ws), ws_bytes, ptr(out),
-                                  stream_ptr()), 'w2l_ctc_beam_search')
-    align_ws = _align_best(x, sz, out, n, t, k, blank_index, log_probs, beam_bytes) if offsets else None
-    host = out.cpu().numpy()                           # the one copy to the host (ordered after the launches on this stream)
-    del align_ws
-    scores = host[:8 * n * k].view(np.float64).reshape(n, k)
-    rest = host[8 * n * k:].view(np.int32)
-    lengths = rest[:n * k].reshape(n, k)
-    status = rest[n * k:n * k + n]
-    idx = rest[n * k + n:n * k + n + n * k * t].reshape(n, k, t)
-    if status.any():
-        raise ValueError('ctc output contains negative numbers (utterances %s)' % np.nonzero(status)[0].tolist())
-    if offsets:
-        return scores, lengths, idx, _align_starts(host, n, t, beam_bytes)
-    return scores, lengths, idx
-
-
-def _resolve_lexicon(lexicon, lm):
-    """a Lexicon from ``lexicon``: a Lexicon, a path, or 'lm' (the vocabulary of the ArpaLM ``lm``, cached on it)"""
-    from .lexicon import Lexicon
-    if isinstance(lexicon, Lexicon):
-        return lexicon
-    if isinstance(lexicon, str) and lexicon == 'lm':
-        if lm is None:
-            raise ValueError("lexicon='lm' needs a language model (lm=)")
-        if getattr(lm, '_lexicon', None) is None:
-            lm._lexicon = Lexicon.from_lm(lm)
-        return lm._lexicon
-    if isinstance(lexicon, (str, os.PathLike)):
-        return Lexicon(lexicon)
-    raise TypeError("lexicon must be a lexicon.Lexicon, a path or 'lm', got %s" % type(lexicon).__name__)
-
-
-def _resolve_hotwords(hotwords):
-    """a Lexicon holding the hotword list ``hotwords``: a Lexicon, a path to a word list, or an iterable of single words (an
-    entry with whitespace is a ValueError)"""
-    from .lexicon import Lexicon
-    return hotwords if isinstance(hotwords, Lexicon) else Lexicon(hotwords)
-
-
-def _beam_search_device_lm(x, sz, labels, info, blank_index, end_index, k, alpha, beta, prune, log_probs, lm, offsets=False,
-                           lexicon=None, complete_only=True, hotwords=None, hotword_weight=0.0):
-    """_beam_search_device's launch of w2l_ctc_beam_search_lm, or with ``lexicon`` of w2l_ctc_beam_search_lm_lex /
-    w2l_ctc_beam_search_lex (``lm`` None), or with ``hotwords`` of w2l_ctc_beam_search_hot (x, sz already on the device)"""
-    from .ngram_lm import ArpaLM
-    if lm is not None and not isinstance(lm, ArpaLM):
-        raise TypeError('lm must be an ngram_lm.ArpaLM, got %s' % type(lm).__name__)
-    odd = [ch for ch in labels if ch.isspace() and ch != ' ']
-    if odd:
-        raise ValueError('prefix_beam_search_gpu: whitespace labels other than a space (%r) cannot be scored by a word LM'
-                         % odd if lm is not None else
-                         'prefix_beam_search_gpu: whitespace labels other than a space (%r) cannot separate the words of a '
-                         'lexicon or of a hotword list' % odd)
-    if hotwords is not None and not math.isfinite(float(hotword_weight)):
-        raise ValueError('prefix_beam_search_gpu: hotword_weight must be finite, got %r' % (hotword_weight,))
-    n, t, a = x.shape
-    dev = x.device
-    info = info | np.array([ch.isspace() << 11 for ch in labels], dtype=np.int32)
-    space_index = labels.index(' ') if ' ' in labels else -1
+        from .ngram_lm import ArpaLM
+        if lm is not None and not isinstance(lm, ArpaLM):
+            raise TypeError('lm must be an ngram_lm.ArpaLM, got %s' % type(lm).__name__)
+        odd = [ch for ch in labels if ch.isspace() and ch != ' ']
+        if odd:
+            raise ValueError('prefix_beam_search_gpu: whitespace labels other than a space (%r) cannot be scored by a word LM'
+                             % odd if lm is not None else
+                             'prefix_beam_search_gpu: whitespace labels other than a space (%r) cannot separate the words of a '
+                             'lexicon or of a hotword list' % odd)
+        if hotwords is not None and not math.isfinite(float(hotword_weight)):
+            raise ValueError('prefix_beam_search_gpu: hotword_weight must be finite, got %r' % (hotword_weight,))
+        info = info | np.array([ch.isspace() << 11 for ch in labels], dtype=np.int32)
+        space_index = labels.index(' ') if ' ' in labels else -1
     tables = lm.to_device(labels, blank_index, dev) if lm is not None else None
     lex = _resolve_lexicon(lexicon, lm).to_device(labels, blank_index, dev) if lexicon is not None else None
     hot = _resolve_hotwords(hotwords).to_device(labels, blank_index, dev) if hotwords is not None else None
-    if hot is not None:
-        ws_bytes = int(lib.w2l_ctc_beam_search_hot_workspace_bytes(n, t, k, lm.order if lm is not None else 0))
-    elif lm is None:
-        ws_bytes = int(lib.w2l_ctc_beam_search_lex_workspace_bytes(n, t, k))
-    elif lex is None:
-        ws_bytes = int(lib.w2l_ctc_beam_search_lm_workspace_bytes(n, t, k, lm.order))
-    else:
-        ws_bytes = int(lib.w2l_ctc_beam_search_lm_lex_workspace_bytes(n, t, k, lm.order))
+    order = lm.order if lm is not None else 0
+    ws_bytes = int(lib.w2l_ctc_beam_search_workspace_bytes(n, t, k, order))
     if ws_bytes < 0:
         raise ValueError('prefix_beam_search_gpu: k=%d with T=%d%s is out of range'
                          % (k, t, '' if lm is None else ' (LM order %d)' % lm.order))
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
     beam_bytes = 12 * n * k + 4 * n + 4 * n * k * t + (4 * n * k if lm is not None else 0)
     out = torch.empty(beam_bytes + (align_sections(n, t, t)[5] if offsets else 0), dtype=torch.uint8, device=dev)
-    head = (ptr(x), ptr(sz), n, t, a, info.ctypes.data_as(C.c_void_p), int(blank_index), int(end_index), space_index, int(k))
-    tail = (ptr(ws), ws_bytes, ptr(out), stream_ptr())
-    if hot is not None:
-        check(lib.w2l_ctc_beam_search_hot(*head, float(alpha), float(beta), float(prune), int(bool(log_probs)),
-                                          tables.desc_ref if tables is not None else None, lm.order if lm is not None else 0,
-                                          lex.desc_ref if lex is not None else None, int(bool(complete_only)), hot.desc_ref,
-                                          float(hotword_weight), *tail), 'w2l_ctc_beam_search_hot')
-    elif lm is None:
-        check(lib.w2l_ctc_beam_search_lex(*head, float(beta), float(prune), int(bool(log_probs)), lex.desc_ref,
-                                          int(bool(complete_only)), *tail), 'w2l_ctc_beam_search_lex')
-    elif lex is None:
-        check(lib.w2l_ctc_beam_search_lm(*head, float(alpha), float(beta), float(prune), int(bool(log_probs)), tables.desc_ref,
-                                         lm.order, *tail), 'w2l_ctc_beam_search_lm')
-    else:
-        check(lib.w2l_ctc_beam_search_lm_lex(*head, float(alpha), float(beta), float(prune), int(bool(log_probs)),
-                                             tables.desc_ref, lm.order, lex.desc_ref, int(bool(complete_only)), *tail),
-              'w2l_ctc_beam_search_lm_lex')
+    check(lib.w2l_ctc_beam_search(ptr(x), ptr(sz), n, t, a, info.ctypes.data_as(C.c_void_p), int(blank_index), int(end_index),
+                                  space_index, int(k), float(alpha), float(beta), float(prune), int(bool(log_probs)),
+                                  tables.desc_ref if tables is not None else None, order,
+                                  lex.desc_ref if lex is not None else None, int(bool(complete_only)),
+                                  hot.desc_ref if hot is not None else None, float(hotword_weight), ptr(ws), ws_bytes, ptr(out),
+                                  stream_ptr()), 'w2l_ctc_beam_search')
     align_ws = _align_best(x, sz, out, n, t, k, blank_index, log_probs, beam_bytes) if offsets else None
-    host = out.cpu().numpy()                           # the one copy to the host
+    host = out.cpu().numpy()                           # the one copy to the host (ordered after the launches on this stream)
     del align_ws
-    scores = host[:8 * n * k].view(np.float64).reshape(n, k)
-    rest = host[8 * n * k:].view(np.int32)
-    lengths = rest[:n * k].reshape(n, k)
-    status = rest[n * k:n * k + n]
-    idx = rest[n * k + n:n * k + n + n * k * t].reshape(n, k, t)
+    scores, lengths, status, idx, lm_log10 = split_search_out(host, n, k, t, lm is not None)
     if status.any():
         raise ValueError('ctc output contains negative numbers (utterances %s)' % np.nonzero(status)[0].tolist())
     got = (scores, lengths, idx)
     if lm is not None:
-        got += (rest[n * k + n + n * k * t:n * k + n + n * k * t + n * k].view(np.float32).reshape(n, k),)
+        got += (lm_log10,)
     if offsets:
         got += (_align_starts(host, n, t, beam_bytes),)
     return got

@@ -1,5 +1,7 @@
 // Decoding an ASG model beyond Viterbi (gfx950): the prefix beam search over emissions plus learned transitions, with an
-// optional word n-gram model (w2l_asg_beam_search, w2l_asg_beam_search_lm; host restatement: asg_beam.asg_prefix_beam_search),
+// optional word n-gram model (w2l_asg_beam_search, which launches asg_beam_search_kernel<lm != NULL>; host restatement:
+// asg_beam.asg_prefix_beam_search; what it shares with the CTC search -- workspace, output stage, argument
+// checks -- is beam_core.h's),
 // and the forced alignment of a given label sequence (w2l_asg_align; host: asg_beam.asg_viterbi_align_host).
 //
 // ---- the search.  ASG has no blank: a hypothesis is an ENCODED label sequence e_1 .. e_m (no two neighbours equal, the
@@ -21,10 +23,7 @@
 //
 // ---- the alignment: Viterbi form of Z_tgt over the S states of the encoded target, fp32, in the structure of
 // ctc_align_kernel (one lane per state, columns through LDS, moves packed over time, back-trace by wave 0).
-#include "common.h"
-#include "beam_lm.h"
-#include "../../include/w2l_hip.h"
-#include <math.h>
+#include "beam_core.h"
 
 namespace {
 
@@ -37,13 +36,6 @@ struct AsgLabelInfo {
     // bits 0-7: canonical (first) index of the label's character; 9: a word character (\w); 10: a word separator ([\s|>])
     int32_t v[AB_AMAX];
 };
-
-__device__ __forceinline__ double lae(double a, double b) {          // log(exp(a) + exp(b))
-    if (a == -INFINITY) return b;
-    if (b == -INFINITY) return a;
-    const double m = a > b ? a : b, d = a > b ? b - a : a - b;
-    return m + log1p(exp(d));
-}
 
 struct AsgBeam {                      // one frame's beam, slot-indexed (chr: last label, dec: last decoded label, -1 none)
     int node[AB_KMAX], parent[AB_KMAX], chr[AB_KMAX], dec[AB_KMAX], words[AB_KMAX], len[AB_KMAX], ps[AB_KMAX],
@@ -77,17 +69,14 @@ __global__ __launch_bounds__(AB_THREADS) void asg_beam_search_kernel(
     uint8_t* mem = (uint8_t*)(gl + A * A);                 // [k][A] 1 + slot of the member that is E(i, c)
     uint8_t* redir = mem + k * A;                          // [k][A] 1 + previous slot whose S entry is E(i, c)
 
-    const int64_t nodes = (int64_t)k * T + 1;
-    char* wsn = ws + (int64_t)n * ws_per_utt;
-    int32_t* nd_parent = (int32_t*)wsn;
-    int32_t* nd_chr = nd_parent + nodes;
-    int32_t* nd_info = nd_chr + nodes;
-    uint64_t* hkeys = (uint64_t*)(wsn + (nodes * 12 + 15) / 16 * 16);
-    int32_t* hvals = (int32_t*)(hkeys + hash_cap);
-    NodeLM* nd_lm = (NodeLM*)(wsn + lmargs.state_off);    // LM only
+    const TrieWs w = carve_ws<3>(ws, n, ws_per_utt, T, k, hash_cap, lmargs.state_off);
+    int32_t* nd_parent = w.nd_parent;
+    int32_t* nd_chr = w.nd_chr;
+    int32_t* nd_info = w.nd_info;
+    NodeLM* nd_lm = w.nd_lm;                               // LM only
 
     bool bad_g = false;
-    for (int i = tid; i < hash_cap; i += AB_THREADS) hkeys[i] = BS_EMPTY;
+    for (int i = tid; i < hash_cap; i += AB_THREADS) w.hkeys[i] = BS_EMPTY;
     for (int i = tid; i < 2 * k * A; i += AB_THREADS) mem[i] = 0;         // mem and redir
     for (int i = tid; i < A * A; i += AB_THREADS) {
         const float v = trans[i];
@@ -103,12 +92,7 @@ __global__ __launch_bounds__(AB_THREADS) void asg_beam_search_kernel(
         b0.node[0] = 0; b0.parent[0] = -1; b0.chr[0] = -1; b0.dec[0] = -1; b0.words[0] = 0; b0.len[0] = 0;
         b0.prevslot[0] = -1; b0.mass[0] = 0.0; b0.score[0] = 0.0;
         if constexpr (LM) {
-            NodeLM r;                                      // context <s>
-            for (int i = 0; i < LM_MAXORDER - 1; ++i) { r.ctx[i] = 0; r.bo[i] = 0.f; }
-            r.m = min(1, lmargs.order - 1);
-            if (r.m > 0) { r.ctx[0] = 1; r.bo[0] = lmargs.bo[1]; }
-            r.done = 0.f; r.trie = 0; r.nonspace = 0; r.total = 0.f; r.pad_ = 0;
-            nd_lm[0] = r;
+            nd_lm[0] = lm_root(lmargs);
             lm_w[0][0] = 0.0;
             lm_on[0][0] = 0;
         }
@@ -283,13 +267,13 @@ __global__ __launch_bounds__(AB_THREADS) void asg_beam_search_kernel(
                 int node = -1, dec = -1, words = 0;
                 while (node < 0) {                         // probe by claiming: one round trip per slot
                     const uint64_t cur_key =
-                        atomicCAS((unsigned long long*)&hkeys[h], (unsigned long long)BS_EMPTY, (unsigned long long)key);
+                        atomicCAS((unsigned long long*)&w.hkeys[h], (unsigned long long)BS_EMPTY, (unsigned long long)key);
                     if (cur_key == BS_EMPTY) {             // a new string: its node id is reserved by (frame, rank)
                         node = 1 + t * k + r;
                         const int pd = B.dec[i];
                         dec = c == rep ? pd : c;
                         words = B.words[i] + (dec >= 0 && pd >= 0 && (lab[dec] & 0x400) && (lab[pd] & 0x200));
-                        hvals[h] = node;
+                        w.hvals[h] = node;
                         nd_parent[node] = par;
                         nd_chr[node] = c;
                         nd_info[node] = pack_info(dec, words);
@@ -300,7 +284,7 @@ __global__ __launch_bounds__(AB_THREADS) void asg_beam_search_kernel(
                             lm_on[cur ^ 1][r] = ns.nonspace;
                         }
                     } else if (cur_key == key) {           // interned in an earlier frame
-                        node = hvals[h];
+                        node = w.hvals[h];
                         const int pk = nd_info[node];
                         dec = (pk & 0xff) - 1;
                         words = pk >> 8;
@@ -328,25 +312,7 @@ __global__ __launch_bounds__(AB_THREADS) void asg_beam_search_kernel(
     // ---------------------------------------------------------------- output: backtrack the final beam
     const int m = s_m[cur];
     const AsgBeam& B = beams[cur];
-    if (tid < k) {
-        const int64_t o = (int64_t)n * k + tid;
-        if (tid < m) {
-            const int len = B.len[tid];
-            out_score[o] = B.score[tid];
-            out_len[o] = len;
-            if constexpr (LM) out_lm[o] = nd_lm[B.node[tid]].total;
-            int32_t* lab_out = out_labels + o * T;
-            int node = B.node[tid];
-            for (int p = len - 1; p >= 0; --p) {
-                lab_out[p] = nd_chr[node];
-                node = nd_parent[node];
-            }
-        } else {
-            out_score[o] = -INFINITY;
-            out_len[o] = -1;
-            if constexpr (LM) out_lm[o] = 0.f;
-        }
-    }
+    if (tid < k) write_result<LM>(B, tid < m ? tid : -1, (int64_t)n * k + tid, T, w, out_score, out_len, out_labels, out_lm);
     if (tid == 0) out_status[n] = s_bad;
 }
 
@@ -355,128 +321,51 @@ int64_t lds_bytes(int k, int A) {
     return nE * (2 * 8 + 8 + 4) + (int64_t)A * A * 4 + 2 * (int64_t)k * A;
 }
 
-int hash_capacity(int T, int k) {
-    int64_t need = 2 * ((int64_t)k * T + 1), cap = 1;
-    while (cap < need) cap <<= 1;
-    return (int)cap;
-}
-
-int64_t ws_stride(int T, int k) {
-    const int64_t nodes = (int64_t)k * T + 1;
-    const int64_t bytes = (nodes * 12 + 15) / 16 * 16 + (int64_t)hash_capacity(T, k) * 12;
-    return (bytes + 255) / 256 * 256;
-}
-
-int64_t lm_state_offset(int T, int k) { return ws_stride(T, k); }
-
-int64_t lm_ws_stride(int T, int k) {
-    const int64_t bytes = lm_state_offset(T, k) + ((int64_t)k * T + 1) * (int64_t)sizeof(NodeLM);
-    return (bytes + 255) / 256 * 256;
-}
-
 bool search_range(int N, int T, int A, int k) {
     return N > 0 && T > 0 && T < (1 << 24) && A >= 1 && A <= AB_AMAX && k >= 1 && k <= AB_KMAX && (int64_t)k * T < (1 << 29);
 }
 
-bool pow2_cap(int64_t cap) { return cap >= 16 && cap <= (1ll << 31) && (cap & (cap - 1)) == 0; }
+}  // namespace
 
-// the checks and the launch shared by both entry points (ws_per_utt: the workspace stride of one utterance)
-template <bool LM>
-int launch_search(const char* name, const float* x, const float* transitions, const int32_t* sizes, int N, int T, int A,
-                  const int32_t* label_info_host, int repeat_index, int k, double beta, double prune, void* workspace,
-                  int64_t workspace_bytes, int64_t need, int64_t ws_per_utt, void* out, const LmArgs& lm, void* stream) {
+extern "C" int64_t w2l_asg_beam_search_workspace_bytes(int N, int T, int A, int k, int order) {
+    return search_range(N, T, A, k) ? search_ws_bytes(N, T, k, order, 3) : -1;
+}
+
+extern "C" int w2l_asg_beam_search(const float* x, const float* transitions, const int32_t* sizes, int N, int T, int A,
+                                   const int32_t* label_info_host, int repeat_index, int space_index, int k, double alpha,
+                                   double beta, double prune, const w2l_ngram_lm_t* lm, int order, void* workspace,
+                                   int64_t workspace_bytes, void* out, void* stream) {
+    const char* name = "asg_beam_search";
+    // every check of the arguments comes before the first HIP call (lds_args)
     W2L_CHECK_ARG(x && transitions && label_info_host && workspace && out && N > 0 && T > 0, "%s: bad arguments", name);
     W2L_CHECK_ARG(A >= 1 && A <= AB_AMAX, "%s: %d labels, supported 1..%d", name, A, AB_AMAX);
     W2L_CHECK_ARG(k >= 1 && k <= AB_KMAX, "%s: beam width k=%d, supported 1..%d", name, k, AB_KMAX);
     W2L_CHECK_ARG(repeat_index >= 0 && repeat_index < A, "%s: repeat_index %d outside %d labels", name, repeat_index, A);
     W2L_CHECK_ARG((int64_t)k * T < (1 << 29) && T < (1 << 24), "%s: k*T = %lld too large", name, (long long)k * T);
+    AsgLabelInfo info;
+    if (int rc = label_info_args(name, label_info_host, A, info.v, AB_AMAX)) return rc;
+    LmArgs a{};
+    if (lm) {
+        if (int rc = space_args(name, label_info_host, A, space_index)) return rc;
+        if (int rc = lm_args(name, space_index, alpha, lm, order, T, k, 3, &a)) return rc;
+    }
+    const int64_t need = w2l_asg_beam_search_workspace_bytes(N, T, A, k, lm ? order : 0);
     W2L_CHECK_ARG(need > 0 && workspace_bytes >= need, "%s: workspace of %lld bytes, %lld needed", name,
                   (long long)workspace_bytes, (long long)need);
-    const void* kern = (const void*)asg_beam_search_kernel<LM>;
-    hipFuncAttributes fa;
-    W2L_CHECK_HIP(hipFuncGetAttributes(&fa, kern));
+    const void* kern = lm ? (const void*)asg_beam_search_kernel<true> : (const void*)asg_beam_search_kernel<false>;
     const int64_t lds = lds_bytes(k, A);
-    W2L_CHECK_ARG(lds + (int64_t)fa.sharedSizeBytes <= 160 * 1024, "%s: k=%d with %d labels needs %lld bytes of LDS, the limit is %d",
-                  name, k, A, (long long)(lds + fa.sharedSizeBytes), 160 * 1024);
-    AsgLabelInfo info;
-    for (int i = 0; i < AB_AMAX; ++i) info.v[i] = 0;
-    for (int i = 0; i < A; ++i) {
-        const int canon = label_info_host[i] & 0xff;
-        W2L_CHECK_ARG(canon <= i && (label_info_host[canon] & 0xff) == canon, "%s: label %d: bad canonical index %d", name, i,
-                      canon);
-        info.v[i] = label_info_host[i];
-    }
-    if (lds + (int64_t)fa.sharedSizeBytes > 64 * 1024)    // (the dynamic share is what the kernel's static state leaves of 160 KiB)
-        W2L_CHECK_HIP(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - (int)fa.sharedSizeBytes));
-    double* out_score = (double*)out;
-    int32_t* out_len = (int32_t*)(out_score + (int64_t)N * k);
-    int32_t* out_status = out_len + (int64_t)N * k;
-    int32_t* out_labels = out_status + N;
-    float* out_lm = LM ? (float*)(out_labels + (int64_t)N * k * T) : nullptr;
-    hipLaunchKernelGGL(asg_beam_search_kernel<LM>, dim3(N), dim3(AB_THREADS), (size_t)lds, (hipStream_t)stream, x, transitions,
-                       sizes, T, A, info, repeat_index, k, beta, prune, (char*)workspace, ws_per_utt, hash_capacity(T, k),
-                       out_score, out_len, out_status, out_labels, lm, out_lm);
+    if (int rc = lds_args(name, kern, lds, k, A)) return rc;
+    const OutSections o = out_sections(out, N, T, k, lm != nullptr);
+    const int64_t ws_per_utt = lm ? lm_ws_stride(T, k, 3) : ws_stride(T, k, 3);
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(N), dim3(AB_THREADS), (size_t)lds, (hipStream_t)stream, x, transitions, sizes, T, A, info,
+                           repeat_index, k, beta, prune, (char*)workspace, ws_per_utt, hash_capacity(T, k), o.score, o.len,
+                           o.status, o.labels, a, o.lm);
+    };
+    if (lm) launch(asg_beam_search_kernel<true>);
+    else launch(asg_beam_search_kernel<false>);
     W2L_CHECK_LAUNCH();
     return 0;
-}
-
-}  // namespace
-
-extern "C" int64_t w2l_asg_beam_search_workspace_bytes(int N, int T, int A, int k) {
-    if (!search_range(N, T, A, k)) return -1;
-    return (int64_t)N * ws_stride(T, k);
-}
-
-extern "C" int w2l_asg_beam_search(const float* x, const float* transitions, const int32_t* sizes, int N, int T, int A,
-                                   const int32_t* label_info_host, int repeat_index, int k, double beta, double prune,
-                                   void* workspace, int64_t workspace_bytes, void* out, void* stream) {
-    return launch_search<false>("asg_beam_search", x, transitions, sizes, N, T, A, label_info_host, repeat_index, k, beta, prune,
-                                workspace, workspace_bytes, w2l_asg_beam_search_workspace_bytes(N, T, A, k), ws_stride(T, k), out,
-                                LmArgs{}, stream);
-}
-
-extern "C" int64_t w2l_asg_beam_search_lm_workspace_bytes(int N, int T, int A, int k, int order) {
-    if (!search_range(N, T, A, k) || order < 1 || order > LM_MAXORDER) return -1;
-    return (int64_t)N * lm_ws_stride(T, k);
-}
-
-extern "C" int w2l_asg_beam_search_lm(const float* x, const float* transitions, const int32_t* sizes, int N, int T, int A,
-                                      const int32_t* label_info_host, int repeat_index, int space_index, int k, double alpha,
-                                      double beta, double prune, const w2l_ngram_lm_t* lm, int order, void* workspace,
-                                      int64_t workspace_bytes, void* out, void* stream) {
-    W2L_CHECK_ARG(lm && label_info_host && A >= 1 && A <= AB_AMAX, "asg_beam_search_lm: bad arguments");
-    W2L_CHECK_ARG(order >= 1 && order <= LM_MAXORDER, "asg_beam_search_lm: order %d, supported 1..%d", order, LM_MAXORDER);
-    W2L_CHECK_ARG(space_index >= -1 && space_index < A && (space_index < 0 || (label_info_host[space_index] & 0xff) == space_index),
-                  "asg_beam_search_lm: space index %d is not the first index of a label", space_index);
-    for (int i = 0; i < A; ++i)
-        W2L_CHECK_ARG(!(label_info_host[i] & 0x800) || (label_info_host[i] & 0xff) == space_index,
-                      "asg_beam_search_lm: label %d is whitespace other than ' '", i);
-    W2L_CHECK_ARG(lm->prob && lm->bo && lm->ngram_keys && lm->ngram_vals && lm->trie_keys && lm->trie_vals && lm->trie_word,
-                  "asg_beam_search_lm: a table pointer is NULL");
-    W2L_CHECK_ARG(lm->n_words >= 3 && lm->n_entries >= lm->n_words && lm->n_entries < (1 << 30) && lm->n_trie_nodes >= 1,
-                  "asg_beam_search_lm: %d entries, %d words, %d trie nodes (3 <= words <= entries < 2^30)", lm->n_entries,
-                  lm->n_words, lm->n_trie_nodes);
-    W2L_CHECK_ARG(pow2_cap(lm->ngram_cap) && lm->ngram_cap >= 2 * (int64_t)(lm->n_entries - lm->n_words) && pow2_cap(lm->trie_cap)
-                      && lm->trie_cap >= 2 * (int64_t)(lm->n_trie_nodes - 1),
-                  "asg_beam_search_lm: table capacities %lld / %lld (powers of two in [16, 2^31], at most half full)",
-                  (long long)lm->ngram_cap, (long long)lm->trie_cap);
-    LmArgs a;
-    a.prob = lm->prob;
-    a.bo = lm->bo;
-    a.nkeys = lm->ngram_keys;
-    a.nvals = lm->ngram_vals;
-    a.tkeys = lm->trie_keys;
-    a.tvals = lm->trie_vals;
-    a.tword = lm->trie_word;
-    a.nmask = (uint32_t)(lm->ngram_cap - 1);
-    a.tmask = (uint32_t)(lm->trie_cap - 1);
-    a.order = order;
-    a.space = space_index;
-    a.alpha_ln10 = alpha * 2.302585092994045684;
-    a.state_off = lm_state_offset(T, k);
-    return launch_search<true>("asg_beam_search_lm", x, transitions, sizes, N, T, A, label_info_host, repeat_index, k, beta,
-                               prune, workspace, workspace_bytes, w2l_asg_beam_search_lm_workspace_bytes(N, T, A, k, order),
-                               lm_ws_stride(T, k), out, a, stream);
 }
 
 // ============================================================================================================ alignment

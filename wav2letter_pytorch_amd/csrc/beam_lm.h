@@ -51,12 +51,16 @@ __device__ __forceinline__ int tab_find(const uint64_t* keys, const int32_t* val
 }
 
 // ------------------------------------------------------------------------------------------------------------- lexicon
-struct LexArgs {                              // w2l_lexicon_t on the device (lexicon.Lexicon), plus the search's parameters
+struct TrieArgs {                             // a spelling trie (w2l_lexicon_t) on the device, and the word separator
     const uint64_t* tkeys;
     const int32_t* tvals;
     const int32_t* tword;
     uint32_t tmask;
-    int space, complete_only;
+    int space;
+};
+
+struct LexArgs : TrieArgs {                   // the lexicon (lexicon.Lexicon), plus the search's parameter
+    int complete_only;
 };
 
 // the lexicon's trie node of (partial word at node `trie`) + canonical label c; < 0: the extension leaves the word list.
@@ -69,12 +73,7 @@ __device__ __forceinline__ int lex_step(const LexArgs& X, int trie, int c, int e
 __device__ __forceinline__ bool lex_complete(const LexArgs& X, int trie) { return trie == 0 || X.tword[trie] >= 0; }
 
 // ------------------------------------------------------------------------------------------------------------ hotwords
-struct HotArgs {                              // the hotword list's spelling trie (a w2l_lexicon_t) and the bonus per character
-    const uint64_t* tkeys;
-    const int32_t* tvals;
-    const int32_t* tword;
-    uint32_t tmask;
-    int space;
+struct HotArgs : TrieArgs {                   // the hotword list's spelling trie and the bonus per character
     double gamma;
 };
 

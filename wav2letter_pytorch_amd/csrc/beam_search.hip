@@ -20,25 +20,26 @@
 //       the k first become the next beam, new members are interned
 // LDS holds two frames of entry masses plus the live-candidate list (see lds_bytes); limits in w2l_hip.h.
 //
-// With a language model (LM = true, w2l_ctc_beam_search_lm): every trie node also carries an LM state (NodeLM, after the
+// One entry point, w2l_ctc_beam_search, launches ctc_beam_search_kernel<lm != NULL, lexicon != NULL, hotwords != NULL>; what
+// the search shares with the ASG one (asg_beam.hip) -- workspace, output stage, argument checks -- is
+// beam_core.h's.
+//
+// With a language model (LM = true): every trie node also carries an LM state (NodeLM, after the
 // intern table in the workspace), computed once by the P3 thread that interns the node from its parent's state and its
 // character.  P2 adds a member's LM weight to the one contribution the host weights (parent_part, a word-closing label).
 //
-// With a lexicon (LEX = true, w2l_ctc_beam_search_lex / _lm_lex): every beam slot carries the lexicon's spelling-trie node of
+// With a lexicon (LEX = true): every beam slot carries the lexicon's spelling-trie node of
 // its partial word (lex_trie, LDS).  The P2 thread of an extension entry that is not a beam member probes the trie once
 // (lex_step); an extension that leaves the word list gets no mass, exactly like a pruned label.  The node of a new member is a
 // function of its parent slot's node and its character, so P3 finds it with the same probe and nothing is kept per interned
 // prefix.  The output stage keeps the members whose partial word is empty or a whole word (complete_only).
 //
-// With hotwords (HOT = true, w2l_ctc_beam_search_hot; any LM / LEX combination): every beam slot carries the hotword-trie walk
+// With hotwords (HOT = true; any LM / LEX combination): every beam slot carries the hotword-trie walk
 // of its string (hot_st, LDS: node of the partial word, its depth, the characters credited by closed hotwords).  The rank key
 // gains gamma * h, h = hot_chars(state); masses are untouched.  The state of an extension is a function of its parent slot's
 // state and its character (hot_step: one probe), computed by the P2 thread of a non-member extension for the key and again by
 // the P3 thread that places a new member, as lex_trie is.
-#include "common.h"
-#include "beam_lm.h"
-#include "../../include/w2l_hip.h"
-#include <math.h>
+#include "beam_core.h"
 
 namespace {
 
@@ -52,13 +53,6 @@ struct LabelInfo {
     // 10: a word separator ([\s|>])
     int32_t v[BS_AMAX];
 };
-
-__device__ __forceinline__ double lae(double a, double b) {          // log(exp(a) + exp(b))
-    if (a == -INFINITY) return b;
-    if (b == -INFINITY) return a;
-    const double m = a > b ? a : b, d = a > b ? b - a : a - b;
-    return m + log1p(exp(d));
-}
 
 // host loop position of an operation: beam slot i, label l (-1: the closed-hypothesis assignment), op within the label
 __device__ __forceinline__ int loop_pos(int i, int A, int l, int op) { return ((i * (A + 1) + l + 1) << 2) | op; }
@@ -100,14 +94,12 @@ __global__ __launch_bounds__(BS_THREADS) void ctc_beam_search_kernel(
     int* mem = lent + nE;                                  // [k][A] stamp | slot of the member that is E(i, c)
     int* redir = mem + k * A;                              // [k][A] stamp | previous slot whose S entry is E(i, c)
 
-    char* wsn = ws + (int64_t)n * ws_per_utt;
-    int32_t* nd_parent = (int32_t*)wsn;
-    int32_t* nd_chr = nd_parent + ((int64_t)k * T + 1);
-    uint64_t* hkeys = (uint64_t*)(wsn + (((int64_t)k * T + 1) * 8 + 15) / 16 * 16);
-    int32_t* hvals = (int32_t*)(hkeys + hash_cap);
-    NodeLM* nd_lm = (NodeLM*)(wsn + lmargs.state_off);    // LM only
+    const TrieWs w = carve_ws<2>(ws, n, ws_per_utt, T, k, hash_cap, lmargs.state_off);
+    int32_t* nd_parent = w.nd_parent;
+    int32_t* nd_chr = w.nd_chr;
+    NodeLM* nd_lm = w.nd_lm;                               // LM only
 
-    for (int i = tid; i < hash_cap; i += BS_THREADS) hkeys[i] = BS_EMPTY;
+    for (int i = tid; i < hash_cap; i += BS_THREADS) w.hkeys[i] = BS_EMPTY;
     for (int i = tid; i < 2 * k * A; i += BS_THREADS) mem[i] = 0;         // mem and redir: stamp 0 never matches
     for (int i = tid; i < A; i += BS_THREADS) { lab[i] = info.v[i]; act[i] = 0; }
     if (tid == 0) {
@@ -117,12 +109,7 @@ __global__ __launch_bounds__(BS_THREADS) void ctc_beam_search_kernel(
         b0.node[0] = 0; b0.parent[0] = -1; b0.chr[0] = -1; b0.words[0] = 0; b0.len[0] = 0; b0.prevslot[0] = -1;
         b0.pb[0] = 0.0; b0.pnb[0] = -INFINITY; b0.score[0] = 0.0;
         if constexpr (LM) {
-            NodeLM r;                                      // the root: context <s>
-            for (int i = 0; i < LM_MAXORDER - 1; ++i) { r.ctx[i] = 0; r.bo[i] = 0.f; }
-            r.m = min(1, lmargs.order - 1);
-            if (r.m > 0) { r.ctx[0] = 1; r.bo[0] = lmargs.bo[1]; }
-            r.done = 0.f; r.trie = 0; r.nonspace = 0; r.total = 0.f; r.pad_ = 0;
-            nd_lm[0] = r;
+            nd_lm[0] = lm_root(lmargs);
             lm_w[0][0] = 0.0;
             lm_on[0][0] = 0;
         }
@@ -347,10 +334,10 @@ __global__ __launch_bounds__(BS_THREADS) void ctc_beam_search_kernel(
                 int node = -1;
                 while (node < 0) {                         // probe by claiming: one round trip per slot
                     const uint64_t cur_key =
-                        atomicCAS((unsigned long long*)&hkeys[h], (unsigned long long)BS_EMPTY, (unsigned long long)key);
+                        atomicCAS((unsigned long long*)&w.hkeys[h], (unsigned long long)BS_EMPTY, (unsigned long long)key);
                     if (cur_key == BS_EMPTY) {             // a new string: its node id is reserved by (frame, rank)
                         node = 1 + t * k + r;
-                        hvals[h] = node;
+                        w.hvals[h] = node;
                         nd_parent[node] = par;
                         nd_chr[node] = c;
                         if constexpr (LM) {
@@ -360,7 +347,7 @@ __global__ __launch_bounds__(BS_THREADS) void ctc_beam_search_kernel(
                             lm_on[cur ^ 1][r] = ns.nonspace;
                         }
                     } else if (cur_key == key) {           // interned in an earlier frame
-                        node = hvals[h];
+                        node = w.hvals[h];
                         if constexpr (LM) {
                             lm_w[cur ^ 1][r] = lmargs.alpha_ln10 * (double)nd_lm[node].total;
                             lm_on[cur ^ 1][r] = nd_lm[node].nonspace;
@@ -399,25 +386,8 @@ __global__ __launch_bounds__(BS_THREADS) void ctc_beam_search_kernel(
             }
         }
     }
-    if (tid < k) {
-        const int64_t o = (int64_t)n * k + tid;
-        if (tid < mout) {
-            const int len = B.len[src];
-            out_score[o] = B.score[src];
-            out_len[o] = len;
-            if constexpr (LM) out_lm[o] = nd_lm[B.node[src]].total;
-            int32_t* lab_out = out_labels + o * T;
-            int node = B.node[src];
-            for (int p = len - 1; p >= 0; --p) {
-                lab_out[p] = nd_chr[node];
-                node = nd_parent[node];
-            }
-        } else {
-            out_score[o] = -INFINITY;
-            out_len[o] = -1;
-            if constexpr (LM) out_lm[o] = 0.f;
-        }
-    }
+    if (tid < k)
+        write_result<LM>(B, tid < mout ? src : -1, (int64_t)n * k + tid, T, w, out_score, out_len, out_labels, out_lm);
     if (tid == 0) out_status[n] = s_bad;
 }
 
@@ -426,66 +396,31 @@ int64_t lds_bytes(int k, int A) {
     return nE * (4 * 8 + 8 + 4 + 4) + 2 * (int64_t)k * A * 4;
 }
 
-int hash_capacity(int T, int k) {
-    int64_t need = 2 * ((int64_t)k * T + 1), cap = 1;
-    while (cap < need) cap <<= 1;
-    return (int)cap;
-}
-
-int64_t ws_stride(int T, int k) {
-    const int64_t nodes = (int64_t)k * T + 1;
-    const int64_t bytes = (nodes * 8 + 15) / 16 * 16 + (int64_t)hash_capacity(T, k) * 12;
-    return (bytes + 255) / 256 * 256;
-}
-
-}  // namespace
-
-extern "C" int64_t w2l_ctc_beam_search_workspace_bytes(int N, int T, int k) {
-    if (N <= 0 || T <= 0 || k <= 0 || (int64_t)k * T >= (1 << 29)) return -1;
-    return (int64_t)N * ws_stride(T, k);
-}
-
-namespace {
-
-// the checks and the launch shared by the entry points (ws_per_utt: the workspace stride of one utterance)
-template <bool LM, bool LEX = false, bool HOT = false>
-int launch_search(const char* name, const float* probs, const int32_t* sizes, int N, int T, int A, const int32_t* label_info_host,
-                  int blank, int end_index, int k, double beta, double prune, int log_probs, void* workspace,
-                  int64_t workspace_bytes, int64_t need, int64_t ws_per_utt, void* out, const LmArgs& lm, void* stream,
-                  const LexArgs& lex = LexArgs{}, const HotArgs& hot = HotArgs{}) {
-    W2L_CHECK_ARG(probs && label_info_host && workspace && out && N > 0 && T > 0, "%s: bad arguments", name);
-    W2L_CHECK_ARG(A >= 1 && A <= BS_AMAX, "%s: %d labels, supported 1..%d", name, A, BS_AMAX);
-    W2L_CHECK_ARG(k >= 1 && k <= BS_KMAX, "%s: beam width k=%d, supported 1..%d", name, k, BS_KMAX);
-    W2L_CHECK_ARG(blank >= 0 && blank < A && end_index >= -1 && end_index < A, "%s: blank %d / end %d outside %d labels",
-                  name, blank, end_index, A);
-    W2L_CHECK_ARG((int64_t)k * T < (1 << 29) && T < (1 << 24), "%s: k*T = %lld too large", name, (long long)k * T);
-    W2L_CHECK_ARG(need > 0 && workspace_bytes >= need, "%s: workspace of %lld bytes, %lld needed", name,
-                  (long long)workspace_bytes, (long long)need);
-    const void* kern = (const void*)ctc_beam_search_kernel<LM, LEX, HOT>;
-    hipFuncAttributes fa;
-    W2L_CHECK_HIP(hipFuncGetAttributes(&fa, kern));
-    const int64_t lds = lds_bytes(k, A);
-    W2L_CHECK_ARG(lds + (int64_t)fa.sharedSizeBytes <= 160 * 1024,
-                  "%s: k=%d with %d labels needs %lld bytes of LDS, the limit is %d (k*(A+1) <= ~3200)", name, k, A,
-                  (long long)(lds + fa.sharedSizeBytes), 160 * 1024);
+// what the eight instantiations are launched with: the arguments checked, the tables in their device form
+struct CtcSearch {
+    const float* probs;
+    const int32_t* sizes;
+    int N, T, A, blank, end_index, k, log_probs;
+    double beta, prune;
     LabelInfo info;
-    for (int i = 0; i < BS_AMAX; ++i) info.v[i] = 0;
-    for (int i = 0; i < A; ++i) {
-        const int canon = label_info_host[i] & 0xff;
-        W2L_CHECK_ARG(canon <= i && (label_info_host[canon] & 0xff) == canon, "%s: label %d: bad canonical index %d", name,
-                      i, canon);
-        info.v[i] = label_info_host[i];
-    }
-    if (lds > 64 * 1024)    // (the dynamic share is what the kernel's static state leaves of 160 KiB)
-        W2L_CHECK_HIP(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - (int)fa.sharedSizeBytes));
-    double* out_score = (double*)out;
-    int32_t* out_len = (int32_t*)(out_score + (int64_t)N * k);
-    int32_t* out_status = out_len + (int64_t)N * k;
-    int32_t* out_labels = out_status + N;
-    float* out_lm = LM ? (float*)(out_labels + (int64_t)N * k * T) : nullptr;
-    hipLaunchKernelGGL((ctc_beam_search_kernel<LM, LEX, HOT>), dim3(N), dim3(BS_THREADS), (size_t)lds, (hipStream_t)stream, probs,
-                       sizes, T, A, info, blank, end_index, k, beta, prune, log_probs, (char*)workspace, ws_per_utt,
-                       hash_capacity(T, k), out_score, out_len, out_status, out_labels, lm, out_lm, lex, hot);
+    void* workspace;
+    int64_t ws_per_utt;
+    void* out;
+    void* stream;
+    LmArgs lm;
+    LexArgs lex;
+    HotArgs hot;
+};
+
+template <bool LM, bool LEX, bool HOT>
+int launch_search(const char* name, const CtcSearch& s) {
+    const int64_t lds = lds_bytes(s.k, s.A);
+    if (int rc = lds_args(name, (const void*)ctc_beam_search_kernel<LM, LEX, HOT>, lds, s.k, s.A)) return rc;
+    const OutSections o = out_sections(s.out, s.N, s.T, s.k, LM);
+    hipLaunchKernelGGL((ctc_beam_search_kernel<LM, LEX, HOT>), dim3(s.N), dim3(BS_THREADS), (size_t)lds, (hipStream_t)s.stream,
+                       s.probs, s.sizes, s.T, s.A, s.info, s.blank, s.end_index, s.k, s.beta, s.prune, s.log_probs,
+                       (char*)s.workspace, s.ws_per_utt, hash_capacity(s.T, s.k), o.score, o.len, o.status, o.labels, s.lm, o.lm,
+                       s.lex, s.hot);
     W2L_CHECK_LAUNCH();
     return 0;
 }
@@ -506,24 +441,7 @@ __global__ void ngram_insert_kernel(const uint64_t* __restrict__ keys, const int
     }
 }
 
-int64_t lm_state_offset(int T, int k) { return ws_stride(T, k); }
-
-int64_t lm_ws_stride(int T, int k) {
-    const int64_t bytes = lm_state_offset(T, k) + ((int64_t)k * T + 1) * (int64_t)sizeof(NodeLM);
-    return (bytes + 255) / 256 * 256;
-}
-
-bool pow2_cap(int64_t cap) { return cap >= 16 && cap <= (1ll << 31) && (cap & (cap - 1)) == 0; }
-
 }  // namespace
-
-extern "C" int w2l_ctc_beam_search(const float* probs, const int32_t* sizes, int N, int T, int A,
-                                   const int32_t* label_info_host, int blank, int end_index, int k, double beta, double prune,
-                                   int log_probs, void* workspace, int64_t workspace_bytes, void* out, void* stream) {
-    return launch_search<false>("ctc_beam_search", probs, sizes, N, T, A, label_info_host, blank, end_index, k, beta, prune,
-                                log_probs, workspace, workspace_bytes, w2l_ctc_beam_search_workspace_bytes(N, T, k),
-                                ws_stride(T, k), out, LmArgs{}, stream);
-}
 
 extern "C" int w2l_ngram_lm_build(const uint64_t* keys, const int32_t* vals, int64_t n, uint64_t* table_keys, int32_t* table_vals,
                                   int64_t cap, int32_t* dups, void* stream) {
@@ -540,171 +458,55 @@ extern "C" int w2l_ngram_lm_build(const uint64_t* keys, const int32_t* vals, int
     return 0;
 }
 
-extern "C" int64_t w2l_ctc_beam_search_lm_workspace_bytes(int N, int T, int k, int order) {
-    if (N <= 0 || T <= 0 || k <= 0 || (int64_t)k * T >= (1 << 29) || order < 1 || order > LM_MAXORDER) return -1;
-    return (int64_t)N * lm_ws_stride(T, k);
+// Nothing is kept per interned prefix for a lexicon or for hotwords (see the head of this file): only an LM adds to the workspace.
+extern "C" int64_t w2l_ctc_beam_search_workspace_bytes(int N, int T, int k, int order) {
+    return search_ws_bytes(N, T, k, order, 2);
 }
 
-namespace {
-
-// the argument checks of the LM entry points, and the device form of the tables
-int lm_args(const char* name, const int32_t* label_info_host, int A, int space_index, double alpha, const w2l_ngram_lm_t* lm,
-            int order, int T, int k, LmArgs* a) {
-    W2L_CHECK_ARG(lm && label_info_host && A >= 1 && A <= BS_AMAX, "%s: bad arguments", name);
-    W2L_CHECK_ARG(order >= 1 && order <= LM_MAXORDER, "%s: order %d, supported 1..%d", name, order, LM_MAXORDER);
-    W2L_CHECK_ARG(space_index >= -1 && space_index < A && (space_index < 0 || (label_info_host[space_index] & 0xff) == space_index),
-                  "%s: space index %d is not the first index of a label", name, space_index);
-    for (int i = 0; i < A; ++i)
-        W2L_CHECK_ARG(!(label_info_host[i] & 0x800) || (label_info_host[i] & 0xff) == space_index,
-                      "%s: label %d is whitespace other than ' '", name, i);
-    W2L_CHECK_ARG(lm->prob && lm->bo && lm->ngram_keys && lm->ngram_vals && lm->trie_keys && lm->trie_vals && lm->trie_word,
-                  "%s: a table pointer is NULL", name);
-    W2L_CHECK_ARG(lm->n_words >= 3 && lm->n_entries >= lm->n_words && lm->n_entries < (1 << 30) && lm->n_trie_nodes >= 1,
-                  "%s: %d entries, %d words, %d trie nodes (3 <= words <= entries < 2^30)", name, lm->n_entries,
-                  lm->n_words, lm->n_trie_nodes);
-    W2L_CHECK_ARG(pow2_cap(lm->ngram_cap) && lm->ngram_cap >= 2 * (int64_t)(lm->n_entries - lm->n_words) && pow2_cap(lm->trie_cap)
-                      && lm->trie_cap >= 2 * (int64_t)(lm->n_trie_nodes - 1),
-                  "%s: table capacities %lld / %lld (powers of two in [16, 2^31], at most half full)", name,
-                  (long long)lm->ngram_cap, (long long)lm->trie_cap);
-    a->prob = lm->prob;
-    a->bo = lm->bo;
-    a->nkeys = lm->ngram_keys;
-    a->nvals = lm->ngram_vals;
-    a->tkeys = lm->trie_keys;
-    a->tvals = lm->trie_vals;
-    a->tword = lm->trie_word;
-    a->nmask = (uint32_t)(lm->ngram_cap - 1);
-    a->tmask = (uint32_t)(lm->trie_cap - 1);
-    a->order = order;
-    a->space = space_index;
-    a->alpha_ln10 = alpha * 2.302585092994045684;
-    a->state_off = lm_state_offset(T, k);
-    return 0;
+extern "C" int w2l_ctc_beam_search(const float* probs, const int32_t* sizes, int N, int T, int A,
+                                   const int32_t* label_info_host, int blank, int end_index, int space_index, int k,
+                                   double alpha, double beta, double prune, int log_probs, const w2l_ngram_lm_t* lm, int order,
+                                   const w2l_lexicon_t* lexicon, int complete_only, const w2l_lexicon_t* hotwords,
+                                   double hotword_weight, void* workspace, int64_t workspace_bytes, void* out, void* stream) {
+    const char* name = "ctc_beam_search";
+    // every check of the arguments comes before the first HIP call (launch_search)
+    W2L_CHECK_ARG(probs && label_info_host && workspace && out && N > 0 && T > 0, "%s: bad arguments", name);
+    W2L_CHECK_ARG(A >= 1 && A <= BS_AMAX, "%s: %d labels, supported 1..%d", name, A, BS_AMAX);
+    W2L_CHECK_ARG(k >= 1 && k <= BS_KMAX, "%s: beam width k=%d, supported 1..%d", name, k, BS_KMAX);
+    W2L_CHECK_ARG(blank >= 0 && blank < A && end_index >= -1 && end_index < A, "%s: blank %d / end %d outside %d labels",
+                  name, blank, end_index, A);
+    W2L_CHECK_ARG((int64_t)k * T < (1 << 29) && T < (1 << 24), "%s: k*T = %lld too large", name, (long long)k * T);
+    CtcSearch s{probs, sizes, N, T, A, blank, end_index, k, log_probs, beta, prune};
+    if (int rc = label_info_args(name, label_info_host, A, s.info.v, BS_AMAX)) return rc;
+    if (lm || lexicon || hotwords)
+        if (int rc = space_args(name, label_info_host, A, space_index)) return rc;
+    if (lm)
+        if (int rc = lm_args(name, space_index, alpha, lm, order, T, k, 2, &s.lm)) return rc;
+    if (lexicon) {
+        if (int rc = trie_args(name, "lexicon", space_index, lexicon, &s.lex)) return rc;
+        s.lex.complete_only = complete_only != 0;
+    }
+    if (hotwords) {
+        W2L_CHECK_ARG(std::isfinite(hotword_weight), "%s: the hotword weight is not finite", name);
+        if (int rc = trie_args(name, "hotword", space_index, hotwords, &s.hot)) return rc;
+        s.hot.gamma = hotword_weight;
+    }
+    const int64_t need = w2l_ctc_beam_search_workspace_bytes(N, T, k, lm ? order : 0);
+    W2L_CHECK_ARG(need > 0 && workspace_bytes >= need, "%s: workspace of %lld bytes, %lld needed", name,
+                  (long long)workspace_bytes, (long long)need);
+    s.workspace = workspace;
+    s.ws_per_utt = lm ? lm_ws_stride(T, k, 2) : ws_stride(T, k, 2);
+    s.out = out;
+    s.stream = stream;
+    switch ((lm ? 4 : 0) | (lexicon ? 2 : 0) | (hotwords ? 1 : 0)) {          // the one dispatch: a NULL table is a false flag
+        case 0: return launch_search<false, false, false>(name, s);
+        case 1: return launch_search<false, false, true>(name, s);
+        case 2: return launch_search<false, true, false>(name, s);
+        case 3: return launch_search<false, true, true>(name, s);
+        case 4: return launch_search<true, false, false>(name, s);
+        case 5: return launch_search<true, false, true>(name, s);
+        case 6: return launch_search<true, true, false>(name, s);
+        default: return launch_search<true, true, true>(name, s);
+    }
 }
 
-// ... and of the lexicon entry points
-int lex_args(const char* name, const int32_t* label_info_host, int A, int space_index, const w2l_lexicon_t* lexicon,
-             int complete_only, LexArgs* x) {
-    W2L_CHECK_ARG(lexicon && label_info_host && A >= 1 && A <= BS_AMAX, "%s: bad arguments", name);
-    W2L_CHECK_ARG(space_index >= -1 && space_index < A && (space_index < 0 || (label_info_host[space_index] & 0xff) == space_index),
-                  "%s: space index %d is not the first index of a label", name, space_index);
-    for (int i = 0; i < A; ++i)
-        W2L_CHECK_ARG(!(label_info_host[i] & 0x800) || (label_info_host[i] & 0xff) == space_index,
-                      "%s: label %d is whitespace other than ' '", name, i);
-    W2L_CHECK_ARG(lexicon->trie_keys && lexicon->trie_vals && lexicon->trie_word, "%s: a lexicon table pointer is NULL", name);
-    W2L_CHECK_ARG(lexicon->n_trie_nodes >= 1 && pow2_cap(lexicon->trie_cap)
-                      && lexicon->trie_cap >= 2 * (int64_t)(lexicon->n_trie_nodes - 1),
-                  "%s: lexicon of %d trie nodes in a table of capacity %lld (a power of two in [16, 2^31], at most half full)",
-                  name, lexicon->n_trie_nodes, (long long)lexicon->trie_cap);
-    x->tkeys = lexicon->trie_keys;
-    x->tvals = lexicon->trie_vals;
-    x->tword = lexicon->trie_word;
-    x->tmask = (uint32_t)(lexicon->trie_cap - 1);
-    x->space = space_index;
-    x->complete_only = complete_only != 0;
-    return 0;
-}
-
-}  // namespace
-
-extern "C" int w2l_ctc_beam_search_lm(const float* probs, const int32_t* sizes, int N, int T, int A,
-                                      const int32_t* label_info_host, int blank, int end_index, int space_index, int k,
-                                      double alpha, double beta, double prune, int log_probs, const w2l_ngram_lm_t* lm,
-                                      int order, void* workspace, int64_t workspace_bytes, void* out, void* stream) {
-    LmArgs a;
-    if (int rc = lm_args("ctc_beam_search_lm", label_info_host, A, space_index, alpha, lm, order, T, k, &a)) return rc;
-    return launch_search<true>("ctc_beam_search_lm", probs, sizes, N, T, A, label_info_host, blank, end_index, k, beta, prune,
-                               log_probs, workspace, workspace_bytes, w2l_ctc_beam_search_lm_workspace_bytes(N, T, k, order),
-                               lm_ws_stride(T, k), out, a, stream);
-}
-
-// The lexicon searches keep no state per interned prefix (see the head of this file): their workspaces are their parents'.
-extern "C" int64_t w2l_ctc_beam_search_lex_workspace_bytes(int N, int T, int k) {
-    return w2l_ctc_beam_search_workspace_bytes(N, T, k);
-}
-
-extern "C" int64_t w2l_ctc_beam_search_lm_lex_workspace_bytes(int N, int T, int k, int order) {
-    return w2l_ctc_beam_search_lm_workspace_bytes(N, T, k, order);
-}
-
-extern "C" int w2l_ctc_beam_search_lex(const float* probs, const int32_t* sizes, int N, int T, int A,
-                                       const int32_t* label_info_host, int blank, int end_index, int space_index, int k,
-                                       double beta, double prune, int log_probs, const w2l_lexicon_t* lexicon,
-                                       int complete_only, void* workspace, int64_t workspace_bytes, void* out, void* stream) {
-    LexArgs x;
-    if (int rc = lex_args("ctc_beam_search_lex", label_info_host, A, space_index, lexicon, complete_only, &x)) return rc;
-    return launch_search<false, true>("ctc_beam_search_lex", probs, sizes, N, T, A, label_info_host, blank, end_index, k, beta,
-                                      prune, log_probs, workspace, workspace_bytes,
-                                      w2l_ctc_beam_search_lex_workspace_bytes(N, T, k), ws_stride(T, k), out, LmArgs{}, stream, x);
-}
-
-extern "C" int w2l_ctc_beam_search_lm_lex(const float* probs, const int32_t* sizes, int N, int T, int A,
-                                          const int32_t* label_info_host, int blank, int end_index, int space_index, int k,
-                                          double alpha, double beta, double prune, int log_probs, const w2l_ngram_lm_t* lm,
-                                          int order, const w2l_lexicon_t* lexicon, int complete_only, void* workspace,
-                                          int64_t workspace_bytes, void* out, void* stream) {
-    LmArgs a;
-    LexArgs x;
-    if (int rc = lm_args("ctc_beam_search_lm_lex", label_info_host, A, space_index, alpha, lm, order, T, k, &a)) return rc;
-    if (int rc = lex_args("ctc_beam_search_lm_lex", label_info_host, A, space_index, lexicon, complete_only, &x)) return rc;
-    return launch_search<true, true>("ctc_beam_search_lm_lex", probs, sizes, N, T, A, label_info_host, blank, end_index, k, beta,
-                                     prune, log_probs, workspace, workspace_bytes,
-                                     w2l_ctc_beam_search_lm_lex_workspace_bytes(N, T, k, order), lm_ws_stride(T, k), out, a,
-                                     stream, x);
-}
-
-// ---- hotword boosting: the four searches above with gamma * h in the rank key (HOT = true) ----
-namespace {
-
-int hot_args(const char* name, const int32_t* label_info_host, int A, int space_index, const w2l_lexicon_t* hotwords,
-             double hotword_weight, HotArgs* h) {
-    W2L_CHECK_ARG(hotwords && label_info_host && A >= 1 && A <= BS_AMAX, "%s: bad arguments", name);
-    W2L_CHECK_ARG(std::isfinite(hotword_weight), "%s: the hotword weight is not finite", name);
-    W2L_CHECK_ARG(space_index >= -1 && space_index < A && (space_index < 0 || (label_info_host[space_index] & 0xff) == space_index),
-                  "%s: space index %d is not the first index of a label", name, space_index);
-    for (int i = 0; i < A; ++i)
-        W2L_CHECK_ARG(!(label_info_host[i] & 0x800) || (label_info_host[i] & 0xff) == space_index,
-                      "%s: label %d is whitespace other than ' '", name, i);
-    W2L_CHECK_ARG(hotwords->trie_keys && hotwords->trie_vals && hotwords->trie_word, "%s: a hotword table pointer is NULL", name);
-    W2L_CHECK_ARG(hotwords->n_trie_nodes >= 1 && pow2_cap(hotwords->trie_cap)
-                      && hotwords->trie_cap >= 2 * (int64_t)(hotwords->n_trie_nodes - 1),
-                  "%s: hotwords of %d trie nodes in a table of capacity %lld (a power of two in [16, 2^31], at most half full)",
-                  name, hotwords->n_trie_nodes, (long long)hotwords->trie_cap);
-    h->tkeys = hotwords->trie_keys;
-    h->tvals = hotwords->trie_vals;
-    h->tword = hotwords->trie_word;
-    h->tmask = (uint32_t)(hotwords->trie_cap - 1);
-    h->space = space_index;
-    h->gamma = hotword_weight;
-    return 0;
-}
-
-}  // namespace
-
-// Nothing is kept per interned prefix here either: the workspace is that of the search without hotwords (order 0: no LM).
-extern "C" int64_t w2l_ctc_beam_search_hot_workspace_bytes(int N, int T, int k, int order) {
-    return order == 0 ? w2l_ctc_beam_search_workspace_bytes(N, T, k) : w2l_ctc_beam_search_lm_workspace_bytes(N, T, k, order);
-}
-
-extern "C" int w2l_ctc_beam_search_hot(const float* probs, const int32_t* sizes, int N, int T, int A,
-                                       const int32_t* label_info_host, int blank, int end_index, int space_index, int k,
-                                       double alpha, double beta, double prune, int log_probs, const w2l_ngram_lm_t* lm,
-                                       int order, const w2l_lexicon_t* lexicon, int complete_only,
-                                       const w2l_lexicon_t* hotwords, double hotword_weight, void* workspace,
-                                       int64_t workspace_bytes, void* out, void* stream) {
-    const char* name = "ctc_beam_search_hot";
-    LmArgs a{};
-    LexArgs x{};
-    HotArgs h{};
-    if (int rc = hot_args(name, label_info_host, A, space_index, hotwords, hotword_weight, &h)) return rc;
-    if (lm) if (int rc = lm_args(name, label_info_host, A, space_index, alpha, lm, order, T, k, &a)) return rc;
-    if (lexicon) if (int rc = lex_args(name, label_info_host, A, space_index, lexicon, complete_only, &x)) return rc;
-    const int64_t need = w2l_ctc_beam_search_hot_workspace_bytes(N, T, k, lm ? order : 0);
-    const int64_t stride = lm ? lm_ws_stride(T, k) : ws_stride(T, k);
-#define W2L_HOT_LAUNCH(LM_, LEX_)                                                                                              \
-    launch_search<LM_, LEX_, true>(name, probs, sizes, N, T, A, label_info_host, blank, end_index, k, beta, prune, log_probs,   \
-                                   workspace, workspace_bytes, need, stride, out, a, stream, x, h)
-    if (lm) return lexicon ? W2L_HOT_LAUNCH(true, true) : W2L_HOT_LAUNCH(true, false);
-    return lexicon ? W2L_HOT_LAUNCH(false, true) : W2L_HOT_LAUNCH(false, false);
-#undef W2L_HOT_LAUNCH
-}
