@@ -681,7 +681,7 @@ int64_t w2l_asg_beam_search_workspace_bytes(int N, int T, int A, int k, int orde
  * len[N][k] (-1: empty slot) | int32 status[N] (1: a NaN score or transition) | int32 labels[N][k][T] (ENCODED labels).
  * Limits: 1 <= k <= 64, 1 <= A <= 64 (k = 64 with A = 64 takes 138 KB of dynamic LDS beside 9 KB static).
  *
- * lm may be NULL; the call launches asg_beam_search_kernel<lm != NULL>.  With lm (tables, order, label_info_host bit 11 and
+ * lm may be NULL; the call launches asg_beam_search_kernel<lm != NULL, false, false>.  With lm (tables, order, label_info_host bit 11 and
  * space_index as in w2l_ctc_beam_search, checked only here): a trie node's LM state spells its DECODED characters (an r after
  * a letter spells the letter again, an r after a space closes nothing, a leading r spells nothing).  The weight of member i,
  * alpha * ln 10 * (log10 of its text's words with </s>), is added to exactly one contribution: the extension of member i by
@@ -692,6 +692,33 @@ int w2l_asg_beam_search(const float* x, const float* transitions, const int32_t*
                         const int32_t* label_info_host, int repeat_index, int space_index, int k, double alpha, double beta,
                         double prune, const w2l_ngram_lm_t* lm, int order, void* workspace, int64_t workspace_bytes, void* out,
                         void* stream);
+/* w2l_asg_beam_search with the two word lists of w2l_ctc_beam_search: each of lm, lexicon and hotwords may be
+ * NULL, independently, and the call launches asg_beam_search_kernel<lm != NULL, lexicon != NULL, hotwords != NULL>.  It is a
+ * second symbol, not a longer signature, because w2l_asg_beam_search has positional callers; that symbol is this call with
+ * (NULL, 1, NULL, 0.0), so (NULL, NULL) here is byte for byte the older call.  w2l_asg_beam_search_workspace_bytes serves
+ * both: a lexicon and hotwords keep nothing per trie node (a beam slot's states live in LDS, 2 KB more of static LDS for the
+ * two).  With any table label_info_host bit 11 and space_index are read and checked as in w2l_ctc_beam_search.
+ *
+ * Words are spelled by DECODED characters: member i (last decoded label dec_i, -1 if none) extended by label c spells d = dec_i
+ * if c is the repeat label, else c.  d < 0 (a leading repeat label) spells nothing: the extension is legal and carries its
+ * parent's states.  Otherwise the lexicon node and the hotword walk step with d's canonical label as in w2l_ctc_beam_search;
+ * the only separator is the space (there is no end character), and a repeat label after a space spells a second space, which
+ * is legal.  lexicon: an extension that is not itself a beam member and leaves the word list gets no mass -- not the
+ * extension term, not its own M_{t-1} term.  complete_only and hotwords / hotword_weight: as in w2l_ctc_beam_search (the
+ * score written to out includes hotword_weight * h; weight 0 gives the output of the search without hotwords).
+ *
+ * The participation rule under a lexicon.  Without one, "x[t][c] > log(prune) or c is the frame's first argmax" keeps the beam
+ * alive because every participating label can extend some member.  With one, every participating extension can be illegal
+ * while no member's last label takes part.  So with lexicon != NULL, and only then, label c also takes part in frame t if
+ * t == 0 (every label: any non-empty lexicon has a legal first label) or c is the last label of a member of the current beam
+ * (every member can stay).  It is still one ascending set per frame, used for stays and extensions alike.
+ *
+ * Argument errors as in w2l_ctc_beam_search (nothing is launched); w2l_last_error names asg_beam_search. */
+int w2l_asg_beam_search_tables(const float* x, const float* transitions, const int32_t* sizes, int N, int T, int A,
+                               const int32_t* label_info_host, int repeat_index, int space_index, int k, double alpha,
+                               double beta, double prune, const w2l_ngram_lm_t* lm, int order, const w2l_lexicon_t* lexicon,
+                               int complete_only, const w2l_lexicon_t* hotwords, double hotword_weight, void* workspace,
+                               int64_t workspace_bytes, void* out, void* stream);
 /* workspace bytes for w2l_asg_align: 0 while the moves fit in LDS, else N * ceil(T / 16) * (states rounded up to the block's)
  * * 4; -1 if out of range (T > 32768, Smax > 4095, A outside 1..64) */
 int64_t w2l_asg_align_workspace_bytes(int N, int T, int A, int Smax);

@@ -176,6 +176,9 @@ _SIGNATURES = {
     'w2l_asg_beam_search_workspace_bytes': (c_i64, [c_i, c_i, c_i, c_i, c_i]),
     'w2l_asg_beam_search': (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_i, c_i, c_i, C.c_double, C.c_double, C.c_double,
                                   C.POINTER(LmTables), c_i, c_p, c_i64, c_p, c_p]),
+    'w2l_asg_beam_search_tables': (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_i, c_i, c_i, C.c_double, C.c_double, C.c_double,
+                                         C.POINTER(LmTables), c_i, C.POINTER(LexTables), c_i, C.POINTER(LexTables), C.c_double,
+                                         c_p, c_i64, c_p, c_p]),
     'w2l_asg_align_workspace_bytes': (c_i64, [c_i, c_i, c_i, c_i]),
     'w2l_asg_align': (c_i, [c_p, c_p, c_p, c_p, c_i64, c_p, c_i64, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_i64, c_p, c_p, c_p, c_p,
                             c_p, c_p]),
@@ -303,7 +306,7 @@ TRACE_NAMES = {
     'w2l_quantize_e4m3_dyn': 'quantize_e4m3_dyn', 'w2l_dwconv_fwd': 'dw_fwd_kernel', 'w2l_dwconv_dgrad': 'dw_dgrad_kernel',
     'w2l_dwconv_wgrad': 'dw_wgrad_kernel', 'w2l_argmax': 'argmax_kernel', 'w2l_novograd_pack': 'novograd_pack_kernel',
     'w2l_ctc_beam_search': 'ctc_beam_search_kernel', 'w2l_ngram_lm_build': 'ngram_insert_kernel', 'w2l_ctc_align': 'ctc_align_kernel',
-    'w2l_asg_beam_search': 'asg_beam_search_kernel',
+    'w2l_asg_beam_search': 'asg_beam_search_kernel', 'w2l_asg_beam_search_tables': 'asg_beam_search_kernel',
     'w2l_asg_align': 'asg_align_kernel',
 }
 _trace = {'rows': None, 'saved': {}, 'pool': []}

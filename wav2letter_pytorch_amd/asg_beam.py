@@ -20,8 +20,16 @@ counted as the CTC search counts them), ties in first-insertion order, the best 
 extend contribution gets ``alpha * ln(lm(text of e))`` when c is the space, the member's last decoded character is not, and
 its text has a non-space character (the rule of the CTC search, on decoded characters).
 
+Word lists (``lexicon=``, ``hotwords=``; lexicon.py) act on the DECODED text, so a word with a doubled letter is reached through
+the repeat label (``ALL`` is ``A L r``) and the only separator is the space.  Lexicon: a hypothesis whose text is not legal
+(Lexicon.allows) gets no mass, from its parent or from its own previous mass; ``complete_only`` draws the results from the
+final members whose last word is whole.  Hotwords: the rank key gains ``hotword_weight * Lexicon.boost_chars(text)``.  With no
+blank a constrained beam could die -- every participating extension illegal while no member's last label takes part -- so
+UNDER A LEXICON ONLY a label also takes part in frame t if ``t == 0`` (every label) or it is the last label of a member of
+the current beam (every member can stay); it stays one ascending set per frame, for stays and extensions alike.
+
 asg_prefix_beam_search / asg_viterbi_align_host restate the recursions on the host (the oracles of the device tests);
-asg_beam_search_gpu / asg_forced_align launch csrc/asg_beam.hip (w2l_asg_beam_search, w2l_asg_align)."""
+asg_beam_search_gpu / asg_forced_align launch csrc/asg_beam.hip (w2l_asg_beam_search_tables, w2l_asg_align)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -36,7 +44,8 @@ from . import _lib
 from ._lib import check, lib, ptr, stream_ptr
 from .alignment import Alignment, HostAlignment, _targets_to_array, align_sections, split_align
 from .asg import MAX_LABELS, ASGDecoder, _check_labels, decode_repeats, encode_repeats
-from .beam_search import _SEP_RE, _WORDCH_RE, _n_words, split_search_out
+from .beam_search import (_SEP_RE, _WORDCH_RE, _decoder_hotwords, _n_words, _resolve_hotwords, _resolve_lexicon,
+                          split_search_out)
 
 _NINF = float('-inf')
 
@@ -67,11 +76,22 @@ def _pick(found, nbest, return_weights, return_encoded):
 
 def asg_prefix_beam_search(x, transitions, labels: Sequence[str], repeat_index: int = 0,
                            lm: Optional[Callable[[str], float]] = None, k: int = 5, alpha: float = 0.3, beta: float = 5,
-                           prune: float = 1e-3, nbest: int = 1, return_weights: bool = False, return_encoded: bool = False):
+                           prune: float = 1e-3, nbest: int = 1, return_weights: bool = False, return_encoded: bool = False,
+                           lexicon=None, complete_only: bool = True, hotwords=None, hotword_weight: float = 1.0):
     """The recursion of the module docstring for one utterance, float64: x ``[T, A]`` scores, transitions ``[A, A]`` (None:
     zeros), ``lm`` a callable text -> probability.  Returns the best text; ``(text, weight)`` with ``return_weights`` (weight:
     the rank key, the log mass where beta = 0); with ``nbest > 1`` a list of up to ``nbest`` such pairs, best first.
-    ``return_encoded`` appends the hypothesis' encoded label tuple to every result."""
+    ``return_encoded`` appends the hypothesis' encoded label tuple to every result.
+
+    ``lexicon`` (a lexicon.Lexicon; None: no constraint), stated on the DECODED text with ``str`` operations: a hypothesis gets
+    mass -- in frame 0, as an extension, and from its own previous mass where it fell off the beam -- only if
+    ``lexicon.allows(text, end_char='')`` (the words the labels can spell; the repeat label spells nothing of its own).  With
+    ``complete_only`` the results are the members of the final beam with ``lexicon.complete(text, end_char='')``, in rank order
+    with their own weights; all members if there is none.  Under a lexicon a label also takes part in a frame if the frame is
+    the first or the label is the last label of a member of the current beam (the module docstring), so the beam never empties.
+
+    ``hotwords`` (a lexicon.Lexicon, a path or an iterable of single words; None: no boosting): the rank key gains
+    ``hotword_weight * hotwords.boost_chars(text, end_char='')``; masses are untouched, weight 0 gives the keys of no hotwords."""
     x = np.asarray(x, dtype=np.float64)
     if x.ndim != 2 or x.shape[0] < 1:
         raise ValueError('asg_prefix_beam_search: expected [T >= 1, A] scores, got shape %s' % (x.shape,))
@@ -86,7 +106,15 @@ def asg_prefix_beam_search(x, transitions, labels: Sequence[str], repeat_index: 
         raise ValueError('nbest=%d must lie in [1, k=%d]' % (nbest, k))
     r = int(repeat_index)
     log_prune = math.log(prune) if prune > 0 else _NINF
+    lex = lexicon.spellable(labels, r) if lexicon is not None else None
+    hot, gamma = None, 0.0
+    if hotwords is not None:
+        hot = _resolve_hotwords(hotwords).spellable(labels, r)
+        gamma = float(hotword_weight)
+        if not math.isfinite(gamma):
+            raise ValueError('hotword_weight must be finite, got %r' % (hotword_weight,))
     texts = {}
+    legal = {}
 
     def text_of(e):
         s = texts.get(e)
@@ -106,21 +134,35 @@ def asg_prefix_beam_search(x, transitions, labels: Sequence[str], repeat_index: 
             lm_terms[s] = alpha * math.log(v) if v > 0 else _NINF
         return lm_terms[s]
 
-    def takes_part(frame):
+    def allowed(e):
+        if lex is None:
+            return True
+        if e not in legal:
+            legal[e] = lex.allows(text_of(e), end_char='')
+        return legal[e]
+
+    def takes_part(frame, members=None):
+        """the frame's labels, ascending; under a lexicon every label of frame 0 (``members`` None) and the last label of
+        every member of the beam take part as well"""
         first = int(np.argmax(frame))
-        return [c for c in range(a) if prune <= 0 or frame[c] > log_prune or c == first]
+        also = () if lex is None else (range(a) if members is None else {e[-1] for e in members})
+        return [c for c in range(a) if prune <= 0 or frame[c] > log_prune or c == first or c in also]
 
     def rank(cur):
         live = [e for e in cur if cur[e] > _NINF]
-        keys = {e: cur[e] + beta * math.log(_n_words(text_of(e)) + 1) for e in live}
+        if hot is None:
+            keys = {e: cur[e] + beta * math.log(_n_words(text_of(e)) + 1) for e in live}
+        else:
+            keys = {e: cur[e] + beta * math.log(_n_words(text_of(e)) + 1) + gamma * hot.boost_chars(text_of(e), end_char='')
+                    for e in live}
         return sorted(live, key=lambda e: keys[e], reverse=True), keys       # stable: ties keep first insertion
 
-    cur = {(c,): float(x[0, c]) for c in takes_part(x[0])}
+    cur = {(c,): float(x[0, c]) for c in takes_part(x[0]) if allowed((c,))}
     order, keys = rank(cur)
     beam = order[:k]
     for t in range(1, t_n):
         frame = x[t]
-        part = takes_part(frame)
+        part = takes_part(frame, beam)
         part_set = set(part)
         prev, cur = cur, {}
         in_beam = set(beam)
@@ -133,6 +175,8 @@ def asg_prefix_beam_search(x, transitions, labels: Sequence[str], repeat_index: 
                 if c == l:
                     continue
                 ext = e + (c,)
+                if not allowed(ext):                     # the extension leaves the word list: no mass for it
+                    continue
                 v = float(prev[e] + g[l, c] + frame[c])
                 if labels[c] == ' ':
                     v += closes
@@ -141,6 +185,8 @@ def asg_prefix_beam_search(x, transitions, labels: Sequence[str], repeat_index: 
                     cur[ext] = _lae(cur[ext], float(prev[ext] + g[c, c] + frame[c]))
         order, keys = rank(cur)
         beam = order[:k]
+    if lex is not None and complete_only:
+        beam = [e for e in beam if lex.complete(text_of(e), end_char='')] or beam
     found = [(text_of(e), keys[e], e) for e in beam]
     if not found:
         found = [('', _NINF, ())]
@@ -273,24 +319,35 @@ def launch_asg_align(x, g, sz, tg_ptr: int, tg_stride: int, len_ptr: int, len_st
     return ws
 
 
-def _search_device(x, g, sz, labels, repeat_index, k, beta, prune, lm, alpha, offsets):
-    """one launch of w2l_asg_beam_search (``lm`` None: passed as NULL) for x [N, T, A] on the current stream, with
-    ``offsets`` followed by w2l_asg_align on rank 0 where the search wrote it; one copy to the host.  -> (scores [N, k],
-    lengths [N, k], encoded labels [N, k, T], lm_log10 [N, k] or None, starts [N, T] or None)"""
+def _search_device(x, g, sz, labels, repeat_index, k, beta, prune, lm, alpha, offsets, lexicon=None, complete_only=True,
+                   hotwords=None, hotword_weight=1.0):
+    """one launch of w2l_asg_beam_search_tables (a table that is None: passed as NULL) for x [N, T, A] on the current stream,
+    with ``offsets`` followed by w2l_asg_align on rank 0 where the search wrote it; one copy to the host.  ``lexicon``: a
+    lexicon.Lexicon, a path or 'lm' (the vocabulary of ``lm``); ``hotwords``: a Lexicon, a path or an iterable of single words.
+    -> (scores [N, k], lengths [N, k], encoded labels [N, k, T], lm_log10 [N, k] or None, starts [N, T] or None)"""
     n, t, a = x.shape
     dev = x.device
-    info = _label_info(labels, lm is not None)
+    any_table = lm is not None or lexicon is not None or hotwords is not None
+    info = _label_info(labels, any_table)
     if offsets and t > 4095:
         raise ValueError('return_offsets: %d frames, w2l_asg_align takes targets of at most 4095 labels' % t)
-    tables, space_index = None, -1
-    if lm is not None:
+    tables, lex, hot, space_index = None, None, None, -1
+    if any_table:
         from .ngram_lm import ArpaLM
-        if not isinstance(lm, ArpaLM):
+        if lm is not None and not isinstance(lm, ArpaLM):
             raise TypeError('lm must be an ngram_lm.ArpaLM, got %s' % type(lm).__name__)
         odd = [ch for ch in labels if ch.isspace() and ch != ' ']
         if odd:
-            raise ValueError('asg_beam_search_gpu: whitespace labels other than a space (%r) cannot be scored by a word LM' % odd)
-        tables = lm.to_device(labels, repeat_index, dev)
+            raise ValueError('asg_beam_search_gpu: whitespace labels other than a space (%r) cannot be scored by a word LM' % odd
+                             if lm is not None else
+                             'asg_beam_search_gpu: whitespace labels other than a space (%r) cannot separate the words of a '
+                             'lexicon or of a hotword list' % odd)
+        if hotwords is not None and not math.isfinite(float(hotword_weight)):
+            raise ValueError('asg_beam_search_gpu: hotword_weight must be finite, got %r' % (hotword_weight,))
+        # the repeat label takes the blank's place as the label that spells nothing
+        tables = lm.to_device(labels, repeat_index, dev) if lm is not None else None
+        lex = _resolve_lexicon(lexicon, lm).to_device(labels, repeat_index, dev) if lexicon is not None else None
+        hot = _resolve_hotwords(hotwords).to_device(labels, repeat_index, dev) if hotwords is not None else None
         space_index = labels.index(' ') if ' ' in labels else -1
     order = lm.order if lm is not None else 0
     ws_bytes = int(lib.w2l_asg_beam_search_workspace_bytes(n, t, a, k, order))
@@ -299,10 +356,12 @@ def _search_device(x, g, sz, labels, repeat_index, k, beta, prune, lm, alpha, of
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
     beam_bytes = 12 * n * k + 4 * n + 4 * n * k * t + (4 * n * k if lm is not None else 0)
     out = torch.empty(beam_bytes + (align_sections(n, t, t)[5] if offsets else 0), dtype=torch.uint8, device=dev)
-    check(lib.w2l_asg_beam_search(ptr(x), ptr(g), ptr(sz), n, t, a, info.ctypes.data_as(C.c_void_p), int(repeat_index),
-                                  space_index, int(k), float(alpha), float(beta), float(prune),
-                                  tables.desc_ref if tables is not None else None, order, ptr(ws), ws_bytes, ptr(out),
-                                  stream_ptr()), 'w2l_asg_beam_search')
+    check(lib.w2l_asg_beam_search_tables(ptr(x), ptr(g), ptr(sz), n, t, a, info.ctypes.data_as(C.c_void_p), int(repeat_index),
+                                         space_index, int(k), float(alpha), float(beta), float(prune),
+                                         tables.desc_ref if tables is not None else None, order,
+                                         lex.desc_ref if lex is not None else None, int(bool(complete_only)),
+                                         hot.desc_ref if hot is not None else None, float(hotword_weight), ptr(ws), ws_bytes,
+                                         ptr(out), stream_ptr()), 'w2l_asg_beam_search_tables')
     align_ws = None
     if offsets:
         # rank 0 of every utterance, aligned where it lies: labels int32 [N, k, T] from byte 12 N k + 4 N (row stride k T),
@@ -328,7 +387,8 @@ def _search_device(x, g, sz, labels, repeat_index, k, beta, prune, lm, alpha, of
 
 def asg_beam_search_gpu(x, transitions, labels: Sequence[str], repeat_index: int = 0, k: int = 5, beta: float = 5,
                         prune: float = 1e-3, sizes=None, nbest: int = 1, return_weights: bool = False, lm=None,
-                        alpha: float = 0.3, return_offsets: bool = False, return_encoded: bool = False):
+                        alpha: float = 0.3, return_offsets: bool = False, return_encoded: bool = False, lexicon=None,
+                        complete_only: bool = True, hotwords=None, hotword_weight: float = 1.0):
     """asg_prefix_beam_search on the MI355X: one launch for a whole batch, the host's candidate order and ties.  x: ``[T, A]`` or
     ``[N, T, A]`` scores (numpy or torch, any device), transitions ``[A, A]`` (a tensor, an array, an ASGLoss, or None: zeros),
     ``sizes[n]``: decode only the first sizes[n] frames of utterance n; ``lm``: an ngram_lm.ArpaLM, scored as the host's
@@ -337,7 +397,14 @@ def asg_beam_search_gpu(x, transitions, labels: Sequence[str], repeat_index: int
     utterance holding the first frame of each character of its best text on that hypothesis' best frame path (one more launch,
     w2l_asg_align, on the same stream; still one copy to the host); the state of a leading repeat label emits none, an empty
     result has empty offsets.  ``return_offsets`` takes at most 4095 frames (w2l_asg_align's target limit: a hypothesis can be
-    as long as the utterance)."""
+    as long as the utterance).
+
+    ``lexicon`` (a lexicon.Lexicon, a path to a word list, or 'lm': the vocabulary of ``lm``; None: no constraint), with
+    ``complete_only``, and ``hotwords`` (a Lexicon, a path, or an iterable of single words; None: no boosting) with
+    ``hotword_weight`` (natural-log units per matched character, any finite real; 1.0 is a convention, not a tuned value) are
+    asg_prefix_beam_search's, with or without ``lm``: words are spelled by the decoded text, the results (best, n-best,
+    offsets) come from the complete members of the final beam, the returned weights include the hotword term, and under a
+    lexicon the participation rule of the module docstring keeps the beam alive."""
     labels = list(labels)
     _check_labels(len(labels), 'asg_beam_search_gpu')
     if not 1 <= nbest <= k:
@@ -362,7 +429,8 @@ def asg_beam_search_gpu(x, transitions, labels: Sequence[str], repeat_index: int
     g = _transitions_on(transitions, a, x.device)
     sz = _lengths(sizes, n, t, 'sizes').to(x.device, non_blocking=True) if sizes is not None else None
     scores, lengths, idx, _, starts = _search_device(x, g, sz, labels, int(repeat_index), int(k), beta, prune, lm, alpha,
-                                                     return_offsets)
+                                                     return_offsets, lexicon=lexicon, complete_only=complete_only,
+                                                     hotwords=hotwords, hotword_weight=hotword_weight)
     results = []
     for u in range(n):
         found = []
@@ -434,13 +502,24 @@ def asg_forced_align(x, transitions, targets, input_lengths=None, target_lengths
 class ASGBeamSearchDecoder(ASGDecoder):
     """ASGDecoder with the prefix beam search in the place of the Viterbi path (asg_beam_search_gpu): the same constructor plus
     the search's ``k``, ``beta`` and ``prune``; ``decode`` has ASGDecoder.decode's arguments and return shapes, so it goes
-    wherever the model's own decoder goes (``model.transcribe(decoder=...)``, ``evaluate(decoder=...)``)."""
+    wherever the model's own decoder goes (``model.transcribe(decoder=...)``, ``evaluate(decoder=...)``).  ``lexicon`` (a
+    lexicon.Lexicon or a path to a word list) with ``complete_only`` constrains the search, ``hotwords`` (a Lexicon, a path or
+    an iterable of single words) with ``hotword_weight`` makes it prefer words (asg_beam_search_gpu)."""
     lm = None
     alpha = 0.3
 
-    def __init__(self, labels, repeat_index=0, transitions=None, k=5, beta=5, prune=1e-3):
+    def __init__(self, labels, repeat_index=0, transitions=None, k=5, beta=5, prune=1e-3, lexicon=None, complete_only=True,
+                 hotwords=None, hotword_weight=1.0):
         super().__init__(labels, repeat_index, transitions)
         self.k, self.beta, self.prune = int(k), beta, prune
+        self._set_word_lists(lexicon, complete_only, hotwords, hotword_weight, None)
+
+    def _set_word_lists(self, lexicon, complete_only, hotwords, hotword_weight, lm):
+        self.hotwords, self.hotword_weight = _decoder_hotwords(hotwords, hotword_weight, list(self.labels), self.repeat_index)
+        if lm is None and isinstance(lexicon, str) and lexicon == 'lm':
+            raise ValueError("lexicon='lm' needs a language model: %s has none" % type(self).__name__)
+        self.lexicon = _resolve_lexicon(lexicon, lm) if lexicon is not None else None
+        self.complete_only = bool(complete_only)
 
     def decode(self, probs, sizes=None, transitions=None, return_offsets=False):
         """[N, T, labels] (or [T, labels]) scores -> one string per utterance; with ``return_offsets`` ``(strings, offsets)``,
@@ -454,7 +533,9 @@ class ASGBeamSearchDecoder(ASGDecoder):
             probs = probs.unsqueeze(0) if torch.is_tensor(probs) else np.asarray(probs)[None]
         got = asg_beam_search_gpu(probs, self.transitions if transitions is None else transitions, list(self.labels),
                                   self.repeat_index, k=self.k, beta=self.beta, prune=self.prune, sizes=sizes, lm=self.lm,
-                                  alpha=self.alpha, return_offsets=return_offsets)
+                                  alpha=self.alpha, return_offsets=return_offsets, lexicon=self.lexicon,
+                                  complete_only=self.complete_only, hotwords=self.hotwords,
+                                  hotword_weight=self.hotword_weight)
         if return_offsets:
             return got[0], [[o] for o in got[1]]
         return got
@@ -462,10 +543,12 @@ class ASGBeamSearchDecoder(ASGDecoder):
 
 class ASGBeamSearchLMDecoder(ASGBeamSearchDecoder):
     """ASGBeamSearchDecoder with an ARPA word n-gram model on the device (ngram_lm.ArpaLM, plain or .gz) at weight ``alpha``; a
-    falsy ``lm_path`` decodes without an LM."""
+    falsy ``lm_path`` decodes without an LM.  ``lexicon`` may also be 'lm', the model's vocabulary."""
 
-    def __init__(self, lm_path, labels, repeat_index=0, transitions=None, k=5, alpha=0.3, beta=5, prune=1e-3):
+    def __init__(self, lm_path, labels, repeat_index=0, transitions=None, k=5, alpha=0.3, beta=5, prune=1e-3, lexicon=None,
+                 complete_only=True, hotwords=None, hotword_weight=1.0):
         super().__init__(labels, repeat_index, transitions, k=k, beta=beta, prune=prune)
         from .ngram_lm import ArpaLM
         self.lm = ArpaLM(lm_path) if lm_path else None
         self.alpha = alpha
+        self._set_word_lists(lexicon, complete_only, hotwords, hotword_weight, self.lm)

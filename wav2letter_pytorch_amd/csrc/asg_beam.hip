@@ -1,7 +1,8 @@
 // Decoding an ASG model beyond Viterbi (gfx950): the prefix beam search over emissions plus learned transitions, with an
-// optional word n-gram model (w2l_asg_beam_search, which launches asg_beam_search_kernel<lm != NULL>; host restatement:
-// asg_beam.asg_prefix_beam_search; what it shares with the CTC search -- workspace, output stage, argument
-// checks -- is beam_core.h's),
+// optional word n-gram model, lexicon and hotword list (w2l_asg_beam_search_tables, which launches
+// asg_beam_search_kernel<lm != NULL, lexicon != NULL, hotwords != NULL>, and w2l_asg_beam_search, the same call without the two
+// word lists; host restatement: asg_beam.asg_prefix_beam_search; what it shares with the CTC search -- workspace, output
+// stage, argument checks, the trie steps of the word tables -- is beam_core.h's and beam_lm.h's),
 // and the forced alignment of a given label sequence (w2l_asg_align; host: asg_beam.asg_viterbi_align_host).
 //
 // ---- the search.  ASG has no blank: a hypothesis is an ENCODED label sequence e_1 .. e_m (no two neighbours equal, the
@@ -20,6 +21,21 @@
 // words and feeds the LM is the DECODED one, so every trie node carries its last decoded character, its word count and (LM)
 // a state that spells the decoded character (an r after a letter spells the letter again; a leading r spells nothing).
 // mem[] / redir[] are bytes (slot + 1) that the lane which set one clears a frame later, so that k = 64 with A = 64 fits LDS.
+//
+// With a lexicon (LEX) and with hotwords (HOT) every beam slot carries what the CTC kernel's carries (lex_trie: the lexicon's
+// trie node of its partial word; hot_st: the hotword walk of its string; static LDS, nothing per interned node), stepped by
+// the DECODED character an extension spells: slot i extended by label c spells d = (c == r ? dec[i] : c).  d < 0 (a leading
+// r) spells nothing: the states are the parent's and the extension is legal.  Otherwise the states step with d's canonical
+// label; the only separator is the space (an r after a space spells a second space, legal as doubled spaces are).  P2: the
+// extension entry of a non-member must stay in the lexicon to get mass (last frame's mass of a string that fell off the beam
+// included), and the rank key gains gamma * h; P3: a carried member copies its slot's states, a new member repeats its
+// parent slot's step; output: with complete_only the members whose partial word is empty or a whole word, in rank order (all
+// members if there is none).
+// The participation rule under a lexicon.  "x[t][c] > log(prune) or c is the frame's first argmax" keeps the beam alive only
+// because every participating label can extend; with a lexicon every participating extension can be illegal while no member's
+// last label takes part.  So with LEX -- and only then -- label c also takes part in frame t if t == 0 (every label: a
+// non-empty lexicon has a legal first label) or c is the last label of a member of the current beam (every member can stay).
+// It is still one ascending set per frame, for stays and extensions alike.
 //
 // ---- the alignment: Viterbi form of Z_tgt over the S states of the encoded target, fp32, in the structure of
 // ctc_align_kernel (one lane per state, columns through LDS, moves packed over time, back-trace by wave 0).
@@ -46,15 +62,17 @@ struct AsgBeam {                      // one frame's beam, slot-indexed (chr: la
 // nd_info of a trie node: bits 0-7 last decoded label + 1 (0: none), from bit 8 the word count
 __device__ __forceinline__ int pack_info(int dec, int words) { return (dec + 1) | (words << 8); }
 
-template <bool LM>
+template <bool LM, bool LEX, bool HOT>
 __global__ __launch_bounds__(AB_THREADS) void asg_beam_search_kernel(
     const float* __restrict__ x, const float* __restrict__ trans, const int32_t* __restrict__ sizes, int T, int A,
     AsgLabelInfo info, int rep, int k, double beta, double prune, char* __restrict__ ws, int64_t ws_per_utt, int hash_cap,
     double* __restrict__ out_score, int32_t* __restrict__ out_len, int32_t* __restrict__ out_status,
-    int32_t* __restrict__ out_labels, LmArgs lmargs, float* __restrict__ out_lm) {
+    int32_t* __restrict__ out_labels, LmArgs lmargs, float* __restrict__ out_lm, LexArgs lex, HotArgs hot) {
     __shared__ AsgBeam beams[2];
     __shared__ double lm_w[2][LM ? AB_KMAX : 1];          // LM weight (natural log) of each beam slot
     __shared__ int lm_on[2][LM ? AB_KMAX : 1];             // ... and whether it applies (a non-space character)
+    __shared__ int lex_trie[2][LEX ? AB_KMAX : 1];        // lexicon trie node of each beam slot's partial word
+    __shared__ HotState hot_st[2][HOT ? AB_KMAX : 1];     // hotword walk of each beam slot's string
     __shared__ double xd[AB_AMAX];
     __shared__ int act[AB_AMAX], lab[AB_AMAX];
     __shared__ int s_m[2], s_count, s_bad;
@@ -96,6 +114,8 @@ __global__ __launch_bounds__(AB_THREADS) void asg_beam_search_kernel(
             lm_w[0][0] = 0.0;
             lm_on[0][0] = 0;
         }
+        if constexpr (LEX) lex_trie[0][0] = 0;
+        if constexpr (HOT) hot_st[0][0] = HotState{0, 0, 0};
         s_m[0] = 1;
         s_m[1] = 0;
         s_bad = 0;
@@ -155,9 +175,16 @@ __global__ __launch_bounds__(AB_THREADS) void asg_beam_search_kernel(
                 const int oi = __shfl_xor(bi, off, 64);
                 if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
             }
+            [[maybe_unused]] uint64_t last = 0;            // LEX: the last labels of the beam's members, one bit per label
+            if constexpr (LEX) {
+                // (B.chr is stable here: wave 0 writes only ps in P1; from frame 1 on every member has a label in [0, A))
+                if (t > 0 && prune > 0)
+                    for (int j = 0; j < m; ++j) last |= 1ull << B.chr[j];
+            }
             if (lane < A) {
                 xd[lane] = (double)v;
-                const bool pass = prune <= 0 || (double)v > log_prune || lane == bi;
+                bool pass = prune <= 0 || (double)v > log_prune || lane == bi;
+                if constexpr (LEX) pass = pass || t == 0 || ((last >> lane) & 1);   // so that the beam cannot die (file head)
                 act[lane] = pass ? t + 1 : 0;
             }
         }
@@ -171,11 +198,20 @@ __global__ __launch_bounds__(AB_THREADS) void asg_beam_search_kernel(
             int seq = AB_NOSEQ;
             bool live = false;
             int words = 0;
+            [[maybe_unused]] int hchars = 0;               // HOT: h of the entry's string
             if (e < m * A) {
                 const int i = e / A, c = e - i * A;
                 const int s = (int)mem[ent] - 1;
                 const int l = B.chr[i];
-                const bool ext = act[c] == t + 1 && c != l;
+                bool ext = act[c] == t + 1 && c != l;
+                [[maybe_unused]] int canon = -1;           // LEX / HOT: the canonical label the extension spells (-1: nothing)
+                if constexpr (LEX || HOT) {
+                    const int d = c == rep ? B.dec[i] : c;
+                    if (d >= 0) canon = lab[d] & 0xff;
+                }
+                if constexpr (LEX) {                       // ... and the extension stays in the lexicon
+                    if (ext && s < 0 && canon >= 0) ext = lex_step(lex, lex_trie[cur][i], canon, -1) >= 0;
+                }
                 if (ext || s >= 0) {
                     live = true;
                     // slot i extended by c; where the extension is no member, last frame's mass of the same string joins
@@ -205,8 +241,11 @@ __global__ __launch_bounds__(AB_THREADS) void asg_beam_search_kernel(
                         parent_part();
                         const int pd = B.dec[i], d = c == rep ? pd : c;
                         words = B.words[i] + (d >= 0 && pd >= 0 && (lab[d] & 0x400) && (lab[pd] & 0x200));
+                        if constexpr (HOT)
+                            hchars = hot_chars(canon >= 0 ? hot_step(hot, hot_st[cur][i], canon, -1) : hot_st[cur][i]);
                     } else {
                         words = B.words[s];
+                        if constexpr (HOT) hchars = hot_chars(hot_st[cur][s]);
                         if (i < s) parent_part();
                         if (act[c] == t + 1) {             // member s stays on its last label
                             acc = lae(acc, B.mass[s] + (double)gl[c * A + c] + xd[c]);
@@ -220,6 +259,7 @@ __global__ __launch_bounds__(AB_THREADS) void asg_beam_search_kernel(
                 if (B.ps[s] < 0 && B.parent[s] >= 0) {     // a member whose parent is not in the beam (never the root)
                     live = true;
                     words = B.words[s];
+                    if constexpr (HOT) hchars = hot_chars(hot_st[cur][s]);
                     const int l = B.chr[s];
                     if (act[l] == t + 1) {
                         acc = B.mass[s] + (double)gl[l * A + l] + xd[l];
@@ -230,7 +270,8 @@ __global__ __launch_bounds__(AB_THREADS) void asg_beam_search_kernel(
             mcur[ent] = acc;
             if (live && acc > -INFINITY) {
                 const int slot = atomicAdd(&s_count, 1);
-                lsc[slot] = acc + beta * log((double)(words + 1));
+                if constexpr (HOT) lsc[slot] = acc + beta * log((double)(words + 1)) + hot.gamma * (double)hchars;
+                else lsc[slot] = acc + beta * log((double)(words + 1));
                 lpk[slot] = ((uint32_t)seq << 16) | (uint32_t)ent;
             }
         }
@@ -260,8 +301,18 @@ __global__ __launch_bounds__(AB_THREADS) void asg_beam_search_kernel(
                 NB.node[r] = B.node[s]; NB.parent[r] = B.parent[s]; NB.chr[r] = B.chr[s]; NB.dec[r] = B.dec[s];
                 NB.words[r] = B.words[s]; NB.len[r] = B.len[s]; NB.prevslot[r] = s;
                 if constexpr (LM) { lm_w[cur ^ 1][r] = lm_w[cur][s]; lm_on[cur ^ 1][r] = lm_on[cur][s]; }
+                if constexpr (LEX) lex_trie[cur ^ 1][r] = lex_trie[cur][s];
+                if constexpr (HOT) hot_st[cur ^ 1][r] = hot_st[cur][s];
             } else {
                 const int par = B.node[i];
+                if constexpr (LEX || HOT) {                // the step of P2 again: nothing is kept per interned node
+                    const int d = c == rep ? B.dec[i] : c;
+                    const int canon = d >= 0 ? lab[d] & 0xff : -1;
+                    if constexpr (LEX)                     // (>= 0: P2 let it live)
+                        lex_trie[cur ^ 1][r] = canon >= 0 ? lex_step(lex, lex_trie[cur][i], canon, -1) : lex_trie[cur][i];
+                    if constexpr (HOT)
+                        hot_st[cur ^ 1][r] = canon >= 0 ? hot_step(hot, hot_st[cur][i], canon, -1) : hot_st[cur][i];
+                }
                 const uint64_t key = ((uint64_t)par << 8) | (uint64_t)c;
                 uint32_t h = key_hash(key) & (hash_cap - 1);
                 int node = -1, dec = -1, words = 0;
@@ -312,7 +363,21 @@ __global__ __launch_bounds__(AB_THREADS) void asg_beam_search_kernel(
     // ---------------------------------------------------------------- output: backtrack the final beam
     const int m = s_m[cur];
     const AsgBeam& B = beams[cur];
-    if (tid < k) write_result<LM>(B, tid < m ? tid : -1, (int64_t)n * k + tid, T, w, out_score, out_len, out_labels, out_lm);
+    int src = tid, mout = m;                               // slot tid of the output holds beam member src (if tid < mout)
+    if constexpr (LEX) {
+        // complete_only: the members whose partial word is empty or a whole word, in rank order (all of them if there is none)
+        if (wave == 0 && lex.complete_only) {
+            const uint64_t done = __ballot(tid < m && lex_complete(lex, lex_trie[cur][tid]));
+            if (done) {
+                mout = __popcll(done);
+                uint64_t rest = done;                      // the tid-th set bit
+                for (int j = 0; j < tid && rest; ++j) rest &= rest - 1;
+                src = rest ? __ffsll((unsigned long long)rest) - 1 : 0;
+            }
+        }
+    }
+    if (tid < k)
+        write_result<LM>(B, tid < mout ? src : -1, (int64_t)n * k + tid, T, w, out_score, out_len, out_labels, out_lm);
     if (tid == 0) out_status[n] = s_bad;
 }
 
@@ -325,47 +390,96 @@ bool search_range(int N, int T, int A, int k) {
     return N > 0 && T > 0 && T < (1 << 24) && A >= 1 && A <= AB_AMAX && k >= 1 && k <= AB_KMAX && (int64_t)k * T < (1 << 29);
 }
 
+// what the eight instantiations are launched with: the arguments checked, the tables in their device form
+struct AsgSearch {
+    const float* x;
+    const float* transitions;
+    const int32_t* sizes;
+    int N, T, A, repeat_index, k;
+    double beta, prune;
+    AsgLabelInfo info;
+    void* workspace;
+    int64_t ws_per_utt;
+    void* out;
+    void* stream;
+    LmArgs lm;
+    LexArgs lex;
+    HotArgs hot;
+};
+
+template <bool LM, bool LEX, bool HOT>
+int launch_search(const char* name, const AsgSearch& s) {
+    const int64_t lds = lds_bytes(s.k, s.A);
+    if (int rc = lds_args(name, (const void*)asg_beam_search_kernel<LM, LEX, HOT>, lds, s.k, s.A)) return rc;
+    const OutSections o = out_sections(s.out, s.N, s.T, s.k, LM);
+    hipLaunchKernelGGL((asg_beam_search_kernel<LM, LEX, HOT>), dim3(s.N), dim3(AB_THREADS), (size_t)lds, (hipStream_t)s.stream,
+                       s.x, s.transitions, s.sizes, s.T, s.A, s.info, s.repeat_index, s.k, s.beta, s.prune, (char*)s.workspace,
+                       s.ws_per_utt, hash_capacity(s.T, s.k), o.score, o.len, o.status, o.labels, s.lm, o.lm, s.lex, s.hot);
+    W2L_CHECK_LAUNCH();
+    return 0;
+}
+
 }  // namespace
 
+// Nothing is kept per interned node for a lexicon or for hotwords (see the head of this file): only an LM adds to the workspace.
 extern "C" int64_t w2l_asg_beam_search_workspace_bytes(int N, int T, int A, int k, int order) {
     return search_range(N, T, A, k) ? search_ws_bytes(N, T, k, order, 3) : -1;
 }
 
-extern "C" int w2l_asg_beam_search(const float* x, const float* transitions, const int32_t* sizes, int N, int T, int A,
-                                   const int32_t* label_info_host, int repeat_index, int space_index, int k, double alpha,
-                                   double beta, double prune, const w2l_ngram_lm_t* lm, int order, void* workspace,
-                                   int64_t workspace_bytes, void* out, void* stream) {
+extern "C" int w2l_asg_beam_search_tables(const float* x, const float* transitions, const int32_t* sizes, int N, int T, int A,
+                                          const int32_t* label_info_host, int repeat_index, int space_index, int k,
+                                          double alpha, double beta, double prune, const w2l_ngram_lm_t* lm, int order,
+                                          const w2l_lexicon_t* lexicon, int complete_only, const w2l_lexicon_t* hotwords,
+                                          double hotword_weight, void* workspace, int64_t workspace_bytes, void* out,
+                                          void* stream) {
     const char* name = "asg_beam_search";
-    // every check of the arguments comes before the first HIP call (lds_args)
+    // every check of the arguments comes before the first HIP call (launch_search)
     W2L_CHECK_ARG(x && transitions && label_info_host && workspace && out && N > 0 && T > 0, "%s: bad arguments", name);
     W2L_CHECK_ARG(A >= 1 && A <= AB_AMAX, "%s: %d labels, supported 1..%d", name, A, AB_AMAX);
     W2L_CHECK_ARG(k >= 1 && k <= AB_KMAX, "%s: beam width k=%d, supported 1..%d", name, k, AB_KMAX);
     W2L_CHECK_ARG(repeat_index >= 0 && repeat_index < A, "%s: repeat_index %d outside %d labels", name, repeat_index, A);
     W2L_CHECK_ARG((int64_t)k * T < (1 << 29) && T < (1 << 24), "%s: k*T = %lld too large", name, (long long)k * T);
-    AsgLabelInfo info;
-    if (int rc = label_info_args(name, label_info_host, A, info.v, AB_AMAX)) return rc;
-    LmArgs a{};
-    if (lm) {
+    AsgSearch s{x, transitions, sizes, N, T, A, repeat_index, k, beta, prune};
+    if (int rc = label_info_args(name, label_info_host, A, s.info.v, AB_AMAX)) return rc;
+    if (lm || lexicon || hotwords)
         if (int rc = space_args(name, label_info_host, A, space_index)) return rc;
-        if (int rc = lm_args(name, space_index, alpha, lm, order, T, k, 3, &a)) return rc;
+    if (lm)
+        if (int rc = lm_args(name, space_index, alpha, lm, order, T, k, 3, &s.lm)) return rc;
+    if (lexicon) {
+        if (int rc = trie_args(name, "lexicon", space_index, lexicon, &s.lex)) return rc;
+        s.lex.complete_only = complete_only != 0;
+    }
+    if (hotwords) {
+        W2L_CHECK_ARG(std::isfinite(hotword_weight), "%s: the hotword weight is not finite", name);
+        if (int rc = trie_args(name, "hotword", space_index, hotwords, &s.hot)) return rc;
+        s.hot.gamma = hotword_weight;
     }
     const int64_t need = w2l_asg_beam_search_workspace_bytes(N, T, A, k, lm ? order : 0);
     W2L_CHECK_ARG(need > 0 && workspace_bytes >= need, "%s: workspace of %lld bytes, %lld needed", name,
                   (long long)workspace_bytes, (long long)need);
-    const void* kern = lm ? (const void*)asg_beam_search_kernel<true> : (const void*)asg_beam_search_kernel<false>;
-    const int64_t lds = lds_bytes(k, A);
-    if (int rc = lds_args(name, kern, lds, k, A)) return rc;
-    const OutSections o = out_sections(out, N, T, k, lm != nullptr);
-    const int64_t ws_per_utt = lm ? lm_ws_stride(T, k, 3) : ws_stride(T, k, 3);
-    auto launch = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, dim3(N), dim3(AB_THREADS), (size_t)lds, (hipStream_t)stream, x, transitions, sizes, T, A, info,
-                           repeat_index, k, beta, prune, (char*)workspace, ws_per_utt, hash_capacity(T, k), o.score, o.len,
-                           o.status, o.labels, a, o.lm);
-    };
-    if (lm) launch(asg_beam_search_kernel<true>);
-    else launch(asg_beam_search_kernel<false>);
-    W2L_CHECK_LAUNCH();
-    return 0;
+    s.workspace = workspace;
+    s.ws_per_utt = lm ? lm_ws_stride(T, k, 3) : ws_stride(T, k, 3);
+    s.out = out;
+    s.stream = stream;
+    switch ((lm ? 4 : 0) | (lexicon ? 2 : 0) | (hotwords ? 1 : 0)) {          // the one dispatch: a NULL table is a false flag
+        case 0: return launch_search<false, false, false>(name, s);
+        case 1: return launch_search<false, false, true>(name, s);
+        case 2: return launch_search<false, true, false>(name, s);
+        case 3: return launch_search<false, true, true>(name, s);
+        case 4: return launch_search<true, false, false>(name, s);
+        case 5: return launch_search<true, false, true>(name, s);
+        case 6: return launch_search<true, true, false>(name, s);
+        default: return launch_search<true, true, true>(name, s);
+    }
+}
+
+// the search without a lexicon and without hotwords: the symbol that predates the two tables, kept for its positional callers
+extern "C" int w2l_asg_beam_search(const float* x, const float* transitions, const int32_t* sizes, int N, int T, int A,
+                                   const int32_t* label_info_host, int repeat_index, int space_index, int k, double alpha,
+                                   double beta, double prune, const w2l_ngram_lm_t* lm, int order, void* workspace,
+                                   int64_t workspace_bytes, void* out, void* stream) {
+    return w2l_asg_beam_search_tables(x, transitions, sizes, N, T, A, label_info_host, repeat_index, space_index, k, alpha, beta,
+                                      prune, lm, order, nullptr, 1, nullptr, 0.0, workspace, workspace_bytes, out, stream);
 }
 
 // ============================================================================================================ alignment

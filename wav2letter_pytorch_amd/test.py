@@ -15,8 +15,9 @@ trained with ``model.criterion=asg`` (asg_beam.py), bound to the checkpoint's le
 list, one word per line; ``decoder=beam|beam_lm``) or ``lexicon_from_lm=true`` (the model's vocabulary; ``decoder=beam_lm``)
 constrains the beam search to strings of lexicon words (lexicon.py).  ``hotwords_path=`` (a word list, one single word per
 line; ``decoder=beam|beam_lm``) makes the beam search prefer those words by ``hotword_weight=`` natural-log units per matched
-character (default 1.0: a convention, not a tuned value) without forbidding anything else.  Neither is built for the ASG
-beam searches."""
+character (default 1.0: a convention, not a tuned value) without forbidding anything else.  The ASG beam searches have both
+(``lexicon=`` / ``hotwords=`` of asg_beam.ASGBeamSearchDecoder / ASGBeamSearchLMDecoder), but this command does not take the
+keys with ``decoder=asg_beam|asg_beam_lm`` yet: it refuses them."""
 from __future__ import annotations
 
 import json
@@ -64,7 +65,8 @@ def build_config(argv):
             continue
         if cfg.decoder in ASG_DECODERS:
             raise SystemExit(f'{key} is given but decoder={cfg.decoder}: the lexicon constraint is not built for ASG beam '
-                             'search (decoder=beam|beam_lm have it)')
+                             'search in this command (ASGBeamSearchDecoder / ASGBeamSearchLMDecoder take lexicon=; '
+                             'decoder=beam|beam_lm have the key)')
         if cfg.decoder not in LEXICON_DECODERS:
             raise SystemExit(f'{key} is given but decoder={cfg.decoder}: a lexicon constrains a beam search '
                              '(decoder=beam or decoder=beam_lm)')
@@ -80,7 +82,8 @@ def build_config(argv):
             continue
         if cfg.decoder in ASG_DECODERS:
             raise SystemExit(f'{key} is given but decoder={cfg.decoder}: hotword boosting is not built for ASG beam search '
-                             '(decoder=beam|beam_lm have it)')
+                             'in this command (ASGBeamSearchDecoder / ASGBeamSearchLMDecoder take hotwords=; '
+                             'decoder=beam|beam_lm have the key)')
         if cfg.decoder not in LEXICON_DECODERS:
             raise SystemExit(f'{key} is given but decoder={cfg.decoder}: hotwords bias a beam search '
                              '(decoder=beam or decoder=beam_lm)')
