@@ -165,48 +165,62 @@ int w2l_conv_plan_fp8(int N, int Cin, int Cout, int Tout, int Kw, int dil, int s
  * dw[kw][co][ci] (+)= sum_{n,t} dy[n][t][co] * xp[n][t*stride + kw*dil][ci]
  * dy: bf16, pointer at utterance 0 row 0, dy_bstride elements between utterances; rows
  * [Tout, roundup(Tout,64)) of every utterance must be zero (shared-halo layout with halo >= that).
- * dw fp32 [Kw][Cout][Cin].  accumulate=1 adds to dw (fp32 atomics).  With accumulate=0 the
- * library may still split the (n,t) reduction over blocks and combine with atomics: when
- * w2l_wgrad_needs_zero() != 0 the caller must zero-fill dw first. */
-int w2l_wgrad_needs_zero(int N, int Cin, int Cout, int Tout, int Kw);
-int w2l_conv1d_wgrad(const void* dy, int64_t dy_bstride, const void* xp, int64_t x_bstride, int64_t x_rows_total,
-                     float* dw, int N, int Cin, int Cout, int Tout, int Kw, int stride, int dil, int accumulate,
-                     void* stream);
-
-/* The weight gradient with a split-K workspace (device memory owned by the caller, >= 64 KiB, zero-filled once when
- * allocated; one per stream of execution): the partial tiles of a split reduction go through fp32 slabs and the block
- * that draws a tile's last ticket sums them in split order and writes dw with plain stores -- no atomics, no zero-filled
- * dw, bit-reproducible gradients.  A workspace too small for the chosen split falls back to the atomic path:
- * w2l_wgrad_needs_zero_ws tells whether dw must be zero-filled for this launch. */
+ * dw fp32 [Kw][Cout][Cin].  accumulate=1 adds to dw (fp32 atomics).
+ *
+ * The ladder of entry points.  The GENERAL calls are w2l_conv1d_wgrad_ws (launch), w2l_conv1d_wgrad_tune_x (measure) and
+ * w2l_wgrad_needs_zero_x (query); the others are shorthands of them:
+ *   w2l_conv1d_wgrad         = _ws without a workspace
+ *   w2l_conv1d_wgrad_tune_ws = _tune_x with flags 0;   w2l_conv1d_wgrad_tune = _tune_ws without a workspace
+ *   w2l_wgrad_needs_zero_ws  = _needs_zero_x of a stride-1, dilation-1 layer;   w2l_wgrad_needs_zero = that without a workspace
+ * The library may split the (n,t) reduction over blocks.  Without a workspace the partial tiles are combined with fp32
+ * atomics: where the needs_zero query says so, the caller must zero-fill dw first (also with accumulate=0).  With a
+ * workspace (device memory owned by the caller, >= 64 KiB, zero-filled once when allocated; one per stream of execution;
+ * w2l_wgrad_workspace_bytes covers every classic split) the partial tiles go through fp32 slabs and the block that draws a
+ * tile's last ticket sums them in split order and writes dw with plain stores -- no atomics, no zero-filled dw,
+ * bit-reproducible gradients.  A workspace too small for the chosen split falls back to the atomic path.
+ * Dealt stream-K (plan bit 5, the plan's count = the number of ranges G) needs the workspace too
+ * (w2l_wgrad_dealt_workspace_bytes): the (tile, K step) space of the launch is cut into G equal ranges, one per resident
+ * block slot (512 / 256), so the chip is full whatever the tile count.  A range crosses at most one tile boundary; each of
+ * its one or two segments is a block of its own (the kernel stays the one-segment kernel): the first G blocks take the first
+ * segments, the following blocks the second segments LONGEST FIRST, so the slot that frees first gets the longest remainder.
+ * Partial tiles go through slabs, the last arriver of a tile sums them in range order: no atomics, bit-reproducible.  A
+ * launch without the workspace (or of a shape without a dealt form) falls back to an atomic split of 2.
+ * w2l_conv1d_wgrad_tune_x flags: bit 0 = classic split / stream-K plans are measured and run with fp32 atomics although a
+ * workspace is given (plan bit 6) -- the workspace then only serves dealt plans.
+ *
+ * Host-only queries (no GPU needed, not replayable):
+ * w2l_wgrad_plan: the plan a launch of this shape starts from (forced, measured, or the cost model's), before it is narrowed
+ * to the layer: form bits (see w2l_wgrad_force_plan) | split / range count << 8.
+ * w2l_wgrad_launch_plan: what a launch of this problem runs as -- the counterpart of w2l_conv_plan.  Forcing is an argument
+ * (forced_splits 0 / forced_order -1: automatic); the per-thread hook is neither read nor touched.  out[W2L_WGRAD_PLAN_FIELDS]:
+ * split count, K steps per split, K steps per utterance, K steps in all, block order, stream-K, two tap groups, 32x32x16,
+ * three taps, taps per wave, taps per block, tap groups, tiles, dealt ranges G (0: not dealt), second-segment blocks, slabs,
+ * atomic, needs_zero, x window rows in LDS, LDS bytes, grid x, grid y, block threads, 1.  A refused launch: nonzero return,
+ * out all 0.
+ * w2l_wgrad_dealt_segments (testing): the blocks of a dealt launch in launch order, six ints each (range, tile,
+ * first step, end step, place among the tile's segments, number of them); returns the block count, -1: no dealt form. */
 int w2l_conv1d_wgrad_ws(const void* dy, int64_t dy_bstride, const void* xp, int64_t x_bstride, int64_t x_rows_total, float* dw,
                         int N, int Cin, int Cout, int Tout, int Kw, int stride, int dil, int accumulate, void* ws,
                         int64_t ws_bytes, void* stream);
-int w2l_conv1d_wgrad_tune_ws(const void* dy, int64_t dy_bstride, const void* xp, int64_t x_bstride, int64_t x_rows_total,
-                             float* dw_scratch, int N, int Cin, int Cout, int Tout, int Kw, int stride, int dil, int reps,
-                             void* ws, int64_t ws_bytes, void* stream);
-int w2l_wgrad_needs_zero_ws(int N, int Cin, int Cout, int Tout, int Kw, int64_t ws_bytes);
-int64_t w2l_wgrad_workspace_bytes(int Cin, int Cout, int Kw);
-
-/* Dealt stream-K (round 5; plan order bit 5, the plan's split field = the number of ranges G): the (tile, K step) space of
- * the launch is cut into G equal ranges, one per resident block slot (512 / 256), so the chip is full whatever the tile
- * count.  A range crosses at most one tile boundary; each of its one or two segments is a block of its own (the kernel stays
- * the one-segment kernel): the first G blocks take the first segments, the following blocks the second segments LONGEST FIRST,
- * so the slot that frees first gets the longest remainder.  Partial tiles go through fp32 slabs of the caller's workspace,
- * the last arriver of a tile sums them in range order: no atomics, no zero-filled dw, bit-reproducible.  The plan needs
- * w2l_wgrad_dealt_workspace_bytes(); a launch without it (or of a shape without a dealt form) falls back to an atomic split.
- * w2l_conv1d_wgrad_tune_x = w2l_conv1d_wgrad_tune_ws with flags: bit 0 = classic split / stream-K plans are measured and run
- * with fp32 atomics although a workspace is given (plan order bit 6) -- the workspace then only serves dealt plans.
- * w2l_wgrad_needs_zero_x: must dw be zero-filled for this launch?  Exact (w2l_wgrad_needs_zero_ws assumes stride 1, dilation 1).
- * w2l_wgrad_dealt_segments (host only, testing): the blocks of a dealt launch in launch order, six ints each (range, tile,
- * first step, end step, place among the tile's segments, number of them); returns the block count, -1: no dealt form. */
-int64_t w2l_wgrad_dealt_workspace_bytes(int Cin, int Cout, int Kw);
+int w2l_conv1d_wgrad(const void* dy, int64_t dy_bstride, const void* xp, int64_t x_bstride, int64_t x_rows_total,
+                     float* dw, int N, int Cin, int Cout, int Tout, int Kw, int stride, int dil, int accumulate,
+                     void* stream);
 int w2l_conv1d_wgrad_tune_x(const void* dy, int64_t dy_bstride, const void* xp, int64_t x_bstride, int64_t x_rows_total,
                             float* dw_scratch, int N, int Cin, int Cout, int Tout, int Kw, int stride, int dil, int reps,
                             void* ws, int64_t ws_bytes, int flags, void* stream);
+int w2l_conv1d_wgrad_tune_ws(const void* dy, int64_t dy_bstride, const void* xp, int64_t x_bstride, int64_t x_rows_total,
+                             float* dw_scratch, int N, int Cin, int Cout, int Tout, int Kw, int stride, int dil, int reps,
+                             void* ws, int64_t ws_bytes, void* stream);
 int w2l_wgrad_needs_zero_x(int N, int Cin, int Cout, int Tout, int Kw, int stride, int dil, int64_t ws_bytes);
-int w2l_wgrad_dealt_segments(int tiles, int steps, int ranges, int* out, int max_blocks);
-/* the plan a launch of this problem will take (measured, or the cost model's): order bits | split / range count << 8 */
+int w2l_wgrad_needs_zero_ws(int N, int Cin, int Cout, int Tout, int Kw, int64_t ws_bytes);
+int w2l_wgrad_needs_zero(int N, int Cin, int Cout, int Tout, int Kw);
+int64_t w2l_wgrad_workspace_bytes(int Cin, int Cout, int Kw);
+int64_t w2l_wgrad_dealt_workspace_bytes(int Cin, int Cout, int Kw);
 int w2l_wgrad_plan(int N, int Cin, int Cout, int Tout, int Kw);
+#define W2L_WGRAD_PLAN_FIELDS 24
+int w2l_wgrad_launch_plan(int N, int Cin, int Cout, int Tout, int Kw, int stride, int dil, int64_t ws_bytes, int forced_splits,
+                          int forced_order, int* out);
+int w2l_wgrad_dealt_segments(int tiles, int steps, int ranges, int* out, int max_blocks);
 
 /* A GROUP of layers' weight gradients in ONE launch (round 5): layers of the same N, Tout, stride 1 and dilation (any Cin,
  * Cout, Kw) whose [128 co x 128 ci] x tap-group tiles form one pool of equal-shaped work items -- layers whose own tile

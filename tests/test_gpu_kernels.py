@@ -599,6 +599,88 @@ def test_conv_wgrad_every_plan(L, Kw, s, d):
             L.lib.w2l_wgrad_force_plan(0, -1)
 
 
+def test_wgrad_launch_plan_query_is_what_the_launch_runs(L):
+    """w2l_wgrad_launch_plan against the launch, on the split test's shape (18 two-tap tiles x 18 K steps).  The forced plans are
+    picked so that tests/golden/wgrad_plans.json (pinned on the host by test_cpu_wgrad_plan.py) says every path of the launcher
+    occurs; per plan the query's needs_zero must be w2l_wgrad_needs_zero_x's, a launch that needs no zero fill must overwrite
+    a NaN-filled dw, one that does runs over zeros, both within the other tests' 2e-3 of autograd, tickets back at zero.  Then
+    one w2l_conv1d_wgrad_tune_x: it must remember a plan and leave the w2l_wgrad_force_plan hook automatic -- the next
+    automatic launch takes the remembered plan."""
+    import json
+    import os
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'wgrad_plans.json')) as f:
+        golden = json.load(f)
+    N, Cin, Cout, T, Kw, s, d, pl, pr = 3, 192, 320, 333, 7, 1, 1, 4, 4
+    x, w, b = conv_inputs(N, Cin, Cout, Kw, T, pl, pr, 12)
+    xp = to_ntc_padded(x, pl, pr, 1)
+    rows = xp.shape[1]
+    Tout = rows - (Kw - 1) * d
+    shape = (N, Cin, Cout, Tout, Kw, s, d)
+    dy = torch.randn(N, Cout, Tout, generator=torch.Generator().manual_seed(13))
+    hb = (Kw - 1) * d
+    dyp = to_ntc_padded(dy, hb, max(hb, (Tout + 63) // 64 * 64 - Tout), 0, Cout)
+    drows = dyp.shape[1]
+    dyh, xh = dyp.to(torch.bfloat16).cuda(), xp.to(torch.bfloat16).cuda()
+    wr = bf(w).requires_grad_(True)
+    F.conv1d(F.pad(bf(x), (pl, pr), mode='reflect'), wr, None, stride=s, dilation=d).backward(bf(dy))
+    full = max(int(L.lib.w2l_wgrad_workspace_bytes(Cin, Cout, Kw)), int(L.lib.w2l_wgrad_dealt_workspace_bytes(Cin, Cout, Kw)))
+    ws = torch.zeros(full, dtype=torch.uint8, device='cuda')
+    sweeps = {sw['ws']: sw for sw in golden['sweeps'] if tuple(sw['shape']) == shape}
+    assert set(sweeps) == {0, full}
+    fields, counts = golden['fields'], golden['counts']
+
+    def query(with_ws, splits, order):
+        out = (C.c_int * 24)()
+        assert L.lib.w2l_wgrad_launch_plan(*shape, full if with_ws else 0, splits, order, out) == 0 and out[23] == 1
+        return dict(zip(fields, list(out)[:23]))
+
+    def launch(with_ws, dw):
+        L.check(L.lib.w2l_conv1d_wgrad_ws(C.c_void_p(dyh.data_ptr() + hb * Cout * 2), drows * Cout, L.ptr(xh), rows * Cin, N * rows,
+                                          L.ptr(dw), *shape, 0, L.ptr(ws) if with_ws else None, full if with_ws else 0, L.stream_ptr()))
+        torch.cuda.synchronize()
+
+    # (workspace, count, order) -> the path it must take
+    plans = [((True, 1, 1), 'unsplit'), ((True, 3, 1), 'slabs'), ((False, 3, 0), 'atomic'), ((True, 3, 65), 'atomic'),
+             ((False, 1, 3), 'streamk4'), ((False, 1, 7), 'streamk8'), ((True, 97, 33), 'dealt'), ((True, 97, 37), 'dealt'),
+             ((True, 512, 33), 'fallback'), ((True, 1, 17), 'taps3'), ((True, 2, 21), 'taps6'), ((True, 1, 9), 'm32'),
+             ((False, 5, 8), 'm32')]
+    for (with_ws, splits, order), path in plans:
+        r = query(with_ws, splits, order)
+        sw = sweeps[full if with_ws else 0]
+        assert list(r.values()) == golden['rows'][sw['refs'][sw['per_order'][order]][counts.index(splits)] - 1], (splits, order)
+        assert {'unsplit': r['splits'] == 1 and not r['streamk'] and not r['G'] and r['kwblk'] == 2 and not r['m32'],
+                'slabs': r['slabs'] and r['splits'] == 3 and not r['G'],
+                'atomic': r['atomic'] and r['splits'] == 3,
+                'streamk4': r['streamk'] and r['threads'] == 256, 'streamk8': r['streamk'] and r['threads'] == 512,
+                'dealt': r['G'] == 97 and r['grid_x'] == 97 + r['dealt_b'] and r['slabs'],
+                'fallback': r['G'] == 0 and r['splits'] == 2 and r['slabs'],
+                'taps3': r['taps3'] and r['kwblk'] == 3, 'taps6': r['taps3'] and r['kwblk'] == 6 and r['splits'] == 2,
+                'm32': r['m32'] and r['kwb'] == 2}[path], (path, r)
+        L.lib.w2l_wgrad_force_plan(splits, order)
+        try:
+            assert r['needs_zero'] == L.lib.w2l_wgrad_needs_zero_x(*shape, full if with_ws else 0), (splits, order)
+            dw = torch.zeros(Kw, Cout, Cin, device='cuda') if r['needs_zero'] else torch.full((Kw, Cout, Cin), float('nan'), device='cuda')
+            launch(with_ws, dw)
+        finally:
+            L.lib.w2l_wgrad_force_plan(0, -1)
+        assert not torch.isnan(dw).any(), (splits, order)
+        assert relerr(dw.cpu().permute(1, 2, 0), wr.grad) < 2e-3, (splits, order, relerr(dw.cpu().permute(1, 2, 0), wr.grad))
+        assert not ws[:65536].any(), (splits, order)
+    # the tuner: candidates are arguments of plan() / run(), the hook is not its channel any more
+    scratch = torch.empty(Kw, Cout, Cin, device='cuda')
+    L.check(L.lib.w2l_conv1d_wgrad_tune_x(C.c_void_p(dyh.data_ptr() + hb * Cout * 2), drows * Cout, L.ptr(xh), rows * Cin, N * rows,
+                                          L.ptr(scratch), *shape, 1, L.ptr(ws), full, 1, L.stream_ptr()))
+    torch.cuda.synchronize()
+    tuned = L.lib.w2l_wgrad_plan(*shape[:5])
+    assert tuned >> 8 >= 1 and not ws[:65536].any()
+    auto, same = query(True, 0, -1), query(True, tuned >> 8, tuned & 0xff)
+    assert auto == same, (tuned, auto, same)
+    dw = torch.zeros(Kw, Cout, Cin, device='cuda') if auto['needs_zero'] else torch.full((Kw, Cout, Cin), float('nan'), device='cuda')
+    assert auto['needs_zero'] == L.lib.w2l_wgrad_needs_zero_x(*shape, full)
+    launch(True, dw)
+    assert relerr(dw.cpu().permute(1, 2, 0), wr.grad) < 2e-3 and not ws[:65536].any(), tuned
+
+
 def test_wgrad_slabs_stress_bit_exact(L):
     """the slab + ticket reduction of the split weight gradients (classic split and dealt stream-K) under load: 240 launches
     back to back on a side stream, alternating between two inputs so that every launch re-writes every slab with OTHER

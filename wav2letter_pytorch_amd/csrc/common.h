@@ -105,6 +105,20 @@ void w2l_set_error(const char* fmt, ...);
     } while (0)
 #define W2L_CHECK_LAUNCH() W2L_CHECK_HIP(hipGetLastError())
 
+// the start / stop events of a measuring entry point: destroyed on every return path
+struct W2lEventPair {
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    int create() {
+        W2L_CHECK_HIP(hipEventCreate(&e0));
+        W2L_CHECK_HIP(hipEventCreate(&e1));
+        return 0;
+    }
+    ~W2lEventPair() {
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+    }
+};
+
 // ---- diagnostic hook points.  Empty here, i.e. in every shipped build; tools/ablate_igemm.py and tools/stamp_wgrad.py build
 // experiment libraries that force-include csrc/diag/hooks.h, which defines bodies for them first. ----
 #ifndef W2L_DIAG_SKIP_DMA

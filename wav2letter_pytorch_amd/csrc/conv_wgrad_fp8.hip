@@ -280,19 +280,18 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_fp8_kernel(WgradF8Params p)
 typedef std::tuple<int, int, int, int, int> F8ShapeKey;
 std::map<F8ShapeKey, int> g_f8_tuned;          // shape -> split count | block order << 16
 std::mutex g_f8_mu;
-thread_local int g_f8_force_splits = 0;        // set by the tuner around its own launches only
-thread_local int g_f8_force_order = -1;
 
-int f8_plan(int N, int Cin, int Cout, int Tout, int Kw, int* order_out) {
+// force_splits > 0 / force_order >= 0: the tuner's candidate (0 / -1: what was measured, else the rule below)
+int f8_plan(int N, int Cin, int Cout, int Tout, int Kw, int force_splits, int force_order, int* order_out) {
     const int tsteps = (Tout + BT - 1) / BT;
     const int total = N * tsteps;
-    *order_out = g_f8_force_order >= 0 ? g_f8_force_order : 1;
-    if (g_f8_force_splits > 0) return g_f8_force_splits <= total ? g_f8_force_splits : total;
+    *order_out = force_order >= 0 ? force_order : 1;
+    if (force_splits > 0) return force_splits <= total ? force_splits : total;
     {
         std::lock_guard<std::mutex> lock(g_f8_mu);
         auto it = g_f8_tuned.find(F8ShapeKey(N, Cin, Cout, Tout, Kw));
         if (it != g_f8_tuned.end()) {
-            if (g_f8_force_order < 0) *order_out = it->second >> 16;
+            if (force_order < 0) *order_out = it->second >> 16;
             return it->second & 0xffff;
         }
     }
@@ -311,16 +310,9 @@ int f8_plan(int N, int Cin, int Cout, int Tout, int Kw, int* order_out) {
     return best;
 }
 
-}  // namespace
-
-extern "C" int w2l_wgrad_fp8_needs_zero(int N, int Cin, int Cout, int Tout, int Kw) {
-    int order = 0;
-    return f8_plan(N, Cin, Cout, Tout, Kw, &order) > 1;
-}
-
-extern "C" int w2l_conv1d_wgrad_fp8(const void* dyq, int64_t dy_bstride, const void* xq, int64_t x_bstride,
-                                    int64_t x_rows_total, float* dw, int N, int Cin, int Cout, int Tout, int Kw, int dil,
-                                    float descale, const float* descale_dev, int accumulate, void* stream) {
+int f8_launch(const void* dyq, int64_t dy_bstride, const void* xq, int64_t x_bstride, int64_t x_rows_total, float* dw, int N,
+              int Cin, int Cout, int Tout, int Kw, int dil, float descale, const float* descale_dev, int accumulate,
+              int force_splits, int force_order, void* stream) {
     W2L_CHECK_ARG(dyq && xq && dw, "conv1d_wgrad_fp8: null pointer");
     W2L_CHECK_ARG(N > 0 && Tout > 0 && Kw > 0 && dil > 0, "conv1d_wgrad_fp8: bad sizes");
     W2L_CHECK_ARG(Cin % 64 == 0 && Cout % 64 == 0 && Cin > 0 && Cout > 0,
@@ -344,7 +336,7 @@ extern "C" int w2l_conv1d_wgrad_fp8(const void* dyq, int64_t dy_bstride, const v
     p.tsteps = (Tout + BT - 1) / BT;
     p.total_steps = N * p.tsteps;
     int order = 1;
-    const int splits = f8_plan(N, Cin, Cout, Tout, Kw, &order);
+    const int splits = f8_plan(N, Cin, Cout, Tout, Kw, force_splits, force_order, &order);
     p.order = order & 1;
     p.steps_per_split = (p.total_steps + splits - 1) / splits;
     p.atomic = splits > 1;
@@ -364,6 +356,20 @@ extern "C" int w2l_conv1d_wgrad_fp8(const void* dyq, int64_t dy_bstride, const v
     return 0;
 }
 
+}  // namespace
+
+extern "C" int w2l_wgrad_fp8_needs_zero(int N, int Cin, int Cout, int Tout, int Kw) {
+    int order = 0;
+    return f8_plan(N, Cin, Cout, Tout, Kw, 0, -1, &order) > 1;
+}
+
+extern "C" int w2l_conv1d_wgrad_fp8(const void* dyq, int64_t dy_bstride, const void* xq, int64_t x_bstride,
+                                    int64_t x_rows_total, float* dw, int N, int Cin, int Cout, int Tout, int Kw, int dil,
+                                    float descale, const float* descale_dev, int accumulate, void* stream) {
+    return f8_launch(dyq, dy_bstride, xq, x_bstride, x_rows_total, dw, N, Cin, Cout, Tout, Kw, dil, descale, descale_dev, accumulate,
+                     0, -1, stream);
+}
+
 // Measure split counts x block orders for this problem and remember the fastest (SYNCHRONISING; warm-up only).
 extern "C" int w2l_conv1d_wgrad_fp8_tune(const void* dyq, int64_t dy_bstride, const void* xq, int64_t x_bstride,
                                          int64_t x_rows_total, float* dw_scratch, int N, int Cin, int Cout, int Tout, int Kw,
@@ -373,9 +379,8 @@ extern "C" int w2l_conv1d_wgrad_fp8_tune(const void* dyq, int64_t dy_bstride, co
         std::lock_guard<std::mutex> lock(g_f8_mu);
         if (g_f8_tuned.count(key)) return 0;
     }
-    hipEvent_t e0, e1;
-    W2L_CHECK_HIP(hipEventCreate(&e0));
-    W2L_CHECK_HIP(hipEventCreate(&e1));
+    W2lEventPair ev;
+    if (int rc = ev.create()) return rc;
     hipStream_t st = (hipStream_t)stream;
     const int total = N * ((Tout + BT - 1) / BT);
     const int cands[] = {1, 2, 3, 4, 5, 6, 8, 10, 12, 16};
@@ -386,27 +391,21 @@ extern "C" int w2l_conv1d_wgrad_fp8_tune(const void* dyq, int64_t dy_bstride, co
     for (int ci = 0; ci < 2 * (int)(sizeof(cands) / sizeof(cands[0])); ++ci) {
         const int s = cands[ci >> 1], order = ci & 1;
         if (s > total || (s > 1 && total / s < 4)) break;
-        g_f8_force_splits = s;
-        g_f8_force_order = order;
-        int rc = w2l_conv1d_wgrad_fp8(dyq, dy_bstride, xq, x_bstride, x_rows_total, dw_scratch, N, Cin, Cout, Tout, Kw, dil,
-                                      1.0f, nullptr, 0, stream);
+        int rc = f8_launch(dyq, dy_bstride, xq, x_bstride, x_rows_total, dw_scratch, N, Cin, Cout, Tout, Kw, dil, 1.0f, nullptr, 0,
+                           s, order, stream);
         if (rc != 0) continue;
-        (void)hipEventRecord(e0, st);
+        (void)hipEventRecord(ev.e0, st);
         for (int r = 0; r < reps; ++r) {
             if (s > 1) (void)hipMemsetAsync(dw_scratch, 0, bytes, st);          // the fill is part of a split launch's cost
-            w2l_conv1d_wgrad_fp8(dyq, dy_bstride, xq, x_bstride, x_rows_total, dw_scratch, N, Cin, Cout, Tout, Kw, dil, 1.0f,
-                                 nullptr, 0, stream);
+            f8_launch(dyq, dy_bstride, xq, x_bstride, x_rows_total, dw_scratch, N, Cin, Cout, Tout, Kw, dil, 1.0f, nullptr, 0, s,
+                      order, stream);
         }
-        (void)hipEventRecord(e1, st);
-        if (hipEventSynchronize(e1) != hipSuccess) continue;
+        (void)hipEventRecord(ev.e1, st);
+        if (hipEventSynchronize(ev.e1) != hipSuccess) continue;
         float ms = 0.f;
-        if (hipEventElapsedTime(&ms, e0, e1) != hipSuccess) continue;
+        if (hipEventElapsedTime(&ms, ev.e0, ev.e1) != hipSuccess) continue;
         if (ms < best_ms) { best_ms = ms; best = s | (order << 16); }
     }
-    g_f8_force_splits = 0;
-    g_f8_force_order = -1;
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
     W2L_CHECK_ARG(best >= 1, "conv1d_wgrad_fp8_tune: no candidate ran");
     std::lock_guard<std::mutex> lock(g_f8_mu);
     g_f8_tuned[key] = best;

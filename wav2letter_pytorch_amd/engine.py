@@ -2254,12 +2254,15 @@ class StackEngine:
                                                job.x_rows_total, ptr(dw), N, pk.cinp, pk.coutp, job.Tout, kw, conv.dilation,
                                                1.0 / src.q_scale, ptr(f8[1]), 0, st), 'w2l_conv1d_wgrad_fp8')
         elif not self.precise:
-            # (which kernel family: the three-tap AGPR code object -- plan order bit 4 on a stride-1, dilation <= 4 layer -- or the
-            # two-tap kernels; bench.py reports the two populations side by side)
+            # (which kernel family: the three-tap AGPR code object or the two-tap kernels -- the launcher's own answer for this
+            # launch, w2l_wgrad_launch_plan's taps3 field; bench.py reports the two populations side by side)
             label = 'conv_wgrad_kernel'
-            if KERNEL_TIMER is not None and conv.stride == 1 and conv.dilation <= 4 and kw >= 3 and \
-                    lib.w2l_wgrad_plan(N, pk.cinp, pk.coutp, job.Tout, kw) & 16:
-                label = 'conv_wgrad3_kernel'
+            if KERNEL_TIMER is not None:
+                out = (C.c_int * 24)()
+                lib.w2l_wgrad_launch_plan(N, pk.cinp, pk.coutp, job.Tout, kw, conv.stride, conv.dilation,
+                                          ws.numel() if ws is not None else 0, 0, -1, out)
+                if out[8]:
+                    label = 'conv_wgrad3_kernel'
             with _timed(label, job.flops):
                 run(job.dy_hi, src.hi, 0)
         else:
