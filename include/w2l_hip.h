@@ -845,6 +845,48 @@ int w2l_mix_noise(const float* x, int64_t x_stride, const float* z, int64_t z_st
                   const int32_t* rows_host, const int32_t* rows_dev, const float* snr_db, double* slab, int64_t slab_doubles,
                   void* stream);
 
+/* ---- voice activity detection and segmentation of long recordings (segmentation.py; no reference counterpart: the reference
+ * has no long-form path).  The rule is stated in DESIGN.md ("Long-form transcription") and restated by tests/vad_refs.py. ----
+ * w2l_vad_power: x [N][x_stride] fp32 (device, row n valid up to lens_dev[n] samples; a length outside [0, x_stride] is
+ *   clamped) -> power [N][power_stride] fp32:  F_n = ceil(len_n / hop) frames,
+ *     power[n][f] = float( (sum_{i in [f hop, min(len_n, f hop + win))} double(x[i])^2) / win )   for f < F_n, 0 for f >= F_n,
+ *   the sum in fp64 in a fixed order (a frame's samples in eight slices, each added sample after sample by one lane, the slice
+ *   sums added in slice order): two calls give identical bits, and the result is within (win + 2) 2^-53 relative of the
+ *   sequential sum before the rounding to fp32.  One launch, grid (run of 64 frames, recording); a block stages its frames'
+ *   samples in LDS with 16-byte loads (at most W2L_VAD_MAX_SPAN floats), so a sample is read from memory once.  Rejected: null pointers, N outside [1, 65535],
+ *   hop < 1 or hop > win, win > W2L_VAD_MAX_SPAN - 8, power_stride outside [1, 2^24) or below ceil(x_stride / hop).
+ * w2l_vad_segments: power [N][power_stride] and nframes_dev [N] (clamped to [0, power_stride]) -> out, one record of
+ *   W2L_VAD_HEADER_BYTES + 8 cap bytes per recording:
+ *     int32 count   segments the rule yields (also when that exceeds cap; only the first cap are written)
+ *     int32 status  bit 0: count > cap;  bit 1: a power was NaN or negative (such a power is read as 0 throughout)
+ *     double thr_on, thr_off;  float floor, peak;  int32 seg[cap][2]   half-open frame ranges, ascending
+ *   One launch, one workgroup of 1024 threads per recording, no dependence between workgroups; workspace (device, caller-owned):
+ *   at least w2l_vad_workspace_bytes(N, power_stride) bytes, contents undefined before and after.  Rejected (nothing is launched):
+ *   null pointers, N outside [1, 65535], power_stride outside [1, 2^24), q outside [0, 1], max_frames < 2, a frame count
+ *   outside [0, 2^24], non-finite ratios / abs_min, r_on <= 0, r_hyst outside (0, 1], absolute thresholds that are not finite
+ *   or have thr_off > thr_on, cap outside [1, 2^24], a short workspace, out not 8-byte aligned.
+ * Neither is a replay entry.  Call site: segmentation.vad_segments (ConvCTCASR.transcribe_long). */
+#define W2L_VAD_MAX_SPAN 12288
+#define W2L_VAD_HEADER_BYTES 32
+typedef struct {
+    double q;                /* floor = the floor(q (F - 1))-th smallest power */
+    double r_on;             /* adaptive: thr_on = max(abs_min, min(floor * r_on, sqrt(floor * peak))), in double */
+    double r_hyst;           /* adaptive: thr_off = thr_on * r_hyst */
+    double abs_min;
+    double thr_on, thr_off;  /* absolute != 0: the thresholds themselves (floor and peak are still reported) */
+    int32_t absolute;
+    int32_t min_silence;     /* frames: a gap shorter than this joins its neighbours */
+    int32_t min_speech;      /* frames: a run shorter than this is dropped (after closing gaps) */
+    int32_t pad;             /* frames added on both sides of a run (after dropping), clipped; touching runs merge */
+    int32_t max_frames;      /* a longer run is cut at the lowest index of the minimum power over [a + h, min(a + max_frames, b - h)), h = max_frames / 2 */
+    int32_t reserved_;
+} w2l_vad_params_t;
+int w2l_vad_power(const float* x, int64_t x_stride, const int32_t* lens_dev, int N, int win, int hop, float* power,
+                  int64_t power_stride, void* stream);
+int64_t w2l_vad_workspace_bytes(int N, int Fmax);
+int w2l_vad_segments(const float* power, int64_t power_stride, const int32_t* nframes_dev, int N, const w2l_vad_params_t* p, int cap,
+                     void* workspace, int64_t workspace_bytes, void* out, void* stream);
+
 /* ---- stream concurrency probe -----------------------------------------------------------------------------------------
  * Launches a chip-filling spin kernel (`rounds` waves of 2 blocks per CU, `spin_us` each) on stream_a, then a one-wave
  * kernel on stream_b that records when it started.  stamps_dev: 3 x int64, zero before the call (caller synchronises

@@ -79,6 +79,13 @@ class GradSrc(C.Structure):
                 ('pad_mode', C.c_int32), ('rows', C.c_int32)]
 
 
+class VadParams(C.Structure):
+    """w2l_vad_params_t (include/w2l_hip.h): the segmentation rule's numbers, in frames and ratios (segmentation.VadConfig)."""
+    _fields_ = [('q', C.c_double), ('r_on', C.c_double), ('r_hyst', C.c_double), ('abs_min', C.c_double),
+                ('thr_on', C.c_double), ('thr_off', C.c_double), ('absolute', C.c_int32), ('min_silence', C.c_int32),
+                ('min_speech', C.c_int32), ('pad', C.c_int32), ('max_frames', C.c_int32), ('reserved_', C.c_int32)]
+
+
 _SIGNATURES = {
     'w2l_last_error': (C.c_char_p, []),
     'w2l_abi_version': (c_i, []),
@@ -187,6 +194,9 @@ _SIGNATURES = {
     'w2l_feature_normalize': (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_p, c_p, c_p, c_p]),
     'w2l_zero_rects': (c_i, [c_p, c_i, c_i, c_i, c_p, c_i, c_p]),
     'w2l_resample': (c_i, [c_p, c_i64, c_p, c_i64, c_i, c_p, c_p, c_p, c_p, c_i, c_p, c_i64, c_p]),
+    'w2l_vad_power': (c_i, [c_p, c_i64, c_p, c_i, c_i, c_i, c_p, c_i64, c_p]),
+    'w2l_vad_workspace_bytes': (c_i64, [c_i, c_i]),
+    'w2l_vad_segments': (c_i, [c_p, c_i64, c_p, c_i, C.POINTER(VadParams), c_i, c_p, c_i64, c_p, c_p]),
     'w2l_reverb': (c_i, [c_p, c_i64, c_p, c_i64, c_i, c_p, c_p, c_p, c_p, c_i, c_p, c_i64, c_p]),
     'w2l_mix_noise_slab_doubles': (c_i64, [c_i, c_i64]),
     'w2l_mix_noise': (c_i, [c_p, c_i64, c_p, c_i64, c_p, c_i64, c_i, c_p, c_p, c_p, c_p, c_i64, c_p]),

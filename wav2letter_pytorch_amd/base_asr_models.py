@@ -457,3 +457,21 @@ class ConvCTCASR(_Base):
             if was_training:
                 self.train()
         return results
+
+    def transcribe_long(self, items, max_seconds: float = 20.0, batch_size: int = 8, decoder=None, word_times: bool = False,
+                        vad=None):
+        """recordings longer than an utterance -> text: the inputs of ``transcribe`` (paths, 1-D waveforms at the model's rate,
+        ``(waveform, sample_rate)`` tuples; other rates go through the device resampler, whose limit of 2^31 samples per row is
+        a ValueError).  Each recording is uploaded once, cut at its pauses on the GPU (segmentation.vad_segments: energy VAD
+        with hysteresis; a stretch without a pause is cut at its quietest frame so that no piece exceeds ``max_seconds``), and
+        the pieces -- batched with neighbours in length, ``batch_size`` at a time -- go through the front end, ``infer`` and
+        ``decoder`` as the utterances the model was trained on.  ``vad``: a segmentation.VadConfig (default: its defaults at the
+        model's frame rate).  Returns per input ``{'text': ..., 'segments': [{'start': s, 'end': s, 'text': ...}, ...]}``:
+        ``text`` is the non-empty segment texts joined by one space in time order, start / end are seconds on the recording's
+        clock; ``word_times`` adds ``words`` to every segment ({'word', 'start', 'end'}, the segment's start added to its
+        aligned word times; under criterion asg ``decode_batch``'s NotImplementedError).  A recording of silence gives ``''`` and
+        no segments.  Memory beyond the waveform, its frame powers and the segmentation workspace does not grow with the
+        recording.  As for ``transcribe``: Wav2Letter pads by reflection at the BATCH's padded length and masks nothing, so a
+        piece's last frames depend on what it is batched with; ``batch_size=1`` gives batch-independent text."""
+        from .segmentation import transcribe_long
+        return transcribe_long(self, items, max_seconds, batch_size, decoder, word_times, vad)

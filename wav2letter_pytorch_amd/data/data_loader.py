@@ -223,6 +223,38 @@ class SpectrogramExtractor(torch.nn.Module):
                                         ptr(mean), ptr(std), ptr(out), stream_ptr()), 'w2l_feature_normalize')
         return out, torch.from_numpy(1 + lens // self.hop_length).to(torch.int32)
 
+    def extract_rows(self, audio: torch.Tensor, lens, noise=None):
+        """``extract_batch`` for waveforms that already lie on the device (segmentation.transcribe_long cuts them from a
+        resident recording): audio fp32 [B, L] contiguous on the extractor's device, row b valid up to lens[b] samples (host
+        ints) and zero beyond; noise: None = draw the dither on the device, False = none, or a [B, L] device tensor of N(0,1)
+        draws.  Same launches and the same returns as ``extract_batch`` on the same samples with L = max(lens): with the dither
+        off the features are bit-identical."""
+        dev = self.fb.device
+        if dev.type != 'cuda':
+            raise RuntimeError('SpectrogramExtractor runs on MI355X only (HIP kernels, no CPU path)')
+        if not (torch.is_tensor(audio) and audio.dim() == 2 and audio.device == dev and audio.dtype == torch.float32
+                and audio.is_contiguous()):
+            raise ValueError('extract_rows wants a contiguous fp32 [B, L] tensor on the extractor\'s device')
+        lens = np.asarray(lens, dtype=np.int32).reshape(-1)
+        if lens.shape[0] != audio.shape[0] or lens.max() > audio.shape[1]:
+            raise ValueError(f'{audio.shape[0]} rows of {audio.shape[1]} samples, lengths {lens.tolist()}')
+        if lens.min() <= self.n_fft // 2:
+            raise ValueError(f'an utterance of {int(lens.min())} samples is shorter than the STFT reflect padding '
+                             f'({self.n_fft // 2}); torch.stft rejects it in the reference too')
+        lens_d = torch.from_numpy(lens).to(dev, non_blocking=True)
+        if noise is None:
+            noise = torch.randn(audio.shape, dtype=torch.float32, device=dev) if self.dithering > 0 else None
+        elif noise is False:
+            noise = None
+        n, tmax = audio.shape[0], self.n_frames(int(audio.shape[1]))
+        logmel = self._launch(audio, lens_d, noise, True, tmax)
+        mean = torch.empty(n, self.n_mels, dtype=torch.float32, device=dev)
+        std = torch.empty_like(mean)
+        out = torch.empty(n, self.n_mels, tmax, dtype=torch.float32, device=dev)
+        check(lib.w2l_feature_normalize(ptr(logmel), ptr(lens_d), self.hop_length, n, tmax, self.n_mels, float(self.epsilon),
+                                        ptr(mean), ptr(std), ptr(out), stream_ptr()), 'w2l_feature_normalize')
+        return out, torch.from_numpy(1 + lens // self.hop_length).to(torch.int32)
+
     # ------------------------------------------------------------------ the reference's per-utterance methods
     def _get_spect(self, audio, noise=None):
         """mel power spectrogram [1, n_mels, T] (data_loader.py:64-72)"""

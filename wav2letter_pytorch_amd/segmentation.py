@@ -1,0 +1,293 @@
+"""Long-form transcription: voice activity detection on the GPU (csrc/vad.hip), segmentation of a recording at its pauses,
+and ``transcribe_long`` -- the pieces go through the model as the utterances it was trained on, text and word times come back
+on the recording's clock.  No reference counterpart: the reference transcribes utterances only.
+
+The rule (DESIGN.md "Long-form transcription" has it in full; tests/vad_refs.py restates it in numpy): frame power in fp64,
+``floor`` = the q-quantile and ``peak`` = the largest frame power, ``thr_on = max(abs_min, min(floor * r_on, sqrt(floor * peak)))``,
+``thr_off = thr_on * r_hyst``, hysteresis between the two, gaps shorter than ``min_silence`` closed, runs shorter than
+``min_speech`` dropped, every run widened by ``pad``, and a run longer than ``max_seconds`` cut at its quietest frame.  The
+defaults are conventions; they are not tuned on speech (there is no speech corpus where this was written).
+
+This module imports without a GPU: only ``vad_segments`` and ``transcribe_long`` touch the device."""
+from __future__ import annotations
+
+import math
+from dataclasses import dataclass
+from typing import List, Optional, Sequence
+
+import numpy as np
+
+INITIAL_CAP = 256            # segments per recording the first launch has room for (grown once when a recording has more)
+MAX_FRAMES = 1 << 24         # w2l_vad_segments takes fewer frames than this per recording
+HEADER_BYTES = 32            # W2L_VAD_HEADER_BYTES
+
+
+@dataclass
+class VadConfig:
+    """The numbers of the rule in seconds and dB, and the analysis frames they are counted in.  ``on_dbfs`` (with ``off_dbfs``,
+    default ``on_dbfs - hyst_db``): absolute thresholds instead of the adaptive ones, as frame power relative to a full-scale
+    square wave, 10^(dBFS / 10).  ``sample_rate`` / ``window_size`` / ``window_stride``: the model's ``audio_conf`` values."""
+    q: float = 0.05
+    on_db: float = 10.0
+    hyst_db: float = 3.0
+    abs_min: float = 1e-10
+    min_silence: float = 0.30
+    min_speech: float = 0.10
+    pad: float = 0.20
+    on_dbfs: Optional[float] = None
+    off_dbfs: Optional[float] = None
+    sample_rate: int = 16000
+    window_size: float = 0.02
+    window_stride: float = 0.01
+
+    def __post_init__(self):
+        self.sample_rate = int(self.sample_rate)
+        self.win = int(self.sample_rate * self.window_size)
+        self.hop = int(self.sample_rate * self.window_stride)
+        if self.hop < 1 or self.hop > self.win:
+            raise ValueError(f'window_stride must give 1 <= hop <= win samples (hop={self.hop}, win={self.win})')
+        self.n_fft = 2 ** math.ceil(math.log2(self.win))
+        for name in ('q', 'on_db', 'hyst_db', 'abs_min', 'min_silence', 'min_speech', 'pad'):
+            setattr(self, name, float(getattr(self, name)))
+            if not math.isfinite(getattr(self, name)):
+                raise ValueError(f'{name}={getattr(self, name)!r} is not finite')
+        if not 0.0 <= self.q <= 1.0:
+            raise ValueError(f'q={self.q} outside [0, 1]')
+        if self.hyst_db < 0:
+            raise ValueError(f'hyst_db={self.hyst_db} is negative: thr_off would lie above thr_on')
+        if self.abs_min < 0 or self.min_silence < 0 or self.pad < 0:
+            raise ValueError('abs_min, min_silence and pad must not be negative')
+        if self.off_dbfs is not None and self.on_dbfs is None:
+            raise ValueError('off_dbfs is given without on_dbfs')
+        if self.on_dbfs is not None:
+            self.on_dbfs = float(self.on_dbfs)
+            self.off_dbfs = self.on_dbfs - self.hyst_db if self.off_dbfs is None else float(self.off_dbfs)
+            if not (math.isfinite(self.on_dbfs) and math.isfinite(self.off_dbfs)) or self.off_dbfs > self.on_dbfs:
+                raise ValueError(f'absolute thresholds must be finite with off_dbfs <= on_dbfs ({self.on_dbfs}, {self.off_dbfs})')
+        # the shortest segment the rule can emit is a run of min_speech frames whose last frame is partial; the front end
+        # pads it by reflection, which needs more than n_fft / 2 samples
+        if self.shortest_samples(self.frames(self.min_speech)) <= self.n_fft // 2:
+            raise ValueError(f'min_speech={self.min_speech} s allows segments of {self.shortest_samples(self.frames(self.min_speech))} '
+                             f'samples, not above the front end\'s reflect padding ({self.n_fft // 2} samples)')
+
+    @classmethod
+    def for_model(cls, audio_conf, **kw):
+        return cls(sample_rate=audio_conf['sample_rate'], window_size=audio_conf['window_size'],
+                   window_stride=audio_conf['window_stride'], **kw)
+
+    def frames(self, seconds: float) -> int:
+        """a duration in analysis frames, rounded to the nearest"""
+        return int(round(float(seconds) * self.sample_rate / self.hop))
+
+    def shortest_samples(self, frames: int) -> int:
+        """samples of the shortest recording stretch that ``frames`` frames can cover (the last one partial)"""
+        return (frames - 1) * self.hop + 1 if frames >= 1 else 0
+
+    def numbers(self, max_seconds: float = 20.0) -> dict:
+        """the fields of w2l_vad_params_t: frame counts, and the ratios both device and reference multiply by"""
+        max_frames = int(math.floor(float(max_seconds) * self.sample_rate / self.hop))
+        if max_frames < 2:
+            raise ValueError(f'max_seconds={max_seconds} is {max_frames} frames: at least 2 are needed')
+        if self.shortest_samples(max_frames // 2) <= self.n_fft // 2:
+            raise ValueError(f'max_seconds={max_seconds} allows forced pieces of {self.shortest_samples(max_frames // 2)} samples, '
+                             f'not above the front end\'s reflect padding ({self.n_fft // 2} samples)')
+        absolute = self.on_dbfs is not None
+        return dict(q=self.q, r_on=10.0 ** (self.on_db / 10.0), r_hyst=10.0 ** (-self.hyst_db / 10.0), abs_min=self.abs_min,
+                    thr_on=10.0 ** (self.on_dbfs / 10.0) if absolute else 0.0,
+                    thr_off=10.0 ** (self.off_dbfs / 10.0) if absolute else 0.0, absolute=int(absolute),
+                    min_silence=self.frames(self.min_silence), min_speech=self.frames(self.min_speech), pad=self.frames(self.pad),
+                    max_frames=max_frames)
+
+
+def vad_params(numbers: dict):
+    """w2l_vad_params_t from ``VadConfig.numbers()`` (or a dict with its keys)"""
+    from ._lib import VadParams
+    p = VadParams()
+    for k, v in numbers.items():
+        setattr(p, k, v)
+    return p
+
+
+def parse_records(buf: np.ndarray, n: int, cap: int) -> List[dict]:
+    """the output buffer of w2l_vad_segments (uint8, host) -> one dict per recording"""
+    stride = HEADER_BYTES + 8 * cap
+    out = []
+    for i in range(n):
+        rec = buf[i * stride: (i + 1) * stride]
+        count, status = (int(v) for v in rec[:8].view(np.int32))
+        thr_on, thr_off = (float(v) for v in rec[8:24].view(np.float64))
+        floor, peak = rec[24:32].view(np.float32)
+        segs = rec[HEADER_BYTES:].view(np.int32).reshape(cap, 2)[:min(count, cap)].astype(np.int64)
+        out.append(dict(count=count, status=status, thr_on=thr_on, thr_off=thr_off, floor=floor, peak=peak, frames=segs))
+    return out
+
+
+def segments_from_power(power, nframes_dev, numbers: dict, cap: int = INITIAL_CAP, grow: bool = True) -> List[dict]:
+    """the decision launch on device powers [N, Fmax] (fp32, contiguous) and frame counts [N] (int32, device): one launch, one
+    copy to the host; with ``grow`` ``cap`` is raised and the launch repeated once when a recording has more segments (status
+    bit 0)"""
+    import ctypes as C
+    import torch
+    from ._lib import check, lib, ptr, stream_ptr
+    n, fmax = power.shape
+    if fmax >= MAX_FRAMES:
+        raise ValueError(f'a recording of {fmax} frames: the segmentation takes fewer than 2^24 frames per recording')
+    params = vad_params(numbers)
+    ws_bytes = int(lib.w2l_vad_workspace_bytes(n, fmax))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=power.device)
+    for _ in range(2):
+        out = torch.empty(n * (HEADER_BYTES + 8 * cap), dtype=torch.uint8, device=power.device)
+        check(lib.w2l_vad_segments(ptr(power), fmax, ptr(nframes_dev), n, C.byref(params), cap, ptr(ws), ws_bytes, ptr(out),
+                                   stream_ptr()), 'w2l_vad_segments')
+        recs = parse_records(out.cpu().numpy(), n, cap)
+        most = max(r['count'] for r in recs)
+        if most <= cap or not grow:
+            break
+        cap = most
+    return recs
+
+
+def frame_power(x, lens_dev, fmax: int, win: int, hop: int):
+    """the power launch: device rows x [N, L] (fp32, contiguous) and lengths [N] (int32, device) -> powers [N, fmax]"""
+    import torch
+    from ._lib import check, lib, ptr, stream_ptr
+    power = torch.empty(x.shape[0], fmax, dtype=torch.float32, device=x.device)
+    check(lib.w2l_vad_power(ptr(x), x.shape[1], ptr(lens_dev), x.shape[0], win, hop, ptr(power), fmax, stream_ptr()), 'w2l_vad_power')
+    return power
+
+
+def vad_segments(waves, cfg: Optional[VadConfig] = None, max_seconds: float = 20.0, return_stats: bool = False):
+    """waves: N recordings at the model's rate, each a 1-D device tensor or array (one recording may be passed bare) -> per
+    recording an int64 [S, 2] array of half-open sample ranges, ascending; a recording of silence gives [0, 2].  Two launches
+    (frame power, decisions) and one copy to the host.  ``return_stats``: (segments, stats) with per recording a dict of
+    count, status, thr_on, thr_off, floor, peak and the segments in frames."""
+    import torch
+    cfg = cfg or VadConfig()
+    numbers = cfg.numbers(max_seconds)
+    if torch.is_tensor(waves) and waves.dim() == 1 or isinstance(waves, np.ndarray) and waves.ndim == 1:
+        waves = [waves]
+    waves = list(waves)
+    dev = next((w.device for w in waves if torch.is_tensor(w) and w.is_cuda), None)
+    if dev is None:
+        if not torch.cuda.is_available():
+            raise RuntimeError('vad_segments runs on MI355X only (HIP kernels, no CPU path)')
+        dev = torch.device('cuda', torch.cuda.current_device())
+    rows = [w.reshape(-1) if torch.is_tensor(w) else torch.from_numpy(np.ascontiguousarray(np.asarray(w, dtype=np.float32).reshape(-1)))
+            for w in waves]
+    lens = np.array([int(r.shape[0]) for r in rows], dtype=np.int64)
+    nfr = -(-lens // cfg.hop)
+    fmax = max(1, int(nfr.max()))
+    if fmax >= MAX_FRAMES:
+        raise ValueError(f'a recording of {fmax} frames ({int(lens.max())} samples): the segmentation takes fewer than 2^24 frames '
+                         'per recording')
+    if len(rows) == 1 and rows[0].is_cuda and rows[0].dtype == torch.float32 and rows[0].is_contiguous() and lens[0] > 0:
+        x = rows[0].view(1, -1)                          # the recording as it lies on the device: no copy
+    else:
+        x = torch.zeros(len(rows), max(1, int(lens.max())), dtype=torch.float32, device=dev)
+        for i, r in enumerate(rows):
+            x[i, :r.shape[0]] = r.to(device=dev, dtype=torch.float32)
+    with torch.cuda.device(dev):
+        ints = torch.from_numpy(np.concatenate([lens, nfr]).astype(np.int32)).to(dev)
+        power = frame_power(x, ints[:len(rows)], fmax, cfg.win, cfg.hop)
+        recs = segments_from_power(power, ints[len(rows):], numbers)
+    segs = []
+    for r, n in zip(recs, lens):
+        fr = r['frames']
+        segs.append(np.stack([fr[:, 0] * cfg.hop, np.minimum(int(n), fr[:, 1] * cfg.hop)], 1).astype(np.int64).reshape(-1, 2))
+    return (segs, recs) if return_stats else segs
+
+
+# ---------------------------------------------------------------------------------------------------------------- stitching
+def stitch(pieces: Sequence[dict], sample_rate: int, word_times: bool = False) -> dict:
+    """pieces: per segment {'start': first sample, 'end': one past the last, 'text': ..., 'words': [(word, s, e), ...] on the
+    SEGMENT's clock} in any order -> the result of one recording: ``text`` = the non-empty segment texts joined by one space in
+    time order, ``segments`` with start / end in seconds on the recording's clock, and -- with ``word_times`` -- ``words`` as
+    {'word', 'start', 'end'} with the segment's start added."""
+    segs = []
+    for p in sorted(pieces, key=lambda p: p['start']):
+        t0 = p['start'] / float(sample_rate)
+        seg = {'start': t0, 'end': p['end'] / float(sample_rate), 'text': p['text']}
+        if word_times:
+            seg['words'] = [{'word': w, 'start': t0 + float(s), 'end': t0 + float(e)} for w, s, e in (p.get('words') or [])]
+        segs.append(seg)
+    return {'text': ' '.join(s['text'] for s in segs if s['text'].strip()), 'segments': segs}
+
+
+def batches_by_length(lengths: Sequence[int], batch_size: int) -> List[List[int]]:
+    """segment indices grouped into batches of neighbours in length (longest first), so a batch pads little"""
+    order = sorted(range(len(lengths)), key=lambda i: (-int(lengths[i]), i))
+    bs = max(1, int(batch_size))
+    return [order[i: i + bs] for i in range(0, len(order), bs)]
+
+
+def _device_wave(model, ext, item, model_rate, dev):
+    """one input of transcribe_long -> its waveform at the model's rate, fp32 [L] on the device (uploaded once; other rates go
+    through the device resampler)"""
+    import torch
+    from .data.data_loader import read_audio
+    from .data.resample import plan_rows, resample_device
+    if isinstance(item, str):
+        audio, rate = read_audio(item)
+    elif isinstance(item, tuple) and len(item) == 2:
+        audio, rate = item[0], int(item[1])
+    else:
+        audio, rate = item, model_rate
+    if torch.is_tensor(audio):
+        wave = audio.detach().reshape(-1).to(device=dev, dtype=torch.float32)
+    else:
+        wave = torch.from_numpy(np.ascontiguousarray(np.asarray(audio, dtype=np.float32).reshape(-1))).to(dev)
+    if rate == model_rate or wave.numel() == 0:
+        return wave.contiguous()
+    n_in = int(wave.numel())
+    n_out = -(-n_in * model_rate // rate)
+    if max(n_in, n_out) >= 2 ** 31:
+        raise ValueError(f'a recording of {n_in} samples at {rate} Hz ({n_out} at {model_rate} Hz): the device resampler takes '
+                         'fewer than 2^31 samples per row; split the file first')
+    rows = plan_rows([n_in], [rate], model_rate, None, ext._banks)
+    return resample_device(wave.view(1, -1).contiguous(), rows, ext._banks)[0, :int(rows[0, 1])].contiguous()
+
+
+def transcribe_long(model, items, max_seconds: float = 20.0, batch_size: int = 8, decoder=None, word_times: bool = False,
+                    vad: Optional[VadConfig] = None) -> List[dict]:
+    """the body of ``ConvCTCASR.transcribe_long`` (its docstring has the interface)"""
+    import torch
+    from .data.data_loader import SpectrogramExtractor
+    from .evaluate import decode_batch
+    items = [items] if isinstance(items, str) or torch.is_tensor(items) or isinstance(items, np.ndarray) and items.ndim == 1 \
+        else list(items)
+    dev = next(model.parameters()).device
+    ext = model.__dict__.get('_transcribe_extractor')
+    if ext is None or ext.fb.device != dev:
+        ext = model.__dict__['_transcribe_extractor'] = SpectrogramExtractor(model.audio_conf, model._cfg.input_size, device=dev)
+    decoder = decoder or model.ctc_decoder
+    model_rate = int(model.audio_conf['sample_rate'])
+    vad = vad or VadConfig.for_model(model.audio_conf)
+    if (vad.sample_rate, vad.win, vad.hop) != (model_rate, ext.win_length, ext.hop_length):
+        raise ValueError(f'the VadConfig is for {vad.sample_rate} Hz with frames of {vad.win} / {vad.hop} samples; the model has '
+                         f'{model_rate} Hz and {ext.win_length} / {ext.hop_length}')
+    vad.numbers(max_seconds)                             # (argument errors before any file is read)
+    was_training = model.training
+    model.eval()
+    results = []
+    try:
+        with torch.no_grad(), torch.cuda.device(dev):
+            for item in items:
+                wave = _device_wave(model, ext, item, model_rate, dev)
+                segs = vad_segments([wave], vad, max_seconds)[0] if wave.numel() else np.zeros((0, 2), dtype=np.int64)
+                lengths = (segs[:, 1] - segs[:, 0]).tolist()
+                pieces = []
+                for batch in batches_by_length(lengths, batch_size):
+                    lens = np.array([lengths[i] for i in batch], dtype=np.int32)
+                    rows = torch.zeros(len(batch), int(lens.max()), dtype=torch.float32, device=dev)
+                    for j, i in enumerate(batch):
+                        rows[j, :lens[j]] = wave[int(segs[i, 0]): int(segs[i, 1])]
+                    x, x_lens = ext.extract_rows(rows, lens)
+                    out, out_lens = model.infer(x, x_lens)
+                    hyps, words = decode_batch(model, decoder, out, out_lens, word_times)
+                    for i, hyp, w in zip(batch, hyps, words):
+                        pieces.append({'start': int(segs[i, 0]), 'end': int(segs[i, 1]), 'text': hyp, 'words': w})
+                results.append(stitch(pieces, model_rate, word_times))
+    finally:
+        if was_training:
+            model.train()
+    return results
