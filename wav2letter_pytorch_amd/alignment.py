@@ -168,26 +168,34 @@ def align_sections(n: int, t: int, smax: int):
     return 0, o_status, o_path, o_starts, o_ends, o_ends + 4 * n * smax
 
 
+def _launch(symbol: str, ws_bytes: int, out_of_range: str, head, x, sz, tg_ptr, tg_stride, len_ptr, len_stride, smax, flags, out,
+            out_offset: int):
+    """the launch behind launch_align and asg_beam.launch_asg_align.  ``ws_bytes``: the answer of the symbol's workspace query
+    (negative: ``out_of_range`` is raised); ``head``: the symbol's leading pointer arguments; ``flags``: its two ints after Smax"""
+    import torch
+    from . import _lib
+    from ._lib import check, lib, ptr, stream_ptr
+    n, t, a = x.shape
+    if ws_bytes < 0:
+        raise _lib.W2LError(out_of_range)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device) if ws_bytes else None
+    vp = C.c_void_p
+    sections = [vp(out.data_ptr() + out_offset + o) for o in align_sections(n, t, smax)[:5]]
+    check(getattr(lib, symbol)(*head, ptr(sz), vp(tg_ptr), int(tg_stride), vp(len_ptr), int(len_stride), n, t, a, int(smax),
+                               *flags, ptr(ws), ws_bytes, *sections, stream_ptr()), symbol)
+    return ws
+
+
 def launch_align(x, sz, tg_ptr: int, tg_stride: int, len_ptr: int, len_stride: int, smax: int, blank: int, log_probs: bool,
                  out, out_offset: int):
     """one w2l_ctc_align launch on the current stream: x [N, T, A] float32 contiguous on the device, ``sz`` int32 [N] there or
     None, targets / lengths by device address and stride (elements), outputs into ``out`` (a uint8 device tensor) from byte
     ``out_offset`` in align_sections' layout.  -> the workspace tensor (or None): keep it alive until the stream has passed."""
-    import torch
-    from . import _lib
-    from ._lib import check, lib, ptr, stream_ptr
-    n, t, a = x.shape
-    ws_bytes = int(lib.w2l_ctc_align_workspace_bytes(n, t, smax))
-    if ws_bytes < 0:
-        raise _lib.W2LError('ctc_forced_align: T=%d (max 32768) or target length %d (max 4095) is out of range' % (t, smax))
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device) if ws_bytes else None
-    base = out.data_ptr() + out_offset
-    o = align_sections(n, t, smax)
-    vp = C.c_void_p
-    check(lib.w2l_ctc_align(ptr(x), ptr(sz), vp(tg_ptr), int(tg_stride), vp(len_ptr), int(len_stride), n, t, a, int(smax),
-                            int(blank), int(bool(log_probs)), ptr(ws), ws_bytes, vp(base + o[0]), vp(base + o[1]),
-                            vp(base + o[2]), vp(base + o[3]), vp(base + o[4]), stream_ptr()), 'w2l_ctc_align')
-    return ws
+    from ._lib import lib, ptr
+    n, t, _ = x.shape
+    return _launch('w2l_ctc_align', lib.w2l_ctc_align_workspace_bytes(n, t, smax),
+                   'ctc_forced_align: T=%d (max 32768) or target length %d (max 4095) is out of range' % (t, smax), (ptr(x),),
+                   x, sz, tg_ptr, tg_stride, len_ptr, len_stride, smax, (int(blank), int(bool(log_probs))), out, out_offset)
 
 
 def split_align(host: np.ndarray, n: int, t: int, smax: int):
@@ -201,6 +209,71 @@ def split_align(host: np.ndarray, n: int, t: int, smax: int):
     return scores, status, paths, starts, ends
 
 
+def batch_of(x, lengths):
+    """``x`` as a tensor with a [T, A] input promoted to [1, T, A], its one length (if any) along with it -> (x, lengths,
+    whether it was promoted)"""
+    import torch
+    x = x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x))
+    single = x.dim() == 2
+    if single:
+        x = x.unsqueeze(0)
+        if lengths is not None:
+            lengths = [int(np.asarray(torch.as_tensor(lengths).cpu()).reshape(-1)[0])]
+    return x, lengths, single
+
+
+def host_lengths(lengths, n: int, t: int, what: str):
+    """``lengths`` as an int32 host tensor [N] with every entry in [1, T]"""
+    import torch
+    host = torch.as_tensor(lengths).detach().cpu().to(torch.int64).reshape(-1)
+    if host.numel() != n:
+        raise ValueError('%s holds %d lengths for %d utterances' % (what, host.numel(), n))
+    if bool((host < 1).any()) or bool((host > t).any()):
+        raise ValueError('%s must lie in [1, %d], got %s' % (what, t, host.tolist()))
+    return host.to(torch.int32)
+
+
+def on_device(x, what: str, hint: str = ''):
+    """``x`` (numpy or torch) as a contiguous float32 tensor on the device"""
+    import torch
+    from . import _lib
+    x = x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x))
+    if not x.is_cuda:
+        if not torch.cuda.is_available():
+            raise _lib.W2LError('%s needs the MI355X device (there is no CPU fallback%s)' % (what, hint))
+        x = x.cuda()
+    return x.detach().float().contiguous()
+
+
+def align_targets(targets, target_lengths, labels, n: int, t: int, what: str):
+    """the targets of ``n`` utterances of ``t`` frames as arrays, within the kernels' limits -> (targets [N, Smax], lengths, Smax)"""
+    tg, tl = _targets_to_array(targets, target_lengths, labels, n)
+    if tg.shape[0] != n:
+        raise ValueError('%d targets for %d utterances' % (tg.shape[0], n))
+    smax = tg.shape[1]
+    if smax > 4095 or t > 32768:
+        raise ValueError('%s: T=%d (max 32768) or target length %d (max 4095) is out of range' % (what, t, smax))
+    return tg, tl, smax
+
+
+def align_buffers(x, il, tg, tl):
+    """for x [N, T, A] on the device: the input lengths there (or None), the targets with their lengths in one buffer
+    [N * Smax | N] int32, and the launch's ``out`` in align_sections' layout"""
+    import torch
+    sz = il.to(x.device, non_blocking=True) if il is not None else None
+    tgt = torch.from_numpy(np.concatenate([tg.reshape(-1), tl])).to(x.device, non_blocking=True)
+    return sz, tgt, torch.empty(align_sections(x.shape[0], x.shape[1], tg.shape[1])[5], dtype=torch.uint8, device=x.device)
+
+
+def aligned(out, n: int, t: int, smax: int, tl, bad_input: str):
+    """the one copy to the host of a launch's ``out`` (ordered after the launch on this stream) -> Alignment; a row of status 2
+    raises ValueError(bad_input % rows)"""
+    scores, status, paths, starts, ends = split_align(out.cpu().numpy(), n, t, smax)
+    if (status == 2).any():
+        raise ValueError(bad_input % (np.nonzero(status == 2)[0].tolist(),))
+    return Alignment(scores, status == 0, paths, starts, ends, tl)
+
+
 def ctc_forced_align(probs, targets, input_lengths=None, target_lengths=None, blank: int = 0, log_probs: bool = True,
                      labels: Optional[Sequence[str]] = None) -> Alignment:
     """Align each utterance's target to its posteriors on the MI355X: one launch, one copy to the host.
@@ -212,13 +285,7 @@ def ctc_forced_align(probs, targets, input_lengths=None, target_lengths=None, bl
     (more labels, counting one blank between repeated ones, than frames; or a zero probability on every path) does not
     raise: ``feasible[n]`` is False and ``scores[n]`` -inf.  A negative probability, or a target outside [0, A) or equal to
     ``blank``, is a ValueError."""
-    import torch
-    from . import _lib
-    x = probs if torch.is_tensor(probs) else torch.from_numpy(np.ascontiguousarray(probs))
-    if x.dim() == 2:
-        x = x.unsqueeze(0)
-        if input_lengths is not None:
-            input_lengths = [int(np.asarray(torch.as_tensor(input_lengths).cpu()).reshape(-1)[0])]
+    x, input_lengths, _ = batch_of(probs, input_lengths)
     if x.dim() != 3:
         raise ValueError('expected [N, T, labels] or [T, labels] posteriors, got shape %s' % (tuple(x.shape),))
     n, t, a = x.shape
@@ -228,36 +295,12 @@ def ctc_forced_align(probs, targets, input_lengths=None, target_lengths=None, bl
         raise ValueError('ctc size:%d, labels: %d' % (a, len(labels)))
     if not 0 <= blank < a:
         raise ValueError('blank %d outside %d labels' % (blank, a))
-    tg, tl = _targets_to_array(targets, target_lengths, labels, n)
-    if tg.shape[0] != n:
-        raise ValueError('%d targets for %d utterances' % (tg.shape[0], n))
-    smax = tg.shape[1]
-    if smax > 4095 or t > 32768:
-        raise ValueError('ctc_forced_align: T=%d (max 32768) or target length %d (max 4095) is out of range' % (t, smax))
-    il = None
-    if input_lengths is not None:
-        il = torch.as_tensor(input_lengths).detach().cpu().to(torch.int64).reshape(-1)
-        if il.numel() != n:
-            raise ValueError('input_lengths holds %d lengths for %d utterances' % (il.numel(), n))
-        if bool((il < 1).any()) or bool((il > t).any()):
-            raise ValueError('input_lengths must lie in [1, %d], got %s' % (t, il.tolist()))
-    if not x.is_cuda:
-        if not torch.cuda.is_available():
-            raise _lib.W2LError('ctc_forced_align needs the MI355X device (there is no CPU fallback; viterbi_align_host is '
-                                'the host model)')
-        x = x.cuda()
-    x = x.detach().float().contiguous()
-    dev = x.device
-    sz = il.to(torch.int32).to(dev, non_blocking=True) if il is not None else None
-    # targets and their lengths travel in one buffer: [N * Smax | N] int32
-    tgt = torch.from_numpy(np.concatenate([tg.reshape(-1), tl])).to(dev, non_blocking=True)
-    out = torch.empty(align_sections(n, t, smax)[5], dtype=torch.uint8, device=dev)
+    tg, tl, smax = align_targets(targets, target_lengths, labels, n, t, 'ctc_forced_align')
+    il = host_lengths(input_lengths, n, t, 'input_lengths') if input_lengths is not None else None
+    x = on_device(x, 'ctc_forced_align', '; viterbi_align_host is the host model')
+    sz, tgt, out = align_buffers(x, il, tg, tl)
     ws = launch_align(x, sz, tgt.data_ptr(), max(smax, 1), tgt.data_ptr() + 4 * n * smax, 1, smax, blank, log_probs, out, 0)
-    host = out.cpu().numpy()                           # the one copy to the host (ordered after the launch on this stream)
+    got = aligned(out, n, t, smax, tl, 'ctc_forced_align: a negative probability, or a target outside [0, %d) or equal to the '
+                  'blank (%d), in utterances %%s' % (a, blank))
     del ws
-    scores, status, paths, starts, ends = split_align(host, n, t, smax)
-    if (status == 2).any():
-        rows = np.nonzero(status == 2)[0].tolist()
-        raise ValueError('ctc_forced_align: a negative probability, or a target outside [0, %d) or equal to the blank (%d), '
-                         'in utterances %s' % (a, blank, rows))
-    return Alignment(scores, status == 0, paths, starts, ends, tl)
+    return got

@@ -42,10 +42,11 @@ import torch.nn as nn
 
 from . import _lib
 from ._lib import check, lib, ptr, stream_ptr
-from .alignment import Alignment, HostAlignment, _targets_to_array, align_sections, split_align
+from .alignment import (Alignment, HostAlignment, _launch, align_buffers, align_sections, align_targets, aligned, batch_of,
+                        host_lengths, on_device, split_align)
 from .asg import MAX_LABELS, ASGDecoder, _check_labels, decode_repeats, encode_repeats
-from .beam_search import (_SEP_RE, _WORDCH_RE, _decoder_hotwords, _n_words, _resolve_hotwords, _resolve_lexicon,
-                          split_search_out)
+from .beam_search import (_check_decode_shape, _decoder_hotwords, _desc, _n_words, _pick, _resolve_hotwords, _resolve_lexicon,
+                          _word_tables, search_out_layout, split_search_out, word_flags)
 
 _NINF = float('-inf')
 
@@ -62,16 +63,6 @@ def _lae(a: float, b: float) -> float:
 
 def _text(encoded, labels, repeat_index):
     return ''.join(labels[i] for i in decode_repeats(encoded, repeat_index))
-
-
-def _pick(found, nbest, return_weights, return_encoded):
-    """n-best pairs (text, weight, encoded) -> the result in prefix_beam_search_gpu's conventions"""
-    rows = [row if return_encoded else row[:2] for row in found]
-    if nbest > 1:
-        return rows[:nbest]
-    if return_weights or return_encoded:
-        return rows[0]
-    return rows[0][0]
 
 
 def asg_prefix_beam_search(x, transitions, labels: Sequence[str], repeat_index: int = 0,
@@ -265,8 +256,7 @@ def _label_info(labels, lm: bool = False):
     first = {}
     for i, ch in enumerate(labels):
         first.setdefault(ch, i)
-    return np.array([first[ch] | bool(_WORDCH_RE.fullmatch(ch)) << 9 | bool(_SEP_RE.fullmatch(ch)) << 10
-                     | (lm and ch.isspace()) << 11 for ch in labels], dtype=np.int32)
+    return np.array([first[ch] | word_flags(ch) | (lm and ch.isspace()) << 11 for ch in labels], dtype=np.int32)
 
 
 def _transitions_on(transitions, a: int, dev):
@@ -281,42 +271,16 @@ def _transitions_on(transitions, a: int, dev):
     return g
 
 
-def _scores_on_device(x, what: str):
-    x = x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x))
-    if not x.is_cuda:
-        if not torch.cuda.is_available():
-            raise _lib.W2LError('%s needs the MI355X device (there is no CPU fallback)' % what)
-        x = x.cuda()
-    return x.detach().float().contiguous()
-
-
-def _lengths(lengths, n: int, t: int, what: str):
-    host = torch.as_tensor(lengths).detach().cpu().to(torch.int64).reshape(-1)
-    if host.numel() != n:
-        raise ValueError('%s holds %d lengths for %d utterances' % (what, host.numel(), n))
-    if bool((host < 1).any()) or bool((host > t).any()):
-        raise ValueError('%s must lie in [1, %d], got %s' % (what, t, host.tolist()))
-    return host.to(torch.int32)
-
-
 def launch_asg_align(x, g, sz, tg_ptr: int, tg_stride: int, len_ptr: int, len_stride: int, smax: int, repeat_index: int,
                      encoded: bool, out, out_offset: int):
     """one w2l_asg_align launch on the current stream, addressed as alignment.launch_align: outputs into ``out`` (a uint8 device
     tensor) from byte ``out_offset`` in align_sections' layout.  -> the workspace tensor (or None): keep it alive until the
     stream has passed."""
     n, t, a = x.shape
-    ws_bytes = int(lib.w2l_asg_align_workspace_bytes(n, t, a, smax))
-    if ws_bytes < 0:
-        raise _lib.W2LError('asg_forced_align: T=%d (max 32768), target length %d (max 4095) or %d labels (max %d) out of '
-                            'range' % (t, smax, a, MAX_LABELS))
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device) if ws_bytes else None
-    base = out.data_ptr() + out_offset
-    o = align_sections(n, t, smax)
-    vp = C.c_void_p
-    check(lib.w2l_asg_align(ptr(x), ptr(g), ptr(sz), vp(tg_ptr), int(tg_stride), vp(len_ptr), int(len_stride), n, t, a, int(smax),
-                            int(repeat_index), int(bool(encoded)), ptr(ws), ws_bytes, vp(base + o[0]), vp(base + o[1]),
-                            vp(base + o[2]), vp(base + o[3]), vp(base + o[4]), stream_ptr()), 'w2l_asg_align')
-    return ws
+    return _launch('w2l_asg_align', lib.w2l_asg_align_workspace_bytes(n, t, a, smax),
+                   'asg_forced_align: T=%d (max 32768), target length %d (max 4095) or %d labels (max %d) out of range'
+                   % (t, smax, a, MAX_LABELS), (ptr(x), ptr(g)), x, sz, tg_ptr, tg_stride, len_ptr, len_stride, smax,
+                   (int(repeat_index), int(bool(encoded))), out, out_offset)
 
 
 def _search_device(x, g, sz, labels, repeat_index, k, beta, prune, lm, alpha, offsets, lexicon=None, complete_only=True,
@@ -331,43 +295,26 @@ def _search_device(x, g, sz, labels, repeat_index, k, beta, prune, lm, alpha, of
     info = _label_info(labels, any_table)
     if offsets and t > 4095:
         raise ValueError('return_offsets: %d frames, w2l_asg_align takes targets of at most 4095 labels' % t)
-    tables, lex, hot, space_index = None, None, None, -1
-    if any_table:
-        from .ngram_lm import ArpaLM
-        if lm is not None and not isinstance(lm, ArpaLM):
-            raise TypeError('lm must be an ngram_lm.ArpaLM, got %s' % type(lm).__name__)
-        odd = [ch for ch in labels if ch.isspace() and ch != ' ']
-        if odd:
-            raise ValueError('asg_beam_search_gpu: whitespace labels other than a space (%r) cannot be scored by a word LM' % odd
-                             if lm is not None else
-                             'asg_beam_search_gpu: whitespace labels other than a space (%r) cannot separate the words of a '
-                             'lexicon or of a hotword list' % odd)
-        if hotwords is not None and not math.isfinite(float(hotword_weight)):
-            raise ValueError('asg_beam_search_gpu: hotword_weight must be finite, got %r' % (hotword_weight,))
-        # the repeat label takes the blank's place as the label that spells nothing
-        tables = lm.to_device(labels, repeat_index, dev) if lm is not None else None
-        lex = _resolve_lexicon(lexicon, lm).to_device(labels, repeat_index, dev) if lexicon is not None else None
-        hot = _resolve_hotwords(hotwords).to_device(labels, repeat_index, dev) if hotwords is not None else None
-        space_index = labels.index(' ') if ' ' in labels else -1
-    order = lm.order if lm is not None else 0
+    # the repeat label takes the blank's place as the label that spells nothing
+    tables, lex, hot, space_index, order = _word_tables(labels, repeat_index, lm, lexicon, hotwords, hotword_weight, dev,
+                                                        'asg_beam_search_gpu')
     ws_bytes = int(lib.w2l_asg_beam_search_workspace_bytes(n, t, a, k, order))
     if ws_bytes < 0:
         raise ValueError('asg_beam_search_gpu: k=%d (1..64), %d labels (1..%d) or T=%d is out of range' % (k, a, MAX_LABELS, t))
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-    beam_bytes = 12 * n * k + 4 * n + 4 * n * k * t + (4 * n * k if lm is not None else 0)
+    lay = search_out_layout(n, k, t, lm is not None)
+    beam_bytes = lay.beam_bytes
     out = torch.empty(beam_bytes + (align_sections(n, t, t)[5] if offsets else 0), dtype=torch.uint8, device=dev)
     check(lib.w2l_asg_beam_search_tables(ptr(x), ptr(g), ptr(sz), n, t, a, info.ctypes.data_as(C.c_void_p), int(repeat_index),
                                          space_index, int(k), float(alpha), float(beta), float(prune),
-                                         tables.desc_ref if tables is not None else None, order,
-                                         lex.desc_ref if lex is not None else None, int(bool(complete_only)),
-                                         hot.desc_ref if hot is not None else None, float(hotword_weight), ptr(ws), ws_bytes,
-                                         ptr(out), stream_ptr()), 'w2l_asg_beam_search_tables')
+                                         _desc(tables), order, _desc(lex), int(bool(complete_only)), _desc(hot),
+                                         float(hotword_weight), ptr(ws), ws_bytes, ptr(out), stream_ptr()),
+          'w2l_asg_beam_search_tables')
     align_ws = None
     if offsets:
-        # rank 0 of every utterance, aligned where it lies: labels int32 [N, k, T] from byte 12 N k + 4 N (row stride k T),
-        # lengths int32 [N, k] from byte 8 N k (stride k)
-        align_ws = launch_asg_align(x, g, sz, out.data_ptr() + 12 * n * k + 4 * n, k * t, out.data_ptr() + 8 * n * k, k, t,
-                                    repeat_index, True, out, beam_bytes)
+        # rank 0 of every utterance, aligned where it lies
+        align_ws = launch_asg_align(x, g, sz, out.data_ptr() + lay.labels, lay.labels_stride, out.data_ptr() + lay.lengths,
+                                    lay.lengths_stride, t, repeat_index, True, out, beam_bytes)
     host = out.cpu().numpy()                           # the one copy to the host (ordered after the launches on this stream)
     del align_ws
     scores, lengths, status, idx, lm_log10 = split_search_out(host, n, k, t, lm is not None)
@@ -411,12 +358,8 @@ def asg_beam_search_gpu(x, transitions, labels: Sequence[str], repeat_index: int
         raise ValueError('nbest=%d must lie in [1, k=%d]' % (nbest, k))
     if return_offsets and nbest != 1:
         raise ValueError('return_offsets aligns the best hypothesis only: nbest=%d must be 1' % nbest)
-    x = _scores_on_device(x, 'asg_beam_search_gpu')
-    single = x.dim() == 2
-    if single:
-        x = x.unsqueeze(0)
-        if sizes is not None:
-            sizes = [int(np.asarray(torch.as_tensor(sizes).cpu()).reshape(-1)[0])]
+    x, sizes, single = batch_of(x, sizes)
+    x = on_device(x, 'asg_beam_search_gpu')
     if x.dim() != 3:
         raise ValueError('expected [N, T, labels] or [T, labels] scores, got shape %s' % (tuple(x.shape),))
     n, t, a = x.shape
@@ -427,7 +370,7 @@ def asg_beam_search_gpu(x, transitions, labels: Sequence[str], repeat_index: int
     if not 0 <= int(repeat_index) < a:
         raise ValueError('repeat_index %d outside %d labels' % (repeat_index, a))
     g = _transitions_on(transitions, a, x.device)
-    sz = _lengths(sizes, n, t, 'sizes').to(x.device, non_blocking=True) if sizes is not None else None
+    sz = host_lengths(sizes, n, t, 'sizes').to(x.device, non_blocking=True) if sizes is not None else None
     scores, lengths, idx, _, starts = _search_device(x, g, sz, labels, int(repeat_index), int(k), beta, prune, lm, alpha,
                                                      return_offsets, lexicon=lexicon, complete_only=complete_only,
                                                      hotwords=hotwords, hotword_weight=hotword_weight)
@@ -459,11 +402,7 @@ def asg_forced_align(x, transitions, targets, input_lengths=None, target_lengths
     as the search returns them, the repeat label allowed, in front too.  ``paths`` holds the ENCODED label of each frame;
     ``starts`` / ``ends`` the first / last frame of each target position.  An utterance with an empty target or more labels than
     frames does not raise: ``feasible[n]`` is False."""
-    x = _scores_on_device(x, 'asg_forced_align')
-    if x.dim() == 2:
-        x = x.unsqueeze(0)
-        if input_lengths is not None:
-            input_lengths = [int(np.asarray(torch.as_tensor(input_lengths).cpu()).reshape(-1)[0])]
+    x, input_lengths, _ = batch_of(on_device(x, 'asg_forced_align'), input_lengths)
     if x.dim() != 3:
         raise ValueError('expected [N, T, labels] or [T, labels] scores, got shape %s' % (tuple(x.shape),))
     n, t, a = x.shape
@@ -474,29 +413,17 @@ def asg_forced_align(x, transitions, targets, input_lengths=None, target_lengths
         raise ValueError('asg size:%d, labels: %d' % (a, len(labels)))
     if not 0 <= int(repeat_index) < a:
         raise ValueError('repeat_index %d outside %d labels' % (repeat_index, a))
-    tg, tl = _targets_to_array(targets, target_lengths, labels, n)
-    if tg.shape[0] != n:
-        raise ValueError('%d targets for %d utterances' % (tg.shape[0], n))
-    smax = tg.shape[1]
-    if smax > 4095 or t > 32768:
-        raise ValueError('asg_forced_align: T=%d (max 32768) or target length %d (max 4095) is out of range' % (t, smax))
-    dev = x.device
-    g = _transitions_on(transitions, a, dev)
-    sz = _lengths(input_lengths, n, t, 'input_lengths').to(dev, non_blocking=True) if input_lengths is not None else None
-    # targets and their lengths travel in one buffer: [N * Smax | N] int32
-    tgt = torch.from_numpy(np.concatenate([tg.reshape(-1), tl])).to(dev, non_blocking=True)
-    out = torch.empty(align_sections(n, t, smax)[5], dtype=torch.uint8, device=dev)
+    tg, tl, smax = align_targets(targets, target_lengths, labels, n, t, 'asg_forced_align')
+    g = _transitions_on(transitions, a, x.device)
+    il = host_lengths(input_lengths, n, t, 'input_lengths') if input_lengths is not None else None
+    sz, tgt, out = align_buffers(x, il, tg, tl)
     ws = launch_asg_align(x, g, sz, tgt.data_ptr(), max(smax, 1), tgt.data_ptr() + 4 * n * smax, 1, smax, int(repeat_index),
                           encoded, out, 0)
-    host = out.cpu().numpy()                           # the one copy to the host (ordered after the launch on this stream)
+    got = aligned(out, n, t, smax, tl, 'asg_forced_align: a target outside [0, %d), %s, in utterances %%s'
+                  % (a, 'two equal neighbours in an encoded target' if encoded else
+                     'or equal to the repeat label (%d)' % repeat_index))
     del ws
-    scores, status, paths, starts, ends = split_align(host, n, t, smax)
-    if (status == 2).any():
-        rows = np.nonzero(status == 2)[0].tolist()
-        raise ValueError('asg_forced_align: a target outside [0, %d), %s, in utterances %s'
-                         % (a, 'two equal neighbours in an encoded target' if encoded else
-                            'or equal to the repeat label (%d)' % repeat_index, rows))
-    return Alignment(scores, status == 0, paths, starts, ends, tl)
+    return got
 
 
 class ASGBeamSearchDecoder(ASGDecoder):
@@ -526,9 +453,7 @@ class ASGBeamSearchDecoder(ASGDecoder):
         ``offsets[n] = [IntTensor]``: the first frame of each character of strings[n] on its hypothesis' best frame path (an
         empty string has empty offsets).  Limit: ``return_offsets`` takes at most 4095 frames -- a hypothesis can be as long
         as the utterance and w2l_asg_align takes targets of at most 4095 labels; without offsets the search has no such limit"""
-        if len(probs.shape) not in (2, 3):
-            raise RuntimeError('Decoding with wrong shape: %s, expected either [Batch X Frames X Labels] or '
-                               '[Frames X Labels]' % str(tuple(probs.shape)))
+        _check_decode_shape(probs)
         if len(probs.shape) == 2:
             probs = probs.unsqueeze(0) if torch.is_tensor(probs) else np.asarray(probs)[None]
         got = asg_beam_search_gpu(probs, self.transitions if transitions is None else transitions, list(self.labels),

@@ -21,6 +21,7 @@ import ctypes as C
 import math
 import os
 import re
+from collections import namedtuple
 from typing import Callable, Dict, List, Optional, Sequence
 
 import numpy as np
@@ -197,6 +198,11 @@ _SEP_RE = re.compile(r'[\s|>]')
 _WORDCH_RE = re.compile(r'\w')
 
 
+def word_flags(ch: str) -> int:
+    """the label-info bits both searches share: 9 = a word character (\\w), 10 = a word separator ([\\s|>])"""
+    return bool(_WORDCH_RE.fullmatch(ch)) << 9 | bool(_SEP_RE.fullmatch(ch)) << 10
+
+
 def _label_info(labels: Sequence[str], blank_index: int, end_char: str):
     """per-label flags of w2l_ctc_beam_search (include/w2l_hip.h) and the first index of ``end_char`` (-1: absent)"""
     labels = list(labels)
@@ -206,17 +212,15 @@ def _label_info(labels: Sequence[str], blank_index: int, end_char: str):
     for i, ch in enumerate(labels):
         first_index.setdefault(ch, i)
     blank = labels[blank_index]
-    info = np.array([first_index[ch] | (ch == blank) << 8 | bool(_WORDCH_RE.fullmatch(ch)) << 9
-                     | bool(_SEP_RE.fullmatch(ch)) << 10 for ch in labels], dtype=np.int32)
+    info = np.array([first_index[ch] | (ch == blank) << 8 | word_flags(ch) for ch in labels], dtype=np.int32)
     return info, first_index.get(end_char, -1)
 
 
-def _align_best(x, sz, out, n, t, k, blank_index, log_probs, beam_bytes):
+def _align_best(x, sz, out, lay, t, blank_index, log_probs):
     """w2l_ctc_align right behind the search on the same stream: rank 0 of every utterance, read in ``out`` where the search
-    wrote it (labels int32 [N, k, T] from byte 12 N k + 4 N, row stride k T; lengths int32 [N, k] from byte 8 N k, stride k;
-    an empty slot's -1 aligns as the empty string), results behind the search's ``beam_bytes``"""
-    return launch_align(x, sz, out.data_ptr() + 12 * n * k + 4 * n, k * t, out.data_ptr() + 8 * n * k, k, t, blank_index,
-                        log_probs, out, beam_bytes)
+    wrote it (``lay``: search_out_layout; an empty slot's -1 aligns as the empty string), results behind the search's bytes"""
+    return launch_align(x, sz, out.data_ptr() + lay.labels, lay.labels_stride, out.data_ptr() + lay.lengths, lay.lengths_stride,
+                        t, blank_index, log_probs, out, lay.beam_bytes)
 
 
 def _align_starts(host, n, t, beam_bytes):
@@ -251,17 +255,72 @@ def _resolve_hotwords(hotwords):
     return hotwords if isinstance(hotwords, Lexicon) else Lexicon(hotwords)
 
 
+SearchOutLayout = namedtuple('SearchOutLayout', 'beam_bytes labels labels_stride lengths lengths_stride')
+
+
+def search_out_layout(n, k, t, with_lm):
+    """a beam search's ``out`` buffer (include/w2l_hip.h): scores float64 [n, k] | lengths int32 [n, k] | status int32 [n] |
+    labels int32 [n, k, t] | with an LM lm_log10 float32 [n, k].  -> its size, and for an alignment that reads rank 0 of every
+    utterance in place the byte offset and the stride (elements, one utterance to the next) of its labels and of its length"""
+    return SearchOutLayout(12 * n * k + 4 * n + 4 * n * k * t + (4 * n * k if with_lm else 0), 12 * n * k + 4 * n, k * t,
+                           8 * n * k, k)
+
+
 def split_search_out(host, n, k, t, with_lm):
     """the sections of a beam search's ``out`` buffer (include/w2l_hip.h; ``host``: its bytes on the host, anything after them
     ignored) -> scores float64 [n, k], lengths int32 [n, k], status int32 [n], labels int32 [n, k, t], lm_log10 float32 [n, k]
     (None unless ``with_lm``)"""
     scores = host[:8 * n * k].view(np.float64).reshape(n, k)
-    rest = host[8 * n * k:12 * n * k + 4 * n + 4 * n * k * t + (4 * n * k if with_lm else 0)].view(np.int32)
+    rest = host[8 * n * k:search_out_layout(n, k, t, with_lm).beam_bytes].view(np.int32)
     lengths = rest[:n * k].reshape(n, k)
     status = rest[n * k:n * k + n]
     idx = rest[n * k + n:n * k + n + n * k * t].reshape(n, k, t)
     lm_log10 = rest[n * k + n + n * k * t:].view(np.float32).reshape(n, k) if with_lm else None
     return scores, lengths, status, idx, lm_log10
+
+
+def _word_tables(labels, silent_index, lm, lexicon, hotwords, hotword_weight, dev, what):
+    """the device tables of a search's LM, lexicon and hotword list, checked as both searches check them.  ``silent_index``: the
+    label that spells nothing (the blank; under ASG the repeat label); ``what``: the caller's name in the messages.
+    -> (LM tables, lexicon table, hotword table -- None where there is none --, the space's index or -1, the LM order or 0)"""
+    if lm is None and lexicon is None and hotwords is None:
+        return None, None, None, -1, 0
+    from .ngram_lm import ArpaLM
+    if lm is not None and not isinstance(lm, ArpaLM):
+        raise TypeError('lm must be an ngram_lm.ArpaLM, got %s' % type(lm).__name__)
+    odd = [ch for ch in labels if ch.isspace() and ch != ' ']
+    if odd:
+        raise ValueError('%s: whitespace labels other than a space (%r) cannot %s'
+                         % (what, odd, 'be scored by a word LM' if lm is not None else
+                            'separate the words of a lexicon or of a hotword list'))
+    if hotwords is not None and not math.isfinite(float(hotword_weight)):
+        raise ValueError('%s: hotword_weight must be finite, got %r' % (what, hotword_weight))
+    tables = lm.to_device(labels, silent_index, dev) if lm is not None else None
+    lex = _resolve_lexicon(lexicon, lm).to_device(labels, silent_index, dev) if lexicon is not None else None
+    hot = _resolve_hotwords(hotwords).to_device(labels, silent_index, dev) if hotwords is not None else None
+    return tables, lex, hot, labels.index(' ') if ' ' in labels else -1, lm.order if lm is not None else 0
+
+
+def _desc(table):
+    """a device table as the entry points take it (None: NULL)"""
+    return table.desc_ref if table is not None else None
+
+
+def _pick(found, nbest, return_weights, return_encoded=False):
+    """n-best rows (text, weight[, encoded]), best first -> one utterance's result: the best text; (text, weight) with
+    ``return_weights``; with ``nbest > 1`` a list of up to ``nbest`` such pairs.  ``return_encoded`` keeps the rows whole."""
+    rows = [row if return_encoded else row[:2] for row in found]
+    if nbest > 1:
+        return rows[:nbest]
+    if return_weights or return_encoded:
+        return rows[0]
+    return rows[0][0]
+
+
+def _check_decode_shape(probs):
+    if len(probs.shape) not in (2, 3):
+        raise RuntimeError('Decoding with wrong shape: %s, expected either [Batch X Frames X Labels] or '
+                           '[Frames X Labels]' % str(tuple(probs.shape)))
 
 
 def _beam_search_device(probs, labels, blank_index, k, beta, prune, end_char, sizes, log_probs, lm=None, alpha=0.3,
@@ -297,39 +356,22 @@ def _beam_search_device(probs, labels, blank_index, k, beta, prune, end_char, si
         if bool((host < 2).any()) or bool((host > t).any()):
             raise ValueError('sizes must lie in [2, %d], got %s' % (t, host.tolist()))
         sz = host.to(torch.int32).to(dev, non_blocking=True)
-    space_index = -1
+    tables, lex, hot, space_index, order = _word_tables(labels, blank_index, lm, lexicon, hotwords, hotword_weight, dev,
+                                                        'prefix_beam_search_gpu')
     if lm is not None or lexicon is not None or hotwords is not None:
-        from .ngram_lm import ArpaLM
-        if lm is not None and not isinstance(lm, ArpaLM):
-            raise TypeError('lm must be an ngram_lm.ArpaLM, got %s' % type(lm).__name__)
-        odd = [ch for ch in labels if ch.isspace() and ch != ' ']
-        if odd:
-            raise ValueError('prefix_beam_search_gpu: whitespace labels other than a space (%r) cannot be scored by a word LM'
-                             % odd if lm is not None else
-                             'prefix_beam_search_gpu: whitespace labels other than a space (%r) cannot separate the words of a '
-                             'lexicon or of a hotword list' % odd)
-        if hotwords is not None and not math.isfinite(float(hotword_weight)):
-            raise ValueError('prefix_beam_search_gpu: hotword_weight must be finite, got %r' % (hotword_weight,))
         info = info | np.array([ch.isspace() << 11 for ch in labels], dtype=np.int32)
-        space_index = labels.index(' ') if ' ' in labels else -1
-    tables = lm.to_device(labels, blank_index, dev) if lm is not None else None
-    lex = _resolve_lexicon(lexicon, lm).to_device(labels, blank_index, dev) if lexicon is not None else None
-    hot = _resolve_hotwords(hotwords).to_device(labels, blank_index, dev) if hotwords is not None else None
-    order = lm.order if lm is not None else 0
     ws_bytes = int(lib.w2l_ctc_beam_search_workspace_bytes(n, t, k, order))
     if ws_bytes < 0:
         raise ValueError('prefix_beam_search_gpu: k=%d with T=%d%s is out of range'
                          % (k, t, '' if lm is None else ' (LM order %d)' % lm.order))
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-    beam_bytes = 12 * n * k + 4 * n + 4 * n * k * t + (4 * n * k if lm is not None else 0)
-    out = torch.empty(beam_bytes + (align_sections(n, t, t)[5] if offsets else 0), dtype=torch.uint8, device=dev)
+    lay = search_out_layout(n, k, t, lm is not None)
+    out = torch.empty(lay.beam_bytes + (align_sections(n, t, t)[5] if offsets else 0), dtype=torch.uint8, device=dev)
     check(lib.w2l_ctc_beam_search(ptr(x), ptr(sz), n, t, a, info.ctypes.data_as(C.c_void_p), int(blank_index), int(end_index),
                                   space_index, int(k), float(alpha), float(beta), float(prune), int(bool(log_probs)),
-                                  tables.desc_ref if tables is not None else None, order,
-                                  lex.desc_ref if lex is not None else None, int(bool(complete_only)),
-                                  hot.desc_ref if hot is not None else None, float(hotword_weight), ptr(ws), ws_bytes, ptr(out),
-                                  stream_ptr()), 'w2l_ctc_beam_search')
-    align_ws = _align_best(x, sz, out, n, t, k, blank_index, log_probs, beam_bytes) if offsets else None
+                                  _desc(tables), order, _desc(lex), int(bool(complete_only)), _desc(hot),
+                                  float(hotword_weight), ptr(ws), ws_bytes, ptr(out), stream_ptr()), 'w2l_ctc_beam_search')
+    align_ws = _align_best(x, sz, out, lay, t, blank_index, log_probs) if offsets else None
     host = out.cpu().numpy()                           # the one copy to the host (ordered after the launches on this stream)
     del align_ws
     scores, lengths, status, idx, lm_log10 = split_search_out(host, n, k, t, lm is not None)
@@ -339,7 +381,7 @@ def _beam_search_device(probs, labels, blank_index, k, beta, prune, end_char, si
     if lm is not None:
         got += (lm_log10,)
     if offsets:
-        got += (_align_starts(host, n, t, beam_bytes),)
+        got += (_align_starts(host, n, t, lay.beam_bytes),)
     return got
 
 
@@ -392,12 +434,7 @@ def prefix_beam_search_gpu(probs, labels: Sequence[str], blank_index: int = 0, k
                  for r in range(k) if lengths[u, r] >= 0]
         if not found:                                  # the beam emptied: '' as on the host (weight 0)
             found = [('', float('-inf'))]
-        if nbest > 1:
-            results.append(found[:nbest])
-        elif return_weights:
-            results.append(found[0])
-        else:
-            results.append(found[0][0])
+        results.append(_pick(found, nbest, return_weights))
     if return_offsets:
         offs = [torch.IntTensor(got[-1][u, :max(int(lengths[u, 0]), 0)].copy()) for u in range(scores.shape[0])]
         return (results[0], offs[0]) if single else (results, offs)
@@ -422,7 +459,24 @@ def _decoder_hotwords(hotwords, hotword_weight, labels, blank_index):
     return hot, float(hotword_weight)
 
 
-class GPUPrefixBeamSearchDecoder(Decoder):
+class _GPUPrefixDecoder(Decoder):
+    """what the two device prefix decoders share: ``decode`` over the attributes their constructors set (``lm``: None, or
+    the ngram_lm.ArpaLM that ``alpha`` weighs)"""
+    lm = None
+
+    def decode(self, probs, sizes=None, return_offsets=False):
+        """[N, T, labels] -> N strings (utterance n over its first sizes[n] frames); [T, labels] -> one string.  With
+        ``return_offsets``: ``(strings, offsets)`` nested as GreedyDecoder.decode's, ``offsets[n] = [IntTensor]`` (the first frame
+        of each character of strings[n] on its best frame path), so get_time_per_word(strings[n], offsets[n][0]) applies"""
+        _check_decode_shape(probs)
+        got = prefix_beam_search_gpu(probs, self.labels, self.blank_index, self.k, self.beta, self.prune, sizes=sizes,
+                                     log_probs=self.log_probs, return_offsets=return_offsets, lexicon=self.lexicon,
+                                     hotwords=self.hotwords, hotword_weight=self.hotword_weight,
+                                     **({'lm': self.lm, 'alpha': self.alpha} if self.lm is not None else {}))
+        return _nest_offsets(got, len(probs.shape) == 2) if return_offsets else got
+
+
+class GPUPrefixBeamSearchDecoder(_GPUPrefixDecoder):
     """PrefixBeamSearchLMDecoder on the MI355X (prefix_beam_search_gpu): the same constructor (plus ``log_probs``), no
     language model -- a scoring callable cannot run on the device.  ``lexicon``: a lexicon.Lexicon or a path to a word list
     that constrains the search (prefix_beam_search_gpu).  ``hotwords``: a lexicon.Lexicon, a path or an iterable of single
@@ -440,20 +494,8 @@ class GPUPrefixBeamSearchDecoder(Decoder):
                              'PrefixBeamSearchLMDecoder, the host decoder, for LM scoring' % (lm_path, alpha))
         self.k, self.alpha, self.beta, self.prune, self.log_probs = k, alpha, beta, prune, log_probs
 
-    def decode(self, probs, sizes=None, return_offsets=False):
-        """[N, T, labels] -> N strings (utterance n over its first sizes[n] frames); [T, labels] -> one string.  With
-        ``return_offsets``: ``(strings, offsets)`` nested as GreedyDecoder.decode's, ``offsets[n] = [IntTensor]`` (the first frame
-        of each character of strings[n] on its best frame path), so get_time_per_word(strings[n], offsets[n][0]) applies"""
-        if len(probs.shape) not in (2, 3):
-            raise RuntimeError('Decoding with wrong shape: %s, expected either [Batch X Frames X Labels] or '
-                               '[Frames X Labels]' % str(tuple(probs.shape)))
-        got = prefix_beam_search_gpu(probs, self.labels, self.blank_index, self.k, self.beta, self.prune, sizes=sizes,
-                                     log_probs=self.log_probs, return_offsets=return_offsets, lexicon=self.lexicon,
-                                     hotwords=self.hotwords, hotword_weight=self.hotword_weight)
-        return _nest_offsets(got, len(probs.shape) == 2) if return_offsets else got
 
-
-class GPUPrefixBeamSearchLMDecoder(Decoder):
+class GPUPrefixBeamSearchLMDecoder(_GPUPrefixDecoder):
     """PrefixBeamSearchLMDecoder on the MI355X with an ARPA n-gram model read without kenlm (ngram_lm.ArpaLM, plain or
     .gz): the reference decoder's constructor (plus ``log_probs``); a falsy ``lm_path`` decodes without an LM.  ``lexicon``: a
     lexicon.Lexicon, a path to a word list, or 'lm' (the model's vocabulary) that constrains the search.  ``hotwords`` /
@@ -467,18 +509,6 @@ class GPUPrefixBeamSearchLMDecoder(Decoder):
         self.lm = ArpaLM(lm_path) if lm_path else None
         self.lexicon = _resolve_lexicon(lexicon, self.lm) if lexicon is not None else None
         self.k, self.alpha, self.beta, self.prune, self.log_probs = k, alpha, beta, prune, log_probs
-
-    def decode(self, probs, sizes=None, return_offsets=False):
-        """[N, T, labels] -> N strings (utterance n over its first sizes[n] frames); [T, labels] -> one string.  With
-        ``return_offsets``: ``(strings, offsets)`` nested as GreedyDecoder.decode's, ``offsets[n] = [IntTensor]`` (the first frame
-        of each character of strings[n] on its best frame path), so get_time_per_word(strings[n], offsets[n][0]) applies"""
-        if len(probs.shape) not in (2, 3):
-            raise RuntimeError('Decoding with wrong shape: %s, expected either [Batch X Frames X Labels] or '
-                               '[Frames X Labels]' % str(tuple(probs.shape)))
-        got = prefix_beam_search_gpu(probs, self.labels, self.blank_index, self.k, self.beta, self.prune, sizes=sizes,
-                                     log_probs=self.log_probs, lm=self.lm, alpha=self.alpha, return_offsets=return_offsets,
-                                     lexicon=self.lexicon, hotwords=self.hotwords, hotword_weight=self.hotword_weight)
-        return _nest_offsets(got, len(probs.shape) == 2) if return_offsets else got
 
 
 def get_time_per_word(predictions, offsets, ratio=1.0, end_offsets=None):

@@ -38,7 +38,10 @@
 // It is still one ascending set per frame, for stays and extensions alike.
 //
 // ---- the alignment: Viterbi form of Z_tgt over the S states of the encoded target, fp32, in the structure of
-// ctc_align_kernel (one lane per state, columns through LDS, moves packed over time, back-trace by wave 0).
+// ctc_align_kernel (one lane per state, columns through LDS, moves packed over time, back-trace by wave 0) with ASG's
+// recurrence: transitions added on the way, a tie stays, one state per encoded label.  The params struct, plan, workspace
+// query and launcher are align_core.h's, shared with w2l_ctc_align.
+#include "align_core.h"
 #include "beam_core.h"
 
 namespace {
@@ -485,7 +488,22 @@ extern "C" int w2l_asg_beam_search(const float* x, const float* transitions, con
 // ============================================================================================================ alignment
 namespace {
 
-constexpr float NEG_INF = -INFINITY;
+// the encoded label of position s: a row that is already encoded is read as it is; in a raw one the 2nd, 4th, ... member of a
+// run of equal labels becomes `repeat` (w2l_asg_loss's rule)
+__device__ __forceinline__ int encoded_label(const int32_t* tg, int s, int repeat, int encoded) {
+    const int v = tg[s];
+    if (encoded) return v;
+    int back = 0;
+    while (s - back - 1 >= 0 && tg[s - back - 1] == v) ++back;
+    return (back & 1) ? repeat : v;
+}
+
+struct AsgRule {                               // what align_core.h's plan and launcher ask of a criterion
+    static constexpr const char* NAME = "asg_align";
+    static constexpr int GUARD = 1, MAX_SPT = 4, MAX_STATES = 4095;
+    static int states(int S) { return S; }
+    static size_t lds_round(size_t bytes) { return (bytes + 3) & ~(size_t)3; }
+};
 
 struct AsgAlignParams {
     const float* x;            // [N][T][A] scores
@@ -502,16 +520,6 @@ struct AsgAlignParams {
     int32_t* starts;           // [N][Smax]
     int32_t* ends;             // [N][Smax]
 };
-
-// the encoded label of position s: a row that is already encoded is read as it is; in a raw one the 2nd, 4th, ... member of a
-// run of equal labels becomes `repeat` (w2l_asg_loss's rule)
-__device__ __forceinline__ int encoded_label(const int32_t* tg, int s, int repeat, int encoded) {
-    const int v = tg[s];
-    if (encoded) return v;
-    int back = 0;
-    while (s - back - 1 >= 0 && tg[s - back - 1] == v) ++back;
-    return (back & 1) ? repeat : v;
-}
 
 // NT threads, SPT states per thread (state s = tid + k * NT), PF = frames of emissions held ahead in registers.
 template <int NT, int SPT>
@@ -690,39 +698,16 @@ __global__ __launch_bounds__(NT) void asg_align_kernel(AsgAlignParams p) {
     }
 }
 
-struct AsgAlignPlan {
-    int nt, spt;
-    size_t lds_fixed;      // columns + state sequence
-    size_t bp_bytes;       // moves of one utterance
-    bool bp_lds;
+struct AsgAlignKernels {
+    template <int NT, int SPT>
+    static auto get() { return asg_align_kernel<NT, SPT>; }
 };
-
-// block shape and where the moves live, from the shapes alone (the workspace query and the launch must agree)
-bool asg_align_plan(int T, int Smax, AsgAlignPlan* pl) {
-    if (T <= 0 || T > 32768 || Smax < 0 || Smax > 4095) return false;
-    const int L = Smax < 1 ? 1 : Smax;
-    static const int kWide[] = {64, 128, 256, 512, 1024};
-    int nt = 1024;
-    for (int w : kWide)
-        if (L <= w) { nt = w; break; }
-    int spt = (L + nt - 1) / nt;
-    if (spt > 2) spt = 4;
-    pl->nt = nt;
-    pl->spt = spt;
-    const size_t lw = (size_t)nt * spt;
-    pl->lds_fixed = 4 * sizeof(float) + 2 * (lw + 1) * sizeof(float) + (size_t)((T + 1) & ~1) * sizeof(uint16_t);
-    pl->lds_fixed = (pl->lds_fixed + 3) & ~(size_t)3;
-    pl->bp_bytes = (size_t)((T + 15) >> 4) * lw * sizeof(uint32_t);
-    pl->bp_lds = pl->lds_fixed + pl->bp_bytes <= 150 * 1024;
-    return true;
-}
 
 }  // namespace
 
 extern "C" int64_t w2l_asg_align_workspace_bytes(int N, int T, int A, int Smax) {
-    AsgAlignPlan pl;
-    if (N <= 0 || A < 1 || A > AB_AMAX || !asg_align_plan(T, Smax, &pl)) return -1;
-    return pl.bp_lds ? 0 : (int64_t)N * (int64_t)pl.bp_bytes;
+    if (A < 1 || A > AB_AMAX) return -1;
+    return align_workspace_bytes<AsgRule>(N, T, Smax);
 }
 
 extern "C" int w2l_asg_align(const float* x, const float* transitions, const int32_t* input_lengths, const int32_t* targets,
@@ -734,38 +719,11 @@ extern "C" int w2l_asg_align(const float* x, const float* transitions, const int
     W2L_CHECK_ARG(N > 0 && T > 0 && A >= 1 && A <= AB_AMAX && Smax >= 0 && repeat_index >= 0 && repeat_index < A,
                   "asg_align: bad sizes (labels 1..%d)", AB_AMAX);
     W2L_CHECK_ARG(target_stride >= Smax && length_stride >= 1, "asg_align: bad strides");
-    AsgAlignPlan pl;
-    W2L_CHECK_ARG(asg_align_plan(T, Smax, &pl), "asg_align: T=%d (max 32768) or target length %d (max 4095) out of range", T, Smax);
-    const int64_t need = pl.bp_lds ? 0 : (int64_t)N * (int64_t)pl.bp_bytes;
-    W2L_CHECK_ARG(workspace_bytes >= need && (need == 0 || workspace), "asg_align: workspace of %lld bytes, %lld needed",
-                  (long long)workspace_bytes, (long long)need);
     AsgAlignParams p;
-    p.x = x; p.g = transitions; p.in_len = input_lengths; p.targets = targets; p.tg_len = target_lengths;
+    p.x = x; p.in_len = input_lengths; p.targets = targets; p.tg_len = target_lengths;
     p.tg_stride = target_stride; p.len_stride = length_stride;
-    p.N = N; p.T = T; p.A = A; p.Smax = Smax; p.repeat = repeat_index; p.encoded = encoded != 0; p.bp_lds = pl.bp_lds;
-    p.bp_global = (uint32_t*)workspace;
+    p.N = N; p.T = T; p.A = A; p.Smax = Smax;
+    p.g = transitions; p.repeat = repeat_index; p.encoded = encoded != 0;
     p.score = score; p.status = status; p.path = path; p.starts = starts; p.ends = ends;
-    const size_t lds = pl.lds_fixed + (pl.bp_lds ? pl.bp_bytes : 0);
-    dim3 grid(N), block(pl.nt);
-#define W2L_ASG_ALIGN_LAUNCH(NT, SPT)                                                                   \
-    do {                                                                                                \
-        W2L_CHECK_HIP(w2l_allow_big_lds((const void*)asg_align_kernel<NT, SPT>));                       \
-        hipLaunchKernelGGL((asg_align_kernel<NT, SPT>), grid, block, lds, (hipStream_t)stream, p);      \
-    } while (0)
-    if (pl.spt == 1) {
-        switch (pl.nt) {
-            case 64: W2L_ASG_ALIGN_LAUNCH(64, 1); break;
-            case 128: W2L_ASG_ALIGN_LAUNCH(128, 1); break;
-            case 256: W2L_ASG_ALIGN_LAUNCH(256, 1); break;
-            case 512: W2L_ASG_ALIGN_LAUNCH(512, 1); break;
-            default: W2L_ASG_ALIGN_LAUNCH(1024, 1); break;
-        }
-    } else if (pl.spt == 2) {
-        W2L_ASG_ALIGN_LAUNCH(1024, 2);
-    } else {
-        W2L_ASG_ALIGN_LAUNCH(1024, 4);
-    }
-#undef W2L_ASG_ALIGN_LAUNCH
-    W2L_CHECK_LAUNCH();
-    return 0;
+    return align_launch<AsgRule, AsgAlignKernels>(p, workspace, workspace_bytes, stream);
 }

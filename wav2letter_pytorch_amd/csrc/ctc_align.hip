@@ -11,12 +11,19 @@
 // over TIME, 16 frames to a 32-bit word per state, so packing needs no cross-lane traffic and a word store is coalesced over
 // states; the words live in LDS when they fit, else in the caller's workspace.  Wave 0 walks the moves back, then every thread
 // turns the state sequence into labels, starts and ends.
-#include "common.h"
-#include <math.h>
+//
+// The params struct, the plan (block shape, LDS or workspace), the workspace query and the launcher are align_core.h's, shared
+// with w2l_asg_align; asg_align_kernel (asg_beam.hip) has this kernel's structure with ASG's recurrence.
+#include "align_core.h"
 
 namespace {
 
-constexpr float NEG_INF = -INFINITY;
+struct CtcRule {                               // what align_core.h's plan and launcher ask of a criterion
+    static constexpr const char* NAME = "ctc_align";
+    static constexpr int GUARD = 2, MAX_SPT = 8, MAX_STATES = 8 * 1024;
+    static int states(int S) { return 2 * S + 1; }
+    static size_t lds_round(size_t bytes) { return bytes; }
+};
 
 struct AlignParams {
     const float* x;            // [N][T][A] log-probabilities, or probabilities if is_prob
@@ -220,39 +227,14 @@ __global__ __launch_bounds__(NT) void ctc_align_kernel(AlignParams p) {
     }
 }
 
-struct AlignPlan {
-    int nt, spt;
-    size_t lds_fixed;      // columns + state sequence
-    size_t bp_bytes;       // moves of one utterance
-    bool bp_lds;
+struct CtcAlignKernels {
+    template <int NT, int SPT>
+    static auto get() { return ctc_align_kernel<NT, SPT>; }
 };
-
-// block shape and where the moves live, from the shapes alone (the workspace query and the launch must agree)
-bool align_plan(int T, int Smax, AlignPlan* pl) {
-    const int L = 2 * Smax + 1;
-    if (T <= 0 || T > 32768 || Smax < 0 || L > 8 * 1024) return false;
-    static const int kWide[] = {64, 128, 256, 512, 1024};
-    int nt = 1024;
-    for (int w : kWide)
-        if (L <= w) { nt = w; break; }
-    int spt = (L + nt - 1) / nt;
-    if (spt > 2) spt = spt <= 4 ? 4 : 8;
-    pl->nt = nt;
-    pl->spt = spt;
-    const size_t lw = (size_t)nt * spt;
-    pl->lds_fixed = 4 * sizeof(float) + 2 * (lw + 2) * sizeof(float) + (size_t)((T + 1) & ~1) * sizeof(uint16_t);
-    pl->bp_bytes = (size_t)((T + 15) >> 4) * lw * sizeof(uint32_t);
-    pl->bp_lds = pl->lds_fixed + pl->bp_bytes <= 150 * 1024;
-    return true;
-}
 
 }  // namespace
 
-extern "C" int64_t w2l_ctc_align_workspace_bytes(int N, int T, int Smax) {
-    AlignPlan pl;
-    if (N <= 0 || !align_plan(T, Smax, &pl)) return -1;
-    return pl.bp_lds ? 0 : (int64_t)N * (int64_t)pl.bp_bytes;
-}
+extern "C" int64_t w2l_ctc_align_workspace_bytes(int N, int T, int Smax) { return align_workspace_bytes<CtcRule>(N, T, Smax); }
 
 extern "C" int w2l_ctc_align(const float* x, const int32_t* input_lengths, const int32_t* targets, int64_t target_stride,
                              const int32_t* target_lengths, int64_t length_stride, int N, int T, int A, int Smax, int blank,
@@ -262,40 +244,10 @@ extern "C" int w2l_ctc_align(const float* x, const int32_t* input_lengths, const
     W2L_CHECK_ARG(Smax == 0 || (targets && starts && ends), "ctc_align: null targets / starts / ends");
     W2L_CHECK_ARG(N > 0 && T > 0 && A > 0 && Smax >= 0 && blank >= 0 && blank < A, "ctc_align: bad sizes");
     W2L_CHECK_ARG(target_stride >= Smax && length_stride >= 1, "ctc_align: bad strides");
-    AlignPlan pl;
-    W2L_CHECK_ARG(align_plan(T, Smax, &pl), "ctc_align: T=%d (max 32768) or target length %d (max 4095) out of range", T, Smax);
-    const int64_t need = pl.bp_lds ? 0 : (int64_t)N * (int64_t)pl.bp_bytes;
-    W2L_CHECK_ARG(workspace_bytes >= need && (need == 0 || workspace), "ctc_align: workspace of %lld bytes, %lld needed",
-                  (long long)workspace_bytes, (long long)need);
     AlignParams p;
     p.x = x; p.in_len = input_lengths; p.targets = targets; p.tg_len = target_lengths;
     p.tg_stride = target_stride; p.len_stride = length_stride;
-    p.N = N; p.T = T; p.A = A; p.Smax = Smax; p.blank = blank; p.is_prob = !log_probs; p.bp_lds = pl.bp_lds;
-    p.bp_global = (uint32_t*)workspace;
+    p.N = N; p.T = T; p.A = A; p.Smax = Smax; p.blank = blank; p.is_prob = !log_probs;
     p.score = score; p.status = status; p.path = path; p.starts = starts; p.ends = ends;
-    const size_t lds = pl.lds_fixed + (pl.bp_lds ? pl.bp_bytes : 0);
-    dim3 grid(N), block(pl.nt);
-#define W2L_ALIGN_LAUNCH(NT, SPT)                                                                       \
-    do {                                                                                                \
-        W2L_CHECK_HIP(w2l_allow_big_lds((const void*)ctc_align_kernel<NT, SPT>));                       \
-        hipLaunchKernelGGL((ctc_align_kernel<NT, SPT>), grid, block, lds, (hipStream_t)stream, p);      \
-    } while (0)
-    if (pl.spt == 1) {
-        switch (pl.nt) {
-            case 64: W2L_ALIGN_LAUNCH(64, 1); break;
-            case 128: W2L_ALIGN_LAUNCH(128, 1); break;
-            case 256: W2L_ALIGN_LAUNCH(256, 1); break;
-            case 512: W2L_ALIGN_LAUNCH(512, 1); break;
-            default: W2L_ALIGN_LAUNCH(1024, 1); break;
-        }
-    } else {
-        switch (pl.spt) {
-            case 2: W2L_ALIGN_LAUNCH(1024, 2); break;
-            case 4: W2L_ALIGN_LAUNCH(1024, 4); break;
-            default: W2L_ALIGN_LAUNCH(1024, 8); break;
-        }
-    }
-#undef W2L_ALIGN_LAUNCH
-    W2L_CHECK_LAUNCH();
-    return 0;
+    return align_launch<CtcRule, CtcAlignKernels>(p, workspace, workspace_bytes, stream);
 }
