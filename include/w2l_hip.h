@@ -40,7 +40,8 @@ int w2l_pack_weights(const float* w, int64_t s_co, int64_t s_ci, int64_t s_kw, i
                      int CoutP, int CinP, void* w_fwd_hi, void* w_fwd_lo, void* w_dgr_hi, void* w_dgr_lo,
                      void* stream);
 
-/* torch.optim.SGD(momentum, nesterov, weight_decay; dampening 0) -- configuration/optimizer/exp_lr_optimizer.yaml:2-7
+/* (csrc/optim.hip, like every entry point that applies an update rule)
+ * torch.optim.SGD(momentum, nesterov, weight_decay; dampening 0) -- configuration/optimizer/exp_lr_optimizer.yaml:2-7
  * -- fused with w2l_pack_weights for a tap-major conv weight: p, g, m are dense fp32 [Kw][Cout][Cin];
  * first_step != 0 initialises the momentum buffer with the (decayed) gradient as torch does.  The bf16
  * outputs are the operands of the next step (no channel padding: Cout, Cin multiples of 64).  zero_grad != 0 writes
@@ -953,9 +954,9 @@ int w2l_stream_wait_stream(void* waiter, void* signaler);
  * gradient pools (hipMemsetAsync); the zero- / one-padded copy of a per-channel vector (conv bias of the 29-label classifier
  * padded to 64, wav2letter.py:69); `+= delta` on a device int64 (the dropout step counter of a replayed step: the Philox
  * offset of nn.Dropout, wav2letter.py:38,44, must move every step); num_batches_tracked += 1 of every BatchNorm1d of the
- * stack in one launch (table_dev: n device pointers to int64 scalars; wav2letter.py:37); torch.optim.SGD's update of all
- * the small parameters -- biases, BatchNorm gamma / beta -- in one launch (exp_lr_optimizer.yaml:2-7; dampening 0;
- * m == NULL: no momentum buffer). */
+ * stack in one launch (table_dev: n device pointers to int64 scalars; wav2letter.py:37); and (csrc/optim.hip)
+ * torch.optim.SGD's update of all the small parameters -- biases, BatchNorm gamma / beta -- in one launch
+ * (exp_lr_optimizer.yaml:2-7; dampening 0; m == NULL: no momentum buffer). */
 int w2l_fill_zero(void* p, int64_t bytes, void* stream);
 int w2l_pad_vec_f32(const float* src, int n, float* dst, int cp, float fill, void* stream);
 int w2l_counter_add(void* counter_i64, int64_t delta, void* stream);
@@ -965,8 +966,8 @@ int w2l_sgd_small_multi(const w2l_sgd_small_t* items_dev, int nitems, int max_n 
                         float momentum, float weight_decay, int nesterov, void* stream);
 
 /* ---- gradient clipping (torch.nn.utils.clip_grad_norm_ / clip_grad_value_; Lightning's Trainer(gradient_clip_val=,
- * gradient_clip_algorithm=) around the reference's fit, train.py:34-37), applied on read by the SGD updates ---------------
- * Called by optim.FusedSGD.clip_grad_norm_ / clip_grad_value_ between backward() and step().
+ * gradient_clip_algorithm=) around the reference's fit, train.py:34-37), applied on read by the updates of csrc/optim.hip --
+ * Called by optim.FusedBase.clip_grad_norm_ / clip_grad_value_ between backward() and step().
  *
  * clip: a float[4] device buffer owned by the caller: [W2L_CLIP_NORM] total norm, [W2L_CLIP_COEF] coefficient,
  * [W2L_CLIP_BOUND] clamp bound.  w2l_grad_sqnorm_multi: the total norm of all gradients in the table (norm type 2, or inf

@@ -1,5 +1,5 @@
-"""Float64 reference of the fused Adam / AdamW kernels (csrc/common.h adam_update, csrc/pack.hip adam_pack_kernel,
-csrc/replay.hip adam_small_multi_kernel, adam_tick_kernel), restated from their formulas with kernel_refs.Tr -- plain NumPy.
+"""Float64 reference of the fused Adam / AdamW kernels (csrc/optim.hip: adam_update, adam_pack_kernel,
+adam_small_multi_kernel, adam_tick_kernel), restated from their formulas with kernel_refs.Tr -- plain NumPy.
 
 The rule, in torch's order (_single_tensor_adam; amsgrad, maximize off), with the three step-dependent scalars
 dyn = [lr, lr / (1 - beta1^t), sqrt(1 - beta2^t)] as the device holds them (fp32 values, taken as exact inputs):

@@ -1,5 +1,5 @@
 """Float64 references of the depthwise-convolution, fused-optimizer and pad-cast kernels, restated from the formulas in
-csrc/dwconv.hip, csrc/pack.hip, csrc/replay.hip and csrc/common.h -- plain NumPy, nothing of the engine's Python.
+csrc/dwconv.hip, csrc/pack.hip, csrc/optim.hip and csrc/common.h -- plain NumPy, nothing of the engine's Python.
 
 Every reference returns the exact result (the inputs are fp32 / bf16 values, so float64 holds every product exactly and
 the sums to ~1e-16) AND what the error bound of the fp32 device kernel needs.
@@ -156,7 +156,7 @@ def dw_wgrad_ref(dy, xp, N, Tout, C, K, s, d, lens):
     return dw, A, int(sum(lims))
 
 
-# ---- SGD (csrc/pack.hip sgd_pack_kernel, csrc/replay.hip sgd_small_multi_kernel) --------------------------------------------
+# ---- SGD (csrc/optim.hip sgd_pack_kernel, sgd_small_multi_kernel) ------------------------------------------------------------
 
 def sgd_ref(p, g, m, first, lr, mu, wd, nesterov, coef=None, bound=None):
     """torch.optim.SGD, dampening 0:  g' = clamp(g*coef, -bound, bound) (only if coef is given) + wd*p;
@@ -181,7 +181,7 @@ def sgd_ref(p, g, m, first, lr, mu, wd, nesterov, coef=None, bound=None):
     return P - lr * step, M
 
 
-# ---- Novograd (csrc/pack.hip) --------------------------------------------------------------------------------------------------
+# ---- Novograd (csrc/optim.hip) -------------------------------------------------------------------------------------------------
 
 def novograd_norm_depth(n, nblocks):
     """roundings on the longest path of ||g||^2: the square, a thread's chain of additions over its strided share, the

@@ -405,7 +405,7 @@ def test_sgd_small_multi(L):
 # w2l_novograd_pack
 # ================================================================================================================================
 
-NOVO_SHAPES = [(64, 64, 1), (128, 64, 11), (1024, 1024, 5)]
+NOVO_SHAPES = [(64, 64, 1), (128, 64, 11), (96, 40, 5), (1024, 1024, 5)]      # (96, 40, 5): partial 32x32 tiles on both axes
 NOVO = dict(lr=0.02, b1=0.95, b2=0.5, eps=1e-8)
 
 

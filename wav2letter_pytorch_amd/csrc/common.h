@@ -33,58 +33,26 @@ __device__ __forceinline__ void f32_split_bf16(float f, bf16_raw& hi, bf16_raw& 
     lo = f32_to_bf16_bits(f - bf16_bits_to_f32(hi));
 }
 
-// ---- gradient clipping applied on read (w2l_grad_sqnorm_multi / w2l_grad_clip_value write the buffer; the _clip update
-// kernels read it).  Slots of the float[4] clip buffer, as in include/w2l_hip.h. ----
+// one value -> its place in a bf16 operand buffer: hi, and lo where the split-bf16 mode keeps one
+__device__ __forceinline__ void put_split(bf16_raw* hi, bf16_raw* lo, int64_t off, float v) {
+    bf16_raw h, l;
+    f32_split_bf16(v, h, l);
+    hi[off] = h;
+    if (lo) lo[off] = l;
+}
+// one float -> one OCP e4m3 byte (round to nearest even, saturating at +-448)
+__device__ __forceinline__ uint8_t quant1_e4m3(float v) {
+    v = fminf(fmaxf(v, -448.f), 448.f);
+    return (uint8_t)(__builtin_amdgcn_cvt_pk_fp8_f32(v, 0.f, 0, false) & 0xFF);
+}
+
+// ---- slots of the float[4] gradient-clip buffer, as in include/w2l_hip.h (w2l_grad_sqnorm_multi / w2l_grad_clip_value write
+// it; the update kernels of optim.hip read it) ----
 #ifndef W2L_CLIP_NORM
 #define W2L_CLIP_NORM 0
 #define W2L_CLIP_COEF 1
 #define W2L_CLIP_BOUND 2
 #endif
-// clamp(g * coef, -bound, bound) in torch's order (clip_grad_norm_ multiplies, clip_grad_value_ clamps).  The product is rounded
-// on its own, so that a caller's following `g + wd * p` contracts exactly as it does without clipping; comparisons instead of
-// fminf / fmaxf keep a NaN a NaN (torch.clamp propagates it).
-__device__ __forceinline__ float clip_grad_read(float g, float coef, float bound) {
-    g = __fmul_rn(g, coef);
-    g = g < -bound ? -bound : g;
-    return g > bound ? bound : g;
-}
-
-// ---- Adam / AdamW, one element (w2l_adam_pack, w2l_adam_small_multi): torch's _single_tensor_adam, amsgrad / maximize off.
-// What changes from step to step lives in device memory (the float[4] `dyn` w2l_adam_tick writes): lr, lr / (1 - beta1^t),
-// sqrt(1 - beta2^t) -- a recorded launch names the buffer, not the values.
-//   decoupled (AdamW): p *= 1 - lr*wd        else: g += wd*p
-//   m = beta1*m + (1-beta1)*g;  v = beta2*v + (1-beta2)*g*g;  p -= dyn[1] * m / (sqrt(v)/dyn[2] + eps) ----
-#define W2L_ADAM_LR 0
-#define W2L_ADAM_STEP_SIZE 1
-#define W2L_ADAM_BC2_SQRT 2
-struct adam_scalars {
-    float lr, step_size, bc2_sqrt, beta1, beta2, omb1, omb2, eps, wd;
-    int decoupled;
-};
-__device__ __forceinline__ adam_scalars adam_load_scalars(const float* dyn, float beta1, float beta2, float eps, float wd,
-                                                          int decoupled) {
-    adam_scalars s;
-    s.lr = dyn[W2L_ADAM_LR];
-    s.step_size = dyn[W2L_ADAM_STEP_SIZE];
-    s.bc2_sqrt = dyn[W2L_ADAM_BC2_SQRT];
-    s.beta1 = beta1;
-    s.beta2 = beta2;
-    s.omb1 = 1.f - beta1;
-    s.omb2 = 1.f - beta2;
-    s.eps = eps;
-    s.wd = wd;
-    s.decoupled = decoupled;
-    return s;
-}
-// -> the new p; m and v are updated in place
-__device__ __forceinline__ float adam_update(const adam_scalars& s, float pv, float gv, float& mv, float& vv) {
-    if (s.decoupled) pv *= 1.f - s.lr * s.wd;
-    else if (s.wd != 0.f) gv += s.wd * pv;
-    mv = s.beta1 * mv + s.omb1 * gv;
-    vv = s.beta2 * vv + s.omb2 * (gv * gv);
-    const float denom = sqrtf(vv) / s.bc2_sqrt + s.eps;
-    return pv - s.step_size * (mv / denom);
-}
 
 // ---- error reporting across the C ABI (no exceptions, no exit) ----
 void w2l_set_error(const char* fmt, ...);

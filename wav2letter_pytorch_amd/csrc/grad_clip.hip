@@ -1,8 +1,8 @@
 // Gradient clipping with the coefficient computed on the device: torch.nn.utils.clip_grad_norm_ / clip_grad_value_ (what
 // Lightning's Trainer(gradient_clip_val=...) calls between backward() and step()) without a host read and without a pass
 // that rewrites the gradients.  w2l_grad_sqnorm_multi reads every gradient ONCE (one launch over a table of tensors, then a
-// one-block finalize) and leaves {total norm, coefficient, bound} in a small device buffer; the clipped SGD update kernels
-// (w2l_sgd_pack_clip, w2l_sgd_small_multi_clip) apply clamp(g * coef, -bound, bound) as they read each gradient.
+// one-block finalize) and leaves {total norm, coefficient, bound} in a small device buffer; the update kernels of optim.hip
+// apply clamp(g * coef, -bound, bound) as they read each gradient.
 //
 // Deterministic: fixed grid, fixed chunk-to-block assignment, per-block partials summed in a fixed order -- no atomics on
 // values.  Data-parallel replicas hold bit-identical averaged gradients and must derive bit-identical coefficients.

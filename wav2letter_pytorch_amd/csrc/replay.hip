@@ -89,71 +89,6 @@ __global__ void add_i64_multi_kernel(long long* const* table, int n, long long d
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) table[i][0] += delta;
 }
-// torch.optim.SGD's update of one small parameter (bias, BatchNorm gamma / beta) per block: g' = g + wd p;
-// m = mu m + g' (dampening 0);  p -= lr (nesterov ? g' + mu m : m)
-// grid = (items, chunks of SGD_SMALL_CHUNK elements): most items are one chunk (a few hundred channels); the classifier weight
-// (29 x 1024) is fifteen -- one block walking it alone took 96 us on the caller's stream at every step boundary
-constexpr int SGD_SMALL_CHUNK = 2048;
-// CLIP (w2l_sgd_small_multi_clip): the gradient is read through clip_grad_read (common.h), as in w2l_sgd_pack_clip
-template <bool CLIP>
-__global__ __launch_bounds__(256) void sgd_small_multi_kernel(const w2l_sgd_small_t* items, float lr, float mu, float wd, int nesterov,
-                                                              const float* clip) {
-    const w2l_sgd_small_t it = items[blockIdx.x];
-    const int lo = blockIdx.y * SGD_SMALL_CHUNK, hi = min(it.n, lo + SGD_SMALL_CHUNK);
-    float coef = 1.f, bound = 0.f;
-    if constexpr (CLIP) {
-        coef = clip[W2L_CLIP_COEF];
-        bound = clip[W2L_CLIP_BOUND];
-    }
-    for (int i = lo + threadIdx.x; i < hi; i += 256) {
-        float pv = it.p[i];
-        float gv = it.g[i];
-        if constexpr (CLIP) gv = clip_grad_read(gv, coef, bound);
-        if (wd != 0.f) gv += wd * pv;
-        float step = gv;
-        if (it.m != nullptr) {
-            const float mv = mu * it.m[i] + gv;
-            it.m[i] = mv;
-            step = nesterov ? gv + mu * mv : mv;
-        }
-        it.p[i] = pv - lr * step;
-    }
-}
-// torch.optim.Adam / AdamW's update of one small parameter per block row (common.h adam_update); grid and chunking as above
-template <bool CLIP>
-__global__ __launch_bounds__(256) void adam_small_multi_kernel(const w2l_adam_small_t* items, const float* dyn, float beta1, float beta2,
-                                                               float eps, float wd, int decoupled, const float* clip) {
-    const w2l_adam_small_t it = items[blockIdx.x];
-    const int lo = blockIdx.y * SGD_SMALL_CHUNK, hi = min(it.n, lo + SGD_SMALL_CHUNK);
-    const adam_scalars s = adam_load_scalars(dyn, beta1, beta2, eps, wd, decoupled);
-    float coef = 1.f, bound = 0.f;
-    if constexpr (CLIP) {
-        coef = clip[W2L_CLIP_COEF];
-        bound = clip[W2L_CLIP_BOUND];
-    }
-    for (int i = lo + threadIdx.x; i < hi; i += 256) {
-        float gv = it.g[i];
-        if constexpr (CLIP) gv = clip_grad_read(gv, coef, bound);
-        float mv = it.m[i], vv = it.v[i];
-        const float pv = adam_update(s, it.p[i], gv, mv, vv);
-        it.m[i] = mv;
-        it.v[i] = vv;
-        it.p[i] = pv;
-    }
-}
-// the step-dependent scalars of one parameter group, advanced on the device: running products (not pow), so that a host
-// loop of the same double multiplies reproduces pow1 / pow2 bit for bit; the quotients formed in fp64 and rounded once
-__global__ void adam_tick_kernel(w2l_adam_state_t* st, float* dyn, double lr, double beta1, double beta2) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    const double p1 = st->pow1 * beta1, p2 = st->pow2 * beta2;
-    st->step += 1;
-    st->pow1 = p1;
-    st->pow2 = p2;
-    dyn[W2L_ADAM_LR] = (float)lr;
-    dyn[W2L_ADAM_STEP_SIZE] = (float)(lr / (1.0 - p1));
-    dyn[W2L_ADAM_BC2_SQRT] = (float)sqrt(1.0 - p2);
-    dyn[3] = 0.f;
-}
 }  // namespace
 
 extern "C" int w2l_pad_vec_f32(const float* src, int n, float* dst, int cp, float fill, void* stream) {
@@ -174,55 +109,6 @@ extern "C" int w2l_add_i64_multi(void* table_dev, int n, int64_t delta, void* st
     if (n <= 0) return 0;
     hipLaunchKernelGGL(add_i64_multi_kernel, dim3((n + 63) / 64), dim3(64), 0, (hipStream_t)stream, (long long* const*)table_dev, n,
                        (long long)delta);
-    W2L_CHECK_LAUNCH();
-    return 0;
-}
-extern "C" int w2l_sgd_small_multi(const w2l_sgd_small_t* items_dev, int nitems, int max_n, float lr, float momentum,
-                                   float weight_decay, int nesterov, void* stream) {
-    W2L_CHECK_ARG(items_dev != nullptr || nitems == 0, "sgd_small_multi: null table");
-    W2L_CHECK_ARG(max_n >= 0 && max_n <= (1 << 26), "sgd_small_multi: max_n (the largest item's element count) out of range");
-    if (nitems <= 0 || max_n == 0) return 0;
-    const int chunks = (max_n + SGD_SMALL_CHUNK - 1) / SGD_SMALL_CHUNK;
-    hipLaunchKernelGGL(sgd_small_multi_kernel<false>, dim3(nitems, chunks), dim3(256), 0, (hipStream_t)stream, items_dev, lr,
-                       momentum, weight_decay, nesterov, nullptr);
-    W2L_CHECK_LAUNCH();
-    return 0;
-}
-extern "C" int w2l_sgd_small_multi_clip(const w2l_sgd_small_t* items_dev, int nitems, int max_n, float lr, float momentum,
-                                        float weight_decay, int nesterov, const float* clip, void* stream) {
-    W2L_CHECK_ARG(items_dev != nullptr || nitems == 0, "sgd_small_multi_clip: null table");
-    W2L_CHECK_ARG(clip != nullptr, "sgd_small_multi_clip: null clip buffer");
-    W2L_CHECK_ARG(max_n >= 0 && max_n <= (1 << 26), "sgd_small_multi_clip: max_n (the largest item's element count) out of range");
-    if (nitems <= 0 || max_n == 0) return 0;
-    const int chunks = (max_n + SGD_SMALL_CHUNK - 1) / SGD_SMALL_CHUNK;
-    hipLaunchKernelGGL(sgd_small_multi_kernel<true>, dim3(nitems, chunks), dim3(256), 0, (hipStream_t)stream, items_dev, lr,
-                       momentum, weight_decay, nesterov, clip);
-    W2L_CHECK_LAUNCH();
-    return 0;
-}
-
-extern "C" int w2l_adam_small_multi(const w2l_adam_small_t* items_dev, int nitems, int max_n, const float* dyn, float beta1,
-                                    float beta2, float eps, float weight_decay, int decoupled, const float* clip, void* stream) {
-    W2L_CHECK_ARG(items_dev != nullptr || nitems == 0, "adam_small_multi: null table");
-    W2L_CHECK_ARG(dyn != nullptr, "adam_small_multi: null dyn buffer");
-    W2L_CHECK_ARG(max_n >= 0 && max_n <= (1 << 26), "adam_small_multi: max_n (the largest item's element count) out of range");
-    W2L_CHECK_ARG(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f && eps >= 0.f, "adam_small_multi: betas in [0, 1), eps >= 0");
-    if (nitems <= 0 || max_n == 0) return 0;
-    const int chunks = (max_n + SGD_SMALL_CHUNK - 1) / SGD_SMALL_CHUNK;
-    if (clip == nullptr)
-        hipLaunchKernelGGL(adam_small_multi_kernel<false>, dim3(nitems, chunks), dim3(256), 0, (hipStream_t)stream, items_dev, dyn,
-                           beta1, beta2, eps, weight_decay, decoupled, nullptr);
-    else
-        hipLaunchKernelGGL(adam_small_multi_kernel<true>, dim3(nitems, chunks), dim3(256), 0, (hipStream_t)stream, items_dev, dyn,
-                           beta1, beta2, eps, weight_decay, decoupled, clip);
-    W2L_CHECK_LAUNCH();
-    return 0;
-}
-// NOT in the replay table: the one call of an optimizer step whose arguments change from step to step
-extern "C" int w2l_adam_tick(w2l_adam_state_t* state_dev, float* dyn_dev, double lr, double beta1, double beta2, void* stream) {
-    W2L_CHECK_ARG(state_dev != nullptr && dyn_dev != nullptr, "adam_tick: null pointer");
-    W2L_CHECK_ARG(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0, "adam_tick: betas in [0, 1)");
-    hipLaunchKernelGGL(adam_tick_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, state_dev, dyn_dev, lr, beta1, beta2);
     W2L_CHECK_LAUNCH();
     return 0;
 }

@@ -16,13 +16,6 @@ import torch
 from torch.optim import Optimizer
 
 
-def _is_tap_major(t: torch.Tensor) -> bool:
-    if t.dim() != 3:
-        return False
-    co, ci, kw = t.shape
-    return t.stride() == (ci, 1, co * ci)
-
-
 class Novograd(Optimizer):
     def __init__(self, params, lr=1e-3, betas=(0.95, 0), eps=1e-8, weight_decay=0, grad_averaging=False,
                  amsgrad=False):
@@ -41,27 +34,16 @@ class Novograd(Optimizer):
     fused = True            # use w2l_novograd_pack for eligible conv weights (False: torch ops only)
 
     def _fused_step(self, p, grad, state, group) -> bool:
-        if not (p.is_cuda and p.dtype == torch.float32 and _is_tap_major(p) and grad.stride() == p.stride()
-                and grad.dtype == torch.float32 and p.shape[0] % 64 == 0 and p.shape[1] % 64 == 0
-                and state['exp_avg'].stride() == p.stride()):
+        if not p.is_cuda:                                            # (host tensors need no HIP library: nothing below is imported)
             return False
-        from . import engine as E
         from ._lib import check, lib, ptr, stream_ptr
+        from .optim import _conv_ok, _operands, _packed
+        if not (_conv_ok(p, grad) and grad.dtype == torch.float32 and state['exp_avg'].stride() == p.stride()):
+            return False
         cout, cin, kw = p.shape
         dev = p.device
-        cache = getattr(p, '_w2l_pack', None)
-        if cache is None:
-            cache = E._Volatile()
-            p._w2l_pack = cache
-        precise = any(k for k in cache)
-        old = cache.get(precise)
-        if old is not None and old.fwd_hi.device == dev and old.coutp == cout and old.cinp == cin:
-            fwd_hi, fwd_lo, dgr_hi, dgr_lo = old.fwd_hi, old.fwd_lo, old.dgr_hi, old.dgr_lo
-        else:
-            fwd_hi = torch.empty(kw, cout, cin, dtype=torch.bfloat16, device=dev)
-            dgr_hi = torch.empty(kw, cin, cout, dtype=torch.bfloat16, device=dev)
-            fwd_lo = torch.empty_like(fwd_hi) if precise else None
-            dgr_lo = torch.empty_like(dgr_hi) if precise else None
+        # (no e4m3 operands from this kernel: the parameter's fp8 state keeps its version and the engine requantises)
+        ops = _operands(p, fp8=False)
         scratch = state.get('_scratch')
         if scratch is None or scratch.device != dev:
             scratch = torch.empty(1025, dtype=torch.float32, device=dev)
@@ -71,10 +53,8 @@ class Novograd(Optimizer):
                                     ptr(state['max_exp_avg_sq']) if group['amsgrad'] else None, ptr(scratch), scratch.numel(),
                                     float(group['lr']), float(beta1), float(beta2), float(group['eps']),
                                     float(group['weight_decay']), int(bool(group['grad_averaging'])), cout, cin, kw,
-                                    ptr(fwd_hi), ptr(fwd_lo), ptr(dgr_hi), ptr(dgr_lo), stream_ptr()), 'w2l_novograd_pack')
-        torch.autograd.graph.increment_version(p)                    # p changed through its raw pointer
-        cache.clear()
-        cache[precise] = E._PackedW(p._version, fwd_hi, fwd_lo, dgr_hi, dgr_lo, cin, cout, p.data_ptr())
+                                    *(ptr(b) for b in ops[2]), stream_ptr()), 'w2l_novograd_pack')
+        _packed(p, grad, *ops)
         return True
 
     def state_dict(self):

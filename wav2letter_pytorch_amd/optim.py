@@ -97,6 +97,59 @@ def _is_tap_major(t: torch.Tensor) -> bool:
     return t.stride() == (ci, 1, co * ci)
 
 
+def _conv_ok(p, g=None) -> bool:
+    """a conv weight the fused update + operand pack takes (with its gradient ``g``, where there is one yet)"""
+    return bool(p.is_cuda and p.dtype == torch.float32 and _is_tap_major(p) and (g is None or g.stride() == p.stride())
+                and p.shape[0] % 64 == 0 and p.shape[1] % 64 == 0)
+
+
+def _operands(p, recycle_grads=False, fp8=True):
+    """the operand-pack buffers of the next step for conv weight ``p`` (kept from the last pack when they fit) ->
+    (cache, precise, (fwd_hi, fwd_lo, dgr_hi, dgr_lo), recycle, f8); ``fp8`` False: an update that writes no e4m3 operands"""
+    cout, cin, kw = p.shape
+    dev = p.device
+    cache = getattr(p, '_w2l_pack', None)
+    if cache is None:
+        cache = E._Volatile()
+        p._w2l_pack = cache
+    precise = any(k for k in cache)                              # keep hi/lo pairs alive only if fp32 mode is in use
+    old = cache.get(precise)
+    if old is not None and old.fwd_hi.device == dev and old.coutp == cout and old.cinp == cin:
+        fwd_hi, fwd_lo, dgr_hi, dgr_lo = old.fwd_hi, old.fwd_lo, old.dgr_hi, old.dgr_lo
+    else:
+        _lib.poison('operand pack buffers created')
+        fwd_hi = torch.empty(kw, cout, cin, dtype=torch.bfloat16, device=dev)
+        dgr_hi = torch.empty(kw, cin, cout, dtype=torch.bfloat16, device=dev)
+        fwd_lo = torch.empty_like(fwd_hi) if precise else None
+        dgr_lo = torch.empty_like(dgr_hi) if precise else None
+    # the gradient buffer is handed back to the step engine zero-filled (engine._wgrad_now takes it as the next dW when
+    # zero_grad(set_to_none=True) has dropped p.grad): no fill launch for the split-K weight gradients of the next step
+    recycle = recycle_grads and not precise
+    # fp8 mode (engine._fp8_weights left its state on the parameter): emit the e4m3 operands of the next step here too,
+    # with the scale in force -- its periodic re-derivation from amax stays with the engine (asynchronous: a new scale
+    # is adopted at a forward pass, which then requantises both layouts itself for that one step).  Left alone (``fp8``
+    # False), the state keeps the version of the last quantisation and the engine requantises.
+    f8 = p.__dict__.get('_w2l_fp8') if fp8 else None
+    if f8 is not None and (precise or f8['q'].shape != fwd_hi.shape or f8['q'].device != dev):
+        f8 = None
+    return cache, precise, (fwd_hi, fwd_lo, dgr_hi, dgr_lo), recycle, f8
+
+
+def _packed(p, g, cache, precise, bufs, recycle, f8):
+    """after the update kernel of conv weight ``p`` has been enqueued: the operand pack it wrote is the current one"""
+    cout, cin, kw = p.shape
+    if recycle:
+        p._w2l_dw_zeroed = g.permute(2, 0, 1)                    # the dense [Kw, Cout, Cin] storage of g
+    torch.autograd.graph.increment_version(p)                    # p changed through its raw pointer
+    cache.clear()
+    pk = E._PackedW(p._version, *bufs, cin, cout, p.data_ptr())
+    cache[precise] = pk
+    if f8 is not None:                      # both e4m3 layouts are current for this version
+        f8['version'] = f8['version_d'] = pk.version
+        f8['age'] += 1
+    return pk
+
+
 class FusedBase:
     """What the fused optimizers share, whatever their update rule: the side stream and ``overlap``, held-back weight gradients
     (``defer_wgrad`` / ``apply`` / ``join`` / ``token`` / ``stepped``), gradient clipping on read, the operand-pack buffers of a
@@ -162,8 +215,7 @@ class FusedBase:
                 for q in group['params']:
                     self._deferred_state()['hp'][id(q)] = [ok, group, None]
             hp = self._deferred_state()['hp'].get(id(p))
-        return bool(hp is not None and hp[0] and self.overlap and p.is_cuda and p.dtype == torch.float32 and _is_tap_major(p)
-                    and p.shape[0] % 64 == 0 and p.shape[1] % 64 == 0)
+        return bool(hp is not None and hp[0] and self.overlap and _conv_ok(p))
 
     def token(self) -> int:
         return self._deferred_state()['seq']
@@ -337,12 +389,6 @@ class FusedBase:
             if ent is not None:
                 ent[2] = hp
 
-    @staticmethod
-    def _conv_ok(p, g) -> bool:
-        """a conv weight the fused update + operand pack takes"""
-        return (p.is_cuda and p.dtype == torch.float32 and _is_tap_major(p) and g.stride() == p.stride()
-                and p.shape[0] % 64 == 0 and p.shape[1] % 64 == 0)
-
     def _run_fused(self, fused, hp, clip):
         """the fused conv-weight updates of one group: on the caller's stream, or (``overlap``) on the side stream in forward
         order, each tagging its operand pack with the weight's event"""
@@ -382,50 +428,6 @@ class FusedBase:
             buf = state[key] = torch.empty_like(p).copy_(buf)
         return buf
 
-    def _operands(self, p):
-        """the operand-pack buffers of the next step for conv weight ``p`` (kept from the last pack when they fit) ->
-        (cache, precise, (fwd_hi, fwd_lo, dgr_hi, dgr_lo), recycle, f8)"""
-        cout, cin, kw = p.shape
-        dev = p.device
-        cache = getattr(p, '_w2l_pack', None)
-        if cache is None:
-            cache = E._Volatile()
-            p._w2l_pack = cache
-        precise = any(k for k in cache)                              # keep hi/lo pairs alive only if fp32 mode is in use
-        old = cache.get(precise)
-        if old is not None and old.fwd_hi.device == dev and old.coutp == cout and old.cinp == cin:
-            fwd_hi, fwd_lo, dgr_hi, dgr_lo = old.fwd_hi, old.fwd_lo, old.dgr_hi, old.dgr_lo
-        else:
-            _lib.poison('operand pack buffers created')
-            fwd_hi = torch.empty(kw, cout, cin, dtype=torch.bfloat16, device=dev)
-            dgr_hi = torch.empty(kw, cin, cout, dtype=torch.bfloat16, device=dev)
-            fwd_lo = torch.empty_like(fwd_hi) if precise else None
-            dgr_lo = torch.empty_like(dgr_hi) if precise else None
-        # the gradient buffer is handed back to the step engine zero-filled (engine._wgrad_now takes it as the next dW when
-        # zero_grad(set_to_none=True) has dropped p.grad): no fill launch for the split-K weight gradients of the next step
-        recycle = self.recycle_grads and not precise
-        # fp8 mode (engine._fp8_weights left its state on the parameter): emit the e4m3 operands of the next step here too,
-        # with the scale in force -- its periodic re-derivation from amax stays with the engine (asynchronous: a new scale
-        # is adopted at a forward pass, which then requantises both layouts itself for that one step)
-        f8 = p.__dict__.get('_w2l_fp8')
-        if f8 is not None and (precise or f8['q'].shape != fwd_hi.shape or f8['q'].device != dev):
-            f8 = None
-        return cache, precise, (fwd_hi, fwd_lo, dgr_hi, dgr_lo), recycle, f8
-
-    def _packed(self, p, g, cache, precise, bufs, recycle, f8):
-        """after the update kernel of conv weight ``p`` has been enqueued: the operand pack it wrote is the current one"""
-        cout, cin, kw = p.shape
-        if recycle:
-            p._w2l_dw_zeroed = g.permute(2, 0, 1)                    # the dense [Kw, Cout, Cin] storage of g
-        torch.autograd.graph.increment_version(p)                    # p changed through its raw pointer
-        cache.clear()
-        pk = E._PackedW(p._version, *bufs, cin, cout, p.data_ptr())
-        cache[precise] = pk
-        if f8 is not None:                      # both e4m3 layouts are current for this version
-            f8['version'] = f8['version_d'] = pk.version
-            f8['age'] += 1
-        return pk
-
     def _small_table(self, rows, device):
         """the device table of a one-launch small-parameter update (``rows``: tuples of addresses, the element count last),
         built once per set of addresses"""
@@ -442,6 +444,36 @@ class FusedBase:
         if rec is not None:
             rec.keep.append(table)          # the recorded phase O owns its table: evicting it from the cache must not free it
         return table
+
+    def _launch_small(self, entry, params, rows, *args):
+        """ONE launch of entry point ``entry`` updating all of ``params`` (conv biases, BatchNorm gamma / beta, the
+        classifier) instead of torch._foreach_* calls over ~60 tensors; an entry point, so a recorded launch list replays it"""
+        table = self._small_table(tuple(rows), params[0].device)
+        check(getattr(lib, entry)(ptr(table), len(rows), max(r[-1] for r in rows), *args, stream_ptr()), entry)
+        for p in params:
+            torch.autograd.graph.increment_version(p)
+
+    def _load_in_place(self, state_dict, keys) -> bool:
+        """torch's load_state_dict, except that a loaded state buffer (``keys``) is copied INTO the buffer it replaces when
+        their layouts agree: recorded optimizer phases (replay.py, phases O and X) name the buffers by address.  -> did a
+        buffer go or change layout (those phases are stale then)?"""
+        self.join()
+        old = {id(p): [self.state[p].get(k) for k in keys] for g in self.param_groups for p in g['params'] if p in self.state}
+        super().load_state_dict(state_dict)
+        stale = False
+        for g in self.param_groups:
+            for p in g['params']:
+                for k, buf in zip(keys, old.get(id(p), ())):
+                    new = self.state[p].get(k) if p in self.state else None
+                    if buf is None or new is buf:
+                        continue
+                    if (new is not None and new.shape == buf.shape and new.stride() == buf.stride() and new.dtype == buf.dtype
+                            and new.device == buf.device):
+                        buf.copy_(new)
+                        self.state[p][k] = buf
+                    else:
+                        stale = True
+        return stale
 
     @staticmethod
     def _same_layout(a, b) -> bool:          # (the stride of a size-1 dimension means nothing)
@@ -470,22 +502,9 @@ class FusedSGD(FusedBase, torch.optim.SGD):
         return group['momentum'] != 0 and group['dampening'] == 0 and not group.get('maximize', False)
 
     def load_state_dict(self, state_dict):
-        """torch's load_state_dict, except that a loaded momentum buffer is copied INTO the buffer it replaces when their
-        layouts agree: recorded optimizer phases (replay.py, phases O and X) name the buffers by address"""
-        self.join()
-        old = {id(p): self.state[p].get('momentum_buffer') for g in self.param_groups for p in g['params'] if p in self.state}
-        super().load_state_dict(state_dict)
-        for g in self.param_groups:
-            for p in g['params']:
-                buf, new = old.get(id(p)), self.state[p].get('momentum_buffer') if p in self.state else None
-                if buf is None or new is buf:
-                    continue
-                if (new is not None and new.shape == buf.shape and new.stride() == buf.stride() and new.dtype == buf.dtype
-                        and new.device == buf.device):
-                    buf.copy_(new)
-                    self.state[p]['momentum_buffer'] = buf
-                else:                        # a buffer went or changed layout: recorded optimizer phases are stale
-                    self.__dict__['_w2l_state_epoch'] = self.__dict__.get('_w2l_state_epoch', 0) + 1
+        """torch's load_state_dict with the momentum buffers kept in place (_load_in_place)"""
+        if self._load_in_place(state_dict, ('momentum_buffer',)):
+            self.__dict__['_w2l_state_epoch'] = self.__dict__.get('_w2l_state_epoch', 0) + 1
 
     def _step_eager(self):
         clip = self._begin_eager()
@@ -499,7 +518,7 @@ class FusedSGD(FusedBase, torch.optim.SGD):
                 if p.grad is None:
                     continue
                 g = p.grad
-                if fused_ok and self._conv_ok(p, g):
+                if fused_ok and _conv_ok(p, g):
                     fused.append((p, g))
                 else:
                     rest.append(p)
@@ -509,45 +528,30 @@ class FusedSGD(FusedBase, torch.optim.SGD):
 
     def _fused_conv(self, p, g, lr, mu, wd, nesterov, clip=None):
         state = self.state[p]
-        first = 'momentum_buffer' not in state or state['momentum_buffer'] is None
-        if first:
-            _lib.poison('momentum buffer created')
-            state['momentum_buffer'] = torch.empty_like(p)           # preserves the tap-major strides
-        buf = state['momentum_buffer']
-        if buf.stride() != p.stride():
-            _lib.poison('momentum buffer re-laid out')
-            buf = torch.empty_like(p).copy_(buf)
-            state['momentum_buffer'] = buf
+        first = state.get('momentum_buffer') is None                 # (the kernel is told, and does not read the fresh buffer)
+        buf = self._same_layout_buffer(p, state, 'momentum_buffer', 'momentum buffer')
         cout, cin, kw = p.shape
-        cache, precise, bufs, recycle, f8 = self._operands(p)
-        fwd_hi, fwd_lo, dgr_hi, dgr_lo = bufs
+        cache, precise, bufs, recycle, f8 = _operands(p, self.recycle_grads)
         args = (ptr(p), ptr(g), ptr(buf), int(first), float(lr), float(mu), float(wd), int(nesterov), int(recycle), cout, cin, kw,
-                ptr(fwd_hi), ptr(fwd_lo), ptr(dgr_hi), ptr(dgr_lo), ptr(f8['q']) if f8 else None, ptr(f8['qd']) if f8 else None,
-                f8['scale'] if f8 else 1.0)
+                *(ptr(b) for b in bufs), ptr(f8['q']) if f8 else None, ptr(f8['qd']) if f8 else None, f8['scale'] if f8 else 1.0)
         if clip is None:
             check(lib.w2l_sgd_pack(*args, stream_ptr()), 'w2l_sgd_pack')
         else:                                                        # (gradient clipping armed: clip_grad_norm_ / _value_)
             check(lib.w2l_sgd_pack_clip(*args, ptr(clip), stream_ptr()), 'w2l_sgd_pack_clip')
-        return self._packed(p, g, cache, precise, bufs, recycle, f8)
+        return _packed(p, g, cache, precise, bufs, recycle, f8)
 
     def _small_multi(self, params, lr, mu, wd, nesterov, clip=None) -> bool:
-        """torch.optim.SGD's update of all the small parameters (conv biases, BatchNorm gamma / beta) in ONE launch
-        (w2l_sgd_small_multi) instead of five torch._foreach_* calls over ~60 tensors: a device table of (p, g, m, n) built once
-        per set of addresses (``params``: those _multi_ok admits); an entry point, so a recorded launch list replays it."""
+        """torch.optim.SGD's update of all the small parameters in one launch (w2l_sgd_small_multi): a device table of
+        (p, g, m, n) built once per set of addresses (``params``: those _multi_ok admits)"""
         rows = []
         for p in params:
-            g = p.grad
             m = self.state[p].get('momentum_buffer') if mu != 0 else None
-            rows.append((p.data_ptr(), g.data_ptr(), m.data_ptr() if m is not None else 0, p.numel()))
-        table = self._small_table(tuple(rows), params[0].device)
+            rows.append((p.data_ptr(), p.grad.data_ptr(), m.data_ptr() if m is not None else 0, p.numel()))
+        hp = (float(lr), float(mu), float(wd), int(nesterov))
         if clip is None:
-            check(lib.w2l_sgd_small_multi(ptr(table), len(rows), max(r[3] for r in rows), float(lr), float(mu), float(wd),
-                                          int(nesterov), stream_ptr()), 'w2l_sgd_small_multi')
+            self._launch_small('w2l_sgd_small_multi', params, rows, *hp)
         else:
-            check(lib.w2l_sgd_small_multi_clip(ptr(table), len(rows), max(r[3] for r in rows), float(lr), float(mu), float(wd),
-                                               int(nesterov), ptr(clip), stream_ptr()), 'w2l_sgd_small_multi_clip')
-        for p in params:
-            torch.autograd.graph.increment_version(p)
+            self._launch_small('w2l_sgd_small_multi_clip', params, rows, *hp, ptr(clip))
         return True
 
     def _multi_ok(self, p, mu) -> bool:
@@ -779,7 +783,7 @@ class FusedAdamW(FusedBase, torch.optim.AdamW):
                     continue
                 if id(p) in own or gs['dyn'] is None or g.is_sparse:
                     rest.append(p)
-                elif self._conv_ok(p, g):
+                elif _conv_ok(p, g):
                     fused.append((p, g))
                 elif self._small_ok(p):
                     small.append(p)
@@ -799,11 +803,11 @@ class FusedAdamW(FusedBase, torch.optim.AdamW):
     def _fused_conv(self, p, g, beta1, beta2, eps, wd, decoupled, dyn_ptr, clip=None):
         m, v = self._moments(p)
         cout, cin, kw = p.shape
-        cache, precise, bufs, recycle, f8 = self._operands(p)
+        cache, precise, bufs, recycle, f8 = _operands(p, self.recycle_grads)
         check(lib.w2l_adam_pack(ptr(p), ptr(g), ptr(m), ptr(v), dyn_ptr, beta1, beta2, eps, wd, decoupled, int(recycle), cout, cin,
                                 kw, *(ptr(b) for b in bufs), ptr(f8['q']) if f8 else None, ptr(f8['qd']) if f8 else None,
                                 f8['scale'] if f8 else 1.0, ptr(clip), stream_ptr()), 'w2l_adam_pack')
-        return self._packed(p, g, cache, precise, bufs, recycle, f8)
+        return _packed(p, g, cache, precise, bufs, recycle, f8)
 
     def _small_ok(self, p) -> bool:
         st = self.state[p]
@@ -813,16 +817,12 @@ class FusedAdamW(FusedBase, torch.optim.AdamW):
         return self._elementwise_ok(p, [st['exp_avg'], st['exp_avg_sq']])
 
     def _small_multi(self, params, hp, clip=None):
-        """every small parameter of a group (conv biases, BatchNorm gamma / beta, the classifier) in ONE launch
-        (w2l_adam_small_multi): a device table of (p, g, m, v, n) built once per set of addresses"""
+        """every small parameter of a group in one launch (w2l_adam_small_multi): a device table of (p, g, m, v, n) built
+        once per set of addresses"""
         beta1, beta2, eps, wd, decoupled, dyn_ptr = hp
-        rows = tuple((p.data_ptr(), p.grad.data_ptr(), self.state[p]['exp_avg'].data_ptr(), self.state[p]['exp_avg_sq'].data_ptr(),
-                      p.numel()) for p in params)
-        table = self._small_table(rows, params[0].device)
-        check(lib.w2l_adam_small_multi(ptr(table), len(rows), max(r[4] for r in rows), dyn_ptr, beta1, beta2, eps, wd, decoupled,
-                                       ptr(clip), stream_ptr()), 'w2l_adam_small_multi')
-        for p in params:
-            torch.autograd.graph.increment_version(p)
+        rows = [(p.data_ptr(), p.grad.data_ptr(), self.state[p]['exp_avg'].data_ptr(), self.state[p]['exp_avg_sq'].data_ptr(),
+                 p.numel()) for p in params]
+        self._launch_small('w2l_adam_small_multi', params, rows, dyn_ptr, beta1, beta2, eps, wd, decoupled, ptr(clip))
 
     def _torch_adam(self, params, group, clip=None):
         """torch's own rule (_single_tensor_adam) with each parameter's OWN step count: parameters out of step with their
@@ -876,29 +876,14 @@ class FusedAdamW(FusedBase, torch.optim.AdamW):
         return sd
 
     def load_state_dict(self, state_dict):
-        """torch's load_state_dict; a loaded moment is copied INTO the buffer it replaces when their layouts agree (recorded
-        optimizer phases name the buffers by address), and the group counters are rebuilt from ``step``"""
-        self.join()
-        keys = ('exp_avg', 'exp_avg_sq')
-        old = {id(p): [self.state[p].get(k) for k in keys] for g in self.param_groups for p in g['params'] if p in self.state}
+        """torch's load_state_dict with the moments kept in place (_load_in_place); the group counters are rebuilt from
+        ``step``"""
         mine = [g['decoupled_weight_decay'] for g in self.param_groups]
-        super().load_state_dict(state_dict)
+        stale = self._load_in_place(state_dict, ('exp_avg', 'exp_avg_sq'))
         self._steps_to_host()
-        stale = False
         for g, saved, flag in zip(self.param_groups, state_dict['param_groups'], mine):
             if 'decoupled_weight_decay' not in saved:          # (a state dict of a torch without the key: the rule stays ours)
                 g['decoupled_weight_decay'] = flag
-            for p in g['params']:
-                for k, buf in zip(keys, old.get(id(p), (None, None))):
-                    new = self.state[p].get(k) if p in self.state else None
-                    if buf is None or new is buf:
-                        continue
-                    if (new is not None and new.shape == buf.shape and new.stride() == buf.stride() and new.dtype == buf.dtype
-                            and new.device == buf.device):
-                        buf.copy_(new)
-                        self.state[p][k] = buf
-                    else:
-                        stale = True
         self.__dict__.pop('_w2l_plan', None)
         self._rebuild_counters()
         # (always a new epoch: which parameters share their group's count may have changed, and with it what phase O launches)

@@ -34,7 +34,7 @@ What makes a step replayable
     event per conv weight (engine.weight_event): a recorded forward waits for the same event handles whichever step -- eager
     or replayed, set A or B -- updated the weights before it.
   * No torch ops between the launches of a phase: fills, padded per-channel vectors, BatchNorm counters, the small-parameter
-    SGD update and the dropout step counter are entry points too (csrc/replay.hip).  Code paths that still need torch ops or
+    SGD update and the dropout step counter are entry points too (csrc/optim.hip, csrc/replay.hip).  Code paths that still need torch ops or
     a host synchronisation (measuring launches, fp8 scale upkeep, gradients of the spectrogram, ...) ``poison`` a recording:
     that step simply stays eager and the next one tries again.
   * The batch: the spectrograms are copied into the set's static input buffer (skipped when the caller hands over the very
