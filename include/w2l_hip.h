@@ -553,6 +553,43 @@ int w2l_ctc_align(const float* x, const int32_t* input_lengths, const int32_t* t
                   int log_probs, void* workspace, int64_t workspace_bytes, float* score, int32_t* status, int32_t* path,
                   int32_t* starts, int32_t* ends, void* stream);
 
+/* ---- CTC keyword search: where in the posteriors a phrase is said, with a score (keyword_search.py; host model:
+ *      keyword_scan_host / pick_hits_host).  No reference counterpart ---- */
+/* The keywords of one call, packed by keyword_search.KeywordTable into n_blocks blocks of `width` lanes (64, 128, 256, 512 or
+ * 1024), one lane per extended state c_1, blank, c_2, ..., c_S of a keyword (2 S - 1 states, S <= 255), keywords in their
+ * given order and never split across blocks.  All three arrays are DEVICE memory; the entry point does not read them and the
+ * kernels bound every index they take from them.  labels[b * width + i]: the label of a label state.  meta[b * width + i]:
+ * -1 for a lane without a state, else keyword index << 4 | flags: 1 the keyword's first state, 2 its last, 4 the move from
+ * two states below is allowed (a label state whose label differs from the previous label's), 8 a label state (else the blank
+ * between two labels).  block_kw[b] .. block_kw[b + 1]: the keywords of block b. */
+typedef struct {
+    const int32_t* labels;     /* [n_blocks * width] */
+    const int32_t* meta;       /* [n_blocks * width] */
+    const int32_t* block_kw;   /* [n_blocks + 1] */
+    int32_t n_blocks, width, n_keywords, reserved_;
+} w2l_kws_table_t;
+typedef struct { int32_t start, end; float score; } w2l_kws_hit_t;
+/* workspace bytes for w2l_ctc_kws (the frame maxima, N * T floats, and N ints); -1 where there is no plan: N outside
+ * 1..65535, T outside 1..32768, K outside 1..4096, max_hits outside 1..64 */
+int64_t w2l_ctc_kws_workspace_bytes(int N, int T, int K, int max_hits);
+/* x fp32 [N][T][A] contiguous: log-probabilities, or probabilities if !log_probs; input_lengths int32 [N] (NULL: all T, else
+ * clamped to [0, T]); thr fp32 [K] (device).  With b[t] = max_a lp[t][a] and e[t][s] = lp[t][lab(s)] - b[t] (probabilities:
+ * logf(x) - logf(b)), per keyword and frame, in fp32,
+ *   D[t][s] = e[t][s] + max(D[t-1][s], D[t-1][s-1], D[t-1][s-2] if flag 4, 0 if flag 1 ("enter here")),
+ * a candidate replacing the best so far on a strict > only, in that order; B[t][s] = the frame at which the winning path
+ * entered (t for "enter"); a state at -inf has B = -1.  Three launches, selected by the mask `phases` (7: all; anything less
+ * is for measuring one launch with the others' outputs in place): 1 the frame maxima and status; 2 the scan, which writes
+ * end_score / end_start [N][K][T] = D / B of each keyword's last state (-inf / -1 from input_lengths[n] on); 4 the pick: up to
+ * max_hits times the frame with end_score >= thr[k] whose segment [end_start, t] overlaps no accepted one of the same keyword,
+ * best by (score descending, start ascending, end descending); hit_count [N][K], hits [N][K][max_hits] in start order (unused
+ * slots: -1, -1, -inf).  status[N]: 0 ok; 2 a NaN, a negative probability or a frame without a finite maximum among the
+ * utterance's frames, or a table label outside [0, A) or equal to blank (never used as an index): no hits, and the curves of
+ * the keywords concerned are -inf / -1.  Argument errors launch nothing; w2l_last_error names ctc_kws. */
+int w2l_ctc_kws(const float* x, const int32_t* input_lengths, int N, int T, int A, int blank, int log_probs,
+                const w2l_kws_table_t* table, const float* thr, int max_hits, int phases, void* workspace,
+                int64_t workspace_bytes, float* end_score, int32_t* end_start, int32_t* hit_count, w2l_kws_hit_t* hits,
+                int32_t* status, void* stream);
+
 /* ---- Auto Segmentation criterion: the loss of the Wav2Letter paper, which the reference replaces by CTC (its README,
  *      "Differences from article"; call site: base_asr_models.py:23,81,90 with model.criterion=asg, asg.ASGLoss) ---- */
 /* workspace bytes for w2l_asg_loss (alpha and beta tables of both recursions, encoded targets, gradient slabs); -1 if out of

@@ -12,7 +12,8 @@ _PUBLIC = {
     'Conv1dBlock': '.wav2letter', 'Wav2Letter': '.wav2letter', 'Jasper': '.jasper', 'JasperBlock': '.jasper',
     'MaskedConv1d': '.jasper', 'ctc_forced_align': '.alignment', 'viterbi_align_host': '.alignment',
     'ASGLoss': '.asg', 'ASGDecoder': '.asg', 'ASGBeamSearchDecoder': '.asg_beam', 'ASGBeamSearchLMDecoder': '.asg_beam',
-    'asg_forced_align': '.asg_beam',
+    'asg_forced_align': '.asg_beam', 'ctc_keyword_search': '.keyword_search', 'KeywordTable': '.keyword_search',
+    'keyword_scan_host': '.keyword_search', 'pick_hits_host': '.keyword_search',
 }
 __all__ = sorted(_PUBLIC)
 

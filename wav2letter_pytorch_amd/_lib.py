@@ -86,6 +86,12 @@ class VadParams(C.Structure):
                 ('min_speech', C.c_int32), ('pad', C.c_int32), ('max_frames', C.c_int32), ('reserved_', C.c_int32)]
 
 
+class KwsTable(C.Structure):
+    """w2l_kws_table_t (include/w2l_hip.h): the device arrays of packed keywords (keyword_search.KeywordTable)."""
+    _fields_ = [('labels', c_p), ('meta', c_p), ('block_kw', c_p), ('n_blocks', C.c_int32), ('width', C.c_int32),
+                ('n_keywords', C.c_int32), ('reserved_', C.c_int32)]
+
+
 _SIGNATURES = {
     'w2l_last_error': (C.c_char_p, []),
     'w2l_abi_version': (c_i, []),
@@ -176,6 +182,9 @@ _SIGNATURES = {
     'w2l_ctc_align_workspace_bytes': (c_i64, [c_i, c_i, c_i]),
     'w2l_ctc_align': (c_i, [c_p, c_p, c_p, c_i64, c_p, c_i64, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_i64, c_p, c_p, c_p, c_p, c_p,
                             c_p]),
+    'w2l_ctc_kws_workspace_bytes': (c_i64, [c_i, c_i, c_i, c_i]),
+    'w2l_ctc_kws': (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, C.POINTER(KwsTable), c_p, c_i, c_i, c_p, c_i64, c_p, c_p, c_p, c_p, c_p,
+                          c_p]),
     'w2l_ctc_beam_search_workspace_bytes': (c_i64, [c_i, c_i, c_i, c_i]),
     'w2l_ctc_beam_search': (c_i, [c_p, c_p, c_i, c_i, c_i, c_p, c_i, c_i, c_i, c_i, C.c_double, C.c_double, C.c_double, c_i,
                                   C.POINTER(LmTables), c_i, C.POINTER(LexTables), c_i, C.POINTER(LexTables), C.c_double,

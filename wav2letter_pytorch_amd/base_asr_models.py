@@ -475,3 +475,17 @@ class ConvCTCASR(_Base):
         piece's last frames depend on what it is batched with; ``batch_size=1`` gives batch-independent text."""
         from .segmentation import transcribe_long
         return transcribe_long(self, items, max_seconds, batch_size, decoder, word_times, vad)
+
+    def find_keywords(self, items, phrases, threshold: float = -1.0, max_hits: int = 8, max_seconds: float = 20.0,
+                      batch_size: int = 8, vad=None, also_transcribe: bool = False, decoder=None):
+        """where in recordings are ``phrases`` said?  The inputs, the device segmentation, the front end and ``infer`` of
+        ``transcribe_long``; each piece's posteriors are searched (keyword_search.ctc_keyword_search) instead of decoded.
+        ``phrases``: strings over the model's labels (a phrase contains the space label), or a keyword_search.KeywordTable
+        built with them.  ``threshold``: nats per character, a hit needs a score of at least ``threshold * len(phrase)``; the
+        default of -1.0 is a convention, not a tuned value.  ``max_hits``: per phrase and piece.  Returns per input
+        ``[{'keyword', 'start', 'end', 'score'}]`` in time order, start / end in seconds on the recording's clock (the piece's
+        start plus the hit's first / last frame times the model's seconds per frame, as ``transcribe``'s word times);
+        ``also_transcribe``: per input ``(hits, transcribe_long's result)`` from the same posteriors.  ``model.criterion=asg``:
+        NotImplementedError (the search is the CTC recurrence)."""
+        from .segmentation import find_keywords
+        return find_keywords(self, items, phrases, threshold, max_hits, max_seconds, batch_size, vad, also_transcribe, decoder)

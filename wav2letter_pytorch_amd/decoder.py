@@ -75,6 +75,17 @@ class Decoder(object):
         end_offsets = [[torch.IntTensor(res.ends[n, :len(text)].copy())] for n, text in enumerate(texts)]
         return offsets, end_offsets
 
+    def find(self, probs, phrases, sizes=None, log_probs=False, threshold=-1.0, max_hits=8, return_curves=False):
+        """the counterpart of ``align`` for phrases whose place is not known: every occurrence of each of ``phrases`` (strings
+        over the labels, or a keyword_search.KeywordTable built with them) in the posteriors, by
+        keyword_search.ctc_keyword_search -> per utterance ``[(phrase index, start frame, end frame, score)]``.  ``threshold``
+        is in nats per character; its default is a convention, not a tuned value."""
+        from .keyword_search import ctc_keyword_search
+        if isinstance(phrases, str):
+            phrases = [phrases]
+        return ctc_keyword_search(probs, phrases, input_lengths=sizes, blank=self.blank_index, log_probs=log_probs,
+                                  labels=list(self.labels), threshold=threshold, max_hits=max_hits, return_curves=return_curves)
+
 
 def argmax_indices(probs: torch.Tensor) -> torch.Tensor:
     """int32 [N, T] argmax over the label axis on the device (first maximal index)."""

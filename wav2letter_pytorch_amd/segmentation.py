@@ -8,7 +8,9 @@ The rule (DESIGN.md "Long-form transcription" has it in full; tests/vad_refs.py 
 ``min_speech`` dropped, every run widened by ``pad``, and a run longer than ``max_seconds`` cut at its quietest frame.  The
 defaults are conventions; they are not tuned on speech (there is no speech corpus where this was written).
 
-This module imports without a GPU: only ``vad_segments`` and ``transcribe_long`` touch the device."""
+``find_keywords`` runs the same pieces through the keyword search (keyword_search.py) instead of, or as well as, a decoder.
+
+This module imports without a GPU: only ``vad_segments``, ``transcribe_long`` and ``find_keywords`` touch the device."""
 from __future__ import annotations
 
 import math
@@ -247,19 +249,19 @@ def _device_wave(model, ext, item, model_rate, dev):
     return resample_device(wave.view(1, -1).contiguous(), rows, ext._banks)[0, :int(rows[0, 1])].contiguous()
 
 
-def transcribe_long(model, items, max_seconds: float = 20.0, batch_size: int = 8, decoder=None, word_times: bool = False,
-                    vad: Optional[VadConfig] = None) -> List[dict]:
-    """the body of ``ConvCTCASR.transcribe_long`` (its docstring has the interface)"""
+def for_each_piece(model, items, max_seconds: float, batch_size: int, vad: Optional[VadConfig], handle, finish) -> list:
+    """the loop ``transcribe_long`` and ``find_keywords`` share: every input uploaded once, cut at its pauses on the device, the
+    pieces batched with neighbours in length through the front end and ``model.infer``.  ``handle(batch, segs, out, out_lens)``
+    turns the posteriors of one batch (``batch``: the piece indices into ``segs``, int64 [S, 2] sample ranges) into a list of
+    per-piece records; ``finish(records, sample_rate)`` makes one input's result of them -> the results, in input order."""
     import torch
     from .data.data_loader import SpectrogramExtractor
-    from .evaluate import decode_batch
     items = [items] if isinstance(items, str) or torch.is_tensor(items) or isinstance(items, np.ndarray) and items.ndim == 1 \
         else list(items)
     dev = next(model.parameters()).device
     ext = model.__dict__.get('_transcribe_extractor')
     if ext is None or ext.fb.device != dev:
         ext = model.__dict__['_transcribe_extractor'] = SpectrogramExtractor(model.audio_conf, model._cfg.input_size, device=dev)
-    decoder = decoder or model.ctc_decoder
     model_rate = int(model.audio_conf['sample_rate'])
     vad = vad or VadConfig.for_model(model.audio_conf)
     if (vad.sample_rate, vad.win, vad.hop) != (model_rate, ext.win_length, ext.hop_length):
@@ -283,11 +285,60 @@ def transcribe_long(model, items, max_seconds: float = 20.0, batch_size: int = 8
                         rows[j, :lens[j]] = wave[int(segs[i, 0]): int(segs[i, 1])]
                     x, x_lens = ext.extract_rows(rows, lens)
                     out, out_lens = model.infer(x, x_lens)
-                    hyps, words = decode_batch(model, decoder, out, out_lens, word_times)
-                    for i, hyp, w in zip(batch, hyps, words):
-                        pieces.append({'start': int(segs[i, 0]), 'end': int(segs[i, 1]), 'text': hyp, 'words': w})
-                results.append(stitch(pieces, model_rate, word_times))
+                    pieces += handle(batch, segs, out, out_lens)
+                results.append(finish(pieces, model_rate))
     finally:
         if was_training:
             model.train()
     return results
+
+
+def transcribe_long(model, items, max_seconds: float = 20.0, batch_size: int = 8, decoder=None, word_times: bool = False,
+                    vad: Optional[VadConfig] = None) -> List[dict]:
+    """the body of ``ConvCTCASR.transcribe_long`` (its docstring has the interface)"""
+    from .evaluate import decode_batch
+    decoder = decoder or model.ctc_decoder
+
+    def handle(batch, segs, out, out_lens):
+        hyps, words = decode_batch(model, decoder, out, out_lens, word_times)
+        return [{'start': int(segs[i, 0]), 'end': int(segs[i, 1]), 'text': hyp, 'words': w} for i, hyp, w in zip(batch, hyps, words)]
+
+    return for_each_piece(model, items, max_seconds, batch_size, vad, handle,
+                          lambda pieces, rate: stitch(pieces, rate, word_times))
+
+
+def find_keywords(model, items, phrases, threshold: float = -1.0, max_hits: int = 8, max_seconds: float = 20.0,
+                  batch_size: int = 8, vad: Optional[VadConfig] = None, also_transcribe: bool = False, decoder=None):
+    """the body of ``ConvCTCASR.find_keywords`` (its docstring has the interface)"""
+    from .evaluate import decode_batch, frame_seconds
+    from .keyword_search import KeywordTable, ctc_keyword_search
+    if getattr(getattr(model, 'criterion', None), 'is_asg', False):
+        raise NotImplementedError('find_keywords on a model with criterion asg: the keyword search is the CTC recurrence (a blank '
+                                  'between repeated letters, no transitions); the ASG recurrence is not built')
+    blank = int(model.ctc_decoder.blank_index)
+    table = phrases if isinstance(phrases, KeywordTable) else \
+        KeywordTable([phrases] if isinstance(phrases, str) else list(phrases), labels=list(model.labels), blank=blank)
+    names = [text if text is not None else list(kw) for text, kw in zip(table.texts, table.keywords)]
+    ratio = frame_seconds(model)
+    log_probs = bool(getattr(model, 'infer_log_probs', True))
+    decoder = decoder or model.ctc_decoder
+
+    def handle(batch, segs, out, out_lens):
+        found = ctc_keyword_search(out, table, input_lengths=out_lens, blank=blank, log_probs=log_probs, threshold=threshold,
+                                   max_hits=max_hits)
+        recs = [{'start': int(segs[i, 0]), 'end': int(segs[i, 1]), 'hits': hits} for i, hits in zip(batch, found)]
+        if also_transcribe:
+            for rec, hyp in zip(recs, decode_batch(model, decoder, out, out_lens, False)[0]):
+                rec.update(text=hyp, words=None)
+        return recs
+
+    def finish(pieces, rate):
+        hits = []
+        for p in pieces:
+            t0 = p['start'] / float(rate)
+            hits += [{'keyword': names[k], 'start': t0 + float(s * ratio), 'end': t0 + float(e * ratio), 'score': sc}
+                     for k, s, e, sc in p['hits']]
+        hits.sort(key=lambda h: (h['start'], h['end']))
+        return (hits, stitch(pieces, rate)) if also_transcribe else hits
+
+    return for_each_piece(model, items, max_seconds, batch_size, vad, handle, finish)
