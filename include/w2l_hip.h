@@ -166,7 +166,16 @@ int w2l_conv_plan_fp8(int N, int Cin, int Cout, int Tout, int Kw, int dil, int s
  * dw[kw][co][ci] (+)= sum_{n,t} dy[n][t][co] * xp[n][t*stride + kw*dil][ci]
  * dy: bf16, pointer at utterance 0 row 0, dy_bstride elements between utterances; rows
  * [Tout, roundup(Tout,64)) of every utterance must be zero (shared-halo layout with halo >= that).
- * dw fp32 [Kw][Cout][Cin].  accumulate=1 adds to dw (fp32 atomics).
+ * dw fp32 [Kw][Cout][Cin].  accumulate=1 adds to dw: where ONE block owns an element -- every unsplit plan and every plan
+ * that reduces through slabs (classic split or dealt) -- with a plain read-add-store, once per element, so the result is
+ * bit for bit fp32(dw_before + what accumulate=0 stores under the same plan); fp32 atomics only where several blocks add
+ * into an element (an atomic split, the pieces of a stream-K launch; with accumulate=1 every stream-K tile is a piece).
+ * xp: bf16, x_bstride elements between utterances, x_rows_total rows readable from xp on (the kernel clamps the rows its 64-row
+ * steps and tap groups stage beyond that onto the last one; they only ever meet zero dy rows or taps >= Kw).
+ * Refused with a message, nothing launched (the single and the group launches alike, per layer): dy_bstride / Cout < Tout
+ * ("dy_bstride holds ..."), and x_rows_total < (N-1) * x_bstride / Cin + (Tout-1) * stride + (Kw-1) * dil + 1, the last row a
+ * live product reads ("padded input too small") -- a shorter buffer would be clamped onto its last row and give a wrong
+ * gradient.
  *
  * The ladder of entry points.  The GENERAL calls are w2l_conv1d_wgrad_ws (launch), w2l_conv1d_wgrad_tune_x (measure) and
  * w2l_wgrad_needs_zero_x (query); the others are shorthands of them:

@@ -404,8 +404,9 @@ int launch(const WgradPlan& pl, const WgradParams& p, void* stream) {
 }
 
 // One layer of a launch from its operands: the checks every entry point makes, and the layer's place in the tile pool.
-// who / li: the entry point's name and the layer's index for the messages (li < 0: a single-layer launch)
-int fill_layer(WgradLayer& l, const w2l_wgrad_item_t& it, int kwblk, int tile0, const char* who, int li) {
+// pr: the launch's N, Tout, stride and dilation (what the operands must cover); who / li: the entry point's name and the layer's
+// index for the messages (li < 0: a single-layer launch)
+int fill_layer(WgradLayer& l, const w2l_wgrad_item_t& it, const WgradProblem& pr, int kwblk, int tile0, const char* who, int li) {
     char where[24] = "";
     if (li >= 0) snprintf(where, sizeof(where), " (layer %d)", li);
     W2L_CHECK_ARG(it.dy && it.xp && it.dw, "%s: null pointer%s", who, where);
@@ -413,6 +414,13 @@ int fill_layer(WgradLayer& l, const w2l_wgrad_item_t& it, int kwblk, int tile0, 
                   "%s: channels (%d,%d) must be positive multiples of 64", who, it.Cin, it.Cout);
     W2L_CHECK_ARG(it.dy_bstride % it.Cout == 0 && it.x_bstride % it.Cin == 0, "%s: batch strides must be whole rows", who);
     W2L_CHECK_ARG(it.x_rows_total * (int64_t)it.Cin * 2 < (1LL << 32), "%s: activation buffer exceeds 32-bit byte offsets", who);
+    // (the kernel clamps its x window onto row x_rows_total - 1 and reads 64-row steps of dy: a buffer that is short of a LIVE row
+    // would be clamped onto its last row and give a wrong gradient without a word)
+    W2L_CHECK_ARG(it.dy_bstride / it.Cout >= pr.Tout, "%s: dy_bstride holds %lld rows per utterance, Tout=%d needs as many%s", who,
+                  (long long)(it.dy_bstride / it.Cout), pr.Tout, where);
+    const int64_t x_need = (int64_t)(pr.N - 1) * (it.x_bstride / it.Cin) + (int64_t)(pr.Tout - 1) * pr.stride + (int64_t)(it.Kw - 1) * pr.dil + 1;
+    W2L_CHECK_ARG(it.x_rows_total >= x_need, "%s: padded input too small: x_rows_total=%lld, the last utterance's last tap reads row %lld%s",
+                  who, (long long)it.x_rows_total, (long long)(x_need - 1), where);
     l.dy = (const bf16_raw*)it.dy;
     l.x = (const bf16_raw*)it.xp;
     l.dw = it.dw;
@@ -450,7 +458,7 @@ int run(const WgradPlan& pl, WgradParams& p, void* ws, void* stream) {
 int run_layer(const WgradPlan& pl, const w2l_wgrad_item_t& it, int accumulate, void* ws, void* stream) {
     WgradParams p;
     p.nlayers = 1;
-    if (int rc = fill_layer(p.layers[0], it, pl.kwblk, 0, "conv1d_wgrad", -1)) return rc;
+    if (int rc = fill_layer(p.layers[0], it, pl.pr, pl.kwblk, 0, "conv1d_wgrad", -1)) return rc;
     p.accumulate = accumulate;
     return run(pl, p, ws, stream);
 }
@@ -579,13 +587,13 @@ extern "C" int w2l_conv1d_wgrad_group(const w2l_wgrad_item_t* items, int nitems,
     WgradPlan pl = group_form(form, true, dil);         // (the kernel of a group is the wide one whatever its layers' tap counts)
     W2L_CHECK_ARG(!pl.taps3 || dil <= kTaps3MaxDil, "conv1d_wgrad_group: the three-tap form takes dilation <= %d", kTaps3MaxDil);
     WgradParams p;
+    pl.pr = WgradProblem{N, 0, 0, Tout, 0, 1, dil, false, 0};
     for (int i = 0; i < nitems; ++i) {
-        if (int rc = fill_layer(p.layers[i], items[i], pl.kwblk, pl.tiles, "conv1d_wgrad_group", i)) return rc;
+        if (int rc = fill_layer(p.layers[i], items[i], pl.pr, pl.kwblk, pl.tiles, "conv1d_wgrad_group", i)) return rc;
         pl.tiles += p.layers[i].tiles_m * p.layers[i].tiles_n * p.layers[i].kgroups;
     }
     p.nlayers = nitems;
     p.accumulate = 0;
-    pl.pr = WgradProblem{N, 0, 0, Tout, 0, 1, dil, false, 0};
     pl.tsteps = (Tout + BT - 1) / BT;
     pl.total_steps = pl.steps_per_split = N * pl.tsteps;
     pl.splits = 1;
