@@ -148,7 +148,7 @@ int w2l_conv1d_igemm_fp8_tune(const void* xq, int64_t x_bstride, int64_t x_rows_
  * and so does stream-K under a fused epilogue or where its ranges would be shorter than eight steps: w2l_conv_plan(forced
  * idx) tells what a launch really gets (out[2] blocks per tile, out[3] stream-K blocks). */
 void w2l_conv_force_tile_config(int idx);
-/* likewise for the e4m3 kernel: idx = index into its list of 13 block shapes; an infeasible one (statistics need 128-row
+/* likewise for the e4m3 kernel: idx = index into its list of 15 block shapes; an infeasible one (statistics need 128-row
  * tiles, LDS) makes w2l_conv1d_igemm_fp8 fail with a message */
 void w2l_conv_force_fp8_config(int idx);
 /* Host-only plan query: what a launch of this problem would be given, decided by the very function the launches go through
@@ -277,7 +277,15 @@ int w2l_conv1d_wgrad_tune(const void* dy, int64_t dy_bstride, const void* xp, in
  * ds_read_b64_tr_b8 fragment reads (stride 1; conv_wgrad_fp8.hip).  dyq / xq: the one-byte copies of dy and of the padded
  * input that the fp8 step already holds (w2l_quantize_e4m3_dyn / w2l_bn_act_fwd_q), same row layouts as the bf16 entry
  * point (batch strides in elements = bytes); dw = descale * (*descale_dev, if given) * sum dyq * xq, fp32, tap-major.
- * Split-K partial tiles are added atomically: w2l_wgrad_fp8_needs_zero tells whether dw must be zero-filled.
+ * Rows the kernel reads: it walks every utterance in ceil(Tout / 128) steps of 128 frames, WITHOUT a clamp on dy, so
+ *   dyq  rows [0, 128 * ceil(Tout / 128)) of every utterance are read (the last utterance's included: the buffer must hold them);
+ *        rows [Tout, that) must be ZERO bytes.  dy_bstride must hold at least that many rows (the shared-halo layout with
+ *        halo >= roundup(Tout, 128) - Tout does); a shorter one is refused.
+ *   xq   the rows beneath them, t + kw*dil for every walked t, clamped onto row x_rows_total - 1: they run on into the next
+ *        utterance's rows (or whatever follows) and meet zero dy rows there, so every byte of them must be a FINITE e4m3 code
+ *        (the NaN codes 0x7F / 0xFF times zero would put NaN into dw).
+ * Split-K partial tiles are added atomically: w2l_wgrad_fp8_needs_zero tells whether dw must be zero-filled; accumulate = 1 on
+ * such a plan adds onto what dw holds (no zero fill then), on an unsplit plan it is a plain read-add-store.
  * Replaces aten::convolution_backward's weight half (wav2letter.py:35-36,42 / jasper.py:96-105,127) in that mode. */
 int w2l_wgrad_fp8_needs_zero(int N, int Cin, int Cout, int Tout, int Kw);
 int w2l_conv1d_wgrad_fp8(const void* dyq, int64_t dy_bstride, const void* xq, int64_t x_bstride, int64_t x_rows_total,

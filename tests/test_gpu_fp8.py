@@ -131,6 +131,22 @@ def test_fp8_rejects_unsupported_shapes(L):
     assert rc != 0 and b'multiple of 128' in L.lib.w2l_last_error()
 
 
+def test_wgrad_fp8_rejects_a_dy_stride_shorter_than_its_steps(L):
+    """the e4m3 weight gradient walks 128 ceil(Tout / 128) dy rows per utterance without a clamp: a stride that holds fewer is
+    refused and nothing is launched (tests/test_gpu_fp8_direct.py runs the nearest stride that is allowed)"""
+    x = torch.zeros(2 * 130, 128, dtype=torch.uint8, device='cuda')
+    dy = torch.zeros(2 * 256, 128, dtype=torch.uint8, device='cuda')
+    dw = torch.full((1, 128, 128), float('nan'), device='cuda')
+    rc = L.lib.w2l_conv1d_wgrad_fp8(L.ptr(dy), 255 * 128, L.ptr(x), 130 * 128, 2 * 130, L.ptr(dw), 2, 128, 128, 130, 1, 1, 1.0, None, 0,
+                                    L.stream_ptr())
+    torch.cuda.synchronize()
+    assert rc != 0 and b'dy_bstride holds 255 rows' in L.lib.w2l_last_error() and bool(torch.isnan(dw).all())
+    L.check(L.lib.w2l_conv1d_wgrad_fp8(L.ptr(dy), 256 * 128, L.ptr(x), 130 * 128, 2 * 130, L.ptr(dw), 2, 128, 128, 130, 1, 1, 1.0, None, 0,
+                                       L.stream_ptr()))
+    torch.cuda.synchronize()
+    assert bool((dw == 0).all())
+
+
 @pytest.mark.parametrize('N,T,cin,cout,kw,dil', [(3, 333, 128, 256, 5, 2), (2, 500, 256, 128, 1, 1), (2, 200, 192, 320, 4, 1),
                                                   (4, 500, 384, 256, 11, 1), (1, 75, 128, 128, 29, 2), (2, 130, 128, 128, 3, 17)])
 def test_conv1d_wgrad_fp8_matches_dequantised_reference(L, N, T, cin, cout, kw, dil):

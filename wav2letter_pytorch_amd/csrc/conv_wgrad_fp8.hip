@@ -321,6 +321,12 @@ int f8_launch(const void* dyq, int64_t dy_bstride, const void* xq, int64_t x_bst
     W2L_CHECK_ARG(x_rows_total * (int64_t)Cin < (1LL << 32), "conv1d_wgrad_fp8: activation buffer exceeds 32-bit byte offsets");
     const int kwb = Kw > 1 ? 2 : 1;
     W2L_CHECK_ARG((kwb - 1) * dil <= 32, "conv1d_wgrad_fp8: dilation %d exceeds the staged window", dil);
+    // the K loop stages whole 128-frame steps of dy without a clamp: every utterance must own the rows of all its steps (the rows
+    // from Tout on zero), or a step would multiply the next utterance's first rows -- or rows behind the buffer -- into dw
+    const int64_t dy_walked = (int64_t)((Tout + BT - 1) / BT) * BT;
+    W2L_CHECK_ARG(dy_bstride / Cout >= dy_walked,
+                  "conv1d_wgrad_fp8: dy_bstride holds %lld rows per utterance, the kernel walks %lld (Tout=%d in 128-frame steps)",
+                  (long long)(dy_bstride / Cout), (long long)dy_walked, Tout);
     WgradF8Params p;
     p.dy = (const unsigned char*)dyq;
     p.x = (const unsigned char*)xq;
