@@ -570,6 +570,34 @@ int w2l_ctc_align(const float* x, const int32_t* input_lengths, const int32_t* t
                   int log_probs, void* workspace, int64_t workspace_bytes, float* score, int32_t* status, int32_t* path,
                   int32_t* starts, int32_t* ends, void* stream);
 
+/* ---- CTC forced alignment of one LONG recording to its whole transcript (alignment.ctc_forced_align_long,
+ *      segmentation.align_transcript): w2l_ctc_align's definition for N = 1 beyond its limits, the trellis cut into time blocks
+ *      of tb frames (one launch each, ordered by the stream alone) and state tiles of sb states (one workgroup each, with a
+ *      halo of 2 tb states below its own).  Bit-equal to w2l_ctc_align wherever both take the shape.  DESIGN 8s ---- */
+#define W2L_ALIGN_LONG_MAX_T (1 << 22)   /* frames */
+#define W2L_ALIGN_LONG_MAX_S (1 << 20)   /* labels of the transcript */
+#define W2L_ALIGN_LONG_MAX_TB 256        /* a forced tb: any multiple of 16 in 16 .. 256 */
+#define W2L_ALIGN_LONG_MAX_SB 2048       /* a forced sb, the built tile widths: every multiple of 64 in 64 .. 2048 */
+#define W2L_ALIGN_LONG_TB 64             /* the plan for tb = sb = 0: the measured winner (profiles/align_long_bench.txt) */
+#define W2L_ALIGN_LONG_SB 128
+/* workspace bytes for w2l_ctc_align_long: 16 (status words) + 2 * Lp * 4 (two columns) + T * 4 rounded up to 16 (the walked
+ * states) + ceil(T / 16) * Lp * 4 (the moves), with Lp = 2 S + 1 rounded up to a multiple of sb.  tb = sb = 0: the library's
+ * plan.  -1: T outside 1 .. W2L_ALIGN_LONG_MAX_T, S outside 0 .. W2L_ALIGN_LONG_MAX_S, or an invalid forced plan (only one of
+ * tb, sb zero; tb not a multiple of 16 in 16 .. 256; sb not a multiple of 64 in 64 .. 2048) */
+int64_t w2l_ctc_align_long_workspace_bytes(int T, int S, int tb, int sb);
+/* x fp32 [T][A] contiguous (log-probabilities, or probabilities if !log_probs), targets int32 [S]; recurrence, tie rules,
+ * statuses and outputs as w2l_ctc_align with N = 1 and all T frames valid: score[1], status[1], path[T], starts[S], ends[S].
+ * workspace: device memory, 16-byte aligned, of at least the bytes above for the same (T, S, tb, sb); contents undefined
+ * before and after.  2 + ceil(T / tb) + 2 launches and one 16-byte memset on `stream`, no host synchronisation. */
+int w2l_ctc_align_long(const float* x, int T, int A, const int32_t* targets, int S, int blank, int log_probs, int tb, int sb,
+                       void* workspace, int64_t workspace_bytes, float* score, int32_t* status, int32_t* path, int32_t* starts,
+                       int32_t* ends, void* stream);
+/* w2l_ctc_align_long (= phases 7) by parts, for measuring one part with the others' results in the workspace
+ * (tools/bench_align_long.py): 1 the memset, init and the forward launches; 2 the back-trace; 4 the output kernel */
+int w2l_ctc_align_long_phases(const float* x, int T, int A, const int32_t* targets, int S, int blank, int log_probs, int tb,
+                              int sb, int phases, void* workspace, int64_t workspace_bytes, float* score, int32_t* status,
+                              int32_t* path, int32_t* starts, int32_t* ends, void* stream);
+
 /* ---- CTC keyword search: where in the posteriors a phrase is said, with a score (keyword_search.py; host model:
  *      keyword_scan_host / pick_hits_host).  No reference counterpart ---- */
 /* The keywords of one call, packed by keyword_search.KeywordTable into n_blocks blocks of `width` lanes (64, 128, 256, 512 or

@@ -10,7 +10,7 @@ import importlib
 _PUBLIC = {
     'ConvCTCASR': '.base_asr_models', 'CTCLoss': '.ctc_loss', 'Decoder': '.decoder', 'GreedyDecoder': '.decoder',
     'Conv1dBlock': '.wav2letter', 'Wav2Letter': '.wav2letter', 'Jasper': '.jasper', 'JasperBlock': '.jasper',
-    'MaskedConv1d': '.jasper', 'ctc_forced_align': '.alignment', 'viterbi_align_host': '.alignment',
+    'MaskedConv1d': '.jasper', 'ctc_forced_align': '.alignment', 'ctc_forced_align_long': '.alignment', 'viterbi_align_host': '.alignment',
     'ASGLoss': '.asg', 'ASGDecoder': '.asg', 'ASGBeamSearchDecoder': '.asg_beam', 'ASGBeamSearchLMDecoder': '.asg_beam',
     'asg_forced_align': '.asg_beam', 'ctc_keyword_search': '.keyword_search', 'KeywordTable': '.keyword_search',
     'keyword_scan_host': '.keyword_search', 'pick_hits_host': '.keyword_search',

@@ -182,6 +182,9 @@ _SIGNATURES = {
     'w2l_ctc_align_workspace_bytes': (c_i64, [c_i, c_i, c_i]),
     'w2l_ctc_align': (c_i, [c_p, c_p, c_p, c_i64, c_p, c_i64, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_i64, c_p, c_p, c_p, c_p, c_p,
                             c_p]),
+    'w2l_ctc_align_long_workspace_bytes': (c_i64, [c_i, c_i, c_i, c_i]),
+    'w2l_ctc_align_long': (c_i, [c_p, c_i, c_i, c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_i64, c_p, c_p, c_p, c_p, c_p, c_p]),
+    'w2l_ctc_align_long_phases': (c_i, [c_p, c_i, c_i, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_i64, c_p, c_p, c_p, c_p, c_p, c_p]),
     'w2l_ctc_kws_workspace_bytes': (c_i64, [c_i, c_i, c_i, c_i]),
     'w2l_ctc_kws': (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, C.POINTER(KwsTable), c_p, c_i, c_i, c_p, c_i64, c_p, c_p, c_p, c_p, c_p,
                           c_p]),

@@ -304,3 +304,108 @@ def ctc_forced_align(probs, targets, input_lengths=None, target_lengths=None, bl
                   'blank (%d), in utterances %%s' % (a, blank))
     del ws
     return got
+
+
+# ------------------------------------------------------------------------------------------ one long recording, whole transcript
+LONG_MAX_T, LONG_MAX_S = 1 << 22, 1 << 20      # W2L_ALIGN_LONG_MAX_T / _MAX_S
+LONG_MAX_TB, LONG_MAX_SB = 256, 2048           # W2L_ALIGN_LONG_MAX_TB / _MAX_SB
+LONG_PLAN = (64, 128)                          # W2L_ALIGN_LONG_TB / _SB: what plan=None runs
+# the (tb, sb) pairs tools/bench_align_long.py measures and the default is picked from (DESIGN 8s has the table)
+LONG_CANDIDATES = [(32, 64), (32, 192), (64, 64), (64, 128), (64, 384), (64, 896), (96, 64), (128, 128), (128, 256), (128, 768),
+                   (128, 1024), (256, 512), (256, 1536)]
+
+
+def long_workspace_bytes(t: int, s: int, tb: int, sb: int) -> int:
+    """w2l_ctc_align_long_workspace_bytes on the host (the formula of include/w2l_hip.h; tb, sb as launched, not 0)"""
+    lp = -(-(2 * s + 1) // sb) * sb
+    return 16 + 2 * lp * 4 + -(-t * 4 // 16) * 16 + -(-t // 16) * lp * 4
+
+
+def _long_target(target, labels):
+    """one int sequence, or a string with ``labels`` -> int32 [S]"""
+    import torch
+    if torch.is_tensor(target):
+        target = target.detach().cpu().numpy()
+    if isinstance(target, str):
+        if labels is None:
+            raise ValueError('ctc_forced_align_long: a string target needs ``labels``')
+        first = _first_index(labels)
+        try:
+            return np.array([first[ch] for ch in target], dtype=np.int32)
+        except KeyError as e:
+            raise ValueError('ctc_forced_align_long: character %r is not in the labels' % (e.args[0],)) from None
+    tg = np.asarray(target)
+    if tg.size == 0:
+        return np.zeros(0, dtype=np.int32)
+    if tg.ndim != 1 or not np.issubdtype(tg.dtype, np.integer):
+        raise ValueError('ctc_forced_align_long: the target is ONE sequence of integers (or a string with labels), got shape %s '
+                         'of %s' % (tg.shape, tg.dtype))
+    return np.ascontiguousarray(tg.clip(-1, 1 << 30), dtype=np.int32)      # (anything out of range stays out of range)
+
+
+def launch_align_long(x, tgt, s: int, blank: int, log_probs: bool, plan, ws, out):
+    """the launches of w2l_ctc_align_long on the current stream: x [T, A] float32 contiguous and ``tgt`` int32 [S] on the device,
+    ``ws`` a uint8 device tensor of long_workspace_bytes, outputs into ``out`` in align_sections(1, T, S)'s layout"""
+    from ._lib import check, lib, ptr, stream_ptr
+    t, a = x.shape
+    tb, sb = plan if plan is not None else (0, 0)
+    vp = C.c_void_p
+    sections = [vp(out.data_ptr() + o) for o in align_sections(1, t, s)[:5]]
+    check(lib.w2l_ctc_align_long(ptr(x), t, a, ptr(tgt) if s else None, s, int(blank), int(bool(log_probs)), int(tb), int(sb),
+                                 ptr(ws), int(ws.numel()), *sections, stream_ptr()), 'w2l_ctc_align_long')
+
+
+def ctc_forced_align_long(probs, target, blank: int = 0, log_probs: bool = True, labels: Optional[Sequence[str]] = None,
+                          plan=None, max_workspace_bytes: int = 8 << 30) -> Alignment:
+    """ctc_forced_align for ONE recording of any length up to 2^22 frames against its whole transcript of up to 2^20 labels
+    (w2l_ctc_align_long, csrc/ctc_align_long.hip: the trellis cut into time blocks and state tiles, many workgroups), bit-equal
+    to ctc_forced_align wherever both take the shape.
+
+    probs: [T, A]; target: one int sequence, or a string with ``labels``; ``plan=(tb, sb)`` forces the cut (tb a multiple of
+    16 up to 256 frames, sb a multiple of 64 up to 2048 states; default: the measured one).  -> an Alignment with N = 1.
+    Errors as ctc_forced_align's: bad input is a ValueError, no path is ``feasible[0] == False``.  The workspace holds two bits
+    per trellis cell (about T * S / 4 bytes: 4.5 GB for an hour with 50 000 characters); above ``max_workspace_bytes`` (8 GiB by
+    convention, not tuned) it is a ValueError that states the bytes.  Argument errors come before the device is looked for."""
+    import torch
+    x = probs if torch.is_tensor(probs) else torch.from_numpy(np.ascontiguousarray(probs))
+    if x.dim() != 2:
+        raise ValueError('ctc_forced_align_long: expected [T, labels] posteriors of one recording, got shape %s' % (tuple(x.shape),))
+    t, a = x.shape
+    if t < 1 or a < 1:
+        raise ValueError('ctc_forced_align_long: empty posteriors, shape %s' % (tuple(x.shape),))
+    if labels is not None and len(labels) != a:
+        raise ValueError('ctc size:%d, labels: %d' % (a, len(labels)))
+    if not 0 <= blank < a:
+        raise ValueError('blank %d outside %d labels' % (blank, a))
+    tg = _long_target(target, labels)
+    s = int(tg.size)
+    if t > LONG_MAX_T or s > LONG_MAX_S:
+        raise ValueError('ctc_forced_align_long: T=%d (max %d) or target length %d (max %d) is out of range'
+                         % (t, LONG_MAX_T, s, LONG_MAX_S))
+    if plan is not None:
+        try:
+            tb, sb = (int(v) for v in plan)
+        except (TypeError, ValueError):
+            raise ValueError('ctc_forced_align_long: plan=%r is not a (tb, sb) pair' % (plan,)) from None
+        if not (16 <= tb <= LONG_MAX_TB and tb % 16 == 0 and 64 <= sb <= LONG_MAX_SB and sb % 64 == 0):
+            raise ValueError('ctc_forced_align_long: plan=(%d, %d): tb is a multiple of 16 in 16..%d, sb a multiple of 64 in 64..%d'
+                             % (tb, sb, LONG_MAX_TB, LONG_MAX_SB))
+        plan = (tb, sb)
+    need = long_workspace_bytes(t, s, *(plan or LONG_PLAN))
+    if need > max_workspace_bytes:
+        raise ValueError('ctc_forced_align_long: T=%d frames x %d labels need a workspace of %d bytes, above max_workspace_bytes=%d'
+                         % (t, s, need, max_workspace_bytes))
+    x = on_device(x, 'ctc_forced_align_long', '; viterbi_align_host is the host model')
+    from ._lib import lib
+    with torch.cuda.device(x.device):
+        if int(lib.w2l_ctc_align_long_workspace_bytes(t, s, *(plan or (0, 0)))) != need:
+            raise RuntimeError('ctc_forced_align_long: the library plans %d workspace bytes, alignment.py %d'
+                               % (lib.w2l_ctc_align_long_workspace_bytes(t, s, *(plan or (0, 0))), need))
+        tgt = torch.from_numpy(tg).to(x.device, non_blocking=True)
+        ws = torch.empty(need, dtype=torch.uint8, device=x.device)
+        out = torch.empty(align_sections(1, t, s)[5], dtype=torch.uint8, device=x.device)
+        launch_align_long(x, tgt, s, blank, log_probs, plan, ws, out)
+        got = aligned(out, 1, t, s, np.array([s], dtype=np.int32), 'ctc_forced_align_long: a negative probability, or a target '
+                      'outside [0, %d) or equal to the blank (%d), in utterances %%s' % (a, blank))
+    del ws
+    return got

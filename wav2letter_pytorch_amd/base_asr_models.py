@@ -489,3 +489,18 @@ class ConvCTCASR(_Base):
         NotImplementedError (the search is the CTC recurrence)."""
         from .segmentation import find_keywords
         return find_keywords(self, items, phrases, threshold, max_hits, max_seconds, batch_size, vad, also_transcribe, decoder)
+
+    def align_transcript(self, item, text, max_seconds: float = 20.0, batch_size: int = 8, vad=None):
+        """when in ONE recording is each word and line of its known ``text`` said?  The input, the device segmentation, the
+        front end and ``infer`` of ``transcribe_long``; each piece's posterior rows stay on the device and are concatenated in
+        time order (silence the VAD dropped has no frames), and the whole text is aligned to them in one
+        alignment.ctc_forced_align_long.  ``text``: a string, or a list of strings (lines or sentences); runs of whitespace
+        collapse to one space, lines are joined by one space; a character outside the model's labels is a ValueError naming it.
+        Returns ``{'score', 'words': [{'word', 'start', 'end', 'score'}], 'segments': [{'text', 'start', 'end', 'score'}]}``,
+        one segment per given line, seconds on the recording's clock as ``transcribe_long(word_times=True)`` gives them (the
+        piece's start plus the frame times the model's seconds per frame; a word cut by a forced piece boundary starts in one
+        piece and ends in the next).  A word's or segment's ``score`` is the mean over its frames of the log-posterior of the
+        aligned label -- what bad lines are filtered by; the top-level ``score`` is the path's.  More characters than frames of
+        speech, or no path of finite score: ValueError.  ``model.criterion=asg``: NotImplementedError."""
+        from .segmentation import align_transcript
+        return align_transcript(self, item, text, max_seconds, batch_size, vad)

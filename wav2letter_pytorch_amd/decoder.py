@@ -75,6 +75,16 @@ class Decoder(object):
         end_offsets = [[torch.IntTensor(res.ends[n, :len(text)].copy())] for n, text in enumerate(texts)]
         return offsets, end_offsets
 
+    def align_long(self, probs, text, log_probs=False):
+        """``align`` for ONE recording [T, labels] of any length and its whole transcript ``text``
+        (alignment.ctc_forced_align_long: up to 2^22 frames and 2^20 characters, many workgroups) -> ``(offsets, end_offsets)``
+        in ``align``'s format with one utterance."""
+        from .alignment import ctc_forced_align_long
+        res = ctc_forced_align_long(probs, text, blank=self.blank_index, log_probs=log_probs, labels=list(self.labels))
+        if not res.feasible[0]:
+            raise ValueError('Decoder.align_long: no frame path spells the text')
+        return [[torch.IntTensor(res.starts[0].copy())]], [[torch.IntTensor(res.ends[0].copy())]]
+
     def find(self, probs, phrases, sizes=None, log_probs=False, threshold=-1.0, max_hits=8, return_curves=False):
         """the counterpart of ``align`` for phrases whose place is not known: every occurrence of each of ``phrases`` (strings
         over the labels, or a keyword_search.KeywordTable built with them) in the posteriors, by
@@ -187,7 +197,7 @@ def __getattr__(name):
     if name in ('ASGBeamSearchDecoder', 'ASGBeamSearchLMDecoder', 'asg_beam_search_gpu', 'asg_forced_align'):
         from . import asg_beam
         return getattr(asg_beam, name)
-    if name in ('ctc_forced_align', 'viterbi_align_host'):
+    if name in ('ctc_forced_align', 'ctc_forced_align_long', 'viterbi_align_host'):
         from . import alignment
         return getattr(alignment, name)
     raise AttributeError(f'module {__name__!r} has no attribute {name!r}')

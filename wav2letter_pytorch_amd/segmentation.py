@@ -342,3 +342,112 @@ def find_keywords(model, items, phrases, threshold: float = -1.0, max_hits: int 
         return (hits, stitch(pieces, rate)) if also_transcribe else hits
 
     return for_each_piece(model, items, max_seconds, batch_size, vad, handle, finish)
+
+
+# ------------------------------------------------------------------------------- a whole transcript against a whole recording
+def transcript_lines(text):
+    """``text`` (a string: one line; or a list of strings: lines or sentences) -> (joined, spans): runs of whitespace collapse
+    to one space, lines are joined by one space, ``spans[i]`` is the half-open character range of line i in ``joined``.  A line
+    without a character is a ValueError (it would have no place on the clock)."""
+    lines = [text] if isinstance(text, str) else list(text)
+    if not lines:
+        raise ValueError('align_transcript: no text')
+    spans, parts, at = [], [], 0
+    for i, line in enumerate(lines):
+        if not isinstance(line, str):
+            raise ValueError(f'align_transcript: line {i} is {type(line).__name__}, not a string')
+        line = ' '.join(line.split())
+        if not line:
+            raise ValueError(f'align_transcript: line {i} holds no character')
+        spans.append((at, at + len(line)))
+        parts.append(line)
+        at += len(line) + 1
+    return ' '.join(parts), spans
+
+
+def word_spans(joined: str):
+    """[(word, first character, one past its last)] of a string whose words are separated by single spaces"""
+    out, at = [], 0
+    for w in joined.split(' '):
+        if w:
+            out.append((w, at, at + len(w)))
+        at += len(w) + 1
+    return out
+
+
+def frame_times(frames, table, sample_rate: int, ratio: float):
+    """frames of the concatenated posteriors -> seconds on the recording's clock.  ``table``: per piece in time order (first
+    sample in the recording, first frame in the concatenation); a frame belongs to the last piece that starts at or before it and
+    lies at that piece's start plus its frame offset times ``ratio`` (seconds per frame), transcribe_long's word-time convention.
+    Silence the VAD dropped has no frames, so time jumps between pieces."""
+    table = np.asarray(table, dtype=np.int64).reshape(-1, 2)
+    frames = np.asarray(frames, dtype=np.int64)
+    if table.shape[0] < 1 or (np.diff(table[:, 1]) <= 0).any() or table[0, 1] != 0:
+        raise ValueError('frame_times: the piece table needs first frames ascending from 0')
+    if frames.size and (frames.min() < 0):
+        raise ValueError('frame_times: a negative frame')
+    piece = np.searchsorted(table[:, 1], frames, side='right') - 1
+    return table[piece, 0] / float(sample_rate) + (frames - table[piece, 1]) * float(ratio)
+
+
+def alignment_records(joined: str, line_spans, starts, ends, frame_logp, table, sample_rate: int, ratio: float) -> dict:
+    """the result of align_transcript from the alignment of ``joined`` (``starts`` / ``ends``: first / last frame of each of its
+    characters; ``frame_logp`` [T]: the log-posterior of the path's label at each frame) -> {'score', 'words', 'segments'}.  A
+    word or line starts at its first character's first frame and ends at its last character's last frame, each on the clock of
+    the piece the frame came from (a word cut by a piece boundary takes its start from one piece and its end from the next);
+    its score is the mean of frame_logp over those frames."""
+    starts, ends = np.asarray(starts, dtype=np.int64), np.asarray(ends, dtype=np.int64)
+    cum = np.concatenate(([0.0], np.cumsum(np.asarray(frame_logp, dtype=np.float64))))
+
+    def record(key, what, c0, c1):
+        f0, f1 = int(starts[c0]), int(ends[c1 - 1])
+        t0, t1 = frame_times([f0, f1], table, sample_rate, ratio)
+        return {key: what, 'start': float(t0), 'end': float(t1), 'score': float((cum[f1 + 1] - cum[f0]) / (f1 + 1 - f0))}
+
+    return {'score': float(cum[-1]),
+            'words': [record('word', w, c0, c1) for w, c0, c1 in word_spans(joined)],
+            'segments': [record('text', joined[c0:c1], c0, c1) for c0, c1 in line_spans]}
+
+
+def align_transcript(model, item, text, max_seconds: float = 20.0, batch_size: int = 8, vad: Optional[VadConfig] = None) -> dict:
+    """the body of ``ConvCTCASR.align_transcript`` (its docstring has the interface)"""
+    import torch
+    from .alignment import ctc_forced_align_long
+    from .evaluate import frame_seconds
+    if getattr(getattr(model, 'criterion', None), 'is_asg', False):
+        raise NotImplementedError('align_transcript on a model with criterion asg: the long alignment is the CTC recurrence (a '
+                                  'blank between repeated letters, no transitions); the ASG recurrence is not built')
+    joined, spans = transcript_lines(text)
+    labels = list(model.labels)
+    for ch in joined:
+        if ch not in labels:
+            raise ValueError(f'align_transcript: character {ch!r} is not in the model\'s labels')
+    blank = int(model.ctc_decoder.blank_index)
+    log_probs = bool(getattr(model, 'infer_log_probs', True))
+    ratio = frame_seconds(model)
+
+    def handle(batch, segs, out, out_lens):
+        lens = [out.shape[1]] * len(batch) if out_lens is None else [int(v) for v in torch.as_tensor(out_lens).cpu()]
+        return [{'start': int(segs[i, 0]), 'end': int(segs[i, 1]), 'rows': out[j, :lens[j]]} for j, i in enumerate(batch)]
+
+    def finish(pieces, rate):
+        pieces = sorted((p for p in pieces if p['rows'].shape[0] > 0), key=lambda p: p['start'])
+        frames = sum(p['rows'].shape[0] for p in pieces)
+        if frames < len(joined):
+            raise ValueError(f'align_transcript: {len(joined)} characters on {frames} frames of speech: no frame path spells the text')
+        table, at = [], 0
+        for p in pieces:
+            table.append((p['start'], at))
+            at += p['rows'].shape[0]
+        x = torch.cat([p['rows'].float() for p in pieces], 0).contiguous()
+        res = ctc_forced_align_long(x, joined, blank=blank, log_probs=log_probs, labels=labels)
+        if not res.feasible[0]:
+            raise ValueError(f'align_transcript: no frame path of {frames} frames spells the {len(joined)} characters of the text')
+        path = torch.from_numpy(res.paths[0].astype(np.int64)).to(x.device)
+        picked = x.gather(1, path.view(-1, 1)).view(-1)                # one gather: the path's label at every frame
+        picked = (picked if log_probs else picked.log()).cpu().numpy()
+        got = alignment_records(joined, spans, res.starts[0], res.ends[0], picked, table, rate, ratio)
+        got['score'] = float(res.scores[0])
+        return got
+
+    return for_each_piece(model, [item], max_seconds, batch_size, vad, handle, finish)[0]
