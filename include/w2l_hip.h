@@ -550,6 +550,32 @@ int w2l_ctc_loss(const float* log_probs, const int32_t* targets, const int32_t* 
                  const int32_t* target_lengths, int N, int T, int C, int Smax, int blank, int zero_infinity,
                  float* nll, float* loss, float* grad, void* workspace, void* stream);
 
+/* ---- wildcard CTC: a target may say "here is speech the transcript has no text for" (W-CTC, Star Temporal Classification) ---- */
+/* workspace bytes for w2l_wctc_loss: w2l_ctc_loss's alpha and beta plus the parsed rows (labels, gap flags, label counts) */
+int64_t w2l_wctc_workspace_bytes(int N, int T, int Smax);
+/* w2l_ctc_loss whose target rows may hold the wildcard id `star` (the Python layer passes star = C).  Row n is the first
+ * R = target_lengths[n] (clamped to [0, Smax]) int32 entries of targets [N][Smax]; each is a label in [0, C) other than the
+ * blank, or star.  Parsing (on the device, one block prefix count per row, no host synchronisation): the labels z_1..z_S are
+ * the non-star entries in order; the gap flag w_i, i = 0..S, is 1 iff at least one star lies between z_i and z_{i+1} (w_0:
+ * before z_1, w_S: after z_S); consecutive stars are one wildcard; a row of only stars has S = 0 and w_0 = 1.
+ * States: CTC's L = 2S + 1 extended states, odd s the label z_{(s+1)/2}, even s the gap s/2.  Emissions: a label state
+ * lp[t][z], a plain gap lp[t][blank], a wildcard gap (w = 1) the constant `penalty` <= 0 -- "any label or the blank, with
+ * probability 1, times exp(penalty)" per frame.  Transitions: CTC's (s -> s, s-1 -> s, and s-2 -> s for odd s whose label
+ * differs from the label two states back), so a wildcard gap between different labels may take zero frames, and between equal
+ * labels at least one gap frame is needed, which for a wildcard gap may carry anything.  Start in states 0 and 1, end in L-1
+ * and L-2: nll = -logsumexp(alpha_{Tn-1}(L-1), alpha_{Tn-1}(L-2)), loss[1] = mean_n(nll_n / max(S_n, 1)) -- S_n counts labels,
+ * not stars.  With no star in a row this is w2l_ctc_loss value for value.  With stars the score is NOT a normalised
+ * probability (one frame labelling is reached through more than one state path): nll may be negative.
+ * grad [N][T][C] follows w2l_ctc_loss's convention (the gradient wrt the logits under lp = log_softmax(logits)): with
+ * gamma_t(s) the state posterior, post(t,c) its sum over the non-wildcard states that emit c and omega_t its sum over the
+ * wildcard gaps, grad = (exp(lp[t][c]) * (1 - omega_t) - post(t,c)) / (N * max(S_n, 1)); zero for t >= input_lengths[n]; it
+ * sums to zero over c.  grad may be NULL.  zero_infinity as in w2l_ctc_loss.
+ * status int32 [N]: 0 ok; 1 no finite path (nll +inf, or 0 under zero_infinity); 2 an entry that is neither a valid non-blank
+ * label nor star -- that utterance gets nll, loss term and gradient 0.  Limits: C <= 64, Smax <= 4095; star != blank. */
+int w2l_wctc_loss(const float* log_probs, const int32_t* targets, const int32_t* input_lengths,
+                  const int32_t* target_lengths, int N, int T, int C, int Smax, int blank, int zero_infinity, int star,
+                  float penalty, float* nll, float* loss, float* grad, int32_t* status, void* workspace, void* stream);
+
 /* ---- CTC forced alignment: the offsets decoder.py:238 refuses for beam search, in the format of decoder.py:104-119 ---- */
 /* workspace bytes for w2l_ctc_align: 0 while the back-pointers fit in LDS, else N * ceil(T / 16) * (states rounded up to the
  * block's) * 4; -1 if out of range */

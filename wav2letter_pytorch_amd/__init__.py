@@ -8,7 +8,7 @@ the ranks."""
 import importlib
 
 _PUBLIC = {
-    'ConvCTCASR': '.base_asr_models', 'CTCLoss': '.ctc_loss', 'Decoder': '.decoder', 'GreedyDecoder': '.decoder',
+    'ConvCTCASR': '.base_asr_models', 'CTCLoss': '.ctc_loss', 'WildcardCTCLoss': '.ctc_loss', 'Decoder': '.decoder', 'GreedyDecoder': '.decoder',
     'Conv1dBlock': '.wav2letter', 'Wav2Letter': '.wav2letter', 'Jasper': '.jasper', 'JasperBlock': '.jasper',
     'MaskedConv1d': '.jasper', 'ctc_forced_align': '.alignment', 'ctc_forced_align_long': '.alignment', 'viterbi_align_host': '.alignment',
     'ASGLoss': '.asg', 'ASGDecoder': '.asg', 'ASGBeamSearchDecoder': '.asg_beam', 'ASGBeamSearchLMDecoder': '.asg_beam',

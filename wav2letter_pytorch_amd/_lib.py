@@ -174,6 +174,8 @@ _SIGNATURES = {
     'w2l_log_softmax_bwd': (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_p]),
     'w2l_ctc_workspace_bytes': (c_i64, [c_i, c_i, c_i]),
     'w2l_ctc_loss': (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p]),
+    'w2l_wctc_workspace_bytes': (c_i64, [c_i, c_i, c_i]),
+    'w2l_wctc_loss': (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_p, c_p, c_p, c_p, c_p, c_p]),
     'w2l_asg_workspace_bytes': (c_i64, [c_i, c_i, c_i, c_i]),
     'w2l_asg_loss': (c_i, [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_p]),
     'w2l_asg_viterbi_workspace_bytes': (c_i64, [c_i, c_i, c_i]),
@@ -324,7 +326,7 @@ TRACE_NAMES = {
     'w2l_bn_act_bwd_apply_fin': 'bn_act_bwd_apply_kernel', 'w2l_sgd_pack': 'sgd_pack_kernel', 'w2l_pack_weights': 'pack_weights_kernel',
     'w2l_sgd_pack_clip': 'sgd_pack_kernel', 'w2l_adam_pack': 'adam_pack_kernel', 'w2l_grad_sqnorm_multi': 'grad_norm_kernels',
     'w2l_asg_loss': 'asg_kernels', 'w2l_asg_viterbi': 'asg_viterbi_kernel',
-    'w2l_ctc_loss': 'ctc_kernels', 'w2l_log_softmax_fwd': 'log_softmax_fwd', 'w2l_log_softmax_bwd': 'log_softmax_bwd',
+    'w2l_ctc_loss': 'ctc_kernels', 'w2l_wctc_loss': 'wctc_kernels', 'w2l_log_softmax_fwd': 'log_softmax_fwd', 'w2l_log_softmax_bwd': 'log_softmax_bwd',
     'w2l_nct_to_ntc': 'nct_to_ntc_kernel', 'w2l_pad_cast': 'pad_cast_kernel', 'w2l_quantize_e4m3': 'quantize_e4m3',
     'w2l_quantize_e4m3_dyn': 'quantize_e4m3_dyn', 'w2l_dwconv_fwd': 'dw_fwd_kernel', 'w2l_dwconv_dgrad': 'dw_dgrad_kernel',
     'w2l_dwconv_wgrad': 'dw_wgrad_kernel', 'w2l_argmax': 'argmax_kernel', 'w2l_novograd_pack': 'novograd_pack_kernel',

@@ -10,8 +10,8 @@ from typing import Callable, Dict, Sequence
 import torch
 import torch.nn as nn
 
-from .config import criterion_name, instantiate, scheduler_interval
-from .ctc_loss import CTCLoss
+from .config import criterion_name, instantiate, scheduler_interval, strip_wildcard, wildcard_options
+from .ctc_loss import CTCLoss, WildcardCTCLoss
 
 try:  # PyTorch-Lightning is optional: absent in the build image
     import pytorch_lightning as ptl  # type: ignore
@@ -89,6 +89,9 @@ class ConvCTCASR(_Base):
         self._cfg = cfg
         self.audio_conf = cfg.audio_conf
         self.labels = cfg.labels
+        # model.wildcard: the transcripts' mark for "speech without text here" (targets only: the output classes and every
+        # decoder are unchanged); None when the key is absent
+        self.wildcard, wildcard_penalty = wildcard_options(cfg, self.labels)
         if criterion_name(cfg) == 'asg':
             # the criterion of the paper (asg.py): label 0 is "repeat the previous letter", the decoder is Viterbi over the
             # criterion's learned transitions; cfg.decoder (a CTC decoder) is not instantiated
@@ -102,7 +105,10 @@ class ConvCTCASR(_Base):
             self.ctc_decoder = ASGDecoder(self.labels, transitions=self.criterion)
         else:
             self.ctc_decoder = instantiate(cfg.decoder)
-            self.criterion = CTCLoss(blank=0, reduction='mean', zero_infinity=True)      # base_asr_models.py:23
+            if self.wildcard is not None:
+                self.criterion = WildcardCTCLoss(blank=0, reduction='mean', zero_infinity=True, penalty=wildcard_penalty)
+            else:
+                self.criterion = CTCLoss(blank=0, reduction='mean', zero_infinity=True)      # base_asr_models.py:23
         self.print_decoded_prob = cfg.get('print_decoded_prob', 0)
         self.example_input_array = self.create_example_input_array()
         # load_state_dict(assign=True) swaps Parameter OBJECTS under the engine's specs: rebuild after any load
@@ -197,6 +203,15 @@ class ConvCTCASR(_Base):
             print(f'decoded  : {hyps[0]}')
         return {f'{prefix}_cer': char_err / char_ref, f'{prefix}_wer': word_err / word_ref,
                 f'{prefix}_len_ratio': sum(len(h) for h in hyps) / sum(len(t) for t in texts)}
+
+    def metric_texts(self, texts):
+        """the reference strings CER / WER / the length ratio are scored against: with ``model.wildcard`` set, the transcripts
+        with the mark removed and whitespace collapsed (config.strip_wildcard; the error counts of such utterances are upper
+        bounds: the words spoken where the mark stands count as insertions); without it, ``texts`` itself"""
+        mark = getattr(self, 'wildcard', None)
+        if mark is None:
+            return texts
+        return [strip_wildcard(t, mark) for t in texts]
 
     def add_string_metrics(self, out, output_lengths, texts, prefix) -> Dict[str, float]:
         """greedy decode, then batch-level CER / WER (edit-distance totals over reference-length totals) and the
@@ -376,6 +391,7 @@ class ConvCTCASR(_Base):
         (base_asr_models.py:78-94).  batch = _collator's 6-tuple (data_loader.py:149-158).  Nothing in here waits for the
         GPU when ``async_metrics`` is on and the step is a training step: the metrics are logged by on_train_batch_end."""
         spect, spect_lens, targets, target_lens, _paths, texts = batch
+        texts = self.metric_texts(texts)
         x = self._device_batch(spect)
         out, out_lens = (forward or self.forward)(x, spect_lens)
         if x.is_cuda and torch.is_tensor(out_lens) and torch.is_tensor(targets) and torch.is_tensor(target_lens):

@@ -41,6 +41,38 @@ def criterion_name(model_cfg) -> str:
     return name
 
 
+def wildcard_options(model_cfg, labels=None):
+    """``model.wildcard`` (the mark character of a transcript that stands for "speech without text here", e.g. ``'*'``; absent or
+    empty: the feature is off) and ``model.wildcard_penalty`` (log-domain cost per wildcard frame, <= 0, default 0) ->
+    (mark or None, penalty).  The mark is one character and none of the model's labels (ValueError); with
+    ``model.criterion=asg`` it is a NotImplementedError: the wildcard is defined for CTC only."""
+    get = model_cfg.get if hasattr(model_cfg, 'get') else (lambda k, d=None: d)
+    mark = get('wildcard', None)
+    if mark is None or mark == '':
+        return None, 0.0
+    mark = str(mark)
+    if len(mark) != 1:
+        raise ValueError(f'model.wildcard={mark!r}: the wildcard mark is one character')
+    labels = get('labels', None) if labels is None else labels
+    if labels is not None and not isinstance(labels, str) and mark in list(labels):
+        raise ValueError(f'model.wildcard={mark!r} is one of the model\'s labels: choose a character the transcripts do not use')
+    if criterion_name(model_cfg) == 'asg':
+        raise NotImplementedError('model.wildcard with model.criterion=asg: the wildcard target is implemented for ctc only')
+    penalty = float(get('wildcard_penalty', 0.0) or 0.0)
+    if penalty > 0:
+        raise ValueError(f'model.wildcard_penalty={penalty}: a log-domain cost per frame, it must be <= 0')
+    return mark, penalty
+
+
+def strip_wildcard(text: str, mark) -> str:
+    """the transcript the string metrics score: the wildcard mark removed and whitespace collapsed.  What was spoken where the
+    mark stands is unknown, so the hypothesis' words there count as insertions: CER and WER of such an utterance are upper
+    bounds"""
+    if not mark or mark not in text:
+        return text
+    return ' '.join(text.replace(mark, ' ').split())
+
+
 SCHEDULER_INTERVALS = ('epoch', 'step')
 
 
@@ -127,6 +159,16 @@ def _interpolate(node, root):
 _FLOAT_RE = re.compile(r'^[-+]?(\d+\.?\d*|\.\d+)([eE][-+]?\d+)?$')
 
 
+def override_value(key: str, text: str):
+    """the value of a command-line override ``key=text``: YAML, except that ``model.wildcard`` is the text itself, less one pair
+    of quotes (``model.wildcard='*'`` reaches the program as ``*`` from a shell, and a bare ``*`` or ``#`` is YAML syntax)"""
+    if key == 'model.wildcard':
+        if len(text) >= 2 and text[0] == text[-1] and text[0] in '\'"':
+            text = text[1:-1]
+        return text or None
+    return _yaml_load(text)
+
+
 def _yaml_load(text):
     """yaml.safe_load plus OmegaConf's number rule: `1e-5` (no dot) is a float, not a string
     (optimizer/exp_lr_optimizer.yaml:4 relies on it)."""
@@ -178,7 +220,7 @@ def load_config(config_dir: str, overrides=()):
         parts = k.split('.')
         for p in parts[:-1]:
             cur = cur.setdefault(p, {})
-        cur[parts[-1]] = _yaml_load(v)
+        cur[parts[-1]] = override_value(k, v)
     merged.pop('hydra', None)
     _interpolate(merged, merged)
     if isinstance(merged.get('model'), dict):

@@ -275,10 +275,14 @@ class SpectrogramDataset(Dataset):
     ``resample=True`` (not in the reference): files of any rate and channel count; every row is read with ``read_audio`` and
     converted to ``audio_conf['sample_rate']`` on the GPU, instead of the assertion on the first row's rate.
     ``speed_perturb``: a ``SpeedPerturb`` (or its factors), applied per utterance by BatchAudioDataLoader's batches only.
-    ``wave_augment``: a ``WaveformAugment`` (reverberation and noise on the waveform), likewise for the loader's batches only."""
+    ``wave_augment``: a ``WaveformAugment`` (reverberation and noise on the waveform), likewise for the loader's batches only.
+    ``wildcard``: the transcripts' mark for "speech without text here" (``model.wildcard``, one character outside ``labels``); it
+    becomes the target id ``len(labels)``, which ctc_loss.WildcardCTCLoss reads as its wildcard.  ``wildcard_ends``
+    (``data.wildcard_ends``, needs ``wildcard``): one wildcard before and one after every target -- the transcript covers only
+    part of the audio (W-CTC's use)."""
 
     def __init__(self, manifest_filepath, audio_conf, labels, mel_spec=None, use_cuda=False, resample=False, speed_perturb=None,
-                 wave_augment=None):
+                 wave_augment=None, wildcard=None, wildcard_ends=False):
         super().__init__()
         rows = self._read_manifest(manifest_filepath)
         self.rows = rows
@@ -289,6 +293,13 @@ class SpectrogramDataset(Dataset):
         self.use_cuda = use_cuda
         self.mel_spec = mel_spec
         self.labels_map = dict([(labels[i], i) for i in range(len(labels))])
+        if wildcard is not None and (len(wildcard) != 1 or wildcard in self.labels_map):
+            raise ValueError(f'wildcard={wildcard!r}: the mark is one character that is none of the labels')
+        if wildcard_ends and wildcard is None:
+            raise ValueError('wildcard_ends needs a wildcard mark (model.wildcard)')
+        self.wildcard = wildcard
+        self.wildcard_id = len(labels)
+        self.wildcard_ends = bool(wildcard_ends)
         self.resample = bool(resample)
         if speed_perturb is not None and not isinstance(speed_perturb, SpeedPerturb):
             speed_perturb = SpeedPerturb(speed_perturb)
@@ -314,7 +325,11 @@ class SpectrogramDataset(Dataset):
 
     def _target(self, transcript):
         # filter(None, ...) drops unknown characters AND label 0, the blank (data_loader.py:127)
-        return list(filter(None, [self.labels_map.get(c) for c in list(transcript)]))
+        if self.wildcard is None:
+            return list(filter(None, [self.labels_map.get(c) for c in list(transcript)]))
+        ids = [self.wildcard_id if c == self.wildcard else self.labels_map.get(c) for c in list(transcript)]
+        ids = list(filter(None, ids))
+        return [self.wildcard_id] + ids + [self.wildcard_id] if self.wildcard_ends else ids
 
     def rate(self, index) -> int:
         """sample rate of row ``index``: the model's unless ``resample``, else the file's (read once per row)"""

@@ -78,6 +78,8 @@ def evaluate(model, dataloader, decoder=None, word_times: bool = False) -> Tuple
         with torch.no_grad():
             for batch in dataloader:
                 spect, spect_lens, targets, target_lens, paths, texts = batch
+                if hasattr(model, 'metric_texts'):
+                    texts = model.metric_texts(texts)          # model.wildcard: scored without the mark (upper bounds)
                 x = model._device_batch(spect)
                 out, out_lens = model.infer(x, spect_lens)
                 if x.is_cuda and all(torch.is_tensor(t) for t in (out_lens, targets, target_lens)):

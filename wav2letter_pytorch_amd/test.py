@@ -173,7 +173,8 @@ def main(argv=None):
     from .engine import invalidate_packed
     invalidate_packed(model)
     ds = SpectrogramDataset(cfg.data.test_manifest, cfg.data.audio_conf, cfg.model.labels, mel_spec=cfg.data.mel_spec,
-                            resample=_truth(cfg.data.get('resample', False)))
+                            resample=_truth(cfg.data.get('resample', False)), wildcard=getattr(model, 'wildcard', None),
+                            wildcard_ends=_truth(cfg.data.get('wildcard_ends', False)))
     loader = BatchAudioDataLoader(ds, batch_size=cfg.data.batch_size)
     if cfg.decoder in ASG_DECODERS:
         dec = build_decoder(cfg, True, transitions=model.criterion)

@@ -23,13 +23,17 @@ convolved with one of the room impulse responses (each cut ``data.rir_max_second
 ``data.bucket_rungs=K`` (0, the default: off) batches utterances of similar length together and pads every batch to one of K
 widths chosen from the manifest (data/bucketing.py): the step then meets at most K + 1 shapes, which are tuned once and replayed,
 instead of a new one per batch; ``data.bucket_shuffle`` / ``data.bucket_seed`` shuffle the rows inside each width and the batch
-order per epoch, ``data.drop_last`` drops the one short batch."""
+order per epoch, ``data.drop_last`` drops the one short batch.
+``model.wildcard='*'`` names a mark character: where a transcript holds it, there is speech the text does not cover, and the
+criterion becomes ctc_loss.WildcardCTCLoss (``model.wildcard_penalty``, <= 0, is the log-domain cost per frame spent there);
+``data.wildcard_ends=true`` puts one wildcard before and after every training and validation target.  CER / WER score the
+transcripts without the mark."""
 from __future__ import annotations
 
 import os
 import sys
 
-from .config import _yaml_load, bucket_options, criterion_name, load_config, scheduler_interval, to_cfg
+from .config import bucket_options, criterion_name, load_config, override_value, scheduler_interval, to_cfg, wildcard_options
 from .launch import spawn_ranks, under_launcher
 
 # Nothing above maps libw2l_hip.so (or imports torch): with trainer.gpus=N this process only starts the ranks, and a launch
@@ -81,7 +85,7 @@ class _Models(dict):
 name_to_model = _Models()
 
 
-def get_data_loaders(labels, cfg, rank: int = 0, world: int = 1):
+def get_data_loaders(labels, cfg, rank: int = 0, world: int = 1, wildcard=None):
     """train.py:21-26.  With more than one rank each loader walks its own shard of the manifest: a DistributedSampler
     over the raw items (indices rank, rank + world, ...; the tail padded so every rank takes the same number of steps --
     a rank that ran out of batches early would leave the others waiting in a collective), which is what Lightning's DDP
@@ -96,10 +100,13 @@ def get_data_loaders(labels, cfg, rank: int = 0, world: int = 1):
     resample = _truth(cfg.get('resample', False))
     factors = parse_speed_factors(cfg.get('speed_perturb'))         # the train loader only: validation is never perturbed
     wave = from_config(cfg, int(cfg.audio_conf['sample_rate']))     # None unless data.noise_manifest / data.rir_manifest is set
+    ends = _truth(cfg.get('wildcard_ends', False))                  # one wildcard around every target, validation included
+    if ends and wildcard is None:
+        raise ValueError('data.wildcard_ends=true needs model.wildcard (the mark character, e.g. model.wildcard="*")')
     bucket = bucket_options(cfg)
     for train, (manifest, perturb, augment) in ((True, (cfg.train_manifest, factors, wave)), (False, (cfg.val_manifest, None, None))):
         ds = SpectrogramDataset(manifest, cfg.audio_conf, labels, mel_spec=cfg.mel_spec, resample=resample, speed_perturb=perturb,
-                                wave_augment=augment)
+                                wave_augment=augment, wildcard=wildcard, wildcard_ends=ends)
         if bucket['rungs']:
             from .data.bucketing import BucketBatchSampler, choose_ladder, nominal_frames
             frames, align = nominal_frames(ds), bucket['align']
@@ -151,8 +158,9 @@ def build_config(argv):
         parts = k.split('.')
         for p in parts[:-1]:
             cur = cur.setdefault(p, to_cfg({}))
-        cur[parts[-1]] = to_cfg(_yaml_load(v))
+        cur[parts[-1]] = to_cfg(override_value(k, v))
     criterion_name(cfg.model)      # model.criterion: ctc | asg (absent: ctc), anything else is an error naming the two
+    wildcard_options(cfg.model)    # model.wildcard: one character, none of the labels, not with asg
     scheduler_interval(cfg.model)  # model.scheduler_interval: epoch | step (absent: epoch)
     _check_augment(cfg)
     return cfg
@@ -207,7 +215,8 @@ def main(argv=None):
     rank = int(os.environ.get('RANK', '0'))
     local = 0 if os.environ.get('W2L_DIST_BACKEND') == 'gloo' else int(os.environ.get('LOCAL_RANK', '0'))
     torch.cuda.set_device(local)
-    train_loader, val_loader = get_data_loaders(cfg.model.labels, cfg.data, rank, world)
+    wildcard, _penalty = wildcard_options(cfg.model, cfg.model.labels)
+    train_loader, val_loader = get_data_loaders(cfg.model.labels, cfg.data, rank, world, wildcard=wildcard)
     model = name_to_model[cfg.model.name](cfg.model)
     if world > 1:
         from .distributed import GradReducer, broadcast_parameters, init_process_group_from_env
