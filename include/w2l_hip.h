@@ -859,6 +859,43 @@ int w2l_asg_align(const float* x, const float* transitions, const int32_t* input
                   int32_t* path, int32_t* starts, int32_t* ends, void* stream);
 /* host-side edit distance over int32 symbol arrays */
 int w2l_levenshtein_host(const int32_t* a_host, int na, const int32_t* b_host, int nb);
+/* workspace bytes for w2l_edit_distance: 0 (a pair's two rows live in LDS); -1 if out of range (n_tokens outside [0, 2^31),
+ * S < 1, P < 1, max_len outside [0, 4095]) */
+int64_t w2l_edit_distance_workspace_bytes(int64_t n_tokens, int S, int P, int max_len);
+/* Levenshtein distances of P pairs of int32 sequences in one launch, one wavefront per pair (csrc/edit_distance.hip).  All
+ * pointers are device memory: tokens[n_tokens] is the pool, sequence q is tokens[offsets[q] .. offsets[q+1]) (offsets[S+1]),
+ * pairs[P][2] holds (reference sequence, hypothesis sequence); a sequence may stand in any number of pairs.  max_len: the
+ * longest sequence the launch provides for (<= 4095; it sizes the LDS).  dist[P]; counts[P][3] (NULL: not wanted) = (sub, del,
+ * ins) of the alignment this recurrence picks, reference a[0..na), hypothesis b[0..nb): D[0][0] = 0, D[i][0] = i deletions,
+ * D[0][j] = j insertions; for i, j >= 1 the candidates in the order diagonal D[i-1][j-1] (+ one substitution if a[i-1] !=
+ * b[j-1]), deletion D[i-1][j] + 1, insertion D[i][j-1] + 1, and the cell takes the FIRST candidate of the smallest distance
+ * with that candidate's counts (so ins - del = j - i and sub = d - del - ins at every cell).  status[P]: 0 ok; 1 a sequence
+ * of the pair has offsets outside the pool or out of order, or is longer than max_len; 2 a sequence index outside [0, S) --
+ * then dist and counts are -1 and nothing of the pair is read.  Deterministic (no atomics); the workspace is unused. */
+int w2l_edit_distance(const int32_t* tokens, int64_t n_tokens, const int32_t* offsets, int S, const int32_t* pairs, int P,
+                      int max_len, void* workspace, int64_t workspace_bytes, int32_t* dist, int32_t* counts, int32_t* status,
+                      void* stream);
+/* workspace bytes for w2l_nbest_mbr: (4 N k T + N k) * 4 -- the decoded rows, the token keys and the words' starts and
+ * lengths; -1 if out of range (N outside 1..65535, k outside 1..64, T outside 1..32768) */
+int64_t w2l_nbest_mbr_workspace_bytes(int N, int k, int T);
+/* Minimum-Bayes-risk selection over the n-best list of a beam search, read in the search's out buffer where it lies
+ * (search_out: score[N][k] | len[N][k] | status[N] | labels[N][k][T], as w2l_ctc_beam_search / w2l_asg_beam_search_tables
+ * write it; 8-byte aligned), on the search's stream right behind it.  label_class_host[A] (host memory, A <= 128): the first
+ * label index of the label's character | 0x100 if the character is ' ' | 0x200 if it is whitespace.  Per present row
+ * (len >= 0): under ASG (repeat_index >= 0; -1: CTC) the row is decoded first -- a repeat label becomes the decoded label
+ * before it, leading ones are dropped --; its tokens are, unit 1 (char), the labels whose character is not ' ', unit 0
+ * (word), the maximal runs of labels whose character is not whitespace, two words equal iff they have the same length and the
+ * same characters.  dist[n][i][j]: the Levenshtein distance (w2l_edit_distance's recurrence) of rows i and j, 0 on the
+ * diagonal, -1 against an empty slot.  In float64, j = 0..k-1 in order over the present rows: m = max_j w_j (w: the search's
+ * log weights as they are), e_j = exp(scale * (w_j - m)), p_j = e_j / sum_j e_j, risk[n][i] = sum_j p_j * dist[n][i][j] (NaN
+ * for an empty slot); pick[n]: the present row of least risk, a tie to the lower rank; 0 if every slot is empty.  scale >= 0
+ * (1.0 is a convention, not a tuned value).
+ * mbr_out (8-byte aligned), one section: int32 pick[N] | int32 status[N] | double risk[N][k] | int32 dist[N][k][k] |
+ * int32 pick_len[N] | int32 pick_labels[N][T] -- the picked row as the search wrote it, for w2l_ctc_align / w2l_asg_align
+ * with row stride T.  status[n]: 0 ok; 1 a row of the utterance has a length above T, a label outside [0, A) or more than
+ * 4095 tokens: then pick = 0, the risks are NaN and dist is -1 throughout.  Deterministic; three launches (two for k = 1). */
+int w2l_nbest_mbr(const void* search_out, int N, int k, int T, const int32_t* label_class_host, int A, int unit,
+                  int repeat_index, double scale, void* workspace, int64_t workspace_bytes, void* mbr_out, void* stream);
 /* ConvCTCASR.add_string_metrics (base_asr_models.py:53-69) for one batch in ONE host call (no device work, no interpreter
  * lock held): idx int32 [N][T] = the step's argmax indices on the host, sizes[n] (NULL: T) the valid frames of utterance n.
  * Greedy collapse as GreedyDecoder.process_string(remove_repetitions=True) (decoder.py:104-119: blanks dropped, a frame equal

@@ -215,6 +215,10 @@ _SIGNATURES = {
     'w2l_mix_noise_slab_doubles': (c_i64, [c_i, c_i64]),
     'w2l_mix_noise': (c_i, [c_p, c_i64, c_p, c_i64, c_p, c_i64, c_i, c_p, c_p, c_p, c_p, c_i64, c_p]),
     'w2l_levenshtein_host': (c_i, [c_p, c_i, c_p, c_i]),
+    'w2l_edit_distance_workspace_bytes': (c_i64, [c_i64, c_i, c_i, c_i]),
+    'w2l_edit_distance': (c_i, [c_p, c_i64, c_p, c_i, c_p, c_i, c_i, c_p, c_i64, c_p, c_p, c_p, c_p]),
+    'w2l_nbest_mbr_workspace_bytes': (c_i64, [c_i, c_i, c_i]),
+    'w2l_nbest_mbr': (c_i, [c_p, c_i, c_i, c_i, c_p, c_i, c_i, c_i, C.c_double, c_p, c_i64, c_p, c_p]),
     'w2l_greedy_score_host': (c_i, [c_p, c_i, c_i, c_p, c_i, c_p, c_i, c_p, c_p, c_p, c_p, c_p]),
     'w2l_wgrad_fp8_needs_zero': (c_i, [c_i, c_i, c_i, c_i, c_i]),
     'w2l_conv1d_wgrad_fp8': (c_i, [c_p, c_i64, c_p, c_i64, c_i64, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_p, c_i, c_p]),
@@ -332,7 +336,7 @@ TRACE_NAMES = {
     'w2l_dwconv_wgrad': 'dw_wgrad_kernel', 'w2l_argmax': 'argmax_kernel', 'w2l_novograd_pack': 'novograd_pack_kernel',
     'w2l_ctc_beam_search': 'ctc_beam_search_kernel', 'w2l_ngram_lm_build': 'ngram_insert_kernel', 'w2l_ctc_align': 'ctc_align_kernel',
     'w2l_asg_beam_search': 'asg_beam_search_kernel', 'w2l_asg_beam_search_tables': 'asg_beam_search_kernel',
-    'w2l_asg_align': 'asg_align_kernel',
+    'w2l_asg_align': 'asg_align_kernel', 'w2l_edit_distance': 'edit_distance_kernel', 'w2l_nbest_mbr': 'mbr_kernels',
 }
 _trace = {'rows': None, 'saved': {}, 'pool': []}
 

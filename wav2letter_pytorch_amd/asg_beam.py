@@ -47,6 +47,7 @@ from .alignment import (Alignment, HostAlignment, _launch, align_buffers, align_
 from .asg import MAX_LABELS, ASGDecoder, _check_labels, decode_repeats, encode_repeats
 from .beam_search import (_check_decode_shape, _decoder_hotwords, _desc, _n_words, _pick, _resolve_hotwords, _resolve_lexicon,
                           _word_tables, search_out_layout, split_search_out, word_flags)
+from .mbr import check_mbr, check_mbr_status, launch_mbr, mbr_offset, mbr_rows, mbr_sections, split_mbr
 
 _NINF = float('-inf')
 
@@ -284,11 +285,13 @@ def launch_asg_align(x, g, sz, tg_ptr: int, tg_stride: int, len_ptr: int, len_st
 
 
 def _search_device(x, g, sz, labels, repeat_index, k, beta, prune, lm, alpha, offsets, lexicon=None, complete_only=True,
-                   hotwords=None, hotword_weight=1.0):
+                   hotwords=None, hotword_weight=1.0, mbr=None, mbr_scale=1.0):
     """one launch of w2l_asg_beam_search_tables (a table that is None: passed as NULL) for x [N, T, A] on the current stream,
     with ``offsets`` followed by w2l_asg_align on rank 0 where the search wrote it; one copy to the host.  ``lexicon``: a
     lexicon.Lexicon, a path or 'lm' (the vocabulary of ``lm``); ``hotwords``: a Lexicon, a path or an iterable of single words.
-    -> (scores [N, k], lengths [N, k], encoded labels [N, k, T], lm_log10 [N, k] or None, starts [N, T] or None)"""
+    -> (scores [N, k], lengths [N, k], encoded labels [N, k, T], lm_log10 [N, k] or None, starts [N, T] or None).  With ``mbr``
+    ('word' or 'char') w2l_nbest_mbr follows the search on the decoded text, ``offsets`` aligns ITS pick (the section's
+    pick_labels) instead of rank 0, and the tuple has a sixth element, the mbr.MbrResult."""
     n, t, a = x.shape
     dev = x.device
     any_table = lm is not None or lexicon is not None or hotwords is not None
@@ -304,38 +307,50 @@ def _search_device(x, g, sz, labels, repeat_index, k, beta, prune, lm, alpha, of
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
     lay = search_out_layout(n, k, t, lm is not None)
     beam_bytes = lay.beam_bytes
-    out = torch.empty(beam_bytes + (align_sections(n, t, t)[5] if offsets else 0), dtype=torch.uint8, device=dev)
+    mbr_at = mbr_offset(beam_bytes)
+    align_at = mbr_at + mbr_sections(n, k, t).total if mbr else beam_bytes
+    out = torch.empty(align_at + (align_sections(n, t, t)[5] if offsets else 0), dtype=torch.uint8, device=dev)
     check(lib.w2l_asg_beam_search_tables(ptr(x), ptr(g), ptr(sz), n, t, a, info.ctypes.data_as(C.c_void_p), int(repeat_index),
                                          space_index, int(k), float(alpha), float(beta), float(prune),
                                          _desc(tables), order, _desc(lex), int(bool(complete_only)), _desc(hot),
                                          float(hotword_weight), ptr(ws), ws_bytes, ptr(out), stream_ptr()),
           'w2l_asg_beam_search_tables')
+    mbr_ws = launch_mbr(out, mbr_at, n, k, t, labels, mbr, repeat_index, mbr_scale) if mbr else None
     align_ws = None
-    if offsets:
+    if offsets and mbr:
+        # the pick of every utterance, where w2l_nbest_mbr copied it: encoded rows of stride T
+        sec = mbr_sections(n, k, t)
+        align_ws = launch_asg_align(x, g, sz, out.data_ptr() + mbr_at + sec.pick_labels, t, out.data_ptr() + mbr_at + sec.pick_len,
+                                    1, t, repeat_index, True, out, align_at)
+    elif offsets:
         # rank 0 of every utterance, aligned where it lies
         align_ws = launch_asg_align(x, g, sz, out.data_ptr() + lay.labels, lay.labels_stride, out.data_ptr() + lay.lengths,
                                     lay.lengths_stride, t, repeat_index, True, out, beam_bytes)
     host = out.cpu().numpy()                           # the one copy to the host (ordered after the launches on this stream)
-    del align_ws
+    del align_ws, mbr_ws
     scores, lengths, status, idx, lm_log10 = split_search_out(host, n, k, t, lm is not None)
     if status.any():
         raise ValueError('the scores or transitions contain NaN (utterances %s)' % np.nonzero(status)[0].tolist())
+    res = split_mbr(host[mbr_at:], n, k, t) if mbr else None
     starts = None
     if offsets:
-        _, a_status, _, starts, _ = split_align(host[beam_bytes:], n, t, t)
+        _, a_status, _, starts, _ = split_align(host[align_at:], n, t, t)
         # (an emptied beam -- a frame without one finite score -- decodes to '' and has no characters to place: its empty
         # slot reads as S = 0, which the alignment calls infeasible; every other status is a real failure)
-        a_status = np.where(lengths[:, 0] < 1, 0, a_status)
+        a_status = np.where((res.pick_len if mbr else lengths[:, 0]) < 1, 0, a_status)
         if a_status.any():
             raise _lib.W2LError('w2l_asg_align found no path for the decoded hypothesis of utterances %s (status %s)'
                                 % (np.nonzero(a_status)[0].tolist(), a_status[a_status != 0].tolist()))
+    if mbr:
+        return scores, lengths, idx, lm_log10, starts, res
     return scores, lengths, idx, lm_log10, starts
 
 
 def asg_beam_search_gpu(x, transitions, labels: Sequence[str], repeat_index: int = 0, k: int = 5, beta: float = 5,
                         prune: float = 1e-3, sizes=None, nbest: int = 1, return_weights: bool = False, lm=None,
                         alpha: float = 0.3, return_offsets: bool = False, return_encoded: bool = False, lexicon=None,
-                        complete_only: bool = True, hotwords=None, hotword_weight: float = 1.0):
+                        complete_only: bool = True, hotwords=None, hotword_weight: float = 1.0, mbr=None,
+                        mbr_scale: float = 1.0, return_risks: bool = False):
     """asg_prefix_beam_search on the MI355X: one launch for a whole batch, the host's candidate order and ties.  x: ``[T, A]`` or
     ``[N, T, A]`` scores (numpy or torch, any device), transitions ``[A, A]`` (a tensor, an array, an ASGLoss, or None: zeros),
     ``sizes[n]``: decode only the first sizes[n] frames of utterance n; ``lm``: an ngram_lm.ArpaLM, scored as the host's
@@ -351,8 +366,14 @@ def asg_beam_search_gpu(x, transitions, labels: Sequence[str], repeat_index: int
     ``hotword_weight`` (natural-log units per matched character, any finite real; 1.0 is a convention, not a tuned value) are
     asg_prefix_beam_search's, with or without ``lm``: words are spelled by the decoded text, the results (best, n-best,
     offsets) come from the complete members of the final beam, the returned weights include the hotword term, and under a
-    lexicon the participation rule of the module docstring keeps the beam alive."""
+    lexicon the participation rule of the module docstring keeps the beam alive.
+
+    ``mbr`` ('word' or 'char'; None: today's result, no launch and no byte more), ``mbr_scale`` and ``return_risks`` are
+    beam_search.prefix_beam_search_gpu's: minimum-Bayes-risk selection over the k rows (mbr.py), on their DECODED texts.  The
+    result is the pick instead of rank 0; ``nbest > 1`` gives the rows in ascending risk; ``return_risks`` appends each row's
+    risk (behind the encoded tuple with ``return_encoded``); ``return_offsets`` aligns the picked hypothesis."""
     labels = list(labels)
+    mbr, mbr_scale = check_mbr(mbr, mbr_scale, return_risks)
     _check_labels(len(labels), 'asg_beam_search_gpu')
     if not 1 <= nbest <= k:
         raise ValueError('nbest=%d must lie in [1, k=%d]' % (nbest, k))
@@ -371,24 +392,31 @@ def asg_beam_search_gpu(x, transitions, labels: Sequence[str], repeat_index: int
         raise ValueError('repeat_index %d outside %d labels' % (repeat_index, a))
     g = _transitions_on(transitions, a, x.device)
     sz = host_lengths(sizes, n, t, 'sizes').to(x.device, non_blocking=True) if sizes is not None else None
-    scores, lengths, idx, _, starts = _search_device(x, g, sz, labels, int(repeat_index), int(k), beta, prune, lm, alpha,
-                                                     return_offsets, lexicon=lexicon, complete_only=complete_only,
-                                                     hotwords=hotwords, hotword_weight=hotword_weight)
+    got = _search_device(x, g, sz, labels, int(repeat_index), int(k), beta, prune, lm, alpha, return_offsets, lexicon=lexicon,
+                         complete_only=complete_only, hotwords=hotwords, hotword_weight=hotword_weight, mbr=mbr,
+                         mbr_scale=mbr_scale)
+    scores, lengths, idx, _, starts = got[:5]
+    res = got[5] if mbr else None
+    if mbr:
+        check_mbr_status(res, 'asg_beam_search_gpu')
     results = []
     for u in range(n):
-        found = []
+        found, ranks = [], []
         for rk in range(k):
             if lengths[u, rk] >= 0:
                 e = tuple(int(v) for v in idx[u, rk, :lengths[u, rk]])
                 found.append((_text(e, labels, repeat_index), float(scores[u, rk]), e))
+                ranks.append(rk)
         if not found:
             found = [('', _NINF, ())]
-        results.append(_pick(found, nbest, return_weights, return_encoded))
+        results.append(mbr_rows(found, ranks, res, u, nbest, return_weights, return_risks, return_encoded) if mbr else
+                       _pick(found, nbest, return_weights, return_encoded))
     if return_offsets:
         offs = []
         for u in range(n):
-            m = max(int(lengths[u, 0]), 0)
-            lead = 1 if m and idx[u, 0, 0] == repeat_index else 0
+            row, m = (res.pick_labels[u], int(res.pick_len[u])) if mbr else (idx[u, 0], int(lengths[u, 0]))
+            m = max(m, 0)
+            lead = 1 if m and row[0] == repeat_index else 0
             offs.append(torch.IntTensor(starts[u, lead:m].copy()))
         return (results[0], offs[0]) if single else (results, offs)
     return results[0] if single else results
@@ -431,14 +459,16 @@ class ASGBeamSearchDecoder(ASGDecoder):
     the search's ``k``, ``beta`` and ``prune``; ``decode`` has ASGDecoder.decode's arguments and return shapes, so it goes
     wherever the model's own decoder goes (``model.transcribe(decoder=...)``, ``evaluate(decoder=...)``).  ``lexicon`` (a
     lexicon.Lexicon or a path to a word list) with ``complete_only`` constrains the search, ``hotwords`` (a Lexicon, a path or
-    an iterable of single words) with ``hotword_weight`` makes it prefer words (asg_beam_search_gpu)."""
+    an iterable of single words) with ``hotword_weight`` makes it prefer words (asg_beam_search_gpu).  ``mbr`` ('word' or
+    'char') / ``mbr_scale``: ``decode`` returns the minimum-Bayes-risk pick of the k rows instead of rank 0 (mbr.py)."""
     lm = None
     alpha = 0.3
 
     def __init__(self, labels, repeat_index=0, transitions=None, k=5, beta=5, prune=1e-3, lexicon=None, complete_only=True,
-                 hotwords=None, hotword_weight=1.0):
+                 hotwords=None, hotword_weight=1.0, mbr=None, mbr_scale=1.0):
         super().__init__(labels, repeat_index, transitions)
         self.k, self.beta, self.prune = int(k), beta, prune
+        self.mbr, self.mbr_scale = check_mbr(mbr, mbr_scale)
         self._set_word_lists(lexicon, complete_only, hotwords, hotword_weight, None)
 
     def _set_word_lists(self, lexicon, complete_only, hotwords, hotword_weight, lm):
@@ -460,7 +490,8 @@ class ASGBeamSearchDecoder(ASGDecoder):
                                   self.repeat_index, k=self.k, beta=self.beta, prune=self.prune, sizes=sizes, lm=self.lm,
                                   alpha=self.alpha, return_offsets=return_offsets, lexicon=self.lexicon,
                                   complete_only=self.complete_only, hotwords=self.hotwords,
-                                  hotword_weight=self.hotword_weight)
+                                  hotword_weight=self.hotword_weight,
+                                  **({'mbr': self.mbr, 'mbr_scale': self.mbr_scale} if self.mbr is not None else {}))
         if return_offsets:
             return got[0], [[o] for o in got[1]]
         return got
@@ -471,8 +502,8 @@ class ASGBeamSearchLMDecoder(ASGBeamSearchDecoder):
     falsy ``lm_path`` decodes without an LM.  ``lexicon`` may also be 'lm', the model's vocabulary."""
 
     def __init__(self, lm_path, labels, repeat_index=0, transitions=None, k=5, alpha=0.3, beta=5, prune=1e-3, lexicon=None,
-                 complete_only=True, hotwords=None, hotword_weight=1.0):
-        super().__init__(labels, repeat_index, transitions, k=k, beta=beta, prune=prune)
+                 complete_only=True, hotwords=None, hotword_weight=1.0, mbr=None, mbr_scale=1.0):
+        super().__init__(labels, repeat_index, transitions, k=k, beta=beta, prune=prune, mbr=mbr, mbr_scale=mbr_scale)
         from .ngram_lm import ArpaLM
         self.lm = ArpaLM(lm_path) if lm_path else None
         self.alpha = alpha

@@ -14,7 +14,9 @@ as the host does with ``lm=lambda s: 10 ** arpa.score(s)``.  With ``return_offse
 (w2l_ctc_align, alignment.py) aligns each best prefix to the posteriors where it lies in the search's device buffer, and the
 character offsets come back in the same copy.  ``lexicon=`` confines the searches to a word list (lexicon.py); ``hotwords=`` /
 ``hotword_weight=`` make them prefer a list of words without forbidding anything else: the ranking weight of a string gains
-``exp(hotword_weight * h)``, ``h`` = Lexicon.boost_chars (w2l_ctc_beam_search with hotwords; host and device state the same rule)."""
+``exp(hotword_weight * h)``, ``h`` = Lexicon.boost_chars (w2l_ctc_beam_search with hotwords; host and device state the same rule).
+``mbr='word'|'char'`` returns, instead of the string of the greatest weight, the one of the least expected word / character
+error under the n-best list's own posterior (mbr.py; w2l_nbest_mbr reads the list in the search's buffer, on the same stream)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -31,6 +33,7 @@ from . import _lib
 from ._lib import check, lib, ptr, stream_ptr
 from .alignment import align_sections, launch_align, split_align
 from .decoder import Decoder
+from .mbr import check_mbr, check_mbr_status, launch_mbr, mbr_offset, mbr_rows, mbr_sections, split_mbr
 
 _WORD_RE = re.compile(r'\w+[\s|>]')
 
@@ -81,7 +84,7 @@ def prefix_beam_search(ctc, labels: Sequence[str], blank_index: int = 0, lm: Opt
     Lexicon.boost_chars of the words the labels can spell.  Masses, the LM weight, the prune and ties are untouched.
 
     ``stats`` (a dict): ``frames`` and ``live`` (the candidates with a positive mass, summed over the frames) are added to it,
-    and ``beam`` is set to the final beam, best first."""
+    and ``beam`` is set to the final beam, best first, ``weights`` to its members' ranking weights."""
     ctc = np.asarray(ctc)
     assert ctc.shape[1] == len(labels), "ctc size:%d, labels: %d" % (ctc.shape[1], len(labels))
     assert ctc.shape[0] > 1, "ctc length: %d was too short" % ctc.shape[0]
@@ -158,6 +161,7 @@ def prefix_beam_search(ctc, labels: Sequence[str], blank_index: int = 0, lm: Opt
         beam = ['']
     if stats is not None:
         stats['beam'] = list(beam)                       # the final beam in rank order (before complete_only)
+        stats['weights'] = [weight(s) for s in beam]     # and the members' ranking weights: the n-best list mbr.py reads
     if lexicon is not None and complete_only:
         beam = [s for s in beam if lexicon.complete(s, end_char)] or beam
     best = beam[0]
@@ -324,12 +328,15 @@ def _check_decode_shape(probs):
 
 
 def _beam_search_device(probs, labels, blank_index, k, beta, prune, end_char, sizes, log_probs, lm=None, alpha=0.3,
-                        offsets=False, lexicon=None, complete_only=True, hotwords=None, hotword_weight=0.0):
+                        offsets=False, lexicon=None, complete_only=True, hotwords=None, hotword_weight=0.0, mbr=None,
+                        mbr_scale=1.0):
     """one launch of w2l_ctc_beam_search for probs [N, T, A] on the current stream; returns the host arrays
     (scores [N, k], lengths [N, k], labels [N, k, T]).  With ``lm`` (an ngram_lm.ArpaLM) a fourth array: lm_log10 [N, k]
     float32, the LM total of each result.  With ``offsets`` a launch of w2l_ctc_align follows and one more array: starts
     int32 [N, T], the first frame of each label of rank 0.  ``lexicon`` (a lexicon.Lexicon, or 'lm': the vocabulary of ``lm``)
-    and ``hotwords`` (see _resolve_hotwords) are the entry point's other two tables; a table that is None is passed as NULL."""
+    and ``hotwords`` (see _resolve_hotwords) are the entry point's other two tables; a table that is None is passed as NULL.
+    With ``mbr`` ('word' or 'char') w2l_nbest_mbr follows the search, ``offsets`` aligns ITS pick (the section's pick_labels)
+    instead of rank 0, and the last array is followed by one more element, the mbr.MbrResult."""
     if probs.dim() != 3:
         raise ValueError('expected [N, T, labels] or [T, labels] posteriors, got shape %s' % (tuple(probs.shape),))
     n, t, a = probs.shape
@@ -366,14 +373,23 @@ def _beam_search_device(probs, labels, blank_index, k, beta, prune, end_char, si
                          % (k, t, '' if lm is None else ' (LM order %d)' % lm.order))
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
     lay = search_out_layout(n, k, t, lm is not None)
-    out = torch.empty(lay.beam_bytes + (align_sections(n, t, t)[5] if offsets else 0), dtype=torch.uint8, device=dev)
+    mbr_at = mbr_offset(lay.beam_bytes)
+    align_at = mbr_at + mbr_sections(n, k, t).total if mbr else lay.beam_bytes
+    out = torch.empty(align_at + (align_sections(n, t, t)[5] if offsets else 0), dtype=torch.uint8, device=dev)
     check(lib.w2l_ctc_beam_search(ptr(x), ptr(sz), n, t, a, info.ctypes.data_as(C.c_void_p), int(blank_index), int(end_index),
                                   space_index, int(k), float(alpha), float(beta), float(prune), int(bool(log_probs)),
                                   _desc(tables), order, _desc(lex), int(bool(complete_only)), _desc(hot),
                                   float(hotword_weight), ptr(ws), ws_bytes, ptr(out), stream_ptr()), 'w2l_ctc_beam_search')
-    align_ws = _align_best(x, sz, out, lay, t, blank_index, log_probs) if offsets else None
+    mbr_ws = launch_mbr(out, mbr_at, n, k, t, labels, mbr, -1, mbr_scale) if mbr else None
+    align_ws = None
+    if offsets and mbr:                                # the pick, where w2l_nbest_mbr copied it: rows of stride T
+        sec = mbr_sections(n, k, t)
+        align_ws = launch_align(x, sz, out.data_ptr() + mbr_at + sec.pick_labels, t, out.data_ptr() + mbr_at + sec.pick_len, 1,
+                                t, blank_index, log_probs, out, align_at)
+    elif offsets:
+        align_ws = _align_best(x, sz, out, lay, t, blank_index, log_probs)
     host = out.cpu().numpy()                           # the one copy to the host (ordered after the launches on this stream)
-    del align_ws
+    del align_ws, mbr_ws
     scores, lengths, status, idx, lm_log10 = split_search_out(host, n, k, t, lm is not None)
     if status.any():
         raise ValueError('ctc output contains negative numbers (utterances %s)' % np.nonzero(status)[0].tolist())
@@ -381,14 +397,17 @@ def _beam_search_device(probs, labels, blank_index, k, beta, prune, end_char, si
     if lm is not None:
         got += (lm_log10,)
     if offsets:
-        got += (_align_starts(host, n, t, lay.beam_bytes),)
+        got += (_align_starts(host, n, t, align_at),)
+    if mbr:
+        got += (split_mbr(host[mbr_at:], n, k, t),)
     return got
 
 
 def prefix_beam_search_gpu(probs, labels: Sequence[str], blank_index: int = 0, k: int = 5, beta: float = 5,
                            prune: float = 0.001, end_char: str = '>', sizes=None, log_probs: bool = False, nbest: int = 1,
                            return_weights: bool = False, lm=None, alpha: float = 0.3, return_offsets: bool = False,
-                           lexicon=None, complete_only: bool = True, hotwords=None, hotword_weight: float = 1.0):
+                           lexicon=None, complete_only: bool = True, hotwords=None, hotword_weight: float = 1.0, mbr=None,
+                           mbr_scale: float = 1.0, return_risks: bool = False):
     """prefix_beam_search on the MI355X: one launch for a whole batch, masses as fp64 logs (no underflow on long
     utterances; the host function's float32 products do underflow), the host's candidate order and ties.  ``lm``: an
     ngram_lm.ArpaLM scored as the host's ``lm=lambda s: 10 ** lm.score(s)`` with weight ``alpha`` (None: no LM).
@@ -412,8 +431,17 @@ def prefix_beam_search_gpu(probs, labels: Sequence[str], blank_index: int = 0, k
     tuned value): the ranking weight gets the factor ``exp(hotword_weight * h)``, ``h`` = Lexicon.boost_chars of the string
     -- the characters of its closed words that are hotwords plus, provisionally, those of a partial word that is a prefix of a
     hotword -- as in prefix_beam_search(hotwords=...).  It goes with every other argument; the returned log weights include it.
-    Weight 0 gives the results of no hotwords.  Single words only; one weight for the whole list."""
+    Weight 0 gives the results of no hotwords.  Single words only; one weight for the whole list.
+
+    ``mbr`` ('word' or 'char'; None: today's result, no launch and no byte more): minimum-Bayes-risk selection over the k rows
+    of the search (mbr.py: least expected word / character error under the posterior ``softmax(mbr_scale * log weights)``;
+    ``mbr_scale`` = 1.0 is a convention, not a tuned value; any finite number >= 0).  The result is the pick instead of rank 0,
+    with its own log weight under ``return_weights``; ``nbest > 1`` gives the rows in ascending risk, a tie by rank;
+    ``return_risks`` appends each row's risk to it (``(text, risk)``, or ``(text, log weight, risk)`` with weights or
+    ``nbest > 1``); ``return_offsets`` aligns the picked string.  One more entry point on the same stream, w2l_nbest_mbr; still
+    one copy to the host.  A hypothesis of more than 4095 words / characters is a ValueError."""
     labels = list(labels)
+    mbr, mbr_scale = check_mbr(mbr, mbr_scale, return_risks)
     if not 1 <= nbest <= k:
         raise ValueError('nbest=%d must lie in [1, k=%d]' % (nbest, k))
     if return_offsets and nbest != 1:
@@ -426,17 +454,23 @@ def prefix_beam_search_gpu(probs, labels: Sequence[str], blank_index: int = 0, k
             sizes = [int(np.asarray(sizes).reshape(-1)[0])]
     got = _beam_search_device(x, labels, blank_index, k, beta, prune, end_char, sizes, log_probs, lm=lm, alpha=alpha,
                               offsets=return_offsets, lexicon=lexicon, complete_only=complete_only, hotwords=hotwords,
-                              hotword_weight=hotword_weight)
+                              hotword_weight=hotword_weight, mbr=mbr, mbr_scale=mbr_scale)
     scores, lengths, idx = got[:3]
+    res = None
+    if mbr:
+        got, res = got[:-1], got[-1]
+        check_mbr_status(res, 'prefix_beam_search_gpu')
     results = []
     for u in range(scores.shape[0]):
-        found = [(''.join(labels[j] for j in idx[u, r, :lengths[u, r]]), float(scores[u, r]))
-                 for r in range(k) if lengths[u, r] >= 0]
+        ranks = [r for r in range(k) if lengths[u, r] >= 0]
+        found = [(''.join(labels[j] for j in idx[u, r, :lengths[u, r]]), float(scores[u, r])) for r in ranks]
         if not found:                                  # the beam emptied: '' as on the host (weight 0)
             found = [('', float('-inf'))]
-        results.append(_pick(found, nbest, return_weights))
+        results.append(mbr_rows(found, ranks, res, u, nbest, return_weights, return_risks) if mbr else
+                       _pick(found, nbest, return_weights))
     if return_offsets:
-        offs = [torch.IntTensor(got[-1][u, :max(int(lengths[u, 0]), 0)].copy()) for u in range(scores.shape[0])]
+        aligned_len = res.pick_len if mbr else lengths[:, 0]
+        offs = [torch.IntTensor(got[-1][u, :max(int(aligned_len[u]), 0)].copy()) for u in range(scores.shape[0])]
         return (results[0], offs[0]) if single else (results, offs)
     return results[0] if single else results
 
@@ -463,6 +497,7 @@ class _GPUPrefixDecoder(Decoder):
     """what the two device prefix decoders share: ``decode`` over the attributes their constructors set (``lm``: None, or
     the ngram_lm.ArpaLM that ``alpha`` weighs)"""
     lm = None
+    mbr, mbr_scale = None, 1.0
 
     def decode(self, probs, sizes=None, return_offsets=False):
         """[N, T, labels] -> N strings (utterance n over its first sizes[n] frames); [T, labels] -> one string.  With
@@ -472,7 +507,8 @@ class _GPUPrefixDecoder(Decoder):
         got = prefix_beam_search_gpu(probs, self.labels, self.blank_index, self.k, self.beta, self.prune, sizes=sizes,
                                      log_probs=self.log_probs, return_offsets=return_offsets, lexicon=self.lexicon,
                                      hotwords=self.hotwords, hotword_weight=self.hotword_weight,
-                                     **({'lm': self.lm, 'alpha': self.alpha} if self.lm is not None else {}))
+                                     **({'lm': self.lm, 'alpha': self.alpha} if self.lm is not None else {}),
+                                     **({'mbr': self.mbr, 'mbr_scale': self.mbr_scale} if self.mbr is not None else {}))
         return _nest_offsets(got, len(probs.shape) == 2) if return_offsets else got
 
 
@@ -480,11 +516,13 @@ class GPUPrefixBeamSearchDecoder(_GPUPrefixDecoder):
     """PrefixBeamSearchLMDecoder on the MI355X (prefix_beam_search_gpu): the same constructor (plus ``log_probs``), no
     language model -- a scoring callable cannot run on the device.  ``lexicon``: a lexicon.Lexicon or a path to a word list
     that constrains the search (prefix_beam_search_gpu).  ``hotwords``: a lexicon.Lexicon, a path or an iterable of single
-    words that the search prefers by ``hotword_weight`` per matched character (1.0 is a convention, not a tuned value)."""
+    words that the search prefers by ``hotword_weight`` per matched character (1.0 is a convention, not a tuned value).  ``mbr``
+    ('word' or 'char') / ``mbr_scale``: ``decode`` returns the minimum-Bayes-risk pick of the k rows instead of rank 0 (mbr.py)."""
 
     def __init__(self, lm_path, labels, blank_index=0, k=5, alpha=0.3, beta=5, prune=1e-3, log_probs=False, lexicon=None,
-                 hotwords=None, hotword_weight=1.0):
+                 hotwords=None, hotword_weight=1.0, mbr=None, mbr_scale=1.0):
         super(GPUPrefixBeamSearchDecoder, self).__init__(labels, blank_index)
+        self.mbr, self.mbr_scale = check_mbr(mbr, mbr_scale)
         self.hotwords, self.hotword_weight = _decoder_hotwords(hotwords, hotword_weight, self.labels, blank_index)
         if isinstance(lexicon, str) and lexicon == 'lm':
             raise ValueError("GPUPrefixBeamSearchDecoder has no language model: lexicon='lm' needs GPUPrefixBeamSearchLMDecoder")
@@ -499,11 +537,12 @@ class GPUPrefixBeamSearchLMDecoder(_GPUPrefixDecoder):
     """PrefixBeamSearchLMDecoder on the MI355X with an ARPA n-gram model read without kenlm (ngram_lm.ArpaLM, plain or
     .gz): the reference decoder's constructor (plus ``log_probs``); a falsy ``lm_path`` decodes without an LM.  ``lexicon``: a
     lexicon.Lexicon, a path to a word list, or 'lm' (the model's vocabulary) that constrains the search.  ``hotwords`` /
-    ``hotword_weight``: as in GPUPrefixBeamSearchDecoder."""
+    ``hotword_weight``, ``mbr`` / ``mbr_scale``: as in GPUPrefixBeamSearchDecoder."""
 
     def __init__(self, lm_path, labels, blank_index=0, k=5, alpha=0.3, beta=5, prune=1e-3, log_probs=False, lexicon=None,
-                 hotwords=None, hotword_weight=1.0):
+                 hotwords=None, hotword_weight=1.0, mbr=None, mbr_scale=1.0):
         super(GPUPrefixBeamSearchLMDecoder, self).__init__(labels, blank_index)
+        self.mbr, self.mbr_scale = check_mbr(mbr, mbr_scale)
         self.hotwords, self.hotword_weight = _decoder_hotwords(hotwords, hotword_weight, self.labels, blank_index)
         from .ngram_lm import ArpaLM
         self.lm = ArpaLM(lm_path) if lm_path else None

@@ -63,11 +63,30 @@ def decode_batch(model, decoder, out, out_lens, word_times: bool = False):
     return hyps, words
 
 
-def evaluate(model, dataloader, decoder=None, word_times: bool = False) -> Tuple[Dict[str, float], List[dict]]:
+def add_error_counts(records: List[dict], metrics: Dict[str, float]) -> None:
+    """what the errors are made of: every (text, hypothesis) pair of the set scored by ONE mbr.edit_distance_gpu(...,
+    counts=True) per unit -> ``word_sub`` / ``word_del`` / ``word_ins`` and the ``char`` trio in each record (they sum to its
+    word_errors / char_errors), ``test_word_sub`` ... ``test_char_ins`` in the metrics: each count summed over the set divided
+    by the summed reference length (0.0 / inf on an empty denominator, as corpus_metrics).  A transcript or hypothesis of more
+    than 4095 words / characters is edit_distance_gpu's ValueError."""
+    from .mbr import edit_distance_gpu
+    refs, hyps = [r['text'] for r in records], [r['hypothesis'] for r in records]
+    for unit in ('word', 'char'):
+        _, counts = edit_distance_gpu(refs, hyps, unit=unit, counts=True)
+        ref_len = sum(r[unit + '_ref'] for r in records)
+        for col, kind in enumerate(('sub', 'del', 'ins')):
+            for r, row in zip(records, counts):
+                r['%s_%s' % (unit, kind)] = int(row[col])
+            total = int(counts[:, col].sum()) if len(records) else 0
+            metrics['test_%s_%s' % (unit, kind)] = total / ref_len if ref_len else (0.0 if not total else float('inf'))
+
+
+def evaluate(model, dataloader, decoder=None, word_times: bool = False,
+             error_counts: bool = False) -> Tuple[Dict[str, float], List[dict]]:
     """``model.infer`` over every batch of ``dataloader`` (the 6-tuples of data_loader._collator) -> (metrics, records):
     metrics = test_loss (batch-size-weighted mean of the batch losses, as the validation epoch mean is formed), test_cer,
     test_wer, test_len_ratio (corpus_metrics); one record per utterance with path, text, hypothesis, char_errors, char_ref,
-    word_errors, word_ref (and words with ``word_times``)."""
+    word_errors, word_ref (and words with ``word_times``).  ``error_counts``: add_error_counts' keys on both."""
     import torch
     decoder = decoder or model.ctc_decoder
     was_training = model.training
@@ -103,4 +122,6 @@ def evaluate(model, dataloader, decoder=None, word_times: bool = False) -> Tuple
             model.train()
     metrics = {'test_loss': loss_sum / n_sum if n_sum else float('nan')}
     metrics.update(corpus_metrics(decoder, [(r['text'], r['hypothesis']) for r in records]))
+    if error_counts:
+        add_error_counts(records, metrics)
     return metrics, records

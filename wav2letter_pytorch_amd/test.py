@@ -5,7 +5,7 @@ shipped:
            data.test_manifest=test.csv [model=jasper] [model.mid_layers=20] [decoder=greedy|beam|beam_lm|asg_beam|asg_beam_lm] [lm_path=lm.arpa] \\
            [beam.k=5] [beam.alpha=0.3] [beam.beta=5] [beam.prune=1e-3] [print_samples=K | print_all=true] \\
            [lexicon_path=words.txt | lexicon_from_lm=true] [hotwords_path=words.txt [hotword_weight=1.0]] \\
-           [output=hyps.jsonl] [word_times=true] [data.resample=true]
+           [output=hyps.jsonl] [word_times=true] [data.resample=true] [mbr=word|char [mbr_scale=1.0]] [error_counts=true]
 
 ``train.py``'s override syntax and config tree.  The forward pass is ``model.infer`` (one fused launch per convolution);
 ``test_loss``, corpus-level ``test_cer`` / ``test_wer`` and ``test_len_ratio`` are printed and returned.  ``output=`` writes one
@@ -17,7 +17,11 @@ constrains the beam search to strings of lexicon words (lexicon.py).  ``hotwords
 line; ``decoder=beam|beam_lm``) makes the beam search prefer those words by ``hotword_weight=`` natural-log units per matched
 character (default 1.0: a convention, not a tuned value) without forbidding anything else.  The ASG beam searches have both
 (``lexicon=`` / ``hotwords=`` of asg_beam.ASGBeamSearchDecoder / ASGBeamSearchLMDecoder), but this command does not take the
-keys with ``decoder=asg_beam|asg_beam_lm`` yet: it refuses them."""
+keys with ``decoder=asg_beam|asg_beam_lm`` yet: it refuses them.  ``mbr=word|char`` (any of the four beam decoders) returns the
+hypothesis of the least expected word / character error over the search's own n-best list instead of its best-weighted one
+(mbr.py; ``mbr_scale=`` scales the log weights in the posterior, default 1.0: a convention, not a tuned value).
+``error_counts=true`` splits the errors into substitutions, deletions and insertions, per record (``word_sub`` ... ``char_ins``)
+and over the set (``test_word_sub`` ... ``test_char_ins``, each divided by the summed reference length)."""
 from __future__ import annotations
 
 import json
@@ -31,6 +35,7 @@ LM_DECODERS = ('beam_lm', 'asg_beam_lm')
 ASG_DECODERS = ('asg_beam', 'asg_beam_lm')
 LEXICON_DECODERS = ('beam', 'beam_lm')
 BEAM_DEFAULTS = dict(k=5, alpha=0.3, beta=5, prune=1e-3)
+MBR_UNITS = ('word', 'char')
 
 
 def _truth(v) -> bool:
@@ -98,6 +103,26 @@ def build_config(argv):
             raise SystemExit(f'hotword_weight={cfg.hotword_weight!r} is not finite')
     if cfg.decoder in ASG_DECODERS and cfg.model.get('criterion', 'ctc') != 'asg':
         raise SystemExit(f'decoder={cfg.decoder} decodes with learned transitions: it needs model.criterion=asg')
+    cfg.setdefault('mbr', None)
+    cfg.setdefault('mbr_scale', None)
+    if cfg.mbr == '':
+        cfg['mbr'] = None
+    if cfg.mbr is not None:
+        if cfg.decoder == 'greedy':
+            raise SystemExit('mbr is given but decoder=greedy: minimum-Bayes-risk selection needs the n-best list of a beam '
+                             'search (decoder=beam, beam_lm, asg_beam or asg_beam_lm)')
+        if cfg.mbr not in MBR_UNITS:
+            raise SystemExit(f'mbr={cfg.mbr!r} is not one of {", ".join(MBR_UNITS)}')
+    if cfg.mbr_scale not in (None, ''):
+        if cfg.mbr is None:
+            raise SystemExit('mbr_scale is given without mbr=word|char')
+        try:
+            cfg['mbr_scale'] = float(cfg.mbr_scale)
+        except (TypeError, ValueError):
+            raise SystemExit(f'mbr_scale={cfg.mbr_scale!r} is not a number')
+        if not math.isfinite(cfg.mbr_scale) or cfg.mbr_scale < 0:
+            raise SystemExit(f'mbr_scale={cfg.mbr_scale!r} is not a finite number >= 0')
+    cfg['error_counts'] = _truth(cfg.get('error_counts', False))
     beam = dict(BEAM_DEFAULTS)
     beam.update(cfg.get('beam') or {})
     unknown = sorted(set(beam) - set(BEAM_DEFAULTS))
@@ -124,13 +149,18 @@ def decoder_spec(cfg, log_probs: bool):
     labels = cfg.model.labels
     if cfg.decoder == 'greedy':
         return 'GreedyDecoder', dict(labels=labels)
+    mbr = {}
+    if cfg.get('mbr'):                         # (the keys are absent without mbr=: the decoders' defaults)
+        mbr['mbr'] = cfg.mbr
+        if cfg.get('mbr_scale') not in (None, ''):
+            mbr['mbr_scale'] = float(cfg.mbr_scale)
     if cfg.decoder in ASG_DECODERS:            # (``transitions`` is bound by main(), to the model's criterion)
-        kw = dict(labels=labels, k=int(cfg.beam.k), beta=float(cfg.beam.beta), prune=float(cfg.beam.prune))
+        kw = dict(labels=labels, k=int(cfg.beam.k), beta=float(cfg.beam.beta), prune=float(cfg.beam.prune), **mbr)
         if cfg.decoder == 'asg_beam':
             return 'ASGBeamSearchDecoder', kw
         return 'ASGBeamSearchLMDecoder', dict(lm_path=cfg.lm_path, alpha=float(cfg.beam.alpha), **kw)
     kw = dict(labels=labels, k=int(cfg.beam.k), alpha=float(cfg.beam.alpha), beta=float(cfg.beam.beta),
-              prune=float(cfg.beam.prune), log_probs=log_probs)
+              prune=float(cfg.beam.prune), log_probs=log_probs, **mbr)
     lexicon = 'lm' if cfg.get('lexicon_from_lm') else cfg.get('lexicon_path')
     if lexicon:                                # (the key is absent without a lexicon: the decoders' defaults)
         kw['lexicon'] = lexicon
@@ -182,7 +212,8 @@ def main(argv=None):
         dec = model.ctc_decoder              # decoder=greedy under asg: the model's Viterbi decoder, bound to its transitions
     else:
         dec = build_decoder(cfg, bool(getattr(model, 'infer_log_probs', True)))
-    metrics, records = evaluate(model, loader, decoder=dec, word_times=cfg.word_times)
+    metrics, records = evaluate(model, loader, decoder=dec, word_times=cfg.word_times,
+                                **({'error_counts': True} if cfg.error_counts else {}))
     shown = len(records) if cfg.print_all else min(cfg.print_samples, len(records))
     for r in records[:shown]:
         print(f'reference : {r["text"]}')

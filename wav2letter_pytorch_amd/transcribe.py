@@ -6,7 +6,7 @@
            [beam.prune=1e-3] [lexicon_path=words.txt | lexicon_from_lm=true] [hotwords_path=words.txt [hotword_weight=1.0]] \\
            [segment.max_seconds=20] [segment.on_db=10] [segment.hyst_db=3] [segment.q=0.05] [segment.abs_min=1e-10] \\
            [segment.min_silence=0.3] [segment.min_speech=0.1] [segment.pad=0.2] [segment.on_dbfs=-40 [segment.off_dbfs=-43]] \\
-           [word_times=true] [batch_size=8] [output=out.jsonl]
+           [word_times=true] [batch_size=8] [output=out.jsonl] [mbr=word|char [mbr_scale=1.0]]
 
 ``test.py``'s override syntax, config tree and decoder keys (the decoder is built by ``test.decoder_spec`` /
 ``test.build_decoder``).  Every file is cut at its pauses on the GPU and transcribed piece by piece
