@@ -274,7 +274,7 @@ def argmax_ref(x):
     return np.where(nan.any(axis=1), nan.argmax(axis=1), np.where(nan, -np.inf, x).argmax(axis=1)).astype(np.int32)
 
 
-# ---- CTC (ctc.hip ctc_alpha_beta_kernel, ctc_grad_kernel, ctc_loss_reduce_kernel) --------------------------------------------------
+# ---- CTC (ctc_core.h ctc_alpha_beta_kernel, ctc_grad_kernel, ctc_loss_reduce_kernel, as w2l_ctc_loss of ctc.hip runs them) ---------
 
 # one step  v = lse3(a0, a1, a2) + e  (lse3 = m + __logf(1 + __expf(md - m) + __expf(lo - m))):
 #   each __expf: its argument's subtraction u |x| -> e^x u |x| <= u / e, and HW_EXPF_ABS u;  1 + e1 + e2 <= 3: two additions, 6u;

@@ -4,7 +4,7 @@ EVERY gradient element.  Outputs start as NaN and are followed by a guard region
 
 Which case reaches which kernel (C = 29, N = 3, unequal input lengths, one below T):
 
-  L63    Smax 31,  T 56     wctc_alpha_beta_kernel<64, 1, staged>
+  L63    Smax 31,  T 56     ctc_alpha_beta_kernel<WctcParams, 64, 1, staged> (csrc/ctc_core.h)
   L65    Smax 32,  T 80     <128, 1, staged>
   L129   Smax 64,  T 160    <192, 1, staged>
   L1025  Smax 512, T 600    <1024, 2, staged>: two states per thread; rows longer than one 256-entry chunk of the parse kernel

@@ -8,26 +8,35 @@ from . import _lib
 from ._lib import check, lib, ptr, stream_ptr
 
 
+def _operands(name, workspace_bytes, log_probs, targets, input_lengths, target_lengths):
+    """what both loss entry points take: the batch-major operands (lp, tg, il, tl), the sizes (n, t, c, smax), the workspace
+    (``workspace_bytes(n, t, smax)`` bytes, 4 at the least) and the nll [N], loss [1] and grad [N, T, C] buffers.
+    ``name`` is the module's, for the message."""
+    # log_probs arrives as [T, N, C] (the reference passes out.transpose(0,1)); kernels are batch-major
+    _lib.require_device(log_probs)
+    lp = log_probs.detach().transpose(0, 1)
+    if not lp.is_contiguous() or lp.dtype != torch.float32:
+        lp = lp.contiguous().float()
+    n, t, c = lp.shape
+    dev = lp.device
+    if targets.dim() != 2:
+        raise NotImplementedError(f'{name}: targets must be 2-D [N, S_max] (padded), as the collator produces')
+    tg = targets.to(device=dev, dtype=torch.int32).contiguous()
+    il = torch.as_tensor(input_lengths).to(device=dev, dtype=torch.int32).contiguous()
+    tl = torch.as_tensor(target_lengths).to(device=dev, dtype=torch.int32).contiguous()
+    smax = tg.shape[1]
+    ws = torch.empty(max(int(workspace_bytes(n, t, smax)), 4), dtype=torch.uint8, device=dev)
+    nll = torch.empty(n, dtype=torch.float32, device=dev)
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    grad = torch.empty(n, t, c, dtype=torch.float32, device=dev)
+    return (lp, tg, il, tl), (n, t, c, smax), ws, nll, loss, grad
+
+
 class _CTCFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, log_probs, targets, input_lengths, target_lengths, blank, zero_infinity):
-        # log_probs arrives as [T, N, C] (the reference passes out.transpose(0,1)); kernels are batch-major
-        _lib.require_device(log_probs)
-        lp = log_probs.detach().transpose(0, 1)
-        if not lp.is_contiguous() or lp.dtype != torch.float32:
-            lp = lp.contiguous().float()
-        n, t, c = lp.shape
-        dev = lp.device
-        if targets.dim() != 2:
-            raise NotImplementedError('CTCLoss: targets must be 2-D [N, S_max] (padded), as the collator produces')
-        tg = targets.to(device=dev, dtype=torch.int32).contiguous()
-        il = torch.as_tensor(input_lengths).to(device=dev, dtype=torch.int32).contiguous()
-        tl = torch.as_tensor(target_lengths).to(device=dev, dtype=torch.int32).contiguous()
-        smax = tg.shape[1]
-        ws = torch.empty(max(int(lib.w2l_ctc_workspace_bytes(n, t, smax)), 4), dtype=torch.uint8, device=dev)
-        nll = torch.empty(n, dtype=torch.float32, device=dev)
-        loss = torch.empty(1, dtype=torch.float32, device=dev)
-        grad = torch.empty(n, t, c, dtype=torch.float32, device=dev)
+        (lp, tg, il, tl), (n, t, c, smax), ws, nll, loss, grad = _operands(
+            'CTCLoss', lib.w2l_ctc_workspace_bytes, log_probs, targets, input_lengths, target_lengths)
         check(lib.w2l_ctc_loss(ptr(lp), ptr(tg), ptr(il), ptr(tl), n, t, c, smax, int(blank), int(zero_infinity),
                                ptr(nll), ptr(loss), ptr(grad), ptr(ws), stream_ptr()), 'w2l_ctc_loss')
         ctx.grad = grad
@@ -60,23 +69,9 @@ class CTCLoss(nn.Module):
 class _WildcardCTCFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, log_probs, targets, input_lengths, target_lengths, blank, zero_infinity, penalty, owner):
-        _lib.require_device(log_probs)
-        lp = log_probs.detach().transpose(0, 1)
-        if not lp.is_contiguous() or lp.dtype != torch.float32:
-            lp = lp.contiguous().float()
-        n, t, c = lp.shape
-        dev = lp.device
-        if targets.dim() != 2:
-            raise NotImplementedError('WildcardCTCLoss: targets must be 2-D [N, S_max] (padded), as the collator produces')
-        tg = targets.to(device=dev, dtype=torch.int32).contiguous()
-        il = torch.as_tensor(input_lengths).to(device=dev, dtype=torch.int32).contiguous()
-        tl = torch.as_tensor(target_lengths).to(device=dev, dtype=torch.int32).contiguous()
-        smax = tg.shape[1]
-        ws = torch.empty(max(int(lib.w2l_wctc_workspace_bytes(n, t, smax)), 4), dtype=torch.uint8, device=dev)
-        nll = torch.empty(n, dtype=torch.float32, device=dev)
-        loss = torch.empty(1, dtype=torch.float32, device=dev)
-        grad = torch.empty(n, t, c, dtype=torch.float32, device=dev)
-        status = torch.empty(n, dtype=torch.int32, device=dev)
+        (lp, tg, il, tl), (n, t, c, smax), ws, nll, loss, grad = _operands(
+            'WildcardCTCLoss', lib.w2l_wctc_workspace_bytes, log_probs, targets, input_lengths, target_lengths)
+        status = torch.empty(n, dtype=torch.int32, device=lp.device)
         # the wildcard id is the first index past the model's classes: no output unit, no decoder ever sees it
         check(lib.w2l_wctc_loss(ptr(lp), ptr(tg), ptr(il), ptr(tl), n, t, c, smax, int(blank), int(zero_infinity), c,
                                 float(penalty), ptr(nll), ptr(loss), ptr(grad), ptr(status), ptr(ws), stream_ptr()),
